@@ -8,7 +8,12 @@ device: 9 NITI_Conv_Int8 forwards (+relu/maxpool), NITI_LOSS_Grad, 9 weight grad
 and the exact-mode RCCL all-reduces (MAX of every range, SUM of every int32 weight
 gradient) keep all ranks bit-identical to one device running the global batch.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).
+Prints ONE JSON line on rank 0.  A plain run sets up (one step, GEMM plan autotuning), warms up,
+times `--steps` steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step computed (logits, their exponent, every layer's updated weights) as DIR/<name>.npy.  `--full`
+adds everything else: the probed launch's roofline (HIP events around it inside the timed steps,
+its isolated re-runs, the PMC traffic of profiles/traffic.json), the speculative-pair counters and
+the CPU baseline.  Without it those fields of the line are null.
 
 Launch: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N
 ranks itself (torch.distributed.run as a child process, 127.0.0.1 rendezvous, before anything
@@ -183,6 +188,30 @@ def cpu_baseline_resnet18(sample, threads_list, hw):
     return legs
 
 
+DUMP_MAX_BYTES = 48 << 20  # of float32 in all (the option's limit is 64 MB)
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step left a caller -- the logits and their exponent and
+    every layer's updated int8 weights -- as float32 DIR/<name>.npy.  Where the arrays hold more
+    than DUMP_MAX_BYTES in all (VGG-16's 224-px head), each is cut to its share: a fixed seeded
+    sample of its elements in index order (a smaller array is written whole)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    logits, exp = model.logits()
+    arrays = {"logits": logits, "logits_exp": np.array([exp])}
+    for i in range(len(model.layers)):
+        arrays[f"weight_{i:02d}"] = model.get_weight(i)
+    share = DUMP_MAX_BYTES // 4 // len(arrays)
+    if sum(a.size for a in arrays.values()) * 4 <= DUMP_MAX_BYTES:
+        share = None
+    for name, a in arrays.items():
+        a = a.reshape(-1) if share and a.size > share else a
+        if share and a.size > share:
+            a = a[np.sort(np.random.default_rng(2024).integers(0, a.size, share))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (GPUs of this node); N > 1 outside torchrun "
@@ -229,6 +258,13 @@ def main():
     ap.add_argument("--rc-spec", type=int, default=0, choices=[0, 1, 2],
                     help="fused row kernels' speculative epilogue: 0 off (default), 1 on, 2 always redone "
                          "(results identical; A/B diagnostics)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the probed launch's roofline (timed "
+                         "inside the steps and re-run alone), the speculative-pair counters and the CPU baseline "
+                         "(--probe-*, --cpu-* act only here)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's results (logits, their exponent, every layer's "
+                         "updated weights) as DIR/<name>.npy, float32; at most 64 MB (a fixed seeded sample of more)")
     args = ap.parse_args()
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -322,18 +358,20 @@ def main():
     # The probe (HIP events around one GEMM, on the stream it runs on) is armed before the
     # warmup: the step is replayed as a hipGraph and arming it re-captures the graph, which
     # must not happen inside the timed region.  Warmup launches are read and discarded.
-    model.set_probe(probe_layer, args.probe_phase, args.steps + args.warmup)
+    if args.full:
+        model.set_probe(probe_layer, args.probe_phase, args.steps + args.warmup)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    model.probe_read()
-    model.probe_read_span()
+    if args.full:
+        model.probe_read()
+        model.probe_read_span()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if args.probe_every != 1:
+        if args.full and args.probe_every != 1:
             model.probe_pause(args.probe_every <= 0 or i % args.probe_every != args.probe_every - 1)
         step()
     torch.cuda.synchronize()
@@ -347,6 +385,55 @@ def main():
     # a fused row-kernel launch whose grid barrier timed out computed garbage: no number from it
     if model.rowconv_error() != 0:
         raise RuntimeError("a fused row-kernel grid barrier timed out in the timed region: results invalid")
+
+    ms_per_step = elapsed / args.steps * 1e3
+    images = args.batch * world * args.steps
+    value = images / elapsed
+    step_ops = 2 * model.step_macs() * world
+    tops = step_ops * args.steps / elapsed / 1e12
+    line = {
+        "metric": METRIC if arch == niti_amd.ARCH_VGG11 else METRIC.replace("VGG-11 batch 256",
+                                                                              f"{args.arch.upper()} batch {args.batch}"),
+        "value": round(value, 2),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": ("synthetic (random int8 x, fixed exponent" if args.int8_input else
+                 "synthetic (random uint8 images through the on-device input quantiser") +
+                "; random labels; seeded niti_normal_int8 weights)",
+        "config": {"workload": (f"{args.arch.upper()} NITI int8 training step (fwd+relu+pool, loss grad, "
+                                f"weight grad, input grad, SGD), {l0['c_in']}x{l0['h']}x{l0['w']}"
+                                + (", 4096-4096-1000 head" if arch == niti_amd.ARCH_VGG16 else "")
+                                if arch not in (niti_amd.ARCH_LENET, niti_amd.ARCH_RESNET18) else
+                                "LeNet NITI int8 training step, 1x28x28" if arch == niti_amd.ARCH_LENET else
+                                f"ResNet-18 NITI int8 training step (C++ step driver: convs, residual sums, sum pool, "
+                                f"1000-class loss grad, weight + input grads, SGD), 3x{l0['h']}x{l0['w']}"),
+                   "global_batch": args.batch * world, "per_gpu_batch": args.batch,
+                   "parallelism": parallelism_label(world, "RCCL all-reduce MAX ranges + SUM int32 grads"),
+                   "streams": "weight gradients beside the input-gradient chain on a second stream" if overlap
+                   else "one stream (weight gradient, then input gradient, per layer)"},
+        "int8_mfma_tops": round(tops, 2),
+        "int8_mfma_frac_of_peak": round(tops / PEAK_INT8_TOPS, 4),
+        "roofline": None,  # the three null fields: measured under --full only
+        "autotune_s": round(tune_s, 2) if not (args.no_autotune or args.load_plans) else None,
+        "rowconv_spec": None,
+        "cpu_baseline": None,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
     # the speculative pairs (the row kernels' two-launch form and the GEMM path's plan strategy 3):
     # launches B redid, and pairs the row kernels ran in store mode or the GEMM pair settled from an
     # alternate, per layer over warmup + timed steps (fwd redone, fwd stored/alt, dgrad redone, dgrad
@@ -374,12 +461,6 @@ def main():
     # end on the device wall clock), which leaves out its launch ramp and end-of-kernel writeback
     span_us = span_ms / span_n * 1e3 if span_n else None
     iso_span_us = iso_span_ms / iso_span_n * 1e3 if iso_span_n else None
-
-    ms_per_step = elapsed / args.steps * 1e3
-    images = args.batch * world * args.steps
-    value = images / elapsed
-    step_ops = 2 * model.step_macs() * world
-    tops = step_ops * args.steps / elapsed / 1e12
 
     pl = model.layers[probe_layer]
     k_ops = 2 * args.batch * pl["oh"] * pl["ow"] * pl["c_out"] * pl["c_in"] * pl["kh"] * pl["kw"]
@@ -454,35 +535,7 @@ def main():
                  "while it holds), both launches in the time")
     else:
         kname = f"gemm_kernel {pplan[0]}x{pplan[1]}, implicit im2col"
-    line = {
-        "metric": METRIC if arch == niti_amd.ARCH_VGG11 else METRIC.replace("VGG-11 batch 256",
-                                                                              f"{args.arch.upper()} batch {args.batch}"),
-        "value": round(value, 2),
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "int8",
-        "data": ("synthetic (random int8 x, fixed exponent" if args.int8_input else
-                 "synthetic (random uint8 images through the on-device input quantiser") +
-                "; random labels; seeded niti_normal_int8 weights)",
-        "config": {"workload": (f"{args.arch.upper()} NITI int8 training step (fwd+relu+pool, loss grad, "
-                                f"weight grad, input grad, SGD), {l0['c_in']}x{l0['h']}x{l0['w']}"
-                                + (", 4096-4096-1000 head" if arch == niti_amd.ARCH_VGG16 else "")
-                                if arch not in (niti_amd.ARCH_LENET, niti_amd.ARCH_RESNET18) else
-                                "LeNet NITI int8 training step, 1x28x28" if arch == niti_amd.ARCH_LENET else
-                                f"ResNet-18 NITI int8 training step (C++ step driver: convs, residual sums, sum pool, "
-                                f"1000-class loss grad, weight + input grads, SGD), 3x{l0['h']}x{l0['w']}"),
-                   "global_batch": args.batch * world, "per_gpu_batch": args.batch,
-                   "parallelism": parallelism_label(world, "RCCL all-reduce MAX ranges + SUM int32 grads"),
-                   "streams": "weight gradients beside the input-gradient chain on a second stream" if overlap
-                   else "one stream (weight gradient, then input gradient, per layer)"},
-        "int8_mfma_tops": round(tops, 2),
-        "int8_mfma_frac_of_peak": round(tops / PEAK_INT8_TOPS, 4),
+    line.update({
         "roofline": {
             "kernel": f"{args.arch.upper()} conv{probe_layer + 1} {phase_name} launch ({kname}; layer index {probe_layer})",
             "bound": bound,
@@ -507,10 +560,9 @@ def main():
                          "in_kernel_span_us": round(iso_span_us, 2) if iso_span_us else None,
                          "note": "same launch re-run alone after the timed region (no side-stream overlap)"},
         },
-        "autotune_s": round(tune_s, 2) if not (args.no_autotune or args.load_plans) else None,
         "rowconv_spec": spec,
         "cpu_baseline": cpu,
-    }
+    })
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist:

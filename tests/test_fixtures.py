@@ -1,8 +1,9 @@
 """MNN's tensor fixture text format (niti_amd.fixtures): reading as
 `stream >> v` does (testModel.cpp:43-56), writing as expressDemo's output.txt, checkFile's
-comparison, and the C4 / NHWC element orders of the reference's own fixture files (slices committed
-under tests/golden/ by make_fixture_slices.py; the whole files are read when /root/reference is
-present)."""
+comparison, and the C4 / NHWC element orders of the reference's own fixture files (under
+tests/golden/: first-row slices cut by make_fixture_slices.py, SqueezeNet's input.txt and MobileNet's
+qnt_input.txt whole (gzip-compressed, unpacked by the test), and the first two lines of MobileNet's flt_input.txt)."""
+import gzip
 import os
 import sys
 
@@ -14,7 +15,6 @@ sys.path.insert(0, os.path.join(ROOT, "mandheling-dsp-training_amd"))
 from niti_amd import fixtures as F  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF = "/root/reference/execution-engine/resource/model"
 
 
 def test_squeezenet_c4_slice_layout():
@@ -33,17 +33,25 @@ def test_mobilenet_nhwc_slice_layout():
     assert x[0, :, 0, 0].tolist() == [62, 62, 62] and x[0, :, 0, 1].tolist() == [45, 48, 46]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-def test_reference_fixture_files_whole():
-    sq = F.read_txt(f"{REF}/SqueezeNet/input.txt", dtype=np.float32)
+def unpacked(tmp_path, name):
+    """tests/golden/<name>.gz unpacked into tmp_path: the reference's file, byte for byte."""
+    p = tmp_path / name
+    p.write_bytes(gzip.open(os.path.join(GOLD, name + ".gz")).read())
+    return str(p)
+
+
+def test_reference_fixture_files_whole(tmp_path):
+    sq = F.read_txt(unpacked(tmp_path, "squeezenet_input.txt"), dtype=np.float32)
     assert sq.size == 227 * 227 * 4 and np.all(sq.reshape(-1, 4)[:, 3] == 0)
-    mb = F.read_txt(f"{REF}/MobileNet/qnt_input.txt", 224 * 224 * 3, np.uint8)
+    mb = F.read_txt(unpacked(tmp_path, "mobilenet_qnt_input.txt"), 224 * 224 * 3, np.uint8)
     assert mb.size == 224 * 224 * 3
     # flt_input.txt opens with a stray '>>>' line: `stream >> v` fails at once and leaves the
-    # tensor unread, and read_txt stops there the same way (asking for the tensor's count raises)
-    assert F.read_txt(f"{REF}/MobileNet/flt_input.txt").size == 0
+    # tensor unread, and read_txt stops there the same way (asking for the tensor's count raises);
+    # the stored head is that line and the first line of values
+    flt = os.path.join(GOLD, "mobilenet_flt_input_head.txt")
+    assert open(flt).readline().strip() == ">>>" and F.read_txt(flt).size == 0
     with pytest.raises(ValueError):
-        F.read_txt(f"{REF}/MobileNet/flt_input.txt", 224 * 224 * 3)
+        F.read_txt(flt, 224 * 224 * 3)
 
 
 def test_write_read_check_round_trip(tmp_path):

@@ -2,8 +2,8 @@
 
 CPU: the hand-written flatbuffer encoder / decoder round-trips int8 parameters as TrainableParam
 Blob ops with the reference's default names; the decoder reads the reference's own MNN model files
-(benchmark/models/*.mnn, when /root/reference is present) into self-consistent nets; malformed
-files are ValueError.  GPU: a model restored from a .mnn snapshot continues training exactly like
+(two of its benchmark/models/*.mnn, copied whole to tests/golden/) into self-consistent nets;
+malformed files are ValueError.  GPU: a model restored from a .mnn snapshot continues training exactly like
 the model that wrote it."""
 import os
 
@@ -12,7 +12,7 @@ import pytest
 
 from niti_amd import mnn_snapshot as M
 
-REF_MODELS = "/root/reference/execution-engine/benchmark/models"
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_encode_decode_round_trip(tmp_path):
@@ -57,10 +57,7 @@ def test_load_rejects_malformed(tmp_path):
 def test_decode_reference_model_files(name, first_ops):
     """The decoder on flatbuffers the reference's MNN converter wrote: op names, every output index
     inside tensorName, the first op an Input (OpType 34)."""
-    path = os.path.join(REF_MODELS, name)
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
-    net = M.decode_net(open(path, "rb").read())
+    net = M.decode_net(open(os.path.join(REF_MODELS, name), "rb").read())
     assert [op["name"] for op in net["ops"][:2]] == first_ops
     assert net["ops"][0]["type"] == 34
     n = len(net["tensorName"])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copy tools/gpu_others.sh's results for one tag from gpurun_out/ into profiles/.
+"""Copy tools/gpu_others.sh's results for one tag from the results folder ($RESULTS, default bench_out/) into profiles/.
 
 usage: collect_others.py TAG
 Writes profiles/TAG_{vgg16,lenet,resnet18}_bench.json (the bench lines, with roofline and
@@ -12,7 +12,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, os.environ.get("RESULTS", "bench_out"))  # where the tools/gpu_*.sh scripts write
 P = os.path.join(ROOT, "profiles")
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Copy one round's GPU deliverables from gpurun_out/ (tools/gpu_full.sh) into profiles/.
+"""Copy one round's GPU deliverables from the results folder of tools/gpu_full.sh ($RESULTS, default bench_out/) into profiles/.
 
-usage: collect_profiles.py TAG   (reads gpurun_out/{bench_full,prof,pmcF,pmcW}_TAG)
+usage: collect_profiles.py TAG   (reads $RESULTS/{bench_full,prof,pmcF,pmcW}_TAG)
 Writes profiles/TAG_bench.json, TAG_vgg11_b256_bench_under_rocprof.json, TAG_vgg11_b256_kernel_stats.csv,
 TAG_vgg11_b256_step_breakdown.txt, TAG_probe_dispatches.txt, TAG_pmc_{fetch,write}_size.csv (probe rows +
 calibration), TAG_traffic.txt and profiles/traffic.json.
@@ -15,7 +15,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, os.environ.get("RESULTS", "bench_out"))  # where the tools/gpu_*.sh scripts write
 P = os.path.join(ROOT, "profiles")
 
 
@@ -58,7 +58,7 @@ def main():
         kn = sel[-1]["Kernel_Name"].split("(")[0]
         f.write(f"probe {kn}, grid {int(sel[-1]['Grid_Size_X']) // int(sel[-1]['Workgroup_Size_X'])} x "
                 f"{sel[-1]['Workgroup_Size_X']} threads, plan {plan}\n")
-        f.write(f"rocprofv3 --kernel-trace of `bench.py --cpu-sample 0 --load-plans ...` (tools/gpu_full.sh, TAG={tag}):\n")
+        f.write(f"rocprofv3 --kernel-trace of `bench.py --full --cpu-sample 0 --load-plans ...` (tools/gpu_full.sh, TAG={tag}):\n")
         f.write(f"  isolated re-runs after the timed region (last 20 dispatches): avg {iso_avg:.2f} us, "
                 f"min {min(iso):.2f}, max {max(iso):.2f}\n")
         if instep:

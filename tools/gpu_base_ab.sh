@@ -4,13 +4,13 @@
 # (each with the plan set it autotunes), alternating.
 set -u
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
-OUT=gpurun_out/base_ab.txt
+RESULTS=${RESULTS:-bench_out}; mkdir -p "$RESULTS"
+OUT=$RESULTS/base_ab.txt
 : > $OUT
 run() {  # tag dir args...
   local tag=$1 dir=$2; shift 2
-  (cd $dir && timeout -k 10 400 python3 bench.py --cpu-sample 0 "$@") > gpurun_out/base_ab_$tag.log 2>&1 || return $?
-  echo "$tag $* $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/base_ab_$tag.log) $(grep -o '"redone": [0-9]*, "stored_or_alternate": [0-9]*' gpurun_out/base_ab_$tag.log)" >> $OUT
+  (cd $dir && timeout -k 10 400 python3 bench.py --full --cpu-sample 0 "$@") > $RESULTS/base_ab_$tag.log 2>&1 || return $?
+  echo "$tag $* $(grep -o '"ms_per_step": [0-9.]*' $RESULTS/base_ab_$tag.log) $(grep -o '"redone": [0-9]*, "stored_or_alternate": [0-9]*' $RESULTS/base_ab_$tag.log)" >> $OUT
 }
 for rep in 1 2; do
   for v in new base; do

@@ -5,13 +5,13 @@
 # time limit and the chain stops at the first failure.
 set -u
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+RESULTS=${RESULTS:-bench_out}; mkdir -p "$RESULTS"
 export TMPDIR=/tmp
 TAG=${TAG:-r06}
 TAG=$TAG bash tools/gpu_full.sh || exit $?
 TAG=$TAG NETS="${NETS:-resnet18 vgg16}" bash tools/gpu_nets.sh || exit $?
-timeout -k 10 300 python3 bench.py --dp-path --cpu-sample 0 > gpurun_out/dp_path_$TAG.log 2>&1
-rc=$?; echo "dp-path rc=$rc $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/dp_path_$TAG.log)"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python3 bench.py --arch lenet > gpurun_out/lenet_$TAG.log 2>&1
-rc=$?; echo "lenet rc=$rc $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/lenet_$TAG.log)"
+timeout -k 10 300 python3 bench.py --full --dp-path --cpu-sample 0 > $RESULTS/dp_path_$TAG.log 2>&1
+rc=$?; echo "dp-path rc=$rc $(grep -o '"ms_per_step": [0-9.]*' $RESULTS/dp_path_$TAG.log)"; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 300 python3 bench.py --full --arch lenet > $RESULTS/lenet_$TAG.log 2>&1
+rc=$?; echo "lenet rc=$rc $(grep -o '"ms_per_step": [0-9.]*' $RESULTS/lenet_$TAG.log)"
 exit $rc
