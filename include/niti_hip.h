@@ -350,6 +350,43 @@ int niti_absmax_i32(const int32_t* acc, int64_t n, uint32_t* amax, void* stream)
 int niti_requant_act(const int32_t* acc, int64_t rows, int ldc, const uint32_t* amax, const int8_t* exp_in,
                      const int8_t* wscale, int8_t* exp_out, int relu, const int8_t* relu_mask, int8_t* out_nhwc16,
                      void* stream);
+/* The fused forms of the same pass, which the training step (niti_model_*) otherwise reaches alone:
+ * the remaining options of the requantisation besides acc, rows, ldc and amax.  Every pointer may be
+ * NULL where its form does not need it; the combinations the library cannot run are INVALID_VALUE.
+ *  pool_out             forward 2x2 / 2 max pool: rows = pixels [n][pool_h][pool_w] (even sizes); the
+ *                       (relu'd) output to out_nhwc16 and its window max to pool_out [n][h/2][w/2][ldc]
+ *  pool_dx              its gradient: rows = pooled pixels; each requantised value goes to the first
+ *                       max of its window of pool_x (pre-pool output, pooled pool_y) in pool_dx
+ *                       [n][pool_h][pool_w][ldc], 0 elsewhere and, with pool_relu, where pool_x <= 0;
+ *                       pool_dx_c32 (ldc % 32 == 0): pool_dx also as C32 [n][ldc/32][h][w][32];
+ *                       out_nhwc16 (optional) the requantised dy itself
+ *  out_p16              the P16 copy [pixels/16][ldc][16] of out_nhwc16 (rows % 16 == 0), or of
+ *                       pool_dx (square 2 / 4 / 8 / 16 images, rows a multiple of 4, of 8 at 16)
+ *  zero_cls, zc_h, zc_w rows = pixels [n][zc_h][zc_w]: the parity classes (y & 1, x & 1) whose bit
+ *                       2 (y & 1) + (x & 1) is set are 0, their accumulators never read (plain pass)
+ *  pool3_out, pool3_arg the 3x3 / 2 pad-1 max pool of the output: rows = pixels [n][pool3_h][pool3_w],
+ *                       pooled image and first-max positions ky * 3 + kx [n][pool3_oh][pool3_ow][ldc]
+ *                       (oh = (h - 1) / 2 + 1); out_nhwc16 optional, no relu_mask */
+typedef struct niti_requant_fused {
+    const int8_t* exp_in;
+    const int8_t* wscale;
+    int8_t* exp_out;
+    const int8_t* relu_mask;
+    int8_t* out_nhwc16;
+    int8_t* pool_out;
+    const int8_t* pool_x;
+    const int8_t* pool_y;
+    int8_t* pool_dx;
+    int8_t* pool_dx_c32;
+    int8_t* out_p16;
+    int8_t* pool3_out;
+    int8_t* pool3_arg;
+    int relu, pool_relu, pool_h, pool_w;
+    int zero_cls, zc_h, zc_w;
+    int pool3_h, pool3_w, pool3_oh, pool3_ow;
+} niti_requant_fused;
+int niti_requant_act_fused(const int32_t* acc, int64_t rows, int ldc, const uint32_t* amax,
+                           const niti_requant_fused* f, void* stream);
 /* gradient rules: rule 2 = NITI_GradientConv_Int8 (bw-2), rule 3 = NITI_Matmul_Int8 (bw-3);
  * g_out optional; w_update optional fused NITI_SGD step w <- clip(w - g, +-127). */
 int niti_requant_grad(const int32_t* acc, int64_t n, const uint32_t* amax, int rule, int8_t* g_out,
@@ -407,6 +444,18 @@ int niti_maxpool_grad(const int8_t* x, const int8_t* y, const int8_t* dy, int n,
  * first-max position, then a gather per input pixel); equal results, for overlapping windows */
 int niti_maxpool_grad_ws(const int8_t* x, const int8_t* y, const int8_t* dy, int n, int h, int w, int cp, int k,
                          int s, int p, int oh, int ow, int relu, int8_t* workspace, int8_t* dx, void* stream);
+/* niti_maxpool that also records each window's first-max position ky * k + kx (in-image elements
+ * in (ky, kx) order) in arg [n][oh][ow][cp]; the training step (ResNet-18's stem) is its other caller.
+ * On a map smaller than the kernel y is, as niti_maxpool's, the max of the window clipped to the map
+ * size, and arg the first in-image element >= y of the whole window (-1: none), which is where the
+ * reference's pool gradient routes. */
+int niti_maxpool_arg(const int8_t* x, int n, int h, int w, int cp, int k, int s, int p, int8_t* y, int oh, int ow,
+                     int8_t* arg, void* stream);
+/* the pool gradient from those positions in one pass: dx = the wrapping int8 sum of dy over the
+ * windows whose first max is the pixel; relu masks it by x > 0, or, with pooled (the forward's y; x
+ * may then be NULL), each window's term by pooled > 0.  The training step is its other caller. */
+int niti_maxpool_grad_arg(const int8_t* x, const int8_t* arg, const int8_t* dy, int n, int h, int w, int cp, int k,
+                          int s, int p, int oh, int ow, int relu, const int8_t* pooled, int8_t* dx, void* stream);
 int niti_relu_grad(const int8_t* x, const int8_t* dy, int64_t n, int8_t* out, void* stream);
 int niti_loss_grad(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
                    const int32_t* labels, int8_t* out, void* stream);

@@ -519,6 +519,41 @@ int niti_requant_act(const int32_t* acc, int64_t rows, int ldc, const uint32_t* 
     return code(niti::requant_act(r, S(stream)));
 }
 
+int niti_requant_act_fused(const int32_t* acc, int64_t rows, int ldc, const uint32_t* amax,
+                           const niti_requant_fused* f, void* stream) {
+    if (!f || rows < 0) return NITI_INVALID_VALUE;
+    niti::ActRequant r;
+    r.acc = acc;
+    r.rows = rows;
+    r.ldc = ldc;
+    r.amax = amax;
+    r.exp_in = f->exp_in;
+    r.wscale = f->wscale;
+    r.exp_out = f->exp_out;
+    r.relu = f->relu;
+    r.relu_mask = f->relu_mask;
+    r.out_nhwc16 = f->out_nhwc16;
+    r.pool.pool_out = f->pool_out;
+    r.pool.x = f->pool_x;
+    r.pool.y = f->pool_y;
+    r.pool.dx = f->pool_dx;
+    r.pool.relu = f->pool_relu;
+    r.pool.H = f->pool_h;
+    r.pool.W = f->pool_w;
+    r.pool.dx_c32 = f->pool_dx_c32;
+    r.out_p16 = f->out_p16;
+    r.zero_cls = f->zero_cls;
+    r.zc_h = f->zc_h;
+    r.zc_w = f->zc_w;
+    r.pool3.out = f->pool3_out;
+    r.pool3.arg = f->pool3_arg;
+    r.pool3.H = f->pool3_h;
+    r.pool3.W = f->pool3_w;
+    r.pool3.OH = f->pool3_oh;
+    r.pool3.OW = f->pool3_ow;
+    return code(niti::requant_act(r, S(stream)));
+}
+
 int niti_requant_grad(const int32_t* acc, int64_t n, const uint32_t* amax, int rule, int8_t* g_out, int8_t* w,
                       void* stream) {
     if (rule != 2 && rule != 3) return NITI_INVALID_VALUE;
@@ -593,6 +628,14 @@ int niti_maxpool_grad_ws(const int8_t* x, const int8_t* y, const int8_t* dy, int
                          int s, int p, int oh, int ow, int relu, int8_t* ws, int8_t* dx, void* stream) {
     if (!x || !y || !dy || !ws || !dx || n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return NITI_INVALID_VALUE;
     return code(niti::maxpool_relu_grad_ws(x, y, dy, n, h, w, cp, k, s, p, oh, ow, relu, ws, dx, S(stream)));
+}
+int niti_maxpool_arg(const int8_t* x, int n, int h, int w, int cp, int k, int s, int p, int8_t* y, int oh, int ow,
+                     int8_t* arg, void* stream) {
+    return code(niti::maxpool_nhwc16(x, n, h, w, cp, k, s, p, y, oh, ow, S(stream), arg));
+}
+int niti_maxpool_grad_arg(const int8_t* x, const int8_t* arg, const int8_t* dy, int n, int h, int w, int cp, int k,
+                          int s, int p, int oh, int ow, int relu, const int8_t* pooled, int8_t* dx, void* stream) {
+    return code(niti::maxpool_relu_grad_arg(x, arg, dy, n, h, w, cp, k, s, p, oh, ow, relu, dx, S(stream), pooled));
 }
 int niti_relu_grad(const int8_t* x, const int8_t* dy, int64_t n, int8_t* out, void* stream) {
     if (n % 16) return NITI_INVALID_VALUE;

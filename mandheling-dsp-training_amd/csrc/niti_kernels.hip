@@ -4262,7 +4262,8 @@ hipError_t sgd_update(const int32_t* acc, const uint32_t* amax, int rule, int co
 // NITI_Maxpool_Int8.cpp:24-72 (kernel clipped to the input); one thread per 16 channels (32-bit
 // index math: the host keeps the thread count below 2^31).  With `arg`, each window's first-max
 // position (ky * k + kx, in NITI_CPUPoolGrad_Int8.cpp:21-77's order) goes there too: the first
-// element equal to the max is the first one >= it, the backward pass's choice.
+// element equal to the max is the first one >= it, the backward pass's choice (on a map smaller
+// than the kernel the two windows differ: see below).
 __global__ void maxpool_kernel(const int8_t* __restrict__ x, int n, int h, int w, int cp, int k, int s, int p,
                                int8_t* __restrict__ y, int oh, int ow, int8_t* __restrict__ arg) {
     const uint32_t groups = cp / 16;
@@ -4295,6 +4296,20 @@ __global__ void maxpool_kernel(const int8_t* __restrict__ x, int n, int h, int w
                 }
             }
         *(v16c*)(y + (int64_t)t * 16) = m;
+        if (arg != nullptr && (kh < k || kw < k)) {
+            // A map smaller than the kernel: the reference clips the forward's window (above) but not
+            // the gradient's scan, which takes the first in-image element >= the max of the whole
+            // k x k window (NITI_CPUPoolGrad_Int8.cpp:21-77).  That element is what arg records.
+#pragma unroll
+            for (int j = 0; j < 16; ++j) a[j] = (signed char)-1;
+            for (int yy = max(0, -sy0); yy < min(k, h - sy0); ++yy)
+                for (int xx = max(0, -sx0); xx < min(k, w - sx0); ++xx) {
+                    const v16c v = *(const v16c*)(x + (((int64_t)b * h + sy0 + yy) * w + sx0 + xx) * cp + gi * 16);
+                    const signed char pos = (signed char)(yy * k + xx);
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) a[j] = (a[j] < 0 && v[j] >= m[j]) ? pos : a[j];
+                }
+        }
         if (arg != nullptr) *(v16c*)(arg + (int64_t)t * 16) = a;
     }
 }

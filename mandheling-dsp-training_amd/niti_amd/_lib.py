@@ -74,6 +74,15 @@ class Geom(C.Structure):
         "pad_r", "dilate_h", "dilate_w", "oh", "ow", "cip", "cop", "np")]
 
 
+class RequantFused(C.Structure):
+    """niti_requant_fused: the options of niti_requant_act_fused."""
+    _fields_ = ([(n, C.c_void_p) for n in (
+        "exp_in", "wscale", "exp_out", "relu_mask", "out_nhwc16", "pool_out", "pool_x", "pool_y", "pool_dx",
+        "pool_dx_c32", "out_p16", "pool3_out", "pool3_arg")] + [(n, C.c_int) for n in (
+            "relu", "pool_relu", "pool_h", "pool_w", "zero_cls", "zc_h", "zc_w", "pool3_h", "pool3_w", "pool3_oh",
+            "pool3_ow")])
+
+
 _lib = None
 
 
@@ -140,6 +149,7 @@ def lib():
         "niti_matmul_acc": (ci, [ci, ci, ci, vp, i64, vp, i64, vp, i64, vp, vp, C.c_size_t, vp]),
         "niti_absmax_i32": (ci, [vp, i64, vp, vp]),
         "niti_requant_act": (ci, [vp, i64, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
+        "niti_requant_act_fused": (ci, [vp, i64, ci, vp, C.POINTER(RequantFused), vp]),
         "niti_requant_grad": (ci, [vp, i64, vp, ci, vp, vp, vp]),
         "niti_sgd_update": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
@@ -162,6 +172,8 @@ def lib():
         "niti_maxpool": (ci, [vp] + [ci] * 7 + [vp, ci, ci, vp]),
         "niti_maxpool_grad": (ci, [vp, vp, vp] + [ci] * 10 + [vp, vp]),
         "niti_maxpool_grad_ws": (ci, [vp, vp, vp] + [ci] * 10 + [vp, vp, vp]),
+        "niti_maxpool_arg": (ci, [vp] + [ci] * 7 + [vp, ci, ci, vp, vp]),
+        "niti_maxpool_grad_arg": (ci, [vp, vp, vp] + [ci] * 10 + [vp, vp, vp]),
         "niti_relu_grad": (ci, [vp, vp, i64, vp, vp]),
         "niti_loss_grad": (ci, [vp, ci, ci, ci, vp, vp, vp, vp]),
         "niti_model_create": (ci, [ci, ci, C.POINTER(vp)]),

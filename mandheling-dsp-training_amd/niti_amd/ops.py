@@ -428,6 +428,29 @@ def requant_act(acc, amax, exp_in=None, wscale=None, exp_out=None, relu=False, r
     return out
 
 
+def requant_act_fused(acc, amax, *, exp_in=None, wscale=None, exp_out=None, relu=False, relu_mask=None, out=None,
+                      pool_out=None, pool_x=None, pool_y=None, pool_dx=None, pool_relu=False, pool_hw=(0, 0),
+                      pool_dx_c32=None, out_p16=None, zero_cls=0, zc_hw=(0, 0), pool3_out=None, pool3_arg=None,
+                      pool3_hw=(0, 0), pool3_ohw=(0, 0), stream=None):
+    """The requantisation's fused forms (niti_requant_act_fused; the fields of niti_requant_fused in
+    include/niti_hip.h) on acc [rows][ldc].  Every buffer is the caller's and is written in place."""
+    rows, ldc = acc.shape
+    f = L.RequantFused()
+    for name, t in (("exp_in", exp_in), ("wscale", wscale), ("exp_out", exp_out), ("relu_mask", relu_mask),
+                    ("out_nhwc16", out), ("pool_out", pool_out), ("pool_x", pool_x), ("pool_y", pool_y),
+                    ("pool_dx", pool_dx), ("pool_dx_c32", pool_dx_c32), ("out_p16", out_p16),
+                    ("pool3_out", pool3_out), ("pool3_arg", pool3_arg)):
+        setattr(f, name, None if t is None else t.data_ptr())
+    f.relu, f.pool_relu = (1 if relu else 0), (1 if pool_relu else 0)
+    f.pool_h, f.pool_w = pool_hw
+    f.zero_cls = zero_cls
+    f.zc_h, f.zc_w = zc_hw
+    f.pool3_h, f.pool3_w = pool3_hw
+    f.pool3_oh, f.pool3_ow = pool3_ohw
+    check(L.lib().niti_requant_act_fused(_ptr(acc), rows, ldc, _ptr(amax), C.byref(f), _stream(stream)),
+          "requant_act_fused")
+
+
 def requant_grad(acc, amax, rule=2, w_update=None, stream=None):
     g = torch.empty(acc.shape, dtype=torch.int8, device=acc.device)
     check(L.lib().niti_requant_grad(_ptr(acc), acc.numel(), _ptr(amax), rule, _ptr(g), _ptr(w_update),
@@ -519,10 +542,14 @@ def sum_pool_grad(dy16, h, w, stream=None):
     return dx
 
 
-def maxpool(x16, k=2, s=2, p=0, stream=None):
+def _pool_out(x16, k, s, p, ohw):
     n, h, w, cp = x16.shape
-    oh = (h + 2 * p - min(k, h)) // s + 1
-    ow = (w + 2 * p - min(k, w)) // s + 1
+    return ohw if ohw is not None else ((h + 2 * p - min(k, h)) // s + 1, (w + 2 * p - min(k, w)) // s + 1)
+
+
+def maxpool(x16, k=2, s=2, p=0, stream=None, ohw=None):
+    n, h, w, cp = x16.shape
+    oh, ow = _pool_out(x16, k, s, p, ohw)
     y = torch.empty((n, oh, ow, cp), dtype=torch.int8, device=x16.device)
     check(L.lib().niti_maxpool(_ptr(x16), n, h, w, cp, k, s, p, _ptr(y), oh, ow, _stream(stream)), "maxpool")
     return y
@@ -543,6 +570,35 @@ def maxpool_grad(x16, y16, dy16, k=2, s=2, p=0, relu=False, stream=None, two_pas
     else:
         check(L.lib().niti_maxpool_grad(_ptr(x16), _ptr(y16), _ptr(dy16), n, h, w, cp, k, s, p, oh, ow,
                                         1 if relu else 0, _ptr(dx), _stream(stream)), "maxpool_grad")
+    return dx
+
+
+def maxpool_arg(x16, k=2, s=2, p=0, y=None, arg=None, stream=None, ohw=None):
+    """The max pool with each window's first-max position ky * k + kx -> (y, arg), both
+    [n][oh][ow][cp] (given buffers are written in place; ohw: a pooled size other than the default)."""
+    n, h, w, cp = x16.shape
+    oh, ow = _pool_out(x16, k, s, p, ohw)
+    if y is None:
+        y = torch.empty((n, oh, ow, cp), dtype=torch.int8, device=x16.device)
+    if arg is None:
+        arg = torch.empty((n, oh, ow, cp), dtype=torch.int8, device=x16.device)
+    assert y.shape == arg.shape == (n, oh, ow, cp)
+    check(L.lib().niti_maxpool_arg(_ptr(x16), n, h, w, cp, k, s, p, _ptr(y), oh, ow, _ptr(arg), _stream(stream)),
+          "maxpool_arg")
+    return y, arg
+
+
+def maxpool_grad_arg(arg, dy16, h, w, k=2, s=2, p=0, relu=False, x16=None, pooled=None, dx=None, stream=None):
+    """dx [n][h][w][cp] of the max pool from maxpool_arg's positions; relu masks by x16 > 0 or, with
+    `pooled` (the forward's y), each window's term by pooled > 0."""
+    n, oh, ow, cp = dy16.shape
+    assert arg.shape == dy16.shape
+    if dx is None:
+        dx = torch.empty((n, h, w, cp), dtype=torch.int8, device=dy16.device)
+    assert dx.shape == (n, h, w, cp)
+    check(L.lib().niti_maxpool_grad_arg(_ptr(x16), _ptr(arg), _ptr(dy16), n, h, w, cp, k, s, p, oh, ow,
+                                        1 if relu else 0, _ptr(pooled), _ptr(dx), _stream(stream)),
+          "maxpool_grad_arg")
     return dx
 
 
