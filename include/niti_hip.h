@@ -53,6 +53,7 @@ enum niti_op_type {
     NITI_OP_RELUGRAD_INT8 = 704,           /* NITI_ReluGrad_Int8      -> NITI_CPUReluGrad_Int8.cpp:28-62 */
     NITI_OP_MAXPOOL_INT8 = 705,            /* NITI_Maxpool_Int8       -> NITI_Maxpool_Int8.cpp:24-175 */
     NITI_OP_POOLGRAD_INT8 = 706,           /* NITI_PoolGrad_Int8      -> NITI_CPUPoolGrad_Int8.cpp:21-77 */
+    NITI_OP_LOSS_INT8 = 710,               /* NITI_LOSS_Int8          -> NITI_CPULoss_Int8.cpp:68-128 */
     NITI_OP_LOSS_GRAD_INT8 = 711,          /* NITI_LOSS_Grad_Int8     -> NITI_CPULossGrad_Int8.cpp:81-200 */
     NITI_OP_MATMUL_INT8 = 713,             /* NITI_MatMul_Int8        -> NITI_Matmul_Int8.cpp:140-231 */
     NITI_OP_PAD_INT8 = 714,                /* NITI_PAD_Int8           -> NITI_Pad_Int8.cpp:24-62 */
@@ -159,6 +160,10 @@ int niti_create_execution(int op_type, const niti_conv2d_common* common, niti_ex
  *  NITI_OP_LOSS_GRAD_INT8, NITI_OP_DSP_LOSSGRAD_INT8 (common may be NULL)
  *                             in {logits int8 [batch, classes], ascale int8[1], target int32 one-hot
  *                                 [batch, tc], dy (unused)} out{grad int8 [batch, classes]}; classes <= 2048
+ *  NITI_OP_LOSS_INT8 (common may be NULL)
+ *                             in {logits int8 [batch, classes], ascale int8[1], target int32 one-hot
+ *                                 [batch, tc]} out{loss float32 [1]}: the batch mean of the cross entropy
+ *                                 (niti_head_metrics' loss_i, in double; NCHW or NHWC); classes <= 2048
  *  NITI_OP_DSP_TRANSPOSEGRADIENT_CONV_INT8, NITI_OP_DSP_GRADIENT_SPLITBATCHCONV_INT8 (stride 1; the graph
  *                             dilates dy for stride 2)
  *                             in {x^T NHWC [Ci,N,H,W], dy NHWC [N,Co,OH,OW], 0, 0}
@@ -459,6 +464,33 @@ int niti_maxpool_grad_arg(const int8_t* x, const int8_t* arg, const int8_t* dy, 
 int niti_relu_grad(const int8_t* x, const int8_t* dy, int64_t n, int8_t* out, void* stream);
 int niti_loss_grad(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
                    const int32_t* labels, int8_t* out, void* stream);
+/* Evaluation metrics of a batch of logits (int8 [batch][ld], ld >= classes; lanes classes..ld are
+ * padding and never read as classes), what the reference's training program reports: the loss it
+ * prints every step (NITI_CPULoss_Int8.cpp:89-125) and the _ArgMax(logits) == label count of its
+ * test loop (MnistUtils.cpp:150-181).  Per image i with 0 <= labels[i] < classes:
+ *   pred[i]  the first index of the row maximum (a strict > scan, CPUArgMax.cpp:125-130)
+ *   rank_i   #{j : l[j] > l[label] or (l[j] == l[label] and j < label)}; top-1 correct <=> rank_i == 0
+ *            (<=> pred[i] == label), top-k correct <=> rank_i < topk
+ *   loss_i   logsumexp_j(z_j) - z_label with z = l * 2^ascale, evaluated in double (row maximum
+ *            subtracted, exact scaling); the reference's float32 MNNSoftmax approximation of the
+ *            same value is not reproduced
+ * An image with any other label (-1: the padding of a test set's last partial batch) is counted
+ * nowhere; its pred is still written and its loss_per_image is 0.  The batch's counts and loss sum
+ * are ADDED to *totals (device memory the caller owns and zeroes) in stream order, so a whole test
+ * set accumulates without a host synchronisation; the sum runs in a fixed order without atomics
+ * (the same inputs give a bit-identical loss_sum).  pred (int32 [batch]) and loss_per_image
+ * (double [batch]) may be NULL.  classes <= 2048 (NITI_NOT_SUPPORT above), 1 <= topk <= classes;
+ * workspace: niti_head_metrics_workspace(batch) bytes of device memory, 8-byte aligned.  Two
+ * launches, asynchronous. */
+typedef struct niti_eval_totals {
+    uint64_t images, top1, topk;
+    double loss_sum;
+} niti_eval_totals;
+int niti_head_metrics(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
+                      const int32_t* labels, int topk, int32_t* pred /*may be NULL*/,
+                      double* loss_per_image /*may be NULL*/, niti_eval_totals* totals /*device*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int niti_head_metrics_workspace(int batch, size_t* bytes);
 
 /* NITIInt8Train's input quantiser (execution-engine/tools/train/source/demo/MnistUtils.cpp:83-93):
  * mean / std / range of the uint8 batch, x = round((p - mean) / std / range * 127), ascale =
@@ -508,6 +540,36 @@ int niti_model_train_step(niti_model_t m, const int8_t* x_nchw, int exp_in, cons
  * (niti_image_stats / niti_image_quantize, statistics all-reduced in exact data-parallel mode)
  * runs on device first and supplies x and exp_in -- NITIInt8Train's whole per-batch work. */
 int niti_model_train_step_images(niti_model_t m, const uint8_t* images_nchw, const int32_t* labels, void* stream);
+/* Forward-only step (evaluation): the training step's forward pass on the current weights -- the
+ * logits and their exponent are bit-identical to what niti_model_train_step would have produced
+ * from the same weights and input -- followed by niti_head_metrics on the logits, added to the
+ * model's running totals.  No weight, derived weight copy, gradient buffer or SGD state is written.
+ * Asynchronous, no allocation; always direct launches (the training graph of niti_model_set_graph
+ * is neither dropped nor replayed).  labels[i] = -1 excludes image i from the totals (the padding
+ * of a last partial batch).  The _images form runs the input quantiser on the batch's own
+ * statistics first, as the reference's test loop does (MnistUtils.cpp:161-172).
+ * Side effects: niti_model_get_logits, niti_model_get_input and niti_model_get_tap(which = 0) then
+ * describe the evaluation batch; taps 1 and 2 still hold the last training step's data;
+ * niti_model_rowconv_error covers evaluation launches too.
+ * With a communicator or a local group attached the forward issues the same collectives as in
+ * training (statistics SUM / MAX, every range MAX in exact mode): world x b evaluates exactly as
+ * one device at world * b, all ranks must call it together, and the totals stay rank-local (the
+ * caller adds them). */
+int niti_model_eval_step(niti_model_t m, const int8_t* x_nchw, int exp_in, const int32_t* labels, void* stream);
+int niti_model_eval_step_images(niti_model_t m, const uint8_t* images_nchw, const int32_t* labels, void* stream);
+/* the running totals <- 0 (asynchronous) */
+int niti_model_eval_reset(niti_model_t m, void* stream);
+/* the running totals (synchronises `stream`) */
+int niti_model_eval_read(niti_model_t m, niti_eval_totals* host_out, void* stream);
+/* the k of the totals' topk count for later evaluation steps (default 5; clamped to [1, classes]) */
+int niti_model_eval_topk(niti_model_t m, int k);
+/* pred int32 [batch] of the last evaluation batch (synchronises `stream`) */
+int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream);
+/* Device-to-device weight hand-over: every layer's weights and weight scale of src into dst on
+ * `stream`, dst's derived copies refreshed.  Both models must have the same architecture, input
+ * size and class count (hence the same layer shapes); the batch may differ -- how a batch-64
+ * training model feeds a batch-20 evaluation model.  NITI_INVALID_VALUE otherwise.  Asynchronous. */
+int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream);
 /* Read back (synchronising): the step's quantised input x (NCHW int8) and its exponent. */
 int niti_model_get_input(niti_model_t m, int8_t* x_nchw_host, int* ascale, void* stream);
 /* Read back (synchronising `stream`): logits [batch][classes] int8 and their exponent. */
@@ -537,7 +599,9 @@ int niti_model_spec_stats(niti_model_t m, uint32_t* out, int max_layers);
  * the last 6 pairs' record (bw, input scale, guess) in words 26.. (synchronises) */
 int niti_model_spec_slot(niti_model_t m, int layer, int dgrad, uint32_t* out32);
 /* Replay the step as a hipGraph (single device only -- with a communicator attached the step
- * always runs as direct launches).  Default 0 (direct launches: measured faster on ROCm 7.2). */
+ * always runs as direct launches).  Default 0 (direct launches: measured faster on ROCm 7.2).
+ * The captured step holds kernel nodes only (its fills run as kernels: memset nodes were seen to
+ * replay wrong values on ROCm 7.2). */
 int niti_model_set_graph(niti_model_t m, int enable);
 /* Run the weight gradients on a second HIP stream, overlapping the input-gradient chain
  * (default 1; the update waits for both).  With a communicator every collective is still

@@ -73,8 +73,10 @@ size_t tensor_bytes(int op, bool is_out, int idx, const niti_tensor& t) {
         if (t.dims[k] < 0) return 0;
         d[k] = t.dims[k];
     }
-    if (!is_out && idx == 2 && (op == NITI_OP_LOSS_GRAD_INT8 || op == NITI_OP_DSP_LOSSGRAD_INT8))
+    if (!is_out && idx == 2 &&
+        (op == NITI_OP_LOSS_GRAD_INT8 || op == NITI_OP_DSP_LOSSGRAD_INT8 || op == NITI_OP_LOSS_INT8))
         return (size_t)(d[0] * d[1] * d[2] * d[3] * 4);
+    if (is_out && idx == 0 && op == NITI_OP_LOSS_INT8) return sizeof(float);  // the loss scalar
     if (!is_out && idx == 1 && op == NITI_OP_DSP_TRANSPOSE_INT8) return 4 * sizeof(int32_t);
     if (t.format == NITI_FORMAT_NC4HW4) return (size_t)(d[0] * ((d[1] + 3) / 4) * 4 * d[2] * d[3]);
     return (size_t)(d[0] * d[1] * d[2] * d[3]);
@@ -663,6 +665,23 @@ int niti_image_quantize_nhwc16(const uint8_t* images, int n, int c, int hw, int 
 int niti_loss_grad(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale, const int32_t* labels,
                    int8_t* out, void* stream) {
     return code(niti::loss_grad(logits, batch, classes, ld, ascale, labels, out, S(stream)));
+}
+int niti_head_metrics_workspace(int batch, size_t* bytes) {
+    if (!bytes || batch <= 0) return NITI_INVALID_VALUE;
+    *bytes = niti::head_metrics_workspace(batch);
+    return NITI_NO_ERROR;
+}
+int niti_head_metrics(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
+                      const int32_t* labels, int topk, int32_t* pred, double* loss_per_image, niti_eval_totals* totals,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    // every argument is checked on the host before any device call
+    if (!logits || !ascale || !labels || !totals) return NITI_INVALID_VALUE;
+    if (batch <= 0 || classes <= 0 || ld < classes) return NITI_INVALID_VALUE;
+    if (classes > 2048) return NITI_NOT_SUPPORT;
+    if (topk < 1 || topk > classes) return NITI_INVALID_VALUE;
+    if (!workspace || workspace_bytes < niti::head_metrics_workspace(batch)) return NITI_INVALID_VALUE;
+    return code(niti::head_metrics(logits, batch, classes, ld, ascale, labels, topk, pred, loss_per_image, totals,
+                                   workspace, workspace_bytes, S(stream)));
 }
 
 }  // extern "C"

@@ -1048,6 +1048,55 @@ class LossGradExecution : public Execution {
     int32_t* label_ = nullptr;
 };
 
+// NITI_LOSS_Int8 (710, NITI_CPULoss_Int8.cpp:68-128): {logits int8 [batch][classes], ascale int8[1],
+// target int32 one-hot [batch][tc]} -> {loss float32 [1]}, the batch mean of -log softmax(z)[label],
+// z = logits * 2^ascale (:89-125: average_sum / ib * (-1) over the rows' log-softmax at the target).
+// The rows' losses come from head_metrics in double (niti_metrics.hip); the reference's float32
+// MNNSoftmax approximation is not reproduced.  With tc < classes the classes at and beyond tc never
+// are the label (:103-108).
+struct LossMean {
+    const niti_eval_totals* t;
+    int batch;
+    float* out;
+    __device__ void operator()(int64_t) const { *out = (float)(t->loss_sum / (double)batch); }
+};
+
+class LossExecution : public Execution {
+   public:
+    int onResize(const niti_tensor* in, int nin, const niti_tensor* out, int nout) override {
+        if (nin < 3 || nout < 1) return NITI_INVALID_VALUE;
+        const niti_tensor &x = in[0], &t = in[2];
+        if (x.format == NITI_FORMAT_NC4HW4) return NITI_NOT_SUPPORT;
+        batch_ = x.dims[0];
+        classes_ = x.dims[1] * x.dims[2] * x.dims[3];
+        tc_ = t.dims[1] * t.dims[2] * t.dims[3];
+        if (batch_ <= 0 || classes_ <= 0 || classes_ > 2048 || t.dims[0] != batch_ || tc_ <= 0 || tc_ > classes_)
+            return classes_ > 2048 ? NITI_NOT_SUPPORT : NITI_COMPUTE_SIZE_ERROR;
+        ws_.release();
+        label_ = (int32_t*)ws_.alloc((size_t)batch_ * 4);
+        totals_ = (niti_eval_totals*)ws_.alloc(sizeof(niti_eval_totals));
+        mws_bytes_ = head_metrics_workspace(batch_);
+        mws_ = ws_.alloc(mws_bytes_);
+        return label_ && totals_ && mws_ ? NITI_NO_ERROR : NITI_OUT_OF_MEMORY;
+    }
+    int onExecute(const niti_tensor* in, int nin, const niti_tensor* out, int nout, hipStream_t st) override {
+        if (!label_ || !totals_ || !mws_) return NITI_NO_EXECUTION;
+        NITI_TRY(fill_kernel(totals_, 0, sizeof(niti_eval_totals), st));
+        NITI_TRY(launch_map(batch_, OnehotToIndex{(const int32_t*)in[2].data, tc_, label_}, st));
+        NITI_TRY(head_metrics((const int8_t*)in[0].data, batch_, classes_, classes_, (const int8_t*)in[1].data, label_,
+                              1, nullptr, nullptr, totals_, mws_, mws_bytes_, st));
+        NITI_TRY(launch_map(1, LossMean{totals_, batch_, (float*)out[0].data}, st));
+        return NITI_NO_ERROR;
+    }
+
+   private:
+    int batch_ = 0, classes_ = 0, tc_ = 0;
+    int32_t* label_ = nullptr;
+    niti_eval_totals* totals_ = nullptr;
+    void* mws_ = nullptr;
+    size_t mws_bytes_ = 0;
+};
+
 // ------------------------------------------------------------------ NITI_DSP layout slots
 // The DSP graph's data-movement ops, on the tensors' stored (raw) axis order -- [N][H][W][C] for
 // NHWC, [N][C][H][W] for NCHW -- as MNN's NHWC kernels index them:
@@ -1310,6 +1359,7 @@ Execution* create_execution(int op_type, const niti_conv2d_common* c, int* err) 
                            op_type == NITI_OP_RELU_INT8 || op_type == NITI_OP_RELUGRAD_INT8 ||
                            op_type == NITI_OP_DSP_RELUGRAD_INT8 || op_type == NITI_OP_DSP_NOP_INT8 ||
                            op_type == NITI_OP_LOSS_GRAD_INT8 || op_type == NITI_OP_DSP_LOSSGRAD_INT8 ||
+                           op_type == NITI_OP_LOSS_INT8 ||
                            op_type == NITI_OP_DSP_TRANSPOSE_INT8 || op_type == NITI_OP_DSP_WEIGHTROTATE180_INT8 ||
                            op_type == NITI_OP_DSP_RESHAPE_INT8 || op_type == NITI_OP_DSP_RESHAPEGRAD_INT8;
     if (!no_params && c == nullptr) {
@@ -1333,6 +1383,7 @@ Execution* create_execution(int op_type, const niti_conv2d_common* c, int* err) 
         case NITI_OP_DSP_PARALLEL_GRADIENTCONV_INT8: return new DspMatmulGradientExecution(cc, true);
         case NITI_OP_LOSS_GRAD_INT8:
         case NITI_OP_DSP_LOSSGRAD_INT8: return new LossGradExecution();
+        case NITI_OP_LOSS_INT8: return new LossExecution();
         case NITI_OP_DSP_TRANSPOSE_INT8:
         case NITI_OP_DSP_WEIGHTROTATE180_INT8:
         case NITI_OP_DSP_LEFTPOOLGRAD_DECONV_INT8:

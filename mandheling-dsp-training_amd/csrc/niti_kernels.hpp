@@ -560,6 +560,16 @@ hipError_t maxpool_relu_grad_arg(const int8_t* x, const int8_t* arg, const int8_
 // one block per sample above).  NITI_CPULossGrad_Int8.cpp:81-200.
 hipError_t loss_grad(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
                      const int32_t* labels, int8_t* out, hipStream_t st);
+// Evaluation metrics of a batch of logits (niti_metrics.hip): pred int32 [batch] (may be null) the
+// first index of each row's maximum, loss_per_image double [batch] (may be null) the cross entropy
+// against labels[i] (0 for an excluded image), and the batch's counts and loss sum added to *totals
+// (device) in stream order.  labels[i] outside [0, classes) excludes image i from the totals.
+// classes <= 2048, 1 <= topk <= classes; workspace of head_metrics_workspace(batch) bytes, 8-byte
+// aligned.  Two launches, no atomics: loss_sum is bit-identical from run to run.
+size_t head_metrics_workspace(int batch);
+hipError_t head_metrics(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
+                        const int32_t* labels, int topk, int32_t* pred, double* loss_per_image,
+                        niti_eval_totals* totals, void* workspace, size_t workspace_bytes, hipStream_t st);
 
 // ---- input quantiser (MnistUtils.cpp:83-93; niti_quant.hip states the exact contract) -------
 // stats (4 x u64, device) = {S1 = sum x, S2 = sum x^2, xmax, 255 - xmin} of n uint8 pixels

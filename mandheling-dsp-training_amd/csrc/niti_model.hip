@@ -581,6 +581,20 @@ struct Model {
     // input quantiser (MnistUtils.cpp:83-93)
     int run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
     int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    // the step's forward half: input (quantiser), every layer's forward -- all but the head's when
+    // the head chain launch of run() does it (skip_head)
+    int forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool skip_head, hipStream_t st);
+    int backward(bool head_chain, const int32_t* labels, SgdJob* jobs, hipStream_t st);
+    // evaluation (niti_model_eval_*): forward() and the head metrics of its logits, added to the
+    // running totals; everything it needs is allocated in build()
+    niti_eval_totals* ev_totals = nullptr;
+    int32_t* ev_pred = nullptr;  // the last evaluation batch's predictions
+    void* ev_ws = nullptr;
+    size_t ev_ws_bytes = 0;
+    int ev_topk = 5;
+    bool eval_pass = false;  // forward() fills by kernel instead of hipMemsetAsync (niti_map.hpp: fill_kernel)
+    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    int copy_weights_from(Model& src, hipStream_t st);
     ~Model() {
         clear_probe();
         drop_graph();
@@ -811,6 +825,13 @@ int Model::build(int arch_, int batch_, int in_hw) {
     if (gspec_alt_bytes && !(gspec_alt = (int8_t*)ws.alloc(gspec_alt_bytes))) return NITI_OUT_OF_MEMORY;
     amax_bytes = (size_t)3 * nl * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
+    ev_ws_bytes = head_metrics_workspace(n);
+    ev_ws = ws.alloc(ev_ws_bytes);
+    ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
+    ev_pred = (int32_t*)ws.alloc((size_t)n * 4);
+    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
+    if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess || hipMemset(ev_pred, 0, (size_t)n * 4) != hipSuccess)
+        return NITI_NO_EXECUTION;
     if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
     if (hipMemset(x0, 0, (size_t)n * in_h * in_w * round_up(in_c, 16)) != hipSuccess) return NITI_NO_EXECUTION;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
@@ -1431,7 +1452,6 @@ int Model::autotune(hipStream_t st, int reps) {
 }
 
 int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
-    const int n = batch;
     const int nl = (int)L.size();
     const bool dp = this->dp();
     SgdJob jobs[SGD_MAX_JOBS];
@@ -1450,12 +1470,28 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
         const int rc = size_wslabs();  // (plan changes: no allocation or sync inside the step)
         if (rc != NITI_NO_ERROR) return rc;
     }
+    std::fill(dyc32_valid.begin(), dyc32_valid.end(), 0);
+    const bool hc = head_chain_on();  // (then the head's forward runs in the chain launch below)
+    {
+        const int rc = forward(x_nchw, exp_in, images, hc, st);
+        if (rc != NITI_NO_ERROR) return rc;
+    }
+    return backward(hc, labels, jobs, st);
+}
+
+int Model::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool skip_head, hipStream_t st) {
+    const int n = batch;
+    const int nl = (int)L.size();
+    const bool dp = this->dp();
     invalidate_xp16();  // the forward pass rewrites every layer input
     std::fill(xc32_valid.begin(), xc32_valid.end(), 0);
-    std::fill(dyc32_valid.begin(), dyc32_valid.end(), 0);
     // the range words start each step at zero: zeroed by the input statistics launch (uint8
     // images), else here
-    if (x_nchw != nullptr || amax_bytes % 16 != 0) MTRY(hipMemsetAsync(amax, 0, amax_bytes, st));
+    // (by kernel in an evaluation step and inside a graph capture: niti_map.hpp, fill_kernel)
+    auto fill = [&](void* p, int v, size_t bytes) {
+        return eval_pass || capturing ? fill_kernel(p, v, bytes, st) : hipMemsetAsync(p, v, bytes, st);
+    };
+    if (x_nchw != nullptr || amax_bytes % 16 != 0) MTRY(fill(amax, 0, amax_bytes));
     // the first layer's im2col copy straight from the batch where the fused pass takes the layer
     const ConvGeom& o0 = L[0].og;
     const bool fused_in = L[0].col && input_im2col_ok(o0.c_in, o0.kh, o0.kw) && o0.sh == 1 && o0.sw == 1;
@@ -1470,7 +1506,7 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
     }
     conv0_ranged = r0.w != nullptr;
     if (x_nchw != nullptr) {
-        MTRY(hipMemsetAsync(exp0, exp_in, 1, st));
+        MTRY(fill(exp0, exp_in, 1));
         if (fused_in)
             MTRY(input_im2col(x_nchw, false, n, in_c, in_h, in_w, o0.kh, o0.kw, o0.pt, o0.pl, nullptr, 0, 0, x0n,
                               L[0].xcol, nullptr, st, r0));
@@ -1502,11 +1538,18 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
             MTRY(image_quantize(images, n, in_c, in_h * in_w, round_up(in_c, 16), qstats, count, x0, exp0, true, st));
     }
     if (L[0].col && !fused_in) MTRY(im2col32(L[0].og, x0, L[0].xcol, st));
-    const bool hc = head_chain_on();  // (then the head's forward runs in the chain launch below)
-    for (int i = 0; i < nl - (hc ? 1 : 0); ++i) {
+    for (int i = 0; i < nl - (skip_head ? 1 : 0); ++i) {
         const int rc = fwd_layer(i, st);
         if (rc != NITI_NO_ERROR) return rc;
     }
+    return NITI_NO_ERROR;
+}
+
+// the step's backward half: loss gradient (or the head chain), weight and input gradients, NITI_SGD
+int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st) {
+    const int n = batch;
+    const int nl = (int)L.size();
+    const bool dp = this->dp();
     // weight gradients on the side stream (not inside a graph capture)
     const bool ov = overlap && !capturing && !(dp && shared_comm);  // one communicator: one stream
     bool p16_done = false;
@@ -1631,6 +1674,52 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
         if (L[i].fc_sgd) MTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st));
     g8_written = keep_grads;
     return NITI_NO_ERROR;
+}
+
+// Forward-only step: the training step's forward half (the head through fwd_layer, whatever the
+// head chain setting) as direct launches on `st` -- the training graph is neither dropped nor
+// replayed -- then the head metrics of the logits into the running totals.  Writes the forward's
+// buffers and validity flags only: no weight, derived copy, gradient or SGD state.  The armed
+// kernel probe does not time evaluation launches.
+int Model::eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
+    const bool paused = probe_paused;
+    probe_paused = true;
+    eval_pass = true;
+    const int rc = forward(x_nchw, exp_in, images, false, st);
+    eval_pass = false;
+    probe_paused = paused;
+    if (rc != NITI_NO_ERROR) return rc;
+    const Layer& t = L.back();
+    MTRY(head_metrics(t.r, batch, t.g.c_out, t.g.cop, t.exp, labels, std::min(ev_topk, t.g.c_out), ev_pred, nullptr,
+                      ev_totals, ev_ws, ev_ws_bytes, st));
+    return NITI_NO_ERROR;
+}
+
+// Every layer's weights and weight scale from `src` (same architecture and input size, any batch),
+// device to device on `st`, then this model's derived copies (IHWO16, fragment-major) from them.
+int Model::copy_weights_from(Model& src, hipStream_t st) {
+    if (src.arch != arch || src.in_h != in_h || src.in_w != in_w || src.in_c != in_c || src.L.size() != L.size())
+        return NITI_INVALID_VALUE;
+    for (size_t i = 0; i < L.size(); ++i) {
+        const ConvGeom &a = L[i].g, &b = src.L[i].g;
+        if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
+            L[i].col != src.L[i].col)
+            return NITI_INVALID_VALUE;
+    }
+    if (&src == this) return NITI_NO_ERROR;
+    for (size_t i = 0; i < L.size(); ++i) {
+        Layer& l = L[i];
+        const Layer& s = src.L[i];
+        const ConvGeom& g = l.g;
+        MTRY(copy_kernel(l.w, s.w, (size_t)l.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
+        MTRY(copy_kernel(l.ws_dev, s.ws_dev, 1, st));
+        l.wscale = s.wscale;
+        if (!l.rcd)  // (refresh_wt below rebuilds the row-kernel layers')
+            MTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
+    }
+    int rc = refresh_wt(st);
+    if (rc == NITI_NO_ERROR) rc = refresh_wf(st);
+    return rc;
 }
 
 }  // namespace niti
@@ -1759,6 +1848,56 @@ int niti_model_train_step_images(niti_model_t m, const uint8_t* images_nchw, con
     if (m && m->r) return images_nchw && labels ? m->r->step(nullptr, 0, images_nchw, labels, (hipStream_t)stream) : NITI_INVALID_VALUE;
     if (!m || !images_nchw || !labels) return NITI_INVALID_VALUE;
     return m->m.step(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
+}
+
+int niti_model_eval_step(niti_model_t m, const int8_t* x_nchw, int exp_in, const int32_t* labels, void* stream) {
+    if (!m || !x_nchw || !labels) return NITI_INVALID_VALUE;
+    if (m->r) return m->r->eval(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream);
+    return m->m.eval(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream);
+}
+
+int niti_model_eval_step_images(niti_model_t m, const uint8_t* images_nchw, const int32_t* labels, void* stream) {
+    if (!m || !images_nchw || !labels) return NITI_INVALID_VALUE;
+    if (m->r) return m->r->eval(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
+    return m->m.eval(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
+}
+
+int niti_model_eval_reset(niti_model_t m, void* stream) {
+    if (!m) return NITI_INVALID_VALUE;
+    niti_eval_totals* t = m->r ? m->r->ev_totals : m->m.ev_totals;
+    return niti::fill_kernel(t, 0, sizeof(niti_eval_totals), (hipStream_t)stream) == hipSuccess ? NITI_NO_ERROR
+                                                                                                : NITI_NO_EXECUTION;
+}
+
+int niti_model_eval_read(niti_model_t m, niti_eval_totals* host_out, void* stream) {
+    if (!m || !host_out) return NITI_INVALID_VALUE;
+    const niti_eval_totals* t = m->r ? m->r->ev_totals : m->m.ev_totals;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
+        hipMemcpy(host_out, t, sizeof(niti_eval_totals), hipMemcpyDeviceToHost) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    return NITI_NO_ERROR;
+}
+
+int niti_model_eval_topk(niti_model_t m, int k) {
+    if (!m || k < 1) return NITI_INVALID_VALUE;
+    (m->r ? m->r->ev_topk : m->m.ev_topk) = k;  // (clamped to the class count at each step)
+    return NITI_NO_ERROR;
+}
+
+int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream) {
+    if (!m || !pred_host) return NITI_INVALID_VALUE;
+    const int32_t* p = m->r ? m->r->ev_pred : m->m.ev_pred;
+    const int n = m->r ? m->r->batch : m->m.batch;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
+        hipMemcpy(pred_host, p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    return NITI_NO_ERROR;
+}
+
+int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream) {
+    if (!dst || !src || (dst->r != nullptr) != (src->r != nullptr)) return NITI_INVALID_VALUE;
+    if (dst->r) return dst->r->copy_weights_from(*src->r, (hipStream_t)stream);
+    return dst->m.copy_weights_from(src->m, (hipStream_t)stream);
 }
 
 int niti_model_get_input(niti_model_t m, int8_t* x_nchw_host, int* ascale, void* stream) {

@@ -24,6 +24,7 @@
 #include <set>
 
 #include "../../include/niti_hip.h"
+#include "niti_map.hpp"
 #include "niti_resnet_model.hpp"
 
 namespace niti {
@@ -251,6 +252,14 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     amax_bytes = (3 * C.size() + 2 * B.size() + 1) * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (!amax) return NITI_OUT_OF_MEMORY;
+    ev_ws_bytes = head_metrics_workspace(batch);
+    ev_ws = ws.alloc(ev_ws_bytes);
+    ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
+    ev_pred = (int32_t*)ws.alloc((size_t)batch * 4);
+    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
+    if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess ||
+        hipMemset(ev_pred, 0, (size_t)batch * 4) != hipSuccess)
+        return NITI_NO_EXECUTION;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
 
@@ -630,58 +639,12 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         const int rc = size_wslabs();  // (plan changes: no allocation or sync inside the step)
         if (rc != NITI_NO_ERROR) return rc;
     }
-    // the range words start each step at zero: zeroed by the input statistics launch (uint8
-    // images), else here
-    if (images == nullptr || amax_bytes % 16 != 0) RTRY(hipMemsetAsync(amax, 0, amax_bytes, st));
-    // input: NITIInt8Train's quantiser (MnistUtils.cpp:83-93) on uint8 images, or int8 x as given
-    const int64_t px = (int64_t)n * 3 * in_hw * in_hw;
-    const int8_t* xq = x_nchw;
-    if (images != nullptr) {
-        int ns = 0;
-        RTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
-                               amax_bytes % 16 == 0 ? amax_bytes : 0));
-        RTRY(stats_finalize(qslots, ns, qstats, st));
-        if (dp && exact) {
-            RTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
-            RTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
-        }
-        RTRY(image_quantize(images, n, 3, in_hw * in_hw, 3, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
-        xq = x0n;
-    } else {
-        RTRY(hipMemsetAsync(exp0, exp_in, 1, st));
-        RTRY(hipMemcpyAsync(x0n, x_nchw, (size_t)px, hipMemcpyDeviceToDevice, st));
-    }
-    RTRY(im2col_small(stem, xq, STEM_KP, xcol, st, true));
-    // forward
-    int rc = fwd_conv(0, st);
+    int rc = forward(x_nchw, exp_in, images, st);
     if (rc != NITI_NO_ERROR) return rc;
+    // the loss gradient, then the backward pass
     const int ph = C[B[0].a].g.h;  // the stem's pooled size
-    if (!stem_pooled)  // (else fused into the stem's requantise pass)
-        RTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, 64, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
-    for (int k = 0; k < (int)B.size(); ++k) {
-        const RBlock& b = B[k];
-        if ((rc = fwd_conv(b.a, st)) != NITI_NO_ERROR) return rc;
-        if ((rc = fwd_conv(b.b, st)) != NITI_NO_ERROR) return rc;
-        if (b.p >= 0 && (rc = fwd_conv(b.p, st)) != NITI_NO_ERROR) return rc;
-        if ((rc = residual_fwd(k, st)) != NITI_NO_ERROR) return rc;
-    }
-    // global sum pool + requantisation, the fc head, the loss gradient
     const RBlock& bl = B.back();
     const ConvGeom& gl = C[bl.b].g;
-    RTRY(sum_pool(bl.out, n, gl.oh * gl.ow, gl.cop, gsum, rng_pool(), st));
-    if (dp && exact) RTRY(coll->allreduce(rng_pool(), MAX_WORDS, COLL_MAX_U32, st));
-    {
-        ActRequant r;
-        r.acc = gsum;
-        r.rows = n;
-        r.ldc = 512;
-        r.amax = rng_pool();
-        r.exp_in = bl.out_exp;
-        r.exp_out = eg;
-        r.out_nhwc16 = g8pool;
-        RTRY(requant_act(r, st));
-    }
-    if ((rc = fwd_conv(fc, st)) != NITI_NO_ERROR) return rc;
     RConv& f = C[fc];
     RTRY(loss_grad(f.y, n, classes, f.g.cop, f.y_exp, labels, f.dy, st));
     // backward: weight gradients in descending layer order (gradient buckets close in memory order)
@@ -745,6 +708,112 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     }
     RTRY(sgd_update_many(jobs, nl, st));
     g8_written = keep_grads;
+    return NITI_NO_ERROR;
+}
+
+int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, hipStream_t st) {
+    const int n = batch;
+    const int fc = (int)C.size() - 1;
+    const bool dp = this->dp();
+    // the range words start each step at zero: zeroed by the input statistics launch (uint8
+    // images), else here
+    // (by kernel in an evaluation step and inside a graph capture: niti_map.hpp, fill_kernel)
+    const bool by_kernel = eval_pass || capturing;
+    auto fill = [&](void* p, int v, size_t bytes) {
+        return by_kernel ? fill_kernel(p, v, bytes, st) : hipMemsetAsync(p, v, bytes, st);
+    };
+    if (images == nullptr || amax_bytes % 16 != 0) RTRY(fill(amax, 0, amax_bytes));
+    // input: NITIInt8Train's quantiser (MnistUtils.cpp:83-93) on uint8 images, or int8 x as given
+    const int64_t px = (int64_t)n * 3 * in_hw * in_hw;
+    const int8_t* xq = x_nchw;
+    if (images != nullptr) {
+        int ns = 0;
+        RTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
+                               amax_bytes % 16 == 0 ? amax_bytes : 0));
+        RTRY(stats_finalize(qslots, ns, qstats, st));
+        if (dp && exact) {
+            RTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
+            RTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
+        }
+        RTRY(image_quantize(images, n, 3, in_hw * in_hw, 3, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
+        xq = x0n;
+    } else {
+        RTRY(fill(exp0, exp_in, 1));
+        RTRY(by_kernel ? copy_kernel(x0n, x_nchw, (size_t)px, st)
+                       : hipMemcpyAsync(x0n, x_nchw, (size_t)px, hipMemcpyDeviceToDevice, st));
+    }
+    RTRY(im2col_small(stem, xq, STEM_KP, xcol, st, true));
+    // forward
+    int rc = fwd_conv(0, st);
+    if (rc != NITI_NO_ERROR) return rc;
+    const int ph = C[B[0].a].g.h;  // the stem's pooled size
+    if (!stem_pooled)  // (else fused into the stem's requantise pass)
+        RTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, 64, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
+    for (int k = 0; k < (int)B.size(); ++k) {
+        const RBlock& b = B[k];
+        if ((rc = fwd_conv(b.a, st)) != NITI_NO_ERROR) return rc;
+        if ((rc = fwd_conv(b.b, st)) != NITI_NO_ERROR) return rc;
+        if (b.p >= 0 && (rc = fwd_conv(b.p, st)) != NITI_NO_ERROR) return rc;
+        if ((rc = residual_fwd(k, st)) != NITI_NO_ERROR) return rc;
+    }
+    // global sum pool + requantisation, the fc head
+    const RBlock& bl = B.back();
+    const ConvGeom& gl = C[bl.b].g;
+    RTRY(sum_pool(bl.out, n, gl.oh * gl.ow, gl.cop, gsum, rng_pool(), st));
+    if (dp && exact) RTRY(coll->allreduce(rng_pool(), MAX_WORDS, COLL_MAX_U32, st));
+    {
+        ActRequant r;
+        r.acc = gsum;
+        r.rows = n;
+        r.ldc = 512;
+        r.amax = rng_pool();
+        r.exp_in = bl.out_exp;
+        r.exp_out = eg;
+        r.out_nhwc16 = g8pool;
+        RTRY(requant_act(r, st));
+    }
+    return fwd_conv(fc, st);
+}
+
+// Forward-only step: the training step's forward half as direct launches on `st` (the training
+// graph is neither dropped nor replayed), then the head metrics of the logits into the running
+// totals.  No weight, derived copy, gradient or SGD state is written.  The armed kernel probe does
+// not time evaluation launches.
+int ResNetModel::eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) return NITI_NO_EXECUTION;
+    const bool cap = cs == hipStreamCaptureStatusActive;  // the caller captures it: no fused grid barrier
+    if (cap && coll != nullptr) return NITI_NOT_SUPPORT;
+    const bool paused = probe_paused;
+    probe_paused = true;
+    capturing = cap;
+    eval_pass = true;
+    const int rc = forward(x_nchw, exp_in, images, st);
+    eval_pass = false;
+    capturing = false;
+    probe_paused = paused;
+    if (rc != NITI_NO_ERROR) return rc;
+    const RConv& f = C.back();
+    RTRY(head_metrics(f.y, batch, classes, f.g.cop, f.y_exp, labels, std::min(ev_topk, classes), ev_pred, nullptr,
+                      ev_totals, ev_ws, ev_ws_bytes, st));
+    return NITI_NO_ERROR;
+}
+
+// Every conv's weights and weight scale from `src` (same input size and class count, any batch),
+// device to device on `st`, then this model's derived copies from them.
+int ResNetModel::copy_weights_from(ResNetModel& src, hipStream_t st) {
+    if (src.in_hw != in_hw || src.classes != classes || src.C.size() != C.size()) return NITI_INVALID_VALUE;
+    for (size_t i = 0; i < C.size(); ++i)
+        if (C[i].w_elems() != src.C[i].w_elems()) return NITI_INVALID_VALUE;
+    if (&src == this) return NITI_NO_ERROR;
+    for (size_t i = 0; i < C.size(); ++i) {
+        RConv& c = C[i];
+        RTRY(copy_kernel(c.w, src.C[i].w, (size_t)c.w_elems(), st));
+        RTRY(copy_kernel(c.ws_dev, src.C[i].ws_dev, 1, st));
+        c.wscale = src.C[i].wscale;
+        const int rc = refresh_copies((int)i, st);
+        if (rc != NITI_NO_ERROR) return rc;
+    }
     return NITI_NO_ERROR;
 }
 

@@ -183,6 +183,18 @@ struct ResNetModel {
     int residual_bwd(int k, hipStream_t st);
     int run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
     int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    // the step's forward half (input, every conv and residual sum, the pool, the fc head)
+    int forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, hipStream_t st);
+    // evaluation (niti_model_eval_*): forward() and the head metrics of its logits, added to the
+    // running totals; everything it needs is allocated in build()
+    niti_eval_totals* ev_totals = nullptr;
+    int32_t* ev_pred = nullptr;  // the last evaluation batch's predictions
+    void* ev_ws = nullptr;
+    size_t ev_ws_bytes = 0;
+    int ev_topk = 5;
+    bool eval_pass = false;  // forward() fills / copies by kernel (niti_map.hpp: fill_kernel)
+    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    int copy_weights_from(ResNetModel& src, hipStream_t st);
     int autotune(hipStream_t st, int reps);
     int run_phase(int layer, int phase, hipStream_t st);
     int sum_bucket(int lo, hipStream_t st);

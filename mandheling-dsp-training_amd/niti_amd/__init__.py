@@ -7,6 +7,6 @@ from ._lib import (ARCH_LENET, ARCH_RESNET18, ARCH_VGG11, ARCH_VGG16, FORMAT_NC4
                    OP_CONV_INT8, OP_DECONV_INT8, OP_DSP_CONV_INT8, OP_DSP_DECONV_INT8,
                    OP_DSP_GRADIENT_SPLITBATCHCONV_INT8, OP_DSP_MATMUL_GRADIENT_INT8, OP_DSP_PARALLEL_GRADIENTCONV_INT8,
                    OP_DSP_TRANSPOSEGRADIENT_CONV_INT8, OP_GRADIENT_CONV_INT8,
-                   OP_MATMUL_INT8, PAD_CAFFE, PAD_SAME, PAD_VALID, NitiError, check, header_functions, lib)
+                   OP_LOSS_GRAD_INT8, OP_LOSS_INT8, OP_MATMUL_INT8, PAD_CAFFE, PAD_SAME, PAD_VALID, NitiError, check, header_functions, lib)
 
 lib()  # fail loudly if the HIP library is missing

@@ -23,6 +23,7 @@ OP_RELU_INT8 = 703
 OP_RELUGRAD_INT8 = 704
 OP_MAXPOOL_INT8 = 705
 OP_POOLGRAD_INT8 = 706
+OP_LOSS_INT8 = 710
 OP_LOSS_GRAD_INT8 = 711
 OP_MATMUL_INT8 = 713
 OP_PAD_INT8 = 714
@@ -72,6 +73,11 @@ class Geom(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "n", "c_in", "h", "w", "c_out", "kh", "kw", "stride_h", "stride_w", "pad_t", "pad_l", "pad_b",
         "pad_r", "dilate_h", "dilate_w", "oh", "ow", "cip", "cop", "np")]
+
+
+class EvalTotals(C.Structure):
+    """niti_eval_totals: the running totals of an evaluation pass."""
+    _fields_ = [("images", C.c_uint64), ("top1", C.c_uint64), ("topk", C.c_uint64), ("loss_sum", C.c_double)]
 
 
 class RequantFused(C.Structure):
@@ -176,6 +182,15 @@ def lib():
         "niti_maxpool_grad_arg": (ci, [vp, vp, vp] + [ci] * 10 + [vp, vp, vp]),
         "niti_relu_grad": (ci, [vp, vp, i64, vp, vp]),
         "niti_loss_grad": (ci, [vp, ci, ci, ci, vp, vp, vp, vp]),
+        "niti_head_metrics": (ci, [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, C.c_size_t, vp]),
+        "niti_head_metrics_workspace": (ci, [ci, C.POINTER(C.c_size_t)]),
+        "niti_model_eval_step": (ci, [vp, vp, ci, vp, vp]),
+        "niti_model_eval_step_images": (ci, [vp, vp, vp, vp]),
+        "niti_model_eval_reset": (ci, [vp, vp]),
+        "niti_model_eval_read": (ci, [vp, C.POINTER(EvalTotals), vp]),
+        "niti_model_eval_topk": (ci, [vp, ci]),
+        "niti_model_get_predictions": (ci, [vp, vp, vp]),
+        "niti_model_copy_weights": (ci, [vp, vp, vp]),
         "niti_model_create": (ci, [ci, ci, C.POINTER(vp)]),
         "niti_model_create2": (ci, [ci, ci, ci, C.POINTER(vp)]),
         "niti_model_create3": (ci, [ci, ci, ci, ci, C.POINTER(vp)]),

@@ -116,6 +116,73 @@ class NitiModel:
                                                      C.c_void_p(labels.data_ptr()), _stream(stream)),
               "train_step_images")
 
+    def eval_step(self, x: torch.Tensor, exp_in: int, labels: torch.Tensor, stream=None):
+        """Forward only (no weight is written): the logits of x on the current weights, their
+        argmax / top-k / loss against labels added to the running totals.  labels[i] = -1 excludes
+        image i.  Asynchronous."""
+        assert x.dtype == torch.int8 and x.is_contiguous() and labels.dtype == torch.int32
+        check(self._lib.niti_model_eval_step(self._h, C.c_void_p(x.data_ptr()), int(exp_in),
+                                             C.c_void_p(labels.data_ptr()), _stream(stream)), "eval_step")
+
+    def eval_step_images(self, images: torch.Tensor, labels: torch.Tensor, stream=None):
+        """eval_step from uint8 images [batch][C][H][W], quantised on device with the batch's own
+        statistics (the reference's test loop, MnistUtils.cpp:161-172)."""
+        assert images.dtype == torch.uint8 and images.is_contiguous() and labels.dtype == torch.int32
+        check(self._lib.niti_model_eval_step_images(self._h, C.c_void_p(images.data_ptr()),
+                                                    C.c_void_p(labels.data_ptr()), _stream(stream)),
+              "eval_step_images")
+
+    def eval_reset(self, stream=None):
+        """Zero the running totals (asynchronous)."""
+        check(self._lib.niti_model_eval_reset(self._h, _stream(stream)), "eval_reset")
+
+    def eval_read(self, stream=None) -> dict:
+        """The running totals (synchronises): images, top1, topk, loss_sum, and loss = loss_sum /
+        images, accuracy = top1 / images (nan before any image was counted)."""
+        t = L.EvalTotals()
+        check(self._lib.niti_model_eval_read(self._h, C.byref(t), _stream(stream)), "eval_read")
+        n = int(t.images)
+        return {"images": n, "top1": int(t.top1), "topk": int(t.topk), "loss_sum": float(t.loss_sum),
+                "loss": float(t.loss_sum) / n if n else float("nan"),
+                "accuracy": int(t.top1) / n if n else float("nan")}
+
+    def eval_topk(self, k: int):
+        """The k of the totals' topk count for later evaluation steps (default 5, clamped to the
+        class count)."""
+        check(self._lib.niti_model_eval_topk(self._h, int(k)), "eval_topk")
+
+    def predictions(self, stream=None) -> np.ndarray:
+        """int32 [batch]: the first-maximum class of each image of the last evaluation batch."""
+        out = np.empty(self.batch, np.int32)
+        check(self._lib.niti_model_get_predictions(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
+              "get_predictions")
+        return out
+
+    def copy_weights_from(self, other: "NitiModel", stream=None):
+        """Device-to-device copy of every layer's weights and weight scale from a model of the same
+        architecture, input size and class count (the batch may differ)."""
+        check(self._lib.niti_model_copy_weights(self._h, other._h, _stream(stream)), "copy_weights")
+        self._wscale = dict(other._wscale)
+
+    def evaluate(self, images, labels, stream=None) -> dict:
+        """Evaluate a whole set of uint8 images [N][C][H][W] with int labels [N] (numpy arrays or
+        tensors): resets the totals, runs eval_step_images batch by batch -- the last partial batch
+        padded with zero images and label -1 -- and synchronises once, in eval_read."""
+        img = torch.as_tensor(images)
+        lab = torch.as_tensor(labels).to(torch.int32)
+        assert img.dtype == torch.uint8 and img.shape[0] == lab.shape[0]
+        n, b = int(img.shape[0]), self.batch
+        pad = (-n) % b
+        if pad:
+            img = torch.cat([img, torch.zeros((pad,) + tuple(img.shape[1:]), dtype=torch.uint8, device=img.device)])
+            lab = torch.cat([lab, torch.full((pad,), -1, dtype=torch.int32, device=lab.device)])
+        img = img.cuda().contiguous()
+        lab = lab.cuda().contiguous()
+        self.eval_reset(stream)
+        for i in range(0, n + pad, b):
+            self.eval_step_images(img[i:i + b], lab[i:i + b], stream)
+        return self.eval_read(stream)
+
     def input(self, stream=None):
         """The last step's quantised input x (NCHW int8) and its exponent."""
         l0 = self.layers[0]

@@ -616,6 +616,36 @@ def loss_grad(logits, classes, ascale_dev, labels, stream=None):
     return out
 
 
+def new_eval_totals(device="cuda"):
+    """A zeroed niti_eval_totals {images, top1, topk (uint64), loss_sum (double)} as 4 int64 words."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def read_eval_totals(totals) -> dict:
+    """The totals as a dict (synchronises): images, top1, topk, loss_sum."""
+    a = totals.cpu()
+    return {"images": int(a[0]), "top1": int(a[1]), "topk": int(a[2]), "loss_sum": float(a[3:4].view(torch.float64)[0])}
+
+
+def head_metrics(logits, classes, ascale_dev, labels, topk=1, totals=None, stream=None):
+    """niti_head_metrics on logits int8 [batch][ld] (the first `classes` lanes are classes): returns
+    (pred int32 [batch], loss_per_image float64 [batch], totals); the batch's counts and loss sum are
+    added to `totals` (new_eval_totals(); a fresh one when None).  labels int32 [batch], -1 excludes
+    an image."""
+    b, ld = logits.shape
+    if totals is None:
+        totals = new_eval_totals(logits.device)
+    pred = torch.empty(b, dtype=torch.int32, device=logits.device)
+    loss = torch.empty(b, dtype=torch.float64, device=logits.device)
+    nbytes = C.c_size_t()
+    check(L.lib().niti_head_metrics_workspace(b, C.byref(nbytes)), "head_metrics_workspace")
+    ws = torch.empty(nbytes.value // 8 + 1, dtype=torch.int64, device=logits.device)
+    check(L.lib().niti_head_metrics(_ptr(logits), b, int(classes), ld, _ptr(ascale_dev), _ptr(labels), int(topk),
+                                    _ptr(pred), _ptr(loss), _ptr(totals), _ptr(ws), ws.numel() * 8, _stream(stream)),
+          "head_metrics")
+    return pred, loss, totals
+
+
 def image_stats(images: torch.Tensor, stream=None):
     """{sum p, sum p^2, max p, 255 - min p} (int64 device [4], u64 values) of a uint8 image batch
     (the input quantiser's statistics, MnistUtils.cpp:83-93; SUM / MAX over DP ranks)."""
