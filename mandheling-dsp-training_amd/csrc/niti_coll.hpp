@@ -1,5 +1,5 @@
-// niti_coll.hpp -- the data-parallel transports shared by the step drivers (niti_model.hip: LeNet /
-// VGG, niti_resnet_model.hip: ResNet-18).
+// niti_coll.hpp -- the data-parallel transports of the step drivers (their base, niti_step_driver.hpp;
+// niti_model.hip: LeNet / VGG, niti_resnet_model.hip: ResNet-18).
 #pragma once
 
 #include <rccl/rccl.h>

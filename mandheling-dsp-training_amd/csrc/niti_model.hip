@@ -12,22 +12,18 @@
 // MAX), every forward / input-gradient range with MAX and every int32 weight-gradient
 // accumulator with SUM before it is requantised, so N ranks of batch b reproduce one device of
 // batch N*b bit for bit.
-#include <rccl/rccl.h>
+// What this driver shares with the ResNet-18 one (niti_resnet_model.hip) is its base, StepDriver
+// (niti_step_driver.hpp); the C ABI over both is niti_model_capi.hip.
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
 #include <vector>
 
 #include "../../include/niti_hip.h"
-#include "niti_internal.hpp"
-#include "niti_kernels.hpp"
-#include "niti_coll.hpp"
 #include "niti_map.hpp"
-#include "niti_resnet_model.hpp"
+#include "niti_step_driver.hpp"
 
 namespace niti {
 
@@ -190,17 +186,12 @@ struct Layer {
     int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * og.c_in * og.kh * og.kw; }
 };
 
-struct Model {
-    int arch = 0, batch = 0, in_c = 0, in_h = 0, in_w = 0, classes = 10;
+struct Model final : StepDriver {
+    int arch = 0, in_c = 0, in_h = 0, in_w = 0, classes = 10;
     std::vector<Layer> L;
-    Workspace ws;
     int8_t* x0 = nullptr;   // NHWC16 input
     int8_t* exp0 = nullptr; // input exponent
     int32_t* acc = nullptr; // shared fwd / dgrad accumulator
-    void* slab = nullptr;   // split-K slabs of the forward / input-gradient GEMMs (step stream)
-    size_t slab_bytes = 0;
-    void* slab_w = nullptr; // split-K slabs of the weight-gradient GEMMs (their own stream)
-    size_t slab_w_bytes = 0;
     // P16 copies of the weight-gradient operands (niti_wgrad.hip): one input copy per layer (all
     // converted together when the backward pass starts, off the step stream) and one
     // output-gradient copy per layer, written by the input-gradient requantisation that produces
@@ -214,10 +205,7 @@ struct Model {
     bool fuse_dp16 = true;    // dy's P16 copy written by the requantisation that produces dy
     // register-fed forward (niti_rowconv.hip) for the layers it takes; xc32_valid[i]: L[i].xc32
     // holds L[i].in as it is now (written by the previous layer's epilogue, else converted)
-    bool use_rowconv = true;
     std::vector<char> xc32_valid;
-    uint32_t* rc_err = nullptr;
-    bool in_step = false;  // run(): weight gradients may defer their combine to the update launch
     // a fully connected layer's weight gradient as a range pass plus a recompute that applies
     // NITI_SGD in its epilogue (conv_wgrad_fc_sgd): single device, inside run() (NITI_FC_SGD=0: off)
     bool fc_sgd_layer(int i) const {
@@ -273,8 +261,6 @@ struct Model {
         if (pv.flatten || pv.col || pv.g.cop != L[i].g.cip) return false;
         return pv.pool ? (pv.ph == 1 && pv.pw == 1 && pv.g.oh == 2 && pv.g.ow == 2) : (pv.g.oh == 1 && pv.g.ow == 1);
     }
-    // the int8 weight gradient of the last step kept for niti_model_get (which = 1)
-    bool keep_grads = true;
     bool g8_written = false;  // the last step stored the int8 weight gradients (tap(layer, 1))
     // IHWO16 weights of the layers whose input gradient ran on the row kernel (the SGD kernel
     // skips them there) -- rebuilt when the GEMM input gradient takes over again
@@ -358,52 +344,6 @@ struct Model {
     uint32_t* amax = nullptr;  // 3 ranges per layer (forward, input gradient, weight gradient)
     size_t amax_bytes = 0;
     uint32_t* rng(int layer, int which) { return amax + (size_t)(3 * layer + which) * MAX_WORDS; }
-    // data parallel (see "collectives" above): ranges on the step stream through `coll`,
-    // gradient-bucket SUMs on the comm stream `cst` through `coll_grad`.  Attached at any world
-    // size (a world of 1 runs every collective call site on one GPU).
-    std::unique_ptr<Collective> coll, coll_grad;
-    int world = 1, rank = 0, exact = 1;
-    bool dp() const { return coll != nullptr && coll_grad != nullptr && !tuning; }
-    hipStream_t cst = nullptr;
-    // the gradient SUMs share the range communicator (ncclCommSplit unavailable): they then run on
-    // the weight-gradient stream itself, keeping that one communicator in program order
-    bool shared_comm = false;
-    std::vector<hipEvent_t> ev_bucket;  // per layer: the bucket closed after this layer's weight gradient
-    hipEvent_t ev_grads = nullptr;      // every bucket summed and ranged (the NITI_SGD join)
-    size_t bucket_min_bytes = grad_bucket_bytes();
-    // the bucket a layer's gradient SUM rides in: layers (backward order) accumulate until the
-    // bucket holds bucket_min_bytes; closes_bucket[i] marks the layer whose weight gradient
-    // completes one (its first layer in memory order is bucket_lo[i])
-    std::vector<int> bucket_lo;
-    std::vector<char> closes_bucket;
-    void plan_buckets() {
-        const int nl = (int)L.size();
-        bucket_lo.assign(nl, 0);
-        closes_bucket.assign(nl, 0);
-        size_t acc = 0;
-        int hi = nl - 1;
-        for (int i = nl - 1; i >= 0; --i) {
-            acc += (size_t)L[i].w_elems() * 4;
-            if (acc >= bucket_min_bytes || i == 0) {
-                closes_bucket[i] = 1;
-                for (int j = i; j <= hi; ++j) bucket_lo[j] = i;
-                acc = 0;
-                hi = i - 1;
-            }
-        }
-    }
-    int ensure_comm_stream() {
-        if (cst) return NITI_NO_ERROR;
-        if (hipStreamCreateWithFlags(&cst, hipStreamNonBlocking) != hipSuccess) return NITI_NO_EXECUTION;
-        constexpr unsigned kFlags = hipEventDisableTiming | hipEventReleaseToDevice;
-        ev_bucket.assign(L.size(), nullptr);
-        for (auto& e : ev_bucket)
-            if (hipEventCreateWithFlags(&e, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
-        if (hipEventCreateWithFlags(&ev_grads, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
-        plan_buckets();
-        return NITI_NO_ERROR;
-    }
-    int sum_bucket(int hi_layer, hipStream_t wst);
     // input quantiser statistics {S1, S2, xmax, 255 - xmin} (niti_quant.hip)
     unsigned long long* qstats = nullptr;
     unsigned long long* qslots = nullptr;  // per-block partial statistics (IMAGE_STATS_SLOTS x 4)
@@ -415,9 +355,6 @@ struct Model {
     // inputs (input / label pointers, input exponent, probe target) change.  Off by default:
     // on ROCm 7.2 the replayed step measured 0.97 ms against 0.84 ms for direct launches (each
     // graph kernel node ran slower, e.g. the probed GEMM + reduce 43 us vs 33 us).
-    bool use_graph = false;
-    hipStream_t gstream = nullptr;
-    hipEvent_t gin = nullptr, gout = nullptr;
     std::vector<hipGraphExec_t> segs;
     struct Key {
         const void* x = nullptr;
@@ -427,9 +364,8 @@ struct Model {
             return x == o.x && labels == o.labels && exp_in == o.exp_in && pl == o.pl && pp == o.pp;
         }
     } key;
-    bool capturing = false;
     hipError_t cap_err = hipSuccess;
-    void drop_graph() {
+    void drop_graph() override {
         for (auto e : segs) (void)hipGraphExecDestroy(e);
         segs.clear();
     }
@@ -447,8 +383,6 @@ struct Model {
     }
     // kernel probe: HIP events around one GEMM (layer, phase 0 fwd / 1 dgrad / 2 wgrad); in a
     // graph the probe points are segment boundaries and the events go between the launches
-    int probe_layer = -1, probe_phase = -1, probe_count = 0;
-    std::vector<hipEvent_t> ev0, ev1;
     // kernel-span probe (weight gradient): per launch {min block start, max block end} on the
     // device wall clock, written by the kernel itself (niti_kernels.hpp probe_span_arm)
     unsigned long long* span = nullptr;
@@ -486,21 +420,16 @@ struct Model {
             return nullptr;
         return ev1[probe_count++];
     }
-    void clear_probe() {
-        for (auto e : ev0) (void)hipEventDestroy(e);
-        for (auto e : ev1) (void)hipEventDestroy(e);
-        ev0.clear();
-        ev1.clear();
-        probe_count = 0;
-        probe_layer = probe_phase = -1;
+    void clear_probe() override {
+        StepDriver::clear_probe();
         if (span) (void)hipFree(span);
         span = nullptr;
         span_cap = span_count = 0;
     }
+    int probe_alloc(int phase, int max_launches) override;
+    int probe_read_span(double* total_ms, int* count) override;
 
     int build(int arch_, int batch_, int in_hw = 0);
-    bool tuning = false;  // autotune in progress: no collectives, no probe
-    bool probe_paused = false;  // niti_model_probe_pause: the armed probe skips these launches
     int fwd_layer(int i, hipStream_t st);
     int wgrad_layer(int i, hipStream_t st);
     int dgrad_layer(int i, hipStream_t st);
@@ -521,19 +450,7 @@ struct Model {
         static const bool keep = getenv("NITI_DY16") != nullptr && getenv("NITI_DY16")[0] == '1';
         return !keep && i - 1 >= 1 && next != nullptr && p16 != nullptr && wgrad_p16_splits(i - 1) > 0;
     }
-    int autotune(hipStream_t st, int reps);
-    // grow a split-K workspace (the old one stays owned by ws until the model is destroyed)
-    bool ensure_slab(size_t bytes, bool wgrad) {
-        void*& p = wgrad ? slab_w : slab;
-        size_t& have = wgrad ? slab_w_bytes : slab_bytes;
-        if (have >= bytes) return true;
-        if (hipDeviceSynchronize() != hipSuccess) return false;
-        void* s2 = ws.alloc(bytes);
-        if (!s2) return false;
-        p = s2;
-        have = bytes;
-        return true;
-    }
+    int autotune(hipStream_t st, int reps) override;
     size_t ws_bytes_for(int op) const { return op == PLAN_WGRAD ? slab_w_bytes : slab_bytes; }
     // layer i's own slab buffer for a deferred GEMM weight-gradient combine is big enough for the
     // plan it runs with (false: its plan does not split K into C-shaped slabs, or not sized)
@@ -577,39 +494,42 @@ struct Model {
             if (hipEventCreateWithFlags(&e, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
         return NITI_NO_ERROR;
     }
-    // x_nchw int8 with exponent exp_in, or (x_nchw == null) uint8 images through the on-device
-    // input quantiser (MnistUtils.cpp:83-93)
     int run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
-    int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) override;
     // the step's forward half: input (quantiser), every layer's forward -- all but the head's when
     // the head chain launch of run() does it (skip_head)
     int forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool skip_head, hipStream_t st);
     int backward(bool head_chain, const int32_t* labels, SgdJob* jobs, hipStream_t st);
-    // evaluation (niti_model_eval_*): forward() and the head metrics of its logits, added to the
-    // running totals; everything it needs is allocated in build()
-    niti_eval_totals* ev_totals = nullptr;
-    int32_t* ev_pred = nullptr;  // the last evaluation batch's predictions
-    void* ev_ws = nullptr;
-    size_t ev_ws_bytes = 0;
-    int ev_topk = 5;
-    bool eval_pass = false;  // forward() fills by kernel instead of hipMemsetAsync (niti_map.hpp: fill_kernel)
-    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
-    int copy_weights_from(Model& src, hipStream_t st);
-    ~Model() {
+    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) override;
+    int copy_weights_from(StepDriver& src, hipStream_t st) override;
+    int run_phase(int layer, int phase, hipStream_t st) override;
+    int plan_info(int layer, int phase, int info[4]) override;
+    int plan_set(int layer, int phase, const int plan[4]) override;
+    int set_rowconv(bool enable) override;
+    void set_overlap(bool enable) override { overlap = enable; }
+    // host access
+    bool layer_ok(int layer) const { return layer >= 0 && layer < (int)L.size(); }
+    int num_layers() const override { return (int)L.size(); }
+    int layer_info(int layer, int info[12]) const override;
+    int set_weight(int layer, const int8_t* w_oihw_host, int wscale) override;
+    int get_weight(int layer, int8_t* w_oihw_host) override;
+    int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
+    int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
+    int get_input(int8_t* host, int* ascale, hipStream_t st) override;
+    int64_t step_macs() const override;
+    int spec_stats(uint32_t* out, int max_layers) override;
+    int spec_state(int layer, uint32_t** bar) override {
+        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+        *bar = L[layer].bar;
+        return NITI_NO_ERROR;
+    }
+    ~Model() override {  // (the rest, in order, in ~StepDriver)
         clear_probe();
         drop_graph();
         if (cst) (void)hipStreamSynchronize(cst);
-        for (auto e : ev_bucket) (void)hipEventDestroy(e);
-        if (ev_grads) (void)hipEventDestroy(ev_grads);
-        if (gin) (void)hipEventDestroy(gin);
-        if (gout) (void)hipEventDestroy(gout);
-        if (gstream) (void)hipStreamDestroy(gstream);
         for (auto e : ev_dy) (void)hipEventDestroy(e);
         if (ev_side) (void)hipEventDestroy(ev_side);
         if (side) (void)hipStreamDestroy(side);
-        coll_grad.reset();
-        coll.reset();
-        if (cst) (void)hipStreamDestroy(cst);
     }
 };
 
@@ -825,26 +745,12 @@ int Model::build(int arch_, int batch_, int in_hw) {
     if (gspec_alt_bytes && !(gspec_alt = (int8_t*)ws.alloc(gspec_alt_bytes))) return NITI_OUT_OF_MEMORY;
     amax_bytes = (size_t)3 * nl * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
-    ev_ws_bytes = head_metrics_workspace(n);
-    ev_ws = ws.alloc(ev_ws_bytes);
-    ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
-    ev_pred = (int32_t*)ws.alloc((size_t)n * 4);
-    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
-    if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess || hipMemset(ev_pred, 0, (size_t)n * 4) != hipSuccess)
-        return NITI_NO_EXECUTION;
+    if (const int rc = alloc_eval()) return rc;
     if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
+    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{L[i].dwacc, L[i].w_elems(), rng(i, 2)});  // (the bucket SUMs)
     if (hipMemset(x0, 0, (size_t)n * in_h * in_w * round_up(in_c, 16)) != hipSuccess) return NITI_NO_EXECUTION;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
-
-#define MTRY(expr)                                             \
-    do {                                                       \
-        if ((expr) != hipSuccess) return NITI_NO_EXECUTION;    \
-    } while (0)
-#define CTRY(expr)                                             \
-    do {                                                       \
-        if ((expr) != hipSuccess) return NITI_NO_EXECUTION;    \
-    } while (0)
 
 int Model::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
     if (!use_graph || coll != nullptr) return run(x_nchw, exp_in, images, labels, st);
@@ -856,12 +762,8 @@ int Model::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const i
     k.pp = probe_phase;
     if (segs.empty() || !(k == key)) {
         drop_graph();
-        if (!gstream) {
-            MTRY(hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking));
-            MTRY(hipEventCreateWithFlags(&gin, hipEventDisableTiming));
-            MTRY(hipEventCreateWithFlags(&gout, hipEventDisableTiming));
-        }
-        MTRY(hipStreamBeginCapture(gstream, hipStreamCaptureModeThreadLocal));
+        if (const int rc = ensure_graph_stream()) return rc;
+        DTRY(hipStreamBeginCapture(gstream, hipStreamCaptureModeThreadLocal));
         capturing = true;
         cap_err = hipSuccess;
         const int rc = run(x_nchw, exp_in, images, labels, gstream);
@@ -880,16 +782,16 @@ int Model::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const i
         }
         key = k;
     }
-    MTRY(hipEventRecord(gin, st));
-    MTRY(hipStreamWaitEvent(gstream, gin, 0));
+    DTRY(hipEventRecord(gin, st));
+    DTRY(hipStreamWaitEvent(gstream, gin, 0));
     const bool probing = segs.size() == 3 && !probe_paused && probe_count < (int)ev0.size();
     for (size_t j = 0; j < segs.size(); ++j) {
-        if (probing && j == 1) MTRY(hipEventRecord(ev0[probe_count], gstream));
-        if (probing && j == 2) MTRY(hipEventRecord(ev1[probe_count++], gstream));
-        MTRY(hipGraphLaunch(segs[j], gstream));
+        if (probing && j == 1) DTRY(hipEventRecord(ev0[probe_count], gstream));
+        if (probing && j == 2) DTRY(hipEventRecord(ev1[probe_count++], gstream));
+        DTRY(hipGraphLaunch(segs[j], gstream));
     }
-    MTRY(hipEventRecord(gout, gstream));
-    MTRY(hipStreamWaitEvent(st, gout, 0));
+    DTRY(hipEventRecord(gout, gstream));
+    DTRY(hipStreamWaitEvent(st, gout, 0));
     return NITI_NO_ERROR;
 }
 
@@ -915,10 +817,10 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.pool.pool_out = l.pool ? l.p : nullptr;
         // the (pooled) output also as the next layer's C32 input when it runs on the row kernel
         const bool next_c32 = i + 1 < (int)L.size() && rowconv_layer(i + 1) && !rowconv_nhwc_pref(L[i + 1].g);
-        if (!conv0_ranged) MTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 0, st));
+        if (!conv0_ranged) DTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 0, st));
         conv0_ranged = false;
-        if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        MTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 1, st, next_c32 && l.pool ? L[i + 1].xc32 : nullptr,
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 1, st, next_c32 && l.pool ? L[i + 1].xc32 : nullptr,
                        next_c32 && !l.pool ? L[i + 1].xc32 : nullptr, code ? l.pc : nullptr));
         if (next_c32) xc32_valid[i + 1] = 1;
         probe(i, 0, false, st);
@@ -934,15 +836,15 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.relu = l.relu;
         const int K = g.c_in, rows = g.c_out;
         if (!dp && !capturing && rowconv_fc_ok(n, K, rows, true)) {
-            MTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
+            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {  // the speculative pair: one GEMM pass while the bit width holds
-            MTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
+            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
         } else {
-            MTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
         }
         probe(i, 0, false, st);
         return NITI_NO_ERROR;
@@ -954,7 +856,7 @@ int Model::fwd_layer(int i, hipStream_t st) {
         // a row-segment layer reads its NHWC16 input in place; the others their C32 copy
         const bool xn = rowconv_nhwc_pref(g);
         if (!xn && !xc32_valid[i]) {
-            MTRY(nhwc16_to_c32(l.in, n, g.h * g.w, g.cip, g.c_in, l.xc32, st));
+            DTRY(nhwc16_to_c32(l.in, n, g.h * g.w, g.cip, g.c_in, l.xc32, st));
             xc32_valid[i] = 1;
         }
         const int8_t* xin = xn ? l.in : l.xc32;
@@ -973,23 +875,23 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.exp_out = l.exp;
         o.relu = l.relu;
         if (!dp && !capturing && rowconv_fused_ok(g)) {
-            MTRY(rowconv_fwd(g, xin, l.wf, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
+            DTRY(rowconv_fwd(g, xin, l.wf, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {  // the speculative pair: one GEMM pass while the bit width holds
             o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;  // its store mode after a change
-            MTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
+            DTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
         } else {
             o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;  // else the requantise launch recomputes
-            MTRY(rowconv_fwd(g, xin, l.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fwd(g, xin, l.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fwd(g, xin, l.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(g, xin, l.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
         }
         if (feeds_next) xc32_valid[i + 1] = 1;
         probe(i, 0, false, st);
         if (l.flatten) {
             const int fc = g.c_out * l.ph * l.pw, ld = round_up(fc, 16);
-            MTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
+            DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
         }
         return NITI_NO_ERROR;
     }
@@ -1012,25 +914,25 @@ int Model::fwd_layer(int i, hipStream_t st) {
         fe = conv_fwd_fused(g, l.in, l.w, o, FusedBar{l.bar, l.epoch + 1, rc_err}, st);
         if (fe != hipErrorNotSupported) {
             ++l.epoch;
-            MTRY(fe);
+            DTRY(fe);
         }
     }
     if (fe != hipErrorNotSupported) {
     } else if (spec) {  // the speculative pair: one GEMM pass while the bit width holds, no int32 tensor
         int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        MTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 0, st, alt));
-        if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        MTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 1, st, alt));
+        DTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 0, st, alt));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 1, st, alt));
     } else {
-        MTRY(conv_fwd_phase1(g, l.in, l.w, acc, rng(i, 0), slab, slab_bytes, st));
-        if (dp && exact) CTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        MTRY(conv_fwd_phase2(g, l.in, l.w, acc, rng(i, 0), o, slab_bytes, st));
+        DTRY(conv_fwd_phase1(g, l.in, l.w, acc, rng(i, 0), slab, slab_bytes, st));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_fwd_phase2(g, l.in, l.w, acc, rng(i, 0), o, slab_bytes, st));
     }
     probe(i, 0, false, st);
-    if (l.pool && !fuse_pool) MTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
+    if (l.pool && !fuse_pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
     if (l.flatten) {
         const int fc = g.c_out * l.ph * l.pw, ld = round_up(fc, 16);
-        MTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
+        DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
     }
     return NITI_NO_ERROR;
 }
@@ -1044,14 +946,14 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     if (head_layer(i) && g.c_out <= 32 && g.cip % 32 == 0) {
         // the classifier head: one small launch, its range published (single device)
         probe(i, 2, true, st);
-        MTRY(head_wgrad(g.n, g.c_out, g.cip, l.in, g.cip, l.dy, g.cop, l.dwacc, dp ? nullptr : rng(i, 2), st));
+        DTRY(head_wgrad(g.n, g.c_out, g.cip, l.in, g.cip, l.dy, g.cop, l.dwacc, dp ? nullptr : rng(i, 2), st));
         probe(i, 2, false, st);
         return NITI_NO_ERROR;
     }
     l.fc_sgd = fc_sgd_layer(i);
     if (l.fc_sgd) {  // its range now; the recompute with the update after the backward pass
         l.defer = SgdJob{};
-        MTRY(conv_wgrad_fc_sgd(g, l.in, l.dy, rng(i, 2), SgdJob{}, 0, st));
+        DTRY(conv_wgrad_fc_sgd(g, l.in, l.dy, rng(i, 2), SgdJob{}, 0, st));
         return NITI_NO_ERROR;
     }
     if (const int s = wgrad_p16_splits(i)) {
@@ -1059,11 +961,11 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         // blocks, then the register-fed kernel (+ its split-K reduce); the probe times the kernel
         // launch itself
         if (!xp16_valid[i]) {
-            MTRY(nhwc16_to_p16(l.in, (int64_t)g.n * g.h * g.w, g.cip, xp16[i], st));
+            DTRY(nhwc16_to_p16(l.in, (int64_t)g.n * g.h * g.w, g.cip, xp16[i], st));
             xp16_valid[i] = 1;
         }
         if (!dp16_valid[i]) {
-            MTRY(nhwc16_to_p16(l.dy, (int64_t)g.n * g.oh * g.ow, g.cop, dp16[i], st));
+            DTRY(nhwc16_to_p16(l.dy, (int64_t)g.n * g.oh * g.ow, g.cop, dp16[i], st));
             dp16_valid[i] = 1;
         }
         hipEvent_t eb, ee;
@@ -1075,7 +977,7 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         const bool defer = defer_combine() && s > 1 && l.slab16 != nullptr &&
                            conv_wgrad_p16_workspace(g, s) <= l.slab16_bytes;
         l.defer = SgdJob{};
-        MTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.slab16 : slab_w,
+        DTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.slab16 : slab_w,
                             defer ? l.slab16_bytes : slab_w_bytes, s, st, eb, ee, sp, defer ? &l.defer : nullptr));
         return NITI_NO_ERROR;
     }
@@ -1089,39 +991,9 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     // combine, which sums them and takes the range (no reduce launch, no int32 round trip)
     const bool defer = defer_combine() && ensure_wslab(i);
     l.defer = SgdJob{};
-    MTRY(conv_wgrad_acc(g, l.in, l.dy, l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.wslab : slab_w,
+    DTRY(conv_wgrad_acc(g, l.in, l.dy, l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.wslab : slab_w,
                         defer ? l.wslab_bytes : slab_w_bytes, st, capturing ? probe_end_event(i, 2) : nullptr,
                         defer ? &l.defer : nullptr));
-    return NITI_NO_ERROR;
-}
-
-// Data parallel: the bucket of layers [bucket_lo[hi], hi] (contiguous in grad_bucket) is complete
-// once layer bucket_lo[hi]'s weight gradient is in on `wst`: the comm stream waits for it, SUMs
-// the bucket's int32 gradients over the ranks and takes every layer's range of the summed
-// gradient (NITI_RangeEstimate over the global batch, NITI_GradientConv_Int8.cpp:274-296), while
-// the step stream goes on with the input-gradient chain.
-int Model::sum_bucket(int lo, hipStream_t wst) {
-    int hi = lo;
-    while (hi + 1 < (int)L.size() && bucket_lo[hi + 1] == lo) ++hi;
-    MTRY(hipEventRecord(ev_bucket[lo], wst));
-    if (shared_comm) {  // one communicator: the SUMs stay in the step's program order
-        size_t elems = 0;
-        for (int j = lo; j <= hi; ++j) elems += (size_t)L[j].w_elems();
-        CTRY(coll_grad->allreduce(L[lo].dwacc, elems, COLL_SUM_I32, wst));
-        AbsmaxJob jobs[ABSMAX_MAX_JOBS];
-        if (hi - lo + 1 > ABSMAX_MAX_JOBS) return NITI_NOT_SUPPORT;
-        for (int j = lo; j <= hi; ++j) jobs[j - lo] = AbsmaxJob{L[j].dwacc, L[j].w_elems(), rng(j, 2), 0};
-        MTRY(absmax_many(jobs, hi - lo + 1, wst));
-        return NITI_NO_ERROR;
-    }
-    MTRY(hipStreamWaitEvent(cst, ev_bucket[lo], 0));
-    size_t elems = 0;
-    for (int j = lo; j <= hi; ++j) elems += (size_t)L[j].w_elems();
-    CTRY(coll_grad->allreduce(L[lo].dwacc, elems, COLL_SUM_I32, cst));
-    AbsmaxJob jobs[ABSMAX_MAX_JOBS];
-    if (hi - lo + 1 > ABSMAX_MAX_JOBS) return NITI_NOT_SUPPORT;
-    for (int j = lo; j <= hi; ++j) jobs[j - lo] = AbsmaxJob{L[j].dwacc, L[j].w_elems(), rng(j, 2), 0};
-    MTRY(absmax_many(jobs, hi - lo + 1, cst));
     return NITI_NO_ERROR;
 }
 
@@ -1160,15 +1032,15 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         dy16_valid[i - 1] = !(pv.pool && o.pool_dx_nhwc == 0);
         const int K = g.c_out, rows = g.c_in;
         if (!dp && !capturing && rowconv_fc_ok(n, K, rows, true)) {
-            MTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
+            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {
-            MTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
+            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
         } else {
-            MTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
         }
         probe(i, 1, false, st);
         dp16_valid[i - 1] = o.p16 != nullptr ? 1 : 0;
@@ -1181,9 +1053,9 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         const ConvGeom& d = l.dg;
         // a row-segment input gradient reads dy (NHWC16) in place; the others its C32 copy
         const bool xn = rowconv_nhwc_pref(d);
-        if (xn && !dy16_valid[i]) MTRY(c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, l.dy, st));
+        if (xn && !dy16_valid[i]) DTRY(c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, l.dy, st));
         if (!xn && !dyc32_valid[i]) {
-            MTRY(nhwc16_to_c32(l.dy, n, g.oh * g.ow, g.cop, g.c_out, l.dyc32, st));
+            DTRY(nhwc16_to_c32(l.dy, n, g.oh * g.ow, g.cop, g.c_out, l.dyc32, st));
             dyc32_valid[i] = 1;
         }
         const int8_t* dyin = xn ? l.dy : l.dyc32;
@@ -1213,17 +1085,17 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         }
         dy16_valid[i - 1] = !skip16;
         if (!dp && !capturing && rowconv_fused_ok(d, true)) {
-            MTRY(rowconv_fwd(d, dyin, l.wft, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
+            DTRY(rowconv_fwd(d, dyin, l.wft, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {
             o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            MTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
+            DTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
         } else {
             o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            MTRY(rowconv_fwd(d, dyin, l.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            MTRY(rowconv_fwd(d, dyin, l.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fwd(d, dyin, l.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(d, dyin, l.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
         }
         probe(i, 1, false, st);
         dp16_valid[i - 1] = o.p16 != nullptr ? 1 : 0;
@@ -1269,29 +1141,29 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         fe = conv_dgrad_fused(g, l.dy, l.wT, o, FusedBar{l.bar, l.epoch + 1, rc_err}, st);
         if (fe != hipErrorNotSupported) {
             ++l.epoch;
-            MTRY(fe);
+            DTRY(fe);
         }
     }
     if (fe != hipErrorNotSupported) {
     } else if (spec) {  // the speculative pair (no int32 tensor while the bit width holds)
         int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        MTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 0, st, alt));
-        if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        MTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 1, st, alt));
+        DTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 0, st, alt));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 1, st, alt));
     } else {
-        MTRY(conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st));
-        if (dp && exact) CTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        MTRY(conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), o, slab_bytes, st));
+        DTRY(conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), o, slab_bytes, st));
     }
     probe(i, 1, false, st);
     if (pv.flatten) {
         const int fc = pg.c_out * pv.ph * pv.pw, ld = round_up(fc, 16);
-        MTRY(launch_map((int64_t)n * pv.ph * pv.pw * pg.cop,
+        DTRY(launch_map((int64_t)n * pv.ph * pv.pw * pg.cop,
                         FlattenBwd{pv.dflat, pv.ph * pv.pw, pg.c_out, pg.cop, ld, pv.dtmp}, st));
-        MTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
+        DTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
                                       pv.dy, st));
     } else if (pv.pool && !fuse) {
-        MTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
+        DTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
                                       pv.dy, st));
     }
     if (o.out_p16 != nullptr) dp16_valid[i - 1] = 1;
@@ -1313,39 +1185,13 @@ int Model::autotune(hipStream_t st, int reps) {
     // split-K room for the candidates
     if (!ensure_slab(size_t(96) << 20, false) || !ensure_slab(size_t(96) << 20, true)) return NITI_OUT_OF_MEMORY;
     drop_graph();
-    hipEvent_t ev[4];
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) return NITI_NO_EXECUTION;
+    TuneTimer timer;
+    if (const int rc = timer.init(st, reps)) return rc;
     tuning = true;
     int rc = NITI_NO_ERROR;
-    auto run_op = [&](int i, int op) {
-        return op == PLAN_FWD ? fwd_layer(i, st) : op == PLAN_WGRAD ? wgrad_layer(i, st) : dgrad_layer(i, st);
-    };
-    // min over three event-bracketed batches of `reps` back-to-back runs (no host sync inside)
-    auto time_op = [&](int i, int op, float* us) -> int {
-        int r = run_op(i, op);
-        float best = 1e30f;
-        for (int t = 0; t < 3 && r == NITI_NO_ERROR; ++t) {
-            if (hipEventRecord(ev[0], st) != hipSuccess) return NITI_NO_EXECUTION;
-            for (int k = 0; k < reps && r == NITI_NO_ERROR; ++k) r = run_op(i, op);
-            if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess)
-                return NITI_NO_EXECUTION;
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return NITI_NO_EXECUTION;
-            best = std::min(best, ms * 1000.f / reps);
-        }
-        *us = best;
-        return r;
-    };
     if (hipMemsetAsync(amax, 0, amax_bytes, st) != hipSuccess) rc = NITI_NO_EXECUTION;
     // NITI_DIAG_TUNE_LOG=1 (diagnostics): every candidate's time on stderr
     const bool log = getenv("NITI_DIAG_TUNE_LOG") != nullptr;
-    auto note = [&](int i, int op, const PlanChoice& c, float us) {
-        if (log) fprintf(stderr, "tune layer %d op %d plan (%d,%d,%d,%d) %.2f us\n", i, op, c.bm, c.bn, c.splits, c.strat, us);
-    };
-    static const int tiles[7][2] = {{PLAN_TAPS_TILE, PLAN_TAPS_TILE}, {128, 128}, {128, 64}, {64, 128}, {64, 64},
-                                    {256, 128}, {128, 256}};
-    static const int split_opts[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
     for (int i = 0; i < nl && rc == NITI_NO_ERROR; ++i) {
         for (int op : {PLAN_FWD, PLAN_WGRAD, PLAN_DGRAD}) {
             if (op == PLAN_DGRAD && i == 0) continue;
@@ -1355,12 +1201,17 @@ int Model::autotune(hipStream_t st, int reps) {
             if (op == PLAN_WGRAD && head_layer(i) && L[i].g.c_out <= 32 && L[i].g.cip % 32 == 0) continue;
             const ConvGeom& g = L[i].g;
             const PlanKey key = conv_plan_key(op, g);
-            const int k_step = conv_plan_k_step(op, g);
-            const int steps = (key.K + k_step - 1) / k_step;
-            const bool act = op != PLAN_WGRAD;
+            auto time_op = [&](float* us) {
+                return timer.time(
+                    [&] { return op == PLAN_FWD ? fwd_layer(i, st) : op == PLAN_WGRAD ? wgrad_layer(i, st) : dgrad_layer(i, st); },
+                    us);
+            };
+            auto note = [&](const PlanChoice& c, float us) {
+                if (log) fprintf(stderr, "tune layer %d op %d plan (%d,%d,%d,%d) %.2f us\n", i, op, c.bm, c.bn, c.splits, c.strat, us);
+            };
             plan_override_clear(key);
             const size_t wsb = ws_bytes_for(op);
-            PlanChoice best = conv_plan_query(op, g, act, wsb);
+            PlanChoice best = conv_plan_query(op, g, op != PLAN_WGRAD, wsb);
             if (op == PLAN_WGRAD && wgrad_p16_splits(i) > 0) {
                 best.bm = best.bn = PLAN_P16_TILE;
                 best.splits = wgrad_p16_splits(i);
@@ -1377,9 +1228,8 @@ int Model::autotune(hipStream_t st, int reps) {
                 xp16_valid[i] = 1;
             }
             float best_us = 0.f;
-            rc = time_op(i, op, &best_us);
-            note(i, op, best, best_us);
-            const bool taps = op == PLAN_WGRAD && conv_wgrad_taps_ok(g);
+            rc = time_op(&best_us);
+            note(best, best_us);
             if (op == PLAN_WGRAD && conv_wgrad_p16_ok(g)) {
                 for (int sp : {1, 2, 4, 8}) {
                     if (rc != NITI_NO_ERROR) break;
@@ -1390,55 +1240,15 @@ int Model::autotune(hipStream_t st, int reps) {
                     cand.strat = sp > 1 ? 2 : 0;
                     plan_override_set(key, cand);
                     float us = 0.f;
-                    rc = time_op(i, op, &us);
-                    note(i, op, cand, us);
+                    rc = time_op(&us);
+                    note(cand, us);
                     if (rc == NITI_NO_ERROR && us < best_us) {
                         best_us = us;
                         best = cand;
                     }
                 }
             }
-            for (const auto& t : tiles) {
-                if (rc != NITI_NO_ERROR) break;
-                if (t[0] == PLAN_TAPS_TILE && !taps) continue;
-                std::vector<PlanChoice> cands;
-                PlanChoice c;
-                c.bm = t[0];
-                c.bn = t[1];
-                c.splits = 1;
-                c.strat = 0;
-                cands.push_back(c);
-                if (act) {
-                    c.strat = 1;
-                    cands.push_back(c);
-                    // the speculative pair only on request (NITI_TUNE_SPEC=1): timed here on one
-                    // batch its guess always holds, but over a run of batches 60-80 % of the deep
-                    // layers' pairs miss (profiles/r05_gemm_spec.txt) and then cost more than STORE
-                    if (tune_spec()) {
-                        c.strat = 3;
-                        cands.push_back(c);
-                    }
-                    c.strat = 4;  // one launch, the rescale fused (where every tile is resident)
-                    cands.push_back(c);
-                }
-                for (int s : split_opts) {
-                    if (s > steps / 2 || plan_slab_bytes(key.M, key.N, s) > wsb) break;
-                    c.strat = 2;
-                    c.splits = s;
-                    cands.push_back(c);
-                }
-                for (const PlanChoice& cand : cands) {
-                    plan_override_set(key, cand);
-                    float us = 0.f;
-                    rc = time_op(i, op, &us);
-                    note(i, op, cand, us);
-                    if (rc != NITI_NO_ERROR) break;
-                    if (us < best_us) {
-                        best_us = us;
-                        best = cand;
-                    }
-                }
-            }
+            if (rc == NITI_NO_ERROR) rc = tune_gemm_tiles(op, g, wsb, time_op, note, &best, &best_us);
             plan_override_set(key, best);
             invalidate_xp16();
             if (rc != NITI_NO_ERROR) break;
@@ -1446,7 +1256,6 @@ int Model::autotune(hipStream_t st, int reps) {
     }
     invalidate_xp16();
     tuning = false;
-    for (auto e : ev) (void)hipEventDestroy(e);
     if (hipStreamSynchronize(st) != hipSuccess) rc = NITI_NO_EXECUTION;
     return rc;
 }
@@ -1491,7 +1300,7 @@ int Model::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool
     auto fill = [&](void* p, int v, size_t bytes) {
         return eval_pass || capturing ? fill_kernel(p, v, bytes, st) : hipMemsetAsync(p, v, bytes, st);
     };
-    if (x_nchw != nullptr || amax_bytes % 16 != 0) MTRY(fill(amax, 0, amax_bytes));
+    if (x_nchw != nullptr || amax_bytes % 16 != 0) DTRY(fill(amax, 0, amax_bytes));
     // the first layer's im2col copy straight from the batch where the fused pass takes the layer
     const ConvGeom& o0 = L[0].og;
     const bool fused_in = L[0].col && input_im2col_ok(o0.c_in, o0.kh, o0.kw) && o0.sh == 1 && o0.sw == 1;
@@ -1506,38 +1315,38 @@ int Model::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool
     }
     conv0_ranged = r0.w != nullptr;
     if (x_nchw != nullptr) {
-        MTRY(fill(exp0, exp_in, 1));
+        DTRY(fill(exp0, exp_in, 1));
         if (fused_in)
-            MTRY(input_im2col(x_nchw, false, n, in_c, in_h, in_w, o0.kh, o0.kw, o0.pt, o0.pl, nullptr, 0, 0, x0n,
+            DTRY(input_im2col(x_nchw, false, n, in_c, in_h, in_w, o0.kh, o0.kw, o0.pt, o0.pl, nullptr, 0, 0, x0n,
                               L[0].xcol, nullptr, st, r0));
         else
-            MTRY(nchw_to_nhwc16(x_nchw, n, in_c, in_h * in_w, round_up(in_c, 16), x0, st));
+            DTRY(nchw_to_nhwc16(x_nchw, n, in_c, in_h * in_w, round_up(in_c, 16), x0, st));
     } else {
         // NITIInt8Train's input quantiser (MnistUtils.cpp:83-93): batch statistics (per-block
         // partials; summed and all-reduced over the ranks in exact mode), then x and its exponent
         // ascale straight into the layer-0 input
         const int64_t px = (int64_t)n * in_c * in_h * in_w;
         int ns = 0;
-        MTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
+        DTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
                                amax_bytes % 16 == 0 ? amax_bytes : 0));
         const unsigned long long* slots = qslots;
         if ((dp && exact) || !fused_in) {
-            MTRY(stats_finalize(qslots, ns, qstats, st));
+            DTRY(stats_finalize(qslots, ns, qstats, st));
             slots = qstats;
             ns = 1;
         }
         if (dp && exact) {
-            CTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
-            CTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
+            DTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
+            DTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
         }
         const int64_t count = dp && exact ? px * world : px;
         if (fused_in)
-            MTRY(input_im2col(images, true, n, in_c, in_h, in_w, o0.kh, o0.kw, o0.pt, o0.pl, slots, ns, count, x0n,
+            DTRY(input_im2col(images, true, n, in_c, in_h, in_w, o0.kh, o0.kw, o0.pt, o0.pl, slots, ns, count, x0n,
                               L[0].xcol, exp0, st, r0));
         else
-            MTRY(image_quantize(images, n, in_c, in_h * in_w, round_up(in_c, 16), qstats, count, x0, exp0, true, st));
+            DTRY(image_quantize(images, n, in_c, in_h * in_w, round_up(in_c, 16), qstats, count, x0, exp0, true, st));
     }
-    if (L[0].col && !fused_in) MTRY(im2col32(L[0].og, x0, L[0].xcol, st));
+    if (L[0].col && !fused_in) DTRY(im2col32(L[0].og, x0, L[0].xcol, st));
     for (int i = 0; i < nl - (skip_head ? 1 : 0); ++i) {
         const int rc = fwd_layer(i, st);
         if (rc != NITI_NO_ERROR) return rc;
@@ -1587,9 +1396,9 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
             h.p16 = fuse_dp16 && wgrad_p16_splits(nl - 2) > 0 ? dp16[nl - 2] : nullptr;
             h.pool_dx = skip_dy16(nl - 1, next, h.p16) ? nullptr : pv.dy;
             h.pool_dx_c32 = next;
-            MTRY(head_chain(h, st));
+            DTRY(head_chain(h, st));
             if (with_jobs && nj > 0) {  // (a launch of its own: see niti_head.hip)
-                MTRY(nhwc16_to_p16_many(jobs, nj, st));
+                DTRY(nhwc16_to_p16_many(jobs, nj, st));
                 for (int j = 0; j < nl; ++j)
                     if (wgrad_p16_splits(j)) xp16_valid[j] = 1;
                 p16_done = true;
@@ -1603,12 +1412,12 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
             // one stream: the loss gradient and every P16 input copy in one launch (the copies read
             // forward activations only); A/B on one box, 8 alternating 200-step runs: median step
             // 0.395 vs 0.400 ms (profiles/r03_lossp16_ab.txt)
-            MTRY(loss_grad_p16(t.r, n, t.g.c_out, t.g.cop, t.exp, labels, t.dy, jobs, nj, st));
+            DTRY(loss_grad_p16(t.r, n, t.g.c_out, t.g.cop, t.exp, labels, t.dy, jobs, nj, st));
             for (int j = 0; j < nl; ++j)
                 if (wgrad_p16_splits(j)) xp16_valid[j] = 1;
             p16_done = true;
         } else {
-            MTRY(loss_grad(t.r, n, t.g.c_out, t.g.cop, t.exp, labels, t.dy, st));
+            DTRY(loss_grad(t.r, n, t.g.c_out, t.g.cop, t.exp, labels, t.dy, st));
         }
         dp16_valid[nl - 1] = 0;
     }
@@ -1621,8 +1430,8 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         // (an event record leaves a ~6.5 us bubble before the next launch on the step stream;
         // hipStreamWriteValue64 / WaitValue64 run as blit kernels here and cost more)
         if (ov) {  // dy_i is ready on the step stream
-            MTRY(hipEventRecord(ev_dy[i], st));
-            MTRY(hipStreamWaitEvent(side, ev_dy[i], 0));
+            DTRY(hipEventRecord(ev_dy[i], st));
+            DTRY(hipStreamWaitEvent(side, ev_dy[i], 0));
         }
         if (i == nl - 1 && !p16_done) {  // the forward outputs are final: every P16 input copy in one go
             const int rc = convert_p16_inputs(wst);
@@ -1658,20 +1467,20 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         }
     }
     if (dp) {  // every bucket summed and ranged on the comm stream before the update
-        MTRY(hipEventRecord(ev_grads, cst));
-        MTRY(hipStreamWaitEvent(st, ev_grads, 0));
+        DTRY(hipEventRecord(ev_grads, cst));
+        DTRY(hipStreamWaitEvent(st, ev_grads, 0));
     } else if (ov) {  // every weight gradient is in before the update
-        MTRY(hipEventRecord(ev_side, side));
-        MTRY(hipStreamWaitEvent(st, ev_side, 0));
+        DTRY(hipEventRecord(ev_side, side));
+        DTRY(hipStreamWaitEvent(st, ev_side, 0));
     }
     // the fully connected layers that took the fused form update in their own recompute pass
     SgdJob many[SGD_MAX_JOBS];
     int n_many = 0;
     for (int i = 0; i < nl; ++i)
         if (!L[i].fc_sgd) many[n_many++] = jobs[i];
-    MTRY(sgd_update_many(many, n_many, st));  // (+ the deferred combines) also rewrites the fragment-major weight copies
+    DTRY(sgd_update_many(many, n_many, st));  // (+ the deferred combines) also rewrites the fragment-major weight copies
     for (int i = 0; i < nl; ++i)
-        if (L[i].fc_sgd) MTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st));
+        if (L[i].fc_sgd) DTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st));
     g8_written = keep_grads;
     return NITI_NO_ERROR;
 }
@@ -1690,14 +1499,17 @@ int Model::eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const i
     probe_paused = paused;
     if (rc != NITI_NO_ERROR) return rc;
     const Layer& t = L.back();
-    MTRY(head_metrics(t.r, batch, t.g.c_out, t.g.cop, t.exp, labels, std::min(ev_topk, t.g.c_out), ev_pred, nullptr,
+    DTRY(head_metrics(t.r, batch, t.g.c_out, t.g.cop, t.exp, labels, std::min(ev_topk, t.g.c_out), ev_pred, nullptr,
                       ev_totals, ev_ws, ev_ws_bytes, st));
     return NITI_NO_ERROR;
 }
 
 // Every layer's weights and weight scale from `src` (same architecture and input size, any batch),
 // device to device on `st`, then this model's derived copies (IHWO16, fragment-major) from them.
-int Model::copy_weights_from(Model& src, hipStream_t st) {
+int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
+    Model* sp = dynamic_cast<Model*>(&other);
+    if (sp == nullptr) return NITI_INVALID_VALUE;
+    Model& src = *sp;
     if (src.arch != arch || src.in_h != in_h || src.in_w != in_w || src.in_c != in_c || src.L.size() != L.size())
         return NITI_INVALID_VALUE;
     for (size_t i = 0; i < L.size(); ++i) {
@@ -1711,569 +1523,97 @@ int Model::copy_weights_from(Model& src, hipStream_t st) {
         Layer& l = L[i];
         const Layer& s = src.L[i];
         const ConvGeom& g = l.g;
-        MTRY(copy_kernel(l.w, s.w, (size_t)l.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
-        MTRY(copy_kernel(l.ws_dev, s.ws_dev, 1, st));
+        DTRY(copy_kernel(l.w, s.w, (size_t)l.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
+        DTRY(copy_kernel(l.ws_dev, s.ws_dev, 1, st));
         l.wscale = s.wscale;
         if (!l.rcd)  // (refresh_wt below rebuilds the row-kernel layers')
-            MTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
+            DTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
     }
     int rc = refresh_wt(st);
     if (rc == NITI_NO_ERROR) rc = refresh_wf(st);
     return rc;
 }
 
-}  // namespace niti
-
-// =========================================================================== C ABI (section 3)
-struct niti_model {
-    niti::Model m;                         // LeNet / VGG-11 / VGG-16
-    std::unique_ptr<niti::ResNetModel> r;  // ResNet-18 (niti_resnet_model.hip); m unused then
-};
-
-extern "C" {
-
-int niti_model_create(int arch, int batch, niti_model_t* out) { return niti_model_create2(arch, batch, 0, out); }
-
-int niti_model_create2(int arch, int batch, int in_hw, niti_model_t* out) {
-    return niti_model_create3(arch, batch, in_hw, 0, out);
-}
-
-int niti_model_create3(int arch, int batch, int in_hw, int classes, niti_model_t* out) {
-    if (!out || batch <= 0 || in_hw < 0 || classes < 0) return NITI_INVALID_VALUE;
-    auto* h = new niti_model();
-    int rc;
-    if (arch == NITI_ARCH_RESNET18) {
-        h->r = std::make_unique<niti::ResNetModel>();
-        rc = h->r->build(batch, in_hw, classes);
-    } else {
-        if (classes != 0) {  // the LeNet / VGG heads are fixed (10 or 1000 classes)
-            delete h;
-            return NITI_NOT_SUPPORT;
-        }
-        rc = h->m.build(arch, batch, in_hw);
-    }
-    if (rc != NITI_NO_ERROR) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return NITI_NO_ERROR;
-}
-
-void niti_model_destroy(niti_model_t m) { delete m; }
-
-int niti_model_num_layers(niti_model_t m) { return !m ? 0 : m->r ? (int)m->r->C.size() : (int)m->m.L.size(); }
-
-int niti_model_layer_info(niti_model_t m, int layer, int info[12]) {
-    if (m && m->r) {
-        if (layer < 0 || layer >= (int)m->r->C.size() || !info) return NITI_INVALID_VALUE;
-        const niti::RConv& c = m->r->C[layer];
-        const niti::ConvGeom& g = c.og;
-        const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, c.relu, 0};
-        memcpy(info, v, sizeof(v));
-        return NITI_NO_ERROR;
-    }
-    if (!m || layer < 0 || layer >= (int)m->m.L.size()) return NITI_INVALID_VALUE;
-    const niti::Layer& l = m->m.L[layer];
-    const niti::ConvGeom& g = l.og;  // the layer as the network defines it
-    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, l.relu, l.pool};
-    memcpy(info, v, sizeof(v));
-    return NITI_NO_ERROR;
-}
-
-// the first layer's im2col weights [co][32] (k = (ky * KW + kx) * C_in + c) <-> OIHW
-static void col_from_oihw(const niti::ConvGeom& o, const int8_t* w, int8_t* wc) {
-    memset(wc, 0, (size_t)o.c_out * 32);
-    for (int co = 0; co < o.c_out; ++co)
-        for (int c = 0; c < o.c_in; ++c)
-            for (int t = 0; t < o.kh * o.kw; ++t) wc[co * 32 + t * o.c_in + c] = w[((size_t)co * o.c_in + c) * o.kh * o.kw + t];
-}
-static void oihw_from_col(const niti::ConvGeom& o, const int8_t* wc, int8_t* w) {
-    for (int co = 0; co < o.c_out; ++co)
-        for (int c = 0; c < o.c_in; ++c)
-            for (int t = 0; t < o.kh * o.kw; ++t) w[((size_t)co * o.c_in + c) * o.kh * o.kw + t] = wc[co * 32 + t * o.c_in + c];
-}
-
-int niti_model_set_weight(niti_model_t m, int layer, const int8_t* w_host, int wscale) {
-    if (m && m->r) return m->r->set_weight(layer, w_host, wscale);
-    if (!m || layer < 0 || layer >= (int)m->m.L.size() || !w_host) return NITI_INVALID_VALUE;
-    niti::Layer& l = m->m.L[layer];
-    std::vector<int8_t> colw;
-    if (l.col) {  // upload the [co][32] im2col weights as the 1x1 geometry's OIHW
-        colw.resize((size_t)l.g.c_out * 32);
-        col_from_oihw(l.og, w_host, colw.data());
-        w_host = colw.data();
-    }
-    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
-    int8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int rc = NITI_NO_ERROR;
-    if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
-        niti::oihw_to_ohwi16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
-        niti::oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess ||
-        hipMemset(l.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess ||
-        (l.rc && niti::weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, nullptr) != hipSuccess) ||
-        (l.rcd && niti::weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, nullptr) != hipSuccess) ||
-        hipDeviceSynchronize() != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    l.wscale = (int8_t)wscale;
-    (void)hipFree(tmp);
+// One layer phase of the last step again, alone (single device: collectives off for the call).
+int Model::run_phase(int layer, int phase, hipStream_t st) {
+    if (!layer_ok(layer) || phase < 0 || phase > 2 || (phase == 1 && layer == 0)) return NITI_INVALID_VALUE;
+    const bool t = tuning;
+    tuning = false;  // keep the probe armed; collectives stay off (single-device phase)
+    std::unique_ptr<Collective> c = std::move(coll), cg = std::move(coll_grad);
+    const int rc = phase == 0 ? fwd_layer(layer, st) : phase == 1 ? dgrad_layer(layer, st) : wgrad_layer(layer, st);
+    coll = std::move(c);
+    coll_grad = std::move(cg);
+    tuning = t;
     return rc;
 }
 
-int niti_model_get_weight(niti_model_t m, int layer, int8_t* w_host) {
-    if (m && m->r) return m->r->get_weight(layer, w_host);
-    if (!m || layer < 0 || layer >= (int)m->m.L.size() || !w_host) return NITI_INVALID_VALUE;
-    niti::Layer& l = m->m.L[layer];
-    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
-    int8_t* tmp = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int rc = NITI_NO_ERROR;
-    std::vector<int8_t> colw(l.col ? n : 0);
-    if (niti::ohwi16_to_oihw(l.w, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, tmp, nullptr) != hipSuccess ||
-        hipMemcpy(l.col ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR && l.col) oihw_from_col(l.og, colw.data(), w_host);
-    (void)hipFree(tmp);
-    return rc;
-}
-
-int niti_model_train_step(niti_model_t m, const int8_t* x_nchw, int exp_in, const int32_t* labels, void* stream) {
-    if (m && m->r) return x_nchw && labels ? m->r->step(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream) : NITI_INVALID_VALUE;
-    if (!m || !x_nchw || !labels) return NITI_INVALID_VALUE;
-    return m->m.step(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream);
-}
-
-int niti_model_train_step_images(niti_model_t m, const uint8_t* images_nchw, const int32_t* labels, void* stream) {
-    if (m && m->r) return images_nchw && labels ? m->r->step(nullptr, 0, images_nchw, labels, (hipStream_t)stream) : NITI_INVALID_VALUE;
-    if (!m || !images_nchw || !labels) return NITI_INVALID_VALUE;
-    return m->m.step(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
-}
-
-int niti_model_eval_step(niti_model_t m, const int8_t* x_nchw, int exp_in, const int32_t* labels, void* stream) {
-    if (!m || !x_nchw || !labels) return NITI_INVALID_VALUE;
-    if (m->r) return m->r->eval(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream);
-    return m->m.eval(x_nchw, exp_in, nullptr, labels, (hipStream_t)stream);
-}
-
-int niti_model_eval_step_images(niti_model_t m, const uint8_t* images_nchw, const int32_t* labels, void* stream) {
-    if (!m || !images_nchw || !labels) return NITI_INVALID_VALUE;
-    if (m->r) return m->r->eval(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
-    return m->m.eval(nullptr, 0, images_nchw, labels, (hipStream_t)stream);
-}
-
-int niti_model_eval_reset(niti_model_t m, void* stream) {
-    if (!m) return NITI_INVALID_VALUE;
-    niti_eval_totals* t = m->r ? m->r->ev_totals : m->m.ev_totals;
-    return niti::fill_kernel(t, 0, sizeof(niti_eval_totals), (hipStream_t)stream) == hipSuccess ? NITI_NO_ERROR
-                                                                                                : NITI_NO_EXECUTION;
-}
-
-int niti_model_eval_read(niti_model_t m, niti_eval_totals* host_out, void* stream) {
-    if (!m || !host_out) return NITI_INVALID_VALUE;
-    const niti_eval_totals* t = m->r ? m->r->ev_totals : m->m.ev_totals;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(host_out, t, sizeof(niti_eval_totals), hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_eval_topk(niti_model_t m, int k) {
-    if (!m || k < 1) return NITI_INVALID_VALUE;
-    (m->r ? m->r->ev_topk : m->m.ev_topk) = k;  // (clamped to the class count at each step)
-    return NITI_NO_ERROR;
-}
-
-int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream) {
-    if (!m || !pred_host) return NITI_INVALID_VALUE;
-    const int32_t* p = m->r ? m->r->ev_pred : m->m.ev_pred;
-    const int n = m->r ? m->r->batch : m->m.batch;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(pred_host, p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream) {
-    if (!dst || !src || (dst->r != nullptr) != (src->r != nullptr)) return NITI_INVALID_VALUE;
-    if (dst->r) return dst->r->copy_weights_from(*src->r, (hipStream_t)stream);
-    return dst->m.copy_weights_from(src->m, (hipStream_t)stream);
-}
-
-int niti_model_get_input(niti_model_t m, int8_t* x_nchw_host, int* ascale, void* stream) {
-    if (m && m->r) return x_nchw_host ? m->r->get_input(x_nchw_host, ascale, (hipStream_t)stream) : NITI_INVALID_VALUE;
-    if (!m || !x_nchw_host) return NITI_INVALID_VALUE;
-    niti::Model& mm = m->m;
-    const int n = mm.batch, hw = mm.in_h * mm.in_w;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NITI_NO_EXECUTION;
-    const size_t need = (size_t)n * mm.in_c * hw;
-    int8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int8_t e = 0;
-    hipError_t err = mm.x0_nchw_valid ? hipMemcpy(tmp, mm.x0n, need, hipMemcpyDeviceToDevice)
-                                      : niti::nhwc16_to_nchw(mm.x0, n, mm.in_c, hw, niti::round_up(mm.in_c, 16), tmp, nullptr);
-    if (err == hipSuccess) err = hipMemcpy(x_nchw_host, tmp, need, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(&e, mm.exp0, 1, hipMemcpyDeviceToHost);
-    (void)hipFree(tmp);
-    if (ascale) *ascale = e;
-    return err == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
-}
-
-int niti_model_get_logits(niti_model_t m, int8_t* logits_host, int* exp_out, void* stream) {
-    if (m && m->r) return logits_host ? m->r->get_logits(logits_host, exp_out, (hipStream_t)stream) : NITI_INVALID_VALUE;
-    if (!m) return NITI_INVALID_VALUE;
-    niti::Layer& t = m->m.L.back();
-    const int n = m->m.batch;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NITI_NO_EXECUTION;
-    std::vector<int8_t> buf((size_t)n * t.g.cop);
-    int8_t e = 0;
-    if (hipMemcpy(buf.data(), t.r, buf.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&e, t.exp, 1, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    for (int i = 0; i < n; ++i) memcpy(logits_host + (size_t)i * t.g.c_out, buf.data() + (size_t)i * t.g.cop, t.g.c_out);
-    if (exp_out) *exp_out = e;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_get_tap(niti_model_t m, int layer, int which, int8_t* host, size_t bytes, void* stream) {
-    if (m && m->r) return host ? m->r->get_tap(layer, which, host, bytes, (hipStream_t)stream) : NITI_INVALID_VALUE;
-    if (!m || layer < 0 || layer >= (int)m->m.L.size()) return NITI_INVALID_VALUE;
-    niti::Layer& l = m->m.L[layer];
-    const niti::ConvGeom& g = l.g;
-    const int n = m->m.batch;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NITI_NO_EXECUTION;
-    int8_t* tmp = nullptr;
-    size_t need = 0;
-    if (which == 0 || which == 2)
-        need = (size_t)n * g.c_out * g.oh * g.ow;
-    else if (which == 1 && m->m.g8_written)
-        need = (size_t)g.c_out * g.c_in * g.kh * g.kw;
-    else
-        return NITI_INVALID_VALUE;
-    const size_t out_need = which == 1 && l.col ? (size_t)l.og.c_out * l.og.c_in * l.og.kh * l.og.kw : need;
-    if (bytes < out_need) return NITI_INVALID_VALUE;
-    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    hipError_t e;
-    if (which == 0 && !l.r_written) {  // (a pooled layer whose route went as codes under keep_grads(0))
-        (void)hipFree(tmp);
-        return NITI_INVALID_VALUE;
-    }
-    if (which == 0)
-        e = niti::nhwc16_to_nchw(l.r, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else if (which == 2 && !m->m.dy16_valid[layer]) {  // rebuilt from the C32 copy the step wrote
-        int8_t* d16 = nullptr;
-        e = hipMalloc(&d16, (size_t)n * g.oh * g.ow * g.cop);
-        if (e == hipSuccess) e = niti::c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, d16, nullptr);
-        if (e == hipSuccess) e = niti::nhwc16_to_nchw(d16, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (d16) (void)hipFree(d16);
-    } else if (which == 2)
-        e = niti::nhwc16_to_nchw(l.dy, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else
-        e = niti::ohwi16_to_oihw(l.g8, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
-    if (which == 1 && l.col) {
-        std::vector<int8_t> colw(need);
-        if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) oihw_from_col(l.og, colw.data(), host);
-    } else if (e == hipSuccess) {
-        e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(tmp);
-    return e == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
-}
-
-int64_t niti_model_step_macs(niti_model_t m) {
-    if (m && m->r) return m->r->step_macs();
-    if (!m) return 0;
-    int64_t s = 0;
-    const int world = m->m.world > 0 ? m->m.world : 1;
-    for (size_t i = 0; i < m->m.L.size(); ++i) {
-        const int64_t f = m->m.L[i].macs();
-        s += f;            // forward
-        s += f;            // weight gradient
-        if (i > 0) s += f; // input gradient
-    }
-    (void)world;
-    return s;
-}
-
-int niti_model_set_overlap(niti_model_t m, int enable) {
-    if (m && m->r) return NITI_NO_ERROR;  // one stream (the weight gradients interleave with the input gradients)
-    if (!m) return NITI_INVALID_VALUE;
-    m->m.overlap = enable != 0;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_keep_grads(niti_model_t m, int enable) {
-    if (m && m->r) {
-        m->r->keep_grads = enable != 0;
-        m->r->drop_graph();
-        return NITI_NO_ERROR;
-    }
-    if (!m) return NITI_INVALID_VALUE;
-    m->m.keep_grads = enable != 0;
-    m->m.drop_graph();
-    return NITI_NO_ERROR;
-}
-
-int niti_model_set_rowconv(niti_model_t m, int enable) {
-    if (m && m->r) {
-        niti::ResNetModel& r = *m->r;
-        if (r.use_rowconv && enable == 0) {  // the GEMM input gradients read IHWO16 copies the update skipped
-            for (int i = 0; i < (int)r.C.size(); ++i)
-                if (r.refresh_copies(i, nullptr) != NITI_NO_ERROR) return NITI_NO_EXECUTION;
-            if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-        }
-        r.use_rowconv = enable != 0;
-        r.drop_graph();
-        return NITI_NO_ERROR;
-    }
-    if (!m) return NITI_INVALID_VALUE;
-    if (m->m.use_rowconv && enable == 0) {
-        const int rc = m->m.refresh_wt(nullptr);
-        if (rc != NITI_NO_ERROR || hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-    }
-    m->m.use_rowconv = enable != 0;
-    m->m.drop_graph();
-    return NITI_NO_ERROR;
-}
-
-int niti_model_spec_slot(niti_model_t m, int layer, int dgrad, uint32_t* out32) {
-    if (!m || !out32 || layer < 0) return NITI_INVALID_VALUE;
-    const uint32_t* bar = nullptr;
-    if (m->r) {
-        if (layer >= (int)m->r->C.size()) return NITI_INVALID_VALUE;
-        bar = m->r->C[layer].bar;
-    } else {
-        if (layer >= (int)m->m.L.size()) return NITI_INVALID_VALUE;
-        bar = m->m.L[layer].bar;
-    }
-    std::fill(out32, out32 + 32, 0u);
-    if (bar == nullptr) return NITI_NO_ERROR;
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(out32, niti::rowconv_spec_slot(const_cast<uint32_t*>(bar), dgrad != 0), 32 * 4,
-                  hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_spec_stats(niti_model_t m, uint32_t* out, int max_layers) {
-    if (m && m->r) return out && max_layers >= 0 ? m->r->spec_stats(out, max_layers) : NITI_INVALID_VALUE;
-    if (!m || !out || max_layers < 0) return NITI_INVALID_VALUE;
-    const int nl = std::min(max_layers, (int)m->m.L.size());
-    std::fill(out, out + (size_t)nl * 6, 0u);
-    for (int i = 0; i < nl; ++i) {
-        const niti::Layer& l = m->m.L[i];
-        for (int d = 0; d < 2; ++d) {  // forward / input-gradient slot: hint, redone launches, stored pairs
-            uint32_t w[5] = {0, 0, 0, 0, 0}, gw[4] = {0, 0, 0, 0};
-            if (l.bar != nullptr && hipMemcpy(w, niti::rowconv_spec_slot(const_cast<uint32_t*>(l.bar), d != 0), sizeof(w),
-                                              hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            // the GEMM path's pair (plan strategy 3): its own slot, no store mode
-            if (l.gspec != nullptr && hipMemcpy(gw, l.gspec + d * niti::GEMM_SPEC_SLOT_WORDS, sizeof(gw),
-                                                hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            out[i * 6 + d * 3] = std::max(w[0], gw[0]);
-            out[i * 6 + d * 3 + 1] = w[2] + gw[2];
-            out[i * 6 + d * 3 + 2] = w[4] + gw[3];  // the GEMM pair: misses settled from an alternate
-        }
-    }
-    return NITI_NO_ERROR;
-}
-
-int niti_model_rowconv_error(niti_model_t m) {
-    if (m && m->r) return m->r->rowconv_error();
-    if (!m) return NITI_INVALID_VALUE;
-    uint32_t e = 0;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&e, m->m.rc_err, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    return (int)e;
-}
-
-int niti_model_set_graph(niti_model_t m, int enable) {
-    if (m && m->r) {
-        m->r->drop_graph();
-        m->r->use_graph = enable != 0;
-        return NITI_NO_ERROR;
-    }
-    if (!m) return NITI_INVALID_VALUE;
-    m->m.drop_graph();
-    m->m.use_graph = enable != 0;
-    return NITI_NO_ERROR;
-}
-
-int niti_model_autotune(niti_model_t m, int reps, void* stream) {
-    if (m && m->r) return m->r->autotune((hipStream_t)stream, reps);
-    if (!m) return NITI_INVALID_VALUE;
-    return m->m.autotune((hipStream_t)stream, reps);
-}
-
-int niti_model_run_phase(niti_model_t m, int layer, int phase, void* stream) {
-    if (m && m->r) return m->r->run_phase(layer, phase, (hipStream_t)stream);
-    if (!m || layer < 0 || layer >= (int)m->m.L.size() || phase < 0 || phase > 2 || (phase == 1 && layer == 0))
-        return NITI_INVALID_VALUE;
-    const bool t = m->m.tuning;
-    m->m.tuning = false;  // keep the probe armed; collectives stay off (single-device phase)
-    std::unique_ptr<niti::Collective> c = std::move(m->m.coll), cg = std::move(m->m.coll_grad);
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = phase == 0 ? m->m.fwd_layer(layer, st) : phase == 1 ? m->m.dgrad_layer(layer, st) : m->m.wgrad_layer(layer, st);
-    m->m.coll = std::move(c);
-    m->m.coll_grad = std::move(cg);
-    m->m.tuning = t;
-    return rc;
-}
-
-int niti_model_plan_info(niti_model_t m, int layer, int phase, int info[4]) {
-    if (m && m->r) {
-        if (!info || layer < 0 || layer >= (int)m->r->C.size() || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
-        const int op = phase == 0 ? niti::PLAN_FWD : phase == 1 ? niti::PLAN_DGRAD : niti::PLAN_WGRAD;
-        const niti::PlanChoice c = niti::conv_plan_query(op, m->r->C[layer].g, phase != 2,
-                                                         phase == 2 ? m->r->slab_w_bytes : m->r->slab_bytes);
-        info[0] = c.bm;
-        info[1] = c.bn;
-        info[2] = c.splits;
-        info[3] = c.strat;
-        return NITI_NO_ERROR;
-    }
-    if (!m || !info || layer < 0 || layer >= (int)m->m.L.size() || phase < 0 || phase > 2)
-        return NITI_INVALID_VALUE;
-    const niti::ConvGeom& g = m->m.L[layer].g;
-    const int op = phase == 0 ? niti::PLAN_FWD : phase == 1 ? niti::PLAN_DGRAD : niti::PLAN_WGRAD;
-    niti::PlanChoice c = niti::conv_plan_query(op, g, phase != 2, m->m.ws_bytes_for(op));
-    if (phase == 2 && m->m.wgrad_p16_splits(layer) > 0) {
-        c.bm = c.bn = niti::PLAN_P16_TILE;
-        c.splits = m->m.wgrad_p16_splits(layer);
+int Model::plan_info(int layer, int phase, int info[4]) {
+    if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    const int op = plan_op(phase);
+    PlanChoice c = conv_plan_query(op, L[layer].g, phase != 2, ws_bytes_for(op));
+    if (phase == 2 && wgrad_p16_splits(layer) > 0) {
+        c.bm = c.bn = PLAN_P16_TILE;
+        c.splits = wgrad_p16_splits(layer);
         c.strat = c.splits > 1 ? 2 : 0;
     }
-    info[0] = c.bm;
-    info[1] = c.bn;
-    info[2] = c.splits;
-    info[3] = c.strat;
-    return NITI_NO_ERROR;
+    return plan_out(c, info);
 }
 
-int niti_model_plan_set(niti_model_t m, int layer, int phase, const int plan[4]) {
-    if (m && m->r) {
-        if (layer < 0 || layer >= (int)m->r->C.size() || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
-        const int op = phase == 0 ? niti::PLAN_FWD : phase == 1 ? niti::PLAN_DGRAD : niti::PLAN_WGRAD;
-        const niti::ConvGeom& g = m->r->C[layer].g;
-        const niti::PlanKey k = niti::conv_plan_key(op, g);
-        m->r->drop_graph();
-        if (plan == nullptr) {
-            niti::plan_override_clear(k);
-            return NITI_NO_ERROR;
-        }
-        auto tile_ok = [](int t) { return t == 64 || t == 128 || t == 256; };
-        const bool taps = plan[0] == niti::PLAN_TAPS_TILE && plan[1] == niti::PLAN_TAPS_TILE && op == niti::PLAN_WGRAD &&
-                          niti::conv_wgrad_taps_ok(g);
-        if ((!taps && (!tile_ok(plan[0]) || !tile_ok(plan[1]))) || plan[2] < 1 || plan[2] > 4096 || plan[3] < 0 ||
-            plan[3] > 4 || (taps && plan[3] == 1) || (plan[3] >= 3 && (op == niti::PLAN_WGRAD || plan[2] != 1)))
-            return NITI_INVALID_VALUE;
-        niti::PlanChoice c;
-        c.bm = plan[0];
-        c.bn = plan[1];
-        c.splits = plan[2];
-        c.strat = plan[3];
-        if (c.strat == 2 &&
-            !m->r->ensure_slab(std::min(niti::plan_slab_bytes(k.M, k.N, c.splits), size_t(1) << 30), op == niti::PLAN_WGRAD))
-            return NITI_OUT_OF_MEMORY;
-        niti::plan_override_set(k, c);
-        return NITI_NO_ERROR;
-    }
-    if (!m || layer < 0 || layer >= (int)m->m.L.size() || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
-    const int op = phase == 0 ? niti::PLAN_FWD : phase == 1 ? niti::PLAN_DGRAD : niti::PLAN_WGRAD;
-    const niti::PlanKey k = niti::conv_plan_key(op, m->m.L[layer].g);
+// this driver's own rule: the P16 tile (weight gradients the P16 kernel takes), at most 64 splits,
+// over the weight-gradient slab it grows here
+int Model::plan_set(int layer, int phase, const int plan[4]) {
+    if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    const int op = plan_op(phase);
+    const ConvGeom& g = L[layer].g;
+    const PlanKey k = conv_plan_key(op, g);
     if (plan == nullptr) {
-        niti::plan_override_clear(k);
+        plan_override_clear(k);
     } else {
-        auto tile_ok = [](int t) { return t == 64 || t == 128 || t == 256; };
-        const niti::ConvGeom& g = m->m.L[layer].g;
-        const bool taps = plan[0] == niti::PLAN_TAPS_TILE && plan[1] == niti::PLAN_TAPS_TILE &&
-                          op == niti::PLAN_WGRAD && niti::conv_wgrad_taps_ok(g);
-        const bool p16 = plan[0] == niti::PLAN_P16_TILE && plan[1] == niti::PLAN_P16_TILE &&
-                         op == niti::PLAN_WGRAD && niti::conv_wgrad_p16_ok(g);
-        if ((!taps && !p16 && (!tile_ok(plan[0]) || !tile_ok(plan[1]))) || plan[2] < 1 || plan[3] < 0 ||
-            plan[3] > 4 || ((taps || p16) && plan[3] == 1) || (plan[3] >= 3 && (op == niti::PLAN_WGRAD || plan[2] != 1)))
-            return NITI_INVALID_VALUE;
+        const bool p16 = plan[0] == PLAN_P16_TILE && plan[1] == PLAN_P16_TILE && op == PLAN_WGRAD && conv_wgrad_p16_ok(g);
+        if (!plan_valid(op, g, plan, p16)) return NITI_INVALID_VALUE;
         if (p16) {
             if (plan[2] > 64) return NITI_INVALID_VALUE;
-            if (!m->m.ensure_slab(niti::conv_wgrad_p16_workspace(g, plan[2]), true)) return NITI_OUT_OF_MEMORY;
+            if (!ensure_slab(conv_wgrad_p16_workspace(g, plan[2]), true)) return NITI_OUT_OF_MEMORY;
         }
-        niti::PlanChoice c;
-        c.bm = plan[0];
-        c.bn = plan[1];
-        c.splits = plan[2];
-        c.strat = plan[3];
-        if (c.strat == 2 && !p16 &&
-            !m->m.ensure_slab(std::min(niti::plan_slab_bytes(k.M, k.N, c.splits), size_t(1) << 30), op == niti::PLAN_WGRAD))
-            return NITI_OUT_OF_MEMORY;
-        niti::plan_override_set(k, c);
+        if (const int rc = plan_commit(k, op, plan, !p16)) return rc;
     }
-    m->m.drop_graph();
+    drop_graph();
     return NITI_NO_ERROR;
 }
 
-void niti_plan_reset(void) { niti::plan_override_clear_all(); }
-
-int niti_model_set_probe(niti_model_t m, int layer, int phase, int max_launches) {
-    if (m && m->r) {
-        if (max_launches < 0) return NITI_INVALID_VALUE;
-        niti::ResNetModel& r = *m->r;
-        r.clear_probe();
-        if (layer < 0) return NITI_NO_ERROR;
-        r.probe_layer = layer;
-        r.probe_phase = phase;
-        r.ev0.resize(max_launches);
-        r.ev1.resize(max_launches);
-        for (int i = 0; i < max_launches; ++i)
-            if (hipEventCreateWithFlags(&r.ev0[i], hipEventDisableSystemFence) != hipSuccess ||
-                hipEventCreateWithFlags(&r.ev1[i], hipEventDisableSystemFence) != hipSuccess)
-                return NITI_OUT_OF_MEMORY;
-        return NITI_NO_ERROR;
+int Model::set_rowconv(bool enable) {
+    if (use_rowconv && !enable) {
+        const int rc = refresh_wt(nullptr);
+        if (rc != NITI_NO_ERROR || hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
     }
-    if (!m || max_launches < 0) return NITI_INVALID_VALUE;
-    m->m.clear_probe();
-    if (layer < 0) return NITI_NO_ERROR;
-    m->m.probe_layer = layer;
-    m->m.probe_phase = phase;
-    m->m.ev0.resize(max_launches);
-    m->m.ev1.resize(max_launches);
-    for (int i = 0; i < max_launches; ++i)
-        // timing events without the system-scope cache writeback / invalidate (it delays the
-        // launch after the begin marker and is not needed to read the timestamps)
-        if (hipEventCreateWithFlags(&m->m.ev0[i], hipEventDisableSystemFence) != hipSuccess ||
-            hipEventCreateWithFlags(&m->m.ev1[i], hipEventDisableSystemFence) != hipSuccess)
-            return NITI_OUT_OF_MEMORY;
+    use_rowconv = enable;
+    drop_graph();
+    return NITI_NO_ERROR;
+}
+
+int Model::probe_alloc(int phase, int max_launches) {
     if (phase == 2 && max_launches > 0) {  // per launch, a {start, end} pair per block (zero: no block)
-        const size_t bytes = (size_t)max_launches * 2 * niti::SPAN_MAX_BLOCKS * 8;
-        if (hipMalloc(&m->m.span, bytes) != hipSuccess || hipMemset(m->m.span, 0, bytes) != hipSuccess)
-            return NITI_OUT_OF_MEMORY;
-        m->m.span_cap = max_launches;
+        const size_t bytes = (size_t)max_launches * 2 * SPAN_MAX_BLOCKS * 8;
+        if (hipMalloc(&span, bytes) != hipSuccess || hipMemset(span, 0, bytes) != hipSuccess) return NITI_OUT_OF_MEMORY;
+        span_cap = max_launches;
     }
     return NITI_NO_ERROR;
 }
 
-int niti_model_probe_read_span(niti_model_t m, double* total_ms, int* count) {
-    if (m && m->r) {
-        if (!total_ms || !count) return NITI_INVALID_VALUE;
-        *total_ms = 0;  // no in-kernel span probe on this driver
-        *count = 0;
-        return NITI_NO_ERROR;
-    }
-    if (!m || !total_ms || !count) return NITI_INVALID_VALUE;
+int Model::probe_read_span(double* total_ms, int* count) {
     *total_ms = 0;
     *count = 0;
-    if (m->m.span == nullptr || m->m.span_count == 0) return NITI_NO_ERROR;
+    if (span == nullptr || span_count == 0) return NITI_NO_ERROR;
     int dev = 0, khz = 0;
     if (hipDeviceSynchronize() != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
         return NITI_NO_EXECUTION;
-    constexpr size_t per = 2 * niti::SPAN_MAX_BLOCKS;
-    std::vector<unsigned long long> h(per * (size_t)m->m.span_count);
-    if (hipMemcpy(h.data(), m->m.span, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return NITI_NO_EXECUTION;
+    constexpr size_t per = 2 * SPAN_MAX_BLOCKS;
+    std::vector<unsigned long long> h(per * (size_t)span_count);
+    if (hipMemcpy(h.data(), span, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return NITI_NO_EXECUTION;
     double t = 0;
     int n = 0;
-    for (int i = 0; i < m->m.span_count; ++i) {  // first block start to last block end of launch i
+    for (int i = 0; i < span_count; ++i) {  // first block start to last block end of launch i
         unsigned long long lo = ~0ull, hi = 0;
         for (size_t b = 0; b < per; b += 2) {
             const unsigned long long s0 = h[per * i + b], s1 = h[per * i + b + 1];
@@ -2289,169 +1629,177 @@ int niti_model_probe_read_span(niti_model_t m, double* total_ms, int* count) {
     *total_ms = t;
     *count = n;
     // re-arm the slots for the next measurement
-    if (hipMemset(m->m.span, 0, h.size() * 8) != hipSuccess) return NITI_NO_EXECUTION;
-    m->m.span_count = 0;
+    if (hipMemset(span, 0, h.size() * 8) != hipSuccess) return NITI_NO_EXECUTION;
+    span_count = 0;
     return NITI_NO_ERROR;
 }
 
-int niti_model_probe_pause(niti_model_t m, int paused) {
-    if (!m) return NITI_INVALID_VALUE;
-    if (m->r)
-        m->r->probe_paused = paused != 0;
+// ------------------------------------------------------------------------------ host access
+int Model::layer_info(int layer, int info[12]) const {
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+    const Layer& l = L[layer];
+    const ConvGeom& g = l.og;  // the layer as the network defines it
+    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, l.relu, l.pool};
+    memcpy(info, v, sizeof(v));
+    return NITI_NO_ERROR;
+}
+
+int Model::set_weight(int layer, const int8_t* w_host, int wscale) {
+    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
+    Layer& l = L[layer];
+    std::vector<int8_t> colw;
+    if (l.col) {  // upload the [co][32] im2col weights as the 1x1 geometry's OIHW
+        colw.resize((size_t)l.g.c_out * 32);
+        cols_from_oihw(l.og, w_host, colw.data(), 32);
+        w_host = colw.data();
+    }
+    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
+    int8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    int rc = NITI_NO_ERROR;
+    if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
+        oihw_to_ohwi16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
+        oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess ||
+        hipMemset(l.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess ||
+        (l.rc && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, nullptr) != hipSuccess) ||
+        (l.rcd && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, nullptr) != hipSuccess) ||
+        hipDeviceSynchronize() != hipSuccess)
+        rc = NITI_NO_EXECUTION;
+    l.wscale = (int8_t)wscale;
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int Model::get_weight(int layer, int8_t* w_host) {
+    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
+    Layer& l = L[layer];
+    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
+    int8_t* tmp = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    int rc = NITI_NO_ERROR;
+    std::vector<int8_t> colw(l.col ? n : 0);
+    if (ohwi16_to_oihw(l.w, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, tmp, nullptr) != hipSuccess ||
+        hipMemcpy(l.col ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = NITI_NO_EXECUTION;
+    if (rc == NITI_NO_ERROR && l.col) oihw_from_cols(l.og, colw.data(), w_host, 32);
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int Model::get_input(int8_t* x_nchw_host, int* ascale, hipStream_t st) {
+    const int n = batch, hw = in_h * in_w;
+    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
+    const size_t need = (size_t)n * in_c * hw;
+    int8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    int8_t e = 0;
+    hipError_t err = x0_nchw_valid ? hipMemcpy(tmp, x0n, need, hipMemcpyDeviceToDevice)
+                                   : nhwc16_to_nchw(x0, n, in_c, hw, round_up(in_c, 16), tmp, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(x_nchw_host, tmp, need, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(&e, exp0, 1, hipMemcpyDeviceToHost);
+    (void)hipFree(tmp);
+    if (ascale) *ascale = e;
+    return err == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
+}
+
+int Model::get_logits(int8_t* logits_host, int* exp_out, hipStream_t st) {
+    Layer& t = L.back();
+    const int n = batch;
+    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
+    std::vector<int8_t> buf((size_t)n * t.g.cop);
+    int8_t e = 0;
+    if (hipMemcpy(buf.data(), t.r, buf.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&e, t.exp, 1, hipMemcpyDeviceToHost) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    for (int i = 0; i < n; ++i) memcpy(logits_host + (size_t)i * t.g.c_out, buf.data() + (size_t)i * t.g.cop, t.g.c_out);
+    if (exp_out) *exp_out = e;
+    return NITI_NO_ERROR;
+}
+
+int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) {
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+    Layer& l = L[layer];
+    const ConvGeom& g = l.g;
+    const int n = batch;
+    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
+    int8_t* tmp = nullptr;
+    size_t need = 0;
+    if (which == 0 || which == 2)
+        need = (size_t)n * g.c_out * g.oh * g.ow;
+    else if (which == 1 && g8_written)
+        need = (size_t)g.c_out * g.c_in * g.kh * g.kw;
     else
-        m->m.probe_paused = paused != 0;
-    return NITI_NO_ERROR;
+        return NITI_INVALID_VALUE;
+    const size_t out_need = which == 1 && l.col ? (size_t)l.og.c_out * l.og.c_in * l.og.kh * l.og.kw : need;
+    if (bytes < out_need) return NITI_INVALID_VALUE;
+    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    hipError_t e;
+    if (which == 0 && !l.r_written) {  // (a pooled layer whose route went as codes under keep_grads(0))
+        (void)hipFree(tmp);
+        return NITI_INVALID_VALUE;
+    }
+    if (which == 0)
+        e = nhwc16_to_nchw(l.r, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
+    else if (which == 2 && !dy16_valid[layer]) {  // rebuilt from the C32 copy the step wrote
+        int8_t* d16 = nullptr;
+        e = hipMalloc(&d16, (size_t)n * g.oh * g.ow * g.cop);
+        if (e == hipSuccess) e = c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, d16, nullptr);
+        if (e == hipSuccess) e = nhwc16_to_nchw(d16, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (d16) (void)hipFree(d16);
+    } else if (which == 2)
+        e = nhwc16_to_nchw(l.dy, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
+    else
+        e = ohwi16_to_oihw(l.g8, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
+    if (which == 1 && l.col) {
+        std::vector<int8_t> colw(need);
+        if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) oihw_from_cols(l.og, colw.data(), host, 32);
+    } else if (e == hipSuccess) {
+        e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(tmp);
+    return e == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
 
-int niti_model_probe_read(niti_model_t m, double* total_ms, int* count) {
-    if (m && m->r) {
-        if (!total_ms || !count) return NITI_INVALID_VALUE;
-        niti::ResNetModel& r = *m->r;
-        double t = 0;
-        for (int i = 0; i < r.probe_count; ++i) {
-            float ms = 0.f;
-            if (hipEventSynchronize(r.ev1[i]) != hipSuccess || hipEventElapsedTime(&ms, r.ev0[i], r.ev1[i]) != hipSuccess)
-                return NITI_NO_EXECUTION;
-            t += ms;
+int64_t Model::step_macs() const {
+    int64_t s = 0;
+    for (size_t i = 0; i < L.size(); ++i) {
+        const int64_t f = L[i].macs();
+        s += f;            // forward
+        s += f;            // weight gradient
+        if (i > 0) s += f; // input gradient
+    }
+    return s;
+}
+
+int Model::spec_stats(uint32_t* out, int max_layers) {
+    const int nl = std::min(max_layers, (int)L.size());
+    std::fill(out, out + (size_t)nl * 6, 0u);
+    for (int i = 0; i < nl; ++i) {
+        const Layer& l = L[i];
+        for (int d = 0; d < 2; ++d) {  // forward / input-gradient slot: hint, redone launches, stored pairs
+            uint32_t w[5] = {0, 0, 0, 0, 0}, gw[4] = {0, 0, 0, 0};
+            if (l.bar != nullptr &&
+                hipMemcpy(w, rowconv_spec_slot(l.bar, d != 0), sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
+                return NITI_INVALID_VALUE;
+            // the GEMM path's pair (plan strategy 3): its own slot, no store mode
+            if (l.gspec != nullptr &&
+                hipMemcpy(gw, l.gspec + d * GEMM_SPEC_SLOT_WORDS, sizeof(gw), hipMemcpyDeviceToHost) != hipSuccess)
+                return NITI_INVALID_VALUE;
+            out[i * 6 + d * 3] = std::max(w[0], gw[0]);
+            out[i * 6 + d * 3 + 1] = w[2] + gw[2];
+            out[i * 6 + d * 3 + 2] = w[4] + gw[3];  // the GEMM pair: misses settled from an alternate
         }
-        *total_ms = t;
-        *count = r.probe_count;
-        r.probe_count = 0;
-        return NITI_NO_ERROR;
     }
-    if (!m || !total_ms || !count) return NITI_INVALID_VALUE;
-    double t = 0;
-    for (int i = 0; i < m->m.probe_count; ++i) {
-        float ms = 0.f;
-        if (hipEventSynchronize(m->m.ev1[i]) != hipSuccess ||
-            hipEventElapsedTime(&ms, m->m.ev0[i], m->m.ev1[i]) != hipSuccess)
-            return NITI_NO_EXECUTION;
-        t += ms;
-    }
-    *total_ms = t;
-    *count = m->m.probe_count;
-    m->m.probe_count = 0;
     return NITI_NO_ERROR;
 }
 
-extern "C++" {
-// hand a communicator pair to whichever step driver the handle holds
-template <class M>
-static void attach_to(M& d, std::unique_ptr<niti::Collective> c, std::unique_ptr<niti::Collective> cg, bool shared,
-                      int world, int rank, int exact) {
-    d.drop_graph();
-    d.coll = std::move(c);
-    d.coll_grad = std::move(cg);
-    d.shared_comm = shared;
-    d.world = world;
-    d.rank = rank;
-    d.exact = exact ? 1 : 0;
-}
-static void attach(niti_model_t m, std::unique_ptr<niti::Collective> c, std::unique_ptr<niti::Collective> cg,
-                   bool shared, int world, int rank, int exact) {
-    if (m->r)
-        attach_to(*m->r, std::move(c), std::move(cg), shared, world, rank, exact);
-    else
-        attach_to(m->m, std::move(c), std::move(cg), shared, world, rank, exact);
-}
-}  // extern "C++"
-
-int niti_dp_get_unique_id(char id[NITI_UNIQUE_ID_BYTES]) {
-    static_assert(sizeof(ncclUniqueId) == NITI_UNIQUE_ID_BYTES, "ncclUniqueId size");
-    ncclUniqueId u;
-    if (ncclGetUniqueId(&u) != ncclSuccess) return NITI_NO_EXECUTION;
-    memcpy(id, &u, sizeof(u));
-    return NITI_NO_ERROR;
+std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, int* rc) {
+    auto m = std::make_unique<Model>();
+    *rc = m->build(arch, batch, in_hw);
+    if (*rc != NITI_NO_ERROR) return nullptr;
+    return m;
 }
 
-int niti_model_attach_comm(niti_model_t m, const char id[NITI_UNIQUE_ID_BYTES], int rank, int world, int exact) {
-    if (!m || !id || world < 1 || rank < 0 || rank >= world) return NITI_INVALID_VALUE;
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    // the split-agreement flag and stream first: a local allocation failure then returns before any
-    // collective call, instead of leaving the peers blocked in one this rank never enters
-    int32_t* flag = nullptr;
-    hipStream_t ast = nullptr;
-    if (hipMalloc(&flag, sizeof(int32_t)) != hipSuccess || hipStreamCreate(&ast) != hipSuccess) {
-        if (flag) (void)hipFree(flag);
-        return NITI_OUT_OF_MEMORY;
-    }
-    auto c = std::make_unique<niti::RcclCollective>();
-    if (ncclCommInitRank(&c->comm, world, u, rank) != ncclSuccess) {
-        (void)hipFree(flag);
-        (void)hipStreamDestroy(ast);
-        return NITI_NO_EXECUTION;
-    }
-    c->world = world;
-    // the gradient communicator: split off the first (collective over the ranks), its own
-    // resources, so its SUMs and the ranges' MAXes are not serialised against each other
-    auto cg = std::make_unique<niti::RcclCollective>();
-    const bool split_ok = ncclCommSplit(c->comm, 0, rank, &cg->comm, nullptr) == ncclSuccess;
-    // every rank must pick the same mode (the SUMs run on different communicators and streams in
-    // the two modes): agree on the split's success with a MIN over the range communicator, which
-    // every rank enters whatever its own split did
-    int32_t ok = split_ok ? 1 : 0;
-    const bool agreed = hipMemcpyAsync(flag, &ok, sizeof(ok), hipMemcpyHostToDevice, ast) == hipSuccess &&
-                        ncclAllReduce(flag, flag, 1, ncclInt32, ncclMin, c->comm, ast) == ncclSuccess &&
-                        hipMemcpyAsync(&ok, flag, sizeof(ok), hipMemcpyDeviceToHost, ast) == hipSuccess &&
-                        hipStreamSynchronize(ast) == hipSuccess;
-    (void)hipFree(flag);
-    (void)hipStreamDestroy(ast);
-    if (!agreed) {
-        if (split_ok) (void)ncclCommDestroy(cg->comm);
-        cg->comm = nullptr;
-        (void)ncclCommDestroy(c->comm);
-        c->comm = nullptr;
-        return NITI_NO_EXECUTION;
-    }
-    bool shared = false;
-    if (ok == 0) {
-        // some rank has no split: every rank's gradient SUMs use the range communicator, in the
-        // step's program order
-        if (split_ok) (void)ncclCommDestroy(cg->comm);
-        cg->comm = c->comm;
-        cg->owns = false;
-        shared = true;
-    }
-    cg->world = world;
-    attach(m, std::move(c), std::move(cg), shared, world, rank, exact);
-    return NITI_NO_ERROR;
-}
-
-struct niti_local_group {
-    std::shared_ptr<niti::LocalGroup> g;
-};
-
-int niti_local_group_create(int world, niti_local_group_t* out) {
-    if (!out || world < 1 || world > niti::LocalGroup::MAX_RANKS) return NITI_INVALID_VALUE;
-    auto* h = new niti_local_group();
-    h->g = std::make_shared<niti::LocalGroup>();
-    h->g->world = world;
-    if (hipStreamCreateWithFlags(&h->g->rst, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return NITI_NO_EXECUTION;
-    }
-    *out = h;
-    return NITI_NO_ERROR;
-}
-
-void niti_local_group_destroy(niti_local_group_t g) { delete g; }
-
-int niti_model_attach_local(niti_model_t m, niti_local_group_t g, int rank, int exact) {
-    if (!m || !g || rank < 0 || rank >= g->g->world) return NITI_INVALID_VALUE;
-    auto c = std::make_unique<niti::LocalCollective>();
-    c->g = g->g;
-    c->rank = rank;
-    c->chan = 0;
-    auto cg = std::make_unique<niti::LocalCollective>();
-    cg->g = g->g;
-    cg->rank = rank;
-    // NITI_DIAG_SHARED_COMM=1 (tests): the gradient SUMs on the range channel, as attach_comm's
-    // no-split fallback runs them on one RCCL communicator
-    const bool shared = getenv("NITI_DIAG_SHARED_COMM") != nullptr;
-    cg->chan = shared ? 0 : 1;
-    attach(m, std::move(c), std::move(cg), shared, g->g->world, rank, exact);
-    return NITI_NO_ERROR;
-}
-
-}  // extern "C"
+}  // namespace niti

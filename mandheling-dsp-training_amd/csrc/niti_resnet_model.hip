@@ -29,11 +29,6 @@
 
 namespace niti {
 
-#define RTRY(expr)                                          \
-    do {                                                    \
-        if ((expr) != hipSuccess) return NITI_NO_EXECUTION; \
-    } while (0)
-
 static ConvGeom make_geom(int n, int ci, int h, int co, int k, int s, int p) {
     ConvGeom g{};
     g.n = n;
@@ -252,50 +247,9 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     amax_bytes = (3 * C.size() + 2 * B.size() + 1) * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (!amax) return NITI_OUT_OF_MEMORY;
-    ev_ws_bytes = head_metrics_workspace(batch);
-    ev_ws = ws.alloc(ev_ws_bytes);
-    ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
-    ev_pred = (int32_t*)ws.alloc((size_t)batch * 4);
-    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
-    if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess ||
-        hipMemset(ev_pred, 0, (size_t)batch * 4) != hipSuccess)
-        return NITI_NO_EXECUTION;
+    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2)});  // (the bucket SUMs)
+    if (const int rc = alloc_eval()) return rc;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
-}
-
-ResNetModel::~ResNetModel() {
-    clear_probe();
-    drop_graph();
-    if (cst) (void)hipStreamSynchronize(cst);
-    for (auto e : ev_bucket) (void)hipEventDestroy(e);
-    if (ev_grads) (void)hipEventDestroy(ev_grads);
-    if (gin) (void)hipEventDestroy(gin);
-    if (gout) (void)hipEventDestroy(gout);
-    if (gstream) (void)hipStreamDestroy(gstream);
-    coll_grad.reset();
-    coll.reset();
-    if (cst) (void)hipStreamDestroy(cst);
-}
-
-bool ResNetModel::ensure_slab(size_t bytes, bool wgrad) {
-    void*& p = wgrad ? slab_w : slab;
-    size_t& have = wgrad ? slab_w_bytes : slab_bytes;
-    if (have >= bytes) return true;
-    if (hipDeviceSynchronize() != hipSuccess) return false;
-    void* s2 = ws.alloc(bytes);
-    if (!s2) return false;
-    p = s2;
-    have = bytes;
-    return true;
-}
-
-void ResNetModel::clear_probe() {
-    for (auto e : ev0) (void)hipEventDestroy(e);
-    for (auto e : ev1) (void)hipEventDestroy(e);
-    ev0.clear();
-    ev1.clear();
-    probe_count = 0;
-    probe_layer = probe_phase = -1;
 }
 
 void ResNetModel::probe(int layer, int phase, bool begin, hipStream_t st) {
@@ -324,7 +278,7 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
     probe(i, 0, true, st);
     if (rows_on(i)) {
         const bool xn = rowconv_nhwc_pref(g);
-        if (!xn) RTRY(nhwc16_to_c32(c.in, g.n, g.h * g.w, g.cip, g.c_in, c.xc32, st));
+        if (!xn) DTRY(nhwc16_to_c32(c.in, g.n, g.h * g.w, g.cip, g.c_in, c.xc32, st));
         const int8_t* xin = xn ? c.in : c.xc32;
         RowConvOut o;
         o.x_nhwc = xn ? 1 : 0;
@@ -334,17 +288,17 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
         o.exp_out = c.y_exp;
         o.relu = c.relu;
         if (!dp && !capturing && rowconv_fused_ok(g)) {
-            RTRY(rowconv_fwd(g, xin, c.wf, o, 0, rng(i, 0), c.bar, ++c.epoch, rc_err, st));
+            DTRY(rowconv_fwd(g, xin, c.wf, o, 0, rng(i, 0), c.bar, ++c.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {
             o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;
-            RTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_A, rng(i, 0), c.bar, 0, nullptr, st));
-            if (dp && exact) RTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            RTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_B, rng(i, 0), c.bar, 0, nullptr, st));
+            DTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_A, rng(i, 0), c.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_B, rng(i, 0), c.bar, 0, nullptr, st));
         } else {
             o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;
-            RTRY(rowconv_fwd(g, xin, c.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) RTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            RTRY(rowconv_fwd(g, xin, c.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fwd(g, xin, c.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(g, xin, c.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
         }
         probe(i, 0, false, st);
         return NITI_NO_ERROR;
@@ -372,20 +326,20 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
         const hipError_t e = conv_fwd_fused(g, c.in, c.w, o, FusedBar{c.bar, c.epoch + 1, rc_err}, st);
         if (e != hipErrorNotSupported) {
             ++c.epoch;
-            RTRY(e);
+            DTRY(e);
             probe(i, 0, false, st);
             return NITI_NO_ERROR;
         }
     }
     if (conv_fwd_spec_ok(g)) {  // the GEMM's speculative pair (plan strategy 3)
         int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        RTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 0, st, alt));
-        if (dp && exact) RTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 1, st, alt));
+        DTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 0, st, alt));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 1, st, alt));
     } else {
-        RTRY(conv_fwd_phase1(g, c.in, c.w, acc, rng(i, 0), slab, slab_bytes, st));
-        if (dp && exact) RTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(conv_fwd_phase2(g, c.in, c.w, acc, rng(i, 0), o, slab_bytes, st));
+        DTRY(conv_fwd_phase1(g, c.in, c.w, acc, rng(i, 0), slab, slab_bytes, st));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_fwd_phase2(g, c.in, c.w, acc, rng(i, 0), o, slab_bytes, st));
     }
     probe(i, 0, false, st);
     return NITI_NO_ERROR;
@@ -402,7 +356,7 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
     if (rows_dg_on(i)) {
         const ConvGeom& d = c.dg;
         const bool xn = rowconv_nhwc_pref(d);
-        if (!xn) RTRY(nhwc16_to_c32(c.dy, g.n, g.oh * g.ow, g.cop, g.c_out, c.dyc32, st));
+        if (!xn) DTRY(nhwc16_to_c32(c.dy, g.n, g.oh * g.ow, g.cop, g.c_out, c.dyc32, st));
         const int8_t* dyin = xn ? c.dy : c.dyc32;
         RowConvOut o;
         o.x_nhwc = xn ? 1 : 0;
@@ -413,17 +367,17 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
         o.exp_out = c.dx_exp;
         o.dgrad_slot = 1;
         if (!dp && !capturing && rowconv_fused_ok(d, true)) {
-            RTRY(rowconv_fwd(d, dyin, c.wft, o, 0, rng(i, 1), c.bar, ++c.epoch, rc_err, st));
+            DTRY(rowconv_fwd(d, dyin, c.wft, o, 0, rng(i, 1), c.bar, ++c.epoch, rc_err, st));
         } else if (rowconv_spec2_on()) {
             o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            RTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_A, rng(i, 1), c.bar, 0, nullptr, st));
-            if (dp && exact) RTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            RTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_B, rng(i, 1), c.bar, 0, nullptr, st));
+            DTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_A, rng(i, 1), c.bar, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_B, rng(i, 1), c.bar, 0, nullptr, st));
         } else {
             o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            RTRY(rowconv_fwd(d, dyin, c.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) RTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            RTRY(rowconv_fwd(d, dyin, c.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
+            DTRY(rowconv_fwd(d, dyin, c.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
+            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+            DTRY(rowconv_fwd(d, dyin, c.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
         }
         probe(i, 1, false, st);
         return NITI_NO_ERROR;
@@ -439,21 +393,21 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
         const hipError_t e = conv_dgrad_fused(g, c.dy, c.wT, o, FusedBar{c.bar, c.epoch + 1, rc_err}, st);
         if (e != hipErrorNotSupported) {
             ++c.epoch;
-            RTRY(e);
+            DTRY(e);
             probe(i, 1, false, st);
             return NITI_NO_ERROR;
         }
     }
     if (conv_dgrad_spec_ok(g)) {
         int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        RTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 0, st, alt));
-        if (dp && exact) RTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 1, st, alt));
+        DTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 0, st, alt));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 1, st, alt));
     } else {
         const int8_t* subw = subpix_on() ? c.subw : nullptr;  // stride 2: four sub-pixel class GEMMs
-        RTRY(conv_dgrad_phase1(g, c.dy, c.wT, acc, rng(i, 1), slab, slab_bytes, st, subw));
-        if (dp && exact) RTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(conv_dgrad_phase2(g, c.dy, c.wT, acc, rng(i, 1), o, slab_bytes, st, subw));
+        DTRY(conv_dgrad_phase1(g, c.dy, c.wT, acc, rng(i, 1), slab, slab_bytes, st, subw));
+        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(conv_dgrad_phase2(g, c.dy, c.wT, acc, rng(i, 1), o, slab_bytes, st, subw));
     }
     probe(i, 1, false, st);
     return NITI_NO_ERROR;
@@ -467,7 +421,7 @@ int ResNetModel::wgrad_conv(int i, hipStream_t st) {
     // single device, in the step: a split-K plan leaves its (own) slabs to the update's combine
     const bool defer = in_step && !dp() && !capturing && !tuning && ensure_wslab(i);
     c.defer = SgdJob{};
-    RTRY(conv_wgrad_acc(c.g, c.in, c.dy, c.dwacc, dp() ? nullptr : rng(i, 2), defer ? c.wslab : slab_w,
+    DTRY(conv_wgrad_acc(c.g, c.in, c.dy, c.dwacc, dp() ? nullptr : rng(i, 2), defer ? c.wslab : slab_w,
                         defer ? c.wslab_bytes : slab_w_bytes, st, nullptr, defer ? &c.defer : nullptr));
     probe(i, 2, false, st);
     return NITI_NO_ERROR;
@@ -515,23 +469,23 @@ int ResNetModel::residual_fwd(int k, hipStream_t st) {
         const hipError_t e = residual_fused(cb.y, cb.y_exp, sc, es, b.out_elems, b.ez, b.out_exp, 1, b.out, res_bar,
                                             ++res_epoch, rc_err, st);
         if (e != hipErrorNotSupported) {
-            RTRY(e);
+            DTRY(e);
             return NITI_NO_ERROR;
         }
         --res_epoch;
     }
     if (res_spec_on()) {  // the speculative pair: one pass of the sum while its bit width holds
         uint32_t* slot = res_slot + (2 * k) * RES_SPEC_SLOT_WORDS;
-        RTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
+        DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
                               nullptr, 1, slot));
-        if (dp() && exact) RTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
+        if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
                               nullptr, 2, slot));
         return NITI_NO_ERROR;
     }
-    RTRY(residual_add(cb.y, cb.y_exp, sc, es, b.out_elems, nullptr, nullptr, rng_blk(k, 0), st));
-    if (dp() && exact) RTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
-    RTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st));
+    DTRY(residual_add(cb.y, cb.y_exp, sc, es, b.out_elems, nullptr, nullptr, rng_blk(k, 0), st));
+    if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
+    DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st));
     return NITI_NO_ERROR;
 }
 
@@ -546,7 +500,7 @@ int ResNetModel::residual_bwd(int k, hipStream_t st) {
         const hipError_t e = residual_fused(b.dua, ca.dx_exp, s, es, b.in_elems, b.ezb, b.du_exp, 0, b.du, res_bar,
                                             ++res_epoch, rc_err, st, k > 0 ? B[k - 1].out : nullptr);
         if (e != hipErrorNotSupported) {
-            RTRY(e);
+            DTRY(e);
             return NITI_NO_ERROR;
         }
         --res_epoch;
@@ -554,68 +508,16 @@ int ResNetModel::residual_bwd(int k, hipStream_t st) {
     const int8_t* mask = k > 0 ? B[k - 1].out : nullptr;
     if (res_spec_on()) {  // the speculative pair (residual_fwd)
         uint32_t* slot = res_slot + (2 * k + 1) * RES_SPEC_SLOT_WORDS;
-        RTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
+        DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
                               1, slot));
-        if (dp() && exact) RTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
-        RTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
+        if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
                               2, slot));
         return NITI_NO_ERROR;
     }
-    RTRY(residual_add(b.dua, ca.dx_exp, s, es, b.in_elems, nullptr, nullptr, rng_blk(k, 1), st));
-    if (dp() && exact) RTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
-    RTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask));
-    return NITI_NO_ERROR;
-}
-
-// ------------------------------------------------------------------------------ data parallel
-void ResNetModel::plan_buckets() {
-    const int nl = (int)C.size();
-    bucket_lo.assign(nl, 0);
-    closes_bucket.assign(nl, 0);
-    size_t a = 0;
-    int hi = nl - 1;
-    for (int i = nl - 1; i >= 0; --i) {
-        a += (size_t)C[i].w_elems() * 4;
-        if (a >= bucket_min_bytes || i == 0) {
-            closes_bucket[i] = 1;
-            for (int j = i; j <= hi; ++j) bucket_lo[j] = i;
-            a = 0;
-            hi = i - 1;
-        }
-    }
-}
-
-int ResNetModel::ensure_comm_stream() {
-    if (cst) return NITI_NO_ERROR;
-    if (hipStreamCreateWithFlags(&cst, hipStreamNonBlocking) != hipSuccess) return NITI_NO_EXECUTION;
-    constexpr unsigned kFlags = hipEventDisableTiming | hipEventReleaseToDevice;
-    ev_bucket.assign(C.size(), nullptr);
-    for (auto& e : ev_bucket)
-        if (hipEventCreateWithFlags(&e, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
-    if (hipEventCreateWithFlags(&ev_grads, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
-    plan_buckets();
-    return NITI_NO_ERROR;
-}
-
-// the bucket of convs [lo, hi] (contiguous in grad_bucket; the weight gradients run in descending
-// layer order, so it is complete once conv lo's is in): SUM over the ranks, then every layer's range
-// of the summed gradient (NITI_GradientConv_Int8.cpp:274-296 over the global batch)
-int ResNetModel::sum_bucket(int lo, hipStream_t st) {
-    int hi = lo;
-    while (hi + 1 < (int)C.size() && bucket_lo[hi + 1] == lo) ++hi;
-    if (hi - lo + 1 > ABSMAX_MAX_JOBS) return NITI_NOT_SUPPORT;
-    size_t elems = 0;
-    for (int j = lo; j <= hi; ++j) elems += (size_t)C[j].w_elems();
-    AbsmaxJob jobs[ABSMAX_MAX_JOBS];
-    for (int j = lo; j <= hi; ++j) jobs[j - lo] = AbsmaxJob{C[j].dwacc, C[j].w_elems(), rng(j, 2), 0};
-    hipStream_t s = st;
-    if (!shared_comm) {  // own communicator: its own stream, overlapping the rest of the backward pass
-        RTRY(hipEventRecord(ev_bucket[lo], st));
-        RTRY(hipStreamWaitEvent(cst, ev_bucket[lo], 0));
-        s = cst;
-    }
-    RTRY(coll_grad->allreduce(C[lo].dwacc, elems, COLL_SUM_I32, s));
-    RTRY(absmax_many(jobs, hi - lo + 1, s));
+    DTRY(residual_add(b.dua, ca.dx_exp, s, es, b.in_elems, nullptr, nullptr, rng_blk(k, 1), st));
+    if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
+    DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask));
     return NITI_NO_ERROR;
 }
 
@@ -646,7 +548,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     const RBlock& bl = B.back();
     const ConvGeom& gl = C[bl.b].g;
     RConv& f = C[fc];
-    RTRY(loss_grad(f.y, n, classes, f.g.cop, f.y_exp, labels, f.dy, st));
+    DTRY(loss_grad(f.y, n, classes, f.g.cop, f.y_exp, labels, f.dy, st));
     // backward: weight gradients in descending layer order (gradient buckets close in memory order)
     auto wg = [&](int i) {
         int r = wgrad_conv(i, st);
@@ -654,7 +556,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         return r;
     };
     if ((rc = dgrad_conv(fc, st)) != NITI_NO_ERROR || (rc = wg(fc)) != NITI_NO_ERROR) return rc;
-    RTRY(sum_pool_grad(dg, n, gl.oh * gl.ow, 512, bl.dz, st, bl.out));  // + the last block's relu gradient
+    DTRY(sum_pool_grad(dg, n, gl.oh * gl.ow, 512, bl.dz, st, bl.out));  // + the last block's relu gradient
     for (int k = (int)B.size() - 1; k >= 0; --k) {
         const RBlock& b = B[k];
         if (b.p >= 0 && (rc = wg(b.p)) != NITI_NO_ERROR) return rc;
@@ -666,12 +568,12 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     // the stem: overlapping 3x3 / 2 max-pool gradient (first max wins) with the relu gradient, then
     // its weight gradient over the im2col
     // (the relu mask from the pooled output: the pre-pool output may not exist)
-    RTRY(maxpool_relu_grad_arg(nullptr, pool_ws, B[0].du, n, stem.oh, stem.ow, 64, 3, 2, 1, ph, ph, 1, d0, st, p0));
+    DTRY(maxpool_relu_grad_arg(nullptr, pool_ws, B[0].du, n, stem.oh, stem.ow, 64, 3, 2, 1, ph, ph, 1, d0, st, p0));
     if ((rc = wg(0)) != NITI_NO_ERROR) return rc;
     if (dp) {  // every bucket summed and ranged before the update
         if (!shared_comm) {
-            RTRY(hipEventRecord(ev_grads, cst));
-            RTRY(hipStreamWaitEvent(st, ev_grads, 0));
+            DTRY(hipEventRecord(ev_grads, cst));
+            DTRY(hipStreamWaitEvent(st, ev_grads, 0));
         }
     }
     // NITI_SGD (NITI_SGD.hpp:20-54) for every layer in one launch, after every input gradient read the
@@ -706,7 +608,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
             jobs[i].tb_s = c.defer.tb_s;
         }
     }
-    RTRY(sgd_update_many(jobs, nl, st));
+    DTRY(sgd_update_many(jobs, nl, st));
     g8_written = keep_grads;
     return NITI_NO_ERROR;
 }
@@ -722,33 +624,33 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
     auto fill = [&](void* p, int v, size_t bytes) {
         return by_kernel ? fill_kernel(p, v, bytes, st) : hipMemsetAsync(p, v, bytes, st);
     };
-    if (images == nullptr || amax_bytes % 16 != 0) RTRY(fill(amax, 0, amax_bytes));
+    if (images == nullptr || amax_bytes % 16 != 0) DTRY(fill(amax, 0, amax_bytes));
     // input: NITIInt8Train's quantiser (MnistUtils.cpp:83-93) on uint8 images, or int8 x as given
     const int64_t px = (int64_t)n * 3 * in_hw * in_hw;
     const int8_t* xq = x_nchw;
     if (images != nullptr) {
         int ns = 0;
-        RTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
+        DTRY(image_stats_slots(images, px, qslots, &ns, st, amax_bytes % 16 == 0 ? amax : nullptr,
                                amax_bytes % 16 == 0 ? amax_bytes : 0));
-        RTRY(stats_finalize(qslots, ns, qstats, st));
+        DTRY(stats_finalize(qslots, ns, qstats, st));
         if (dp && exact) {
-            RTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
-            RTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
+            DTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
+            DTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
         }
-        RTRY(image_quantize(images, n, 3, in_hw * in_hw, 3, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
+        DTRY(image_quantize(images, n, 3, in_hw * in_hw, 3, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
         xq = x0n;
     } else {
-        RTRY(fill(exp0, exp_in, 1));
-        RTRY(by_kernel ? copy_kernel(x0n, x_nchw, (size_t)px, st)
+        DTRY(fill(exp0, exp_in, 1));
+        DTRY(by_kernel ? copy_kernel(x0n, x_nchw, (size_t)px, st)
                        : hipMemcpyAsync(x0n, x_nchw, (size_t)px, hipMemcpyDeviceToDevice, st));
     }
-    RTRY(im2col_small(stem, xq, STEM_KP, xcol, st, true));
+    DTRY(im2col_small(stem, xq, STEM_KP, xcol, st, true));
     // forward
     int rc = fwd_conv(0, st);
     if (rc != NITI_NO_ERROR) return rc;
     const int ph = C[B[0].a].g.h;  // the stem's pooled size
     if (!stem_pooled)  // (else fused into the stem's requantise pass)
-        RTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, 64, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
+        DTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, 64, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
     for (int k = 0; k < (int)B.size(); ++k) {
         const RBlock& b = B[k];
         if ((rc = fwd_conv(b.a, st)) != NITI_NO_ERROR) return rc;
@@ -759,8 +661,8 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
     // global sum pool + requantisation, the fc head
     const RBlock& bl = B.back();
     const ConvGeom& gl = C[bl.b].g;
-    RTRY(sum_pool(bl.out, n, gl.oh * gl.ow, gl.cop, gsum, rng_pool(), st));
-    if (dp && exact) RTRY(coll->allreduce(rng_pool(), MAX_WORDS, COLL_MAX_U32, st));
+    DTRY(sum_pool(bl.out, n, gl.oh * gl.ow, gl.cop, gsum, rng_pool(), st));
+    if (dp && exact) DTRY(coll->allreduce(rng_pool(), MAX_WORDS, COLL_MAX_U32, st));
     {
         ActRequant r;
         r.acc = gsum;
@@ -770,7 +672,7 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
         r.exp_in = bl.out_exp;
         r.exp_out = eg;
         r.out_nhwc16 = g8pool;
-        RTRY(requant_act(r, st));
+        DTRY(requant_act(r, st));
     }
     return fwd_conv(fc, st);
 }
@@ -794,22 +696,25 @@ int ResNetModel::eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, c
     probe_paused = paused;
     if (rc != NITI_NO_ERROR) return rc;
     const RConv& f = C.back();
-    RTRY(head_metrics(f.y, batch, classes, f.g.cop, f.y_exp, labels, std::min(ev_topk, classes), ev_pred, nullptr,
+    DTRY(head_metrics(f.y, batch, classes, f.g.cop, f.y_exp, labels, std::min(ev_topk, classes), ev_pred, nullptr,
                       ev_totals, ev_ws, ev_ws_bytes, st));
     return NITI_NO_ERROR;
 }
 
 // Every conv's weights and weight scale from `src` (same input size and class count, any batch),
 // device to device on `st`, then this model's derived copies from them.
-int ResNetModel::copy_weights_from(ResNetModel& src, hipStream_t st) {
+int ResNetModel::copy_weights_from(StepDriver& other, hipStream_t st) {
+    ResNetModel* sp = dynamic_cast<ResNetModel*>(&other);
+    if (sp == nullptr) return NITI_INVALID_VALUE;
+    ResNetModel& src = *sp;
     if (src.in_hw != in_hw || src.classes != classes || src.C.size() != C.size()) return NITI_INVALID_VALUE;
     for (size_t i = 0; i < C.size(); ++i)
         if (C[i].w_elems() != src.C[i].w_elems()) return NITI_INVALID_VALUE;
     if (&src == this) return NITI_NO_ERROR;
     for (size_t i = 0; i < C.size(); ++i) {
         RConv& c = C[i];
-        RTRY(copy_kernel(c.w, src.C[i].w, (size_t)c.w_elems(), st));
-        RTRY(copy_kernel(c.ws_dev, src.C[i].ws_dev, 1, st));
+        DTRY(copy_kernel(c.w, src.C[i].w, (size_t)c.w_elems(), st));
+        DTRY(copy_kernel(c.ws_dev, src.C[i].ws_dev, 1, st));
         c.wscale = src.C[i].wscale;
         const int rc = refresh_copies((int)i, st);
         if (rc != NITI_NO_ERROR) return rc;
@@ -831,12 +736,8 @@ int ResNetModel::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, c
     const void* kx = x_nchw ? (const void*)x_nchw : (const void*)images;
     if (gexec == nullptr || kx != gkey_x || labels != gkey_l || exp_in != gkey_e) {
         drop_graph();
-        if (!gstream) {
-            RTRY(hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking));
-            RTRY(hipEventCreateWithFlags(&gin, hipEventDisableTiming));
-            RTRY(hipEventCreateWithFlags(&gout, hipEventDisableTiming));
-        }
-        RTRY(hipStreamBeginCapture(gstream, hipStreamCaptureModeThreadLocal));
+        if (const int rc = ensure_graph_stream()) return rc;
+        DTRY(hipStreamBeginCapture(gstream, hipStreamCaptureModeThreadLocal));
         capturing = true;
         const int rc = run(x_nchw, exp_in, images, labels, gstream);
         capturing = false;
@@ -854,11 +755,11 @@ int ResNetModel::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, c
         gkey_l = labels;
         gkey_e = exp_in;
     }
-    RTRY(hipEventRecord(gin, st));
-    RTRY(hipStreamWaitEvent(gstream, gin, 0));
-    RTRY(hipGraphLaunch(gexec, gstream));
-    RTRY(hipEventRecord(gout, gstream));
-    RTRY(hipStreamWaitEvent(st, gout, 0));
+    DTRY(hipEventRecord(gin, st));
+    DTRY(hipStreamWaitEvent(gstream, gin, 0));
+    DTRY(hipGraphLaunch(gexec, gstream));
+    DTRY(hipEventRecord(gout, gstream));
+    DTRY(hipStreamWaitEvent(st, gout, 0));
     return NITI_NO_ERROR;
 }
 
@@ -870,9 +771,8 @@ int ResNetModel::autotune(hipStream_t st, int reps) {
     if (reps < 1) reps = 5;
     if (!ensure_slab(size_t(96) << 20, false) || !ensure_slab(size_t(96) << 20, true)) return NITI_OUT_OF_MEMORY;
     drop_graph();
-    hipEvent_t ev[2];
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) return NITI_NO_EXECUTION;
+    TuneTimer timer;
+    if (const int rc = timer.init(st, reps)) return rc;
     tuning = true;
     int rc = NITI_NO_ERROR;
     auto run_op = [&](int i, int op) {
@@ -886,25 +786,7 @@ int ResNetModel::autotune(hipStream_t st, int reps) {
         }
         return op == PLAN_FWD ? fwd_conv(i, st) : op == PLAN_WGRAD ? wgrad_conv(i, st) : dgrad_conv(i, st);
     };
-    auto time_op = [&](int i, int op, float* us) -> int {
-        int r = run_op(i, op);
-        float best = 1e30f;
-        for (int t = 0; t < 3 && r == NITI_NO_ERROR; ++t) {
-            if (hipEventRecord(ev[0], st) != hipSuccess) return NITI_NO_EXECUTION;
-            for (int k = 0; k < reps && r == NITI_NO_ERROR; ++k) r = run_op(i, op);
-            if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess)
-                return NITI_NO_EXECUTION;
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return NITI_NO_EXECUTION;
-            best = std::min(best, ms * 1000.f / reps);
-        }
-        *us = best;
-        return r;
-    };
     const bool log = getenv("NITI_DIAG_TUNE_LOG") != nullptr;
-    static const int tiles[7][2] = {{PLAN_TAPS_TILE, PLAN_TAPS_TILE}, {128, 128}, {128, 64}, {64, 128}, {64, 64},
-                                    {256, 128}, {128, 256}};
-    static const int split_opts[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
     std::set<PlanKey> done;
     for (int i = 0; i < (int)C.size() && rc == NITI_NO_ERROR; ++i) {
         for (int op : {PLAN_FWD, PLAN_WGRAD, PLAN_DGRAD}) {
@@ -913,61 +795,20 @@ int ResNetModel::autotune(hipStream_t st, int reps) {
             const ConvGeom& g = C[i].g;
             const PlanKey key = conv_plan_key(op, g);
             if (!done.insert(key).second) continue;
-            const int k_step = conv_plan_k_step(op, g);
-            const int steps = (key.K + k_step - 1) / k_step;
-            const bool act = op != PLAN_WGRAD;
+            auto time_op = [&](float* us) { return timer.time([&] { return run_op(i, op); }, us); };
+            auto note = [&](const PlanChoice& c, float us) {
+                if (log) fprintf(stderr, "tune conv %d op %d plan (%d,%d,%d,%d) %.2f us\n", i, op, c.bm, c.bn, c.splits, c.strat, us);
+            };
             plan_override_clear(key);
             const size_t wsb = op == PLAN_WGRAD ? slab_w_bytes : slab_bytes;
-            PlanChoice best = conv_plan_query(op, g, act, wsb);
+            PlanChoice best = conv_plan_query(op, g, op != PLAN_WGRAD, wsb);
             float best_us = 0.f;
-            rc = time_op(i, op, &best_us);
-            const bool taps = op == PLAN_WGRAD && conv_wgrad_taps_ok(g);
-            for (const auto& t : tiles) {
-                if (rc != NITI_NO_ERROR) break;
-                if (t[0] == PLAN_TAPS_TILE && !taps) continue;
-                std::vector<PlanChoice> cands;
-                PlanChoice c;
-                c.bm = t[0];
-                c.bn = t[1];
-                cands.push_back(c);
-                if (act) {
-                    c.strat = 1;
-                    cands.push_back(c);
-                    // the speculative pair only on request (NITI_TUNE_SPEC=1): timed here on one
-                    // batch its guess always holds, but over a run of batches 60-80 % of the deep
-                    // layers' pairs miss (profiles/r05_gemm_spec.txt) and then cost more than STORE
-                    if (tune_spec()) {
-                        c.strat = 3;
-                        cands.push_back(c);
-                    }
-                    c.strat = 4;  // one launch, the rescale fused (where every tile is resident)
-                    cands.push_back(c);
-                }
-                for (int s : split_opts) {
-                    if (s > steps / 2 || plan_slab_bytes(key.M, key.N, s) > wsb) break;
-                    c.strat = 2;
-                    c.splits = s;
-                    cands.push_back(c);
-                }
-                for (const PlanChoice& cand : cands) {
-                    plan_override_set(key, cand);
-                    float us = 0.f;
-                    rc = time_op(i, op, &us);
-                    if (log)
-                        fprintf(stderr, "tune conv %d op %d plan (%d,%d,%d,%d) %.2f us\n", i, op, cand.bm, cand.bn,
-                                cand.splits, cand.strat, us);
-                    if (rc != NITI_NO_ERROR) break;
-                    if (us < best_us) {
-                        best_us = us;
-                        best = cand;
-                    }
-                }
-            }
+            rc = time_op(&best_us);
+            if (rc == NITI_NO_ERROR) rc = tune_gemm_tiles(op, g, wsb, time_op, note, &best, &best_us);
             plan_override_set(key, best);
         }
     }
     tuning = false;
-    for (auto e : ev) (void)hipEventDestroy(e);
     if (hipStreamSynchronize(st) != hipSuccess) rc = NITI_NO_EXECUTION;
     return rc;
 }
@@ -983,21 +824,6 @@ int ResNetModel::run_phase(int layer, int phase, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------ host access
-// the stem's weights as the im2col GEMM holds them: [co][STEM_KP], column (ky * 7 + kx) * 3 + c
-static void stem_cols_from_oihw(const ConvGeom& o, const int8_t* w, int8_t* wc, int kp) {
-    memset(wc, 0, (size_t)o.c_out * kp);
-    for (int co = 0; co < o.c_out; ++co)
-        for (int c = 0; c < o.c_in; ++c)
-            for (int t = 0; t < o.kh * o.kw; ++t)
-                wc[(size_t)co * kp + t * o.c_in + c] = w[((size_t)co * o.c_in + c) * o.kh * o.kw + t];
-}
-static void oihw_from_stem_cols(const ConvGeom& o, const int8_t* wc, int8_t* w, int kp) {
-    for (int co = 0; co < o.c_out; ++co)
-        for (int c = 0; c < o.c_in; ++c)
-            for (int t = 0; t < o.kh * o.kw; ++t)
-                w[((size_t)co * o.c_in + c) * o.kh * o.kw + t] = wc[(size_t)co * kp + t * o.c_in + c];
-}
-
 int ResNetModel::refresh_copies(int i, hipStream_t st) {
     RConv& c = C[i];
     const ConvGeom& g = c.g;
@@ -1016,7 +842,7 @@ int ResNetModel::set_weight(int i, const int8_t* w_host, int wscale) {
     std::vector<int8_t> colw;
     if (i == 0) {
         colw.resize((size_t)g.c_out * STEM_KP);
-        stem_cols_from_oihw(c.og, w_host, colw.data(), STEM_KP);
+        cols_from_oihw(c.og, w_host, colw.data(), STEM_KP);
         w_host = colw.data();
     }
     const size_t nb = (size_t)g.c_out * g.c_in * g.kh * g.kw;
@@ -1047,7 +873,7 @@ int ResNetModel::get_weight(int i, int8_t* w_host) {
     if (ohwi16_to_oihw(c.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr) != hipSuccess ||
         hipMemcpy(i == 0 ? colw.data() : w_host, tmp, nb, hipMemcpyDeviceToHost) != hipSuccess)
         rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR && i == 0) oihw_from_stem_cols(c.og, colw.data(), w_host, STEM_KP);
+    if (rc == NITI_NO_ERROR && i == 0) oihw_from_cols(c.og, colw.data(), w_host, STEM_KP);
     (void)hipFree(tmp);
     return rc;
 }
@@ -1080,7 +906,7 @@ int ResNetModel::get_tap(int layer, int which, int8_t* host, size_t bytes, hipSt
     if (which == 1 && layer == 0) {
         std::vector<int8_t> colw(need);
         if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) oihw_from_stem_cols(c.og, colw.data(), host, STEM_KP);
+        if (e == hipSuccess) oihw_from_cols(c.og, colw.data(), host, STEM_KP);
     } else if (e == hipSuccess) {
         e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
     }
@@ -1138,11 +964,51 @@ int ResNetModel::spec_stats(uint32_t* out, int max_layers) {
     return NITI_NO_ERROR;
 }
 
-int ResNetModel::rowconv_error() {
-    uint32_t e = 0;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&e, rc_err, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    return (int)e;
+int ResNetModel::layer_info(int layer, int info[12]) const {
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+    const RConv& c = C[layer];
+    const ConvGeom& g = c.og;
+    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, c.relu, 0};
+    memcpy(info, v, sizeof(v));
+    return NITI_NO_ERROR;
+}
+
+int ResNetModel::plan_info(int layer, int phase, int info[4]) {
+    if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    return plan_out(conv_plan_query(plan_op(phase), C[layer].g, phase != 2, phase == 2 ? slab_w_bytes : slab_bytes), info);
+}
+
+// this driver's own rule: at most 4096 splits
+int ResNetModel::plan_set(int layer, int phase, const int plan[4]) {
+    if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    const int op = plan_op(phase);
+    const ConvGeom& g = C[layer].g;
+    const PlanKey k = conv_plan_key(op, g);
+    drop_graph();
+    if (plan == nullptr) {
+        plan_override_clear(k);
+        return NITI_NO_ERROR;
+    }
+    if (!plan_valid(op, g, plan, false) || plan[2] > 4096) return NITI_INVALID_VALUE;
+    return plan_commit(k, op, plan, true);
+}
+
+int ResNetModel::set_rowconv(bool enable) {
+    if (use_rowconv && !enable) {  // the GEMM input gradients read IHWO16 copies the update skipped
+        for (int i = 0; i < (int)C.size(); ++i)
+            if (refresh_copies(i, nullptr) != NITI_NO_ERROR) return NITI_NO_EXECUTION;
+        if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+    }
+    use_rowconv = enable;
+    drop_graph();
+    return NITI_NO_ERROR;
+}
+
+std::unique_ptr<StepDriver> make_resnet_driver(int batch, int in_hw, int classes, int* rc) {
+    auto m = std::make_unique<ResNetModel>();
+    *rc = m->build(batch, in_hw, classes);
+    if (*rc != NITI_NO_ERROR) return nullptr;
+    return m;
 }
 
 }  // namespace niti

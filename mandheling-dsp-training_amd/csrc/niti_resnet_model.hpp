@@ -1,5 +1,6 @@
 // niti_resnet_model.hpp -- the ResNet-18 NITI training step driven from C++ (BASELINE config 5),
-// behind the same niti_model_* C ABI as the LeNet / VGG driver (niti_model.hip).
+// behind the same niti_model_* C ABI (niti_model_capi.hip) as the LeNet / VGG driver (niti_model.hip),
+// on the same base (niti_step_driver.hpp).
 //
 // The reference has no ResNet NITI model: its graph builder would chain NITI_Conv_Int8_Module
 // instances (tools/train/source/nn/NN.cpp:1181-1207) and its residual op NITI_Eltwise_Int8 is an
@@ -12,9 +13,7 @@
 #include <memory>
 #include <vector>
 
-#include "niti_coll.hpp"
-#include "niti_internal.hpp"
-#include "niti_kernels.hpp"
+#include "niti_step_driver.hpp"
 
 namespace niti {
 
@@ -75,12 +74,11 @@ struct RBlock {
     int64_t out_elems = 0, in_elems = 0;
 };
 
-struct ResNetModel {
+struct ResNetModel final : StepDriver {
     static constexpr int STEM_KP = 160;  // the stem's im2col columns: 7 * 7 * 3 = 147, padded
-    int batch = 0, in_hw = 0, classes = 1000;
+    int in_hw = 0, classes = 1000;
     std::vector<RConv> C;
     std::vector<RBlock> B;
-    Workspace ws;
     ConvGeom stem{};              // conv1 as defined (the im2col's geometry)
     int8_t* x0n = nullptr;        // the quantised input, NCHW int8
     int8_t* exp0 = nullptr;
@@ -104,15 +102,10 @@ struct ResNetModel {
     int n_exps = 0;
     int32_t* acc = nullptr;       // shared int32 accumulator of the GEMM paths
     size_t acc_bytes = 0;
-    void* slab = nullptr;         // split-K slabs (forward / input gradient)
-    size_t slab_bytes = 0;
-    void* slab_w = nullptr;       // split-K slabs (weight gradients)
-    size_t slab_w_bytes = 0;
     int32_t* rc_acc = nullptr;    // the row kernels' accumulator store (two-launch store mode)
     size_t rc_acc_size = 0;
     int8_t* gspec_alt = nullptr;  // the GEMM speculative pairs' alternates (shared)
     size_t gspec_alt_bytes = 0;
-    uint32_t* rc_err = nullptr;
     // the residual sums' single-launch form (residual_fused, NITI_RES_FUSED=1: measured slower than
     // the two launches): one grid-barrier state for all of them (in order on the step stream)
     // the stride-2 input gradients as sub-pixel classes (NITI_SUBPIX=0: the generic masked loader)
@@ -140,30 +133,7 @@ struct ResNetModel {
     uint32_t* rng(int conv, int which) { return amax + (size_t)(3 * conv + which) * MAX_WORDS; }
     uint32_t* rng_blk(int blk, int bwd) { return amax + (size_t)(3 * C.size() + 2 * blk + bwd) * MAX_WORDS; }
     uint32_t* rng_pool() { return amax + (size_t)(3 * C.size() + 2 * B.size()) * MAX_WORDS; }
-    bool keep_grads = true;
-    bool use_rowconv = true;
-    bool tuning = false;
-    bool probe_paused = false;  // niti_model_probe_pause
-    bool capturing = false;
-    // data parallel: ranges on the step stream (coll), gradient-bucket SUMs on cst (coll_grad)
-    std::unique_ptr<Collective> coll, coll_grad;
-    int world = 1, rank = 0, exact = 1;
-    bool shared_comm = false;
-    bool dp() const { return coll != nullptr && coll_grad != nullptr && !tuning; }
-    hipStream_t cst = nullptr;
-    std::vector<hipEvent_t> ev_bucket;
-    hipEvent_t ev_grads = nullptr;
-    std::vector<int> bucket_lo;
-    std::vector<char> closes_bucket;
-    size_t bucket_min_bytes = grad_bucket_bytes();
-    // kernel probe: HIP events on the step stream around one conv phase (both launches of a
-    // two-launch form), up to ev0.size() launches
-    int probe_layer = -1, probe_phase = -1, probe_count = 0;
-    std::vector<hipEvent_t> ev0, ev1;
-    // optional hipGraph replay of the single-device step
-    bool use_graph = false;
-    hipStream_t gstream = nullptr;
-    hipEvent_t gin = nullptr, gout = nullptr;
+    // optional hipGraph replay of the single-device step: one executable
     hipGraphExec_t gexec = nullptr;
     const void* gkey_x = nullptr;
     const void* gkey_l = nullptr;
@@ -175,45 +145,44 @@ struct ResNetModel {
     int fwd_conv(int i, hipStream_t st);
     int dgrad_conv(int i, hipStream_t st);
     int wgrad_conv(int i, hipStream_t st);
-    bool in_step = false;  // run(): weight gradients may leave their split-K combine to the update
     bool ensure_wslab(int i);
     int size_wslabs();
     unsigned wslab_epoch = 0;  // plan_override_epoch() the slabs were last sized for
     int residual_fwd(int k, hipStream_t st);
     int residual_bwd(int k, hipStream_t st);
     int run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
-    int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
+    int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) override;
     // the step's forward half (input, every conv and residual sum, the pool, the fc head)
     int forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, hipStream_t st);
-    // evaluation (niti_model_eval_*): forward() and the head metrics of its logits, added to the
-    // running totals; everything it needs is allocated in build()
-    niti_eval_totals* ev_totals = nullptr;
-    int32_t* ev_pred = nullptr;  // the last evaluation batch's predictions
-    void* ev_ws = nullptr;
-    size_t ev_ws_bytes = 0;
-    int ev_topk = 5;
-    bool eval_pass = false;  // forward() fills / copies by kernel (niti_map.hpp: fill_kernel)
-    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
-    int copy_weights_from(ResNetModel& src, hipStream_t st);
-    int autotune(hipStream_t st, int reps);
-    int run_phase(int layer, int phase, hipStream_t st);
-    int sum_bucket(int lo, hipStream_t st);
-    void plan_buckets();
-    int ensure_comm_stream();
-    bool ensure_slab(size_t bytes, bool wgrad);
+    int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) override;
+    int copy_weights_from(StepDriver& src, hipStream_t st) override;
+    int autotune(hipStream_t st, int reps) override;
+    int run_phase(int layer, int phase, hipStream_t st) override;
+    int plan_info(int layer, int phase, int info[4]) override;
+    int plan_set(int layer, int phase, const int plan[4]) override;
+    int set_rowconv(bool enable) override;
+    void set_overlap(bool) override {}  // one stream (the weight gradients interleave with the input gradients)
+    // kernel probe: the events on the step stream around one conv phase (both launches of a
+    // two-launch form)
     void probe(int layer, int phase, bool begin, hipStream_t st);
-    void clear_probe();
-    void drop_graph();
+    void drop_graph() override;
     int refresh_copies(int i, hipStream_t st);  // wT / wf / wft from w
-    int set_weight(int i, const int8_t* w_oihw_host, int wscale);
-    int get_weight(int i, int8_t* w_oihw_host);
-    int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st);
-    int get_logits(int8_t* host, int* exp_out, hipStream_t st);
-    int get_input(int8_t* host, int* ascale, hipStream_t st);
-    int64_t step_macs() const;
-    int spec_stats(uint32_t* out, int max_layers);
-    int rowconv_error();
-    ~ResNetModel();
+    bool layer_ok(int layer) const { return layer >= 0 && layer < (int)C.size(); }
+    int num_layers() const override { return (int)C.size(); }
+    int layer_info(int layer, int info[12]) const override;
+    int set_weight(int i, const int8_t* w_oihw_host, int wscale) override;
+    int get_weight(int i, int8_t* w_oihw_host) override;
+    int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
+    int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
+    int get_input(int8_t* host, int* ascale, hipStream_t st) override;
+    int64_t step_macs() const override;
+    int spec_stats(uint32_t* out, int max_layers) override;
+    int spec_state(int layer, uint32_t** bar) override {
+        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+        *bar = C[layer].bar;
+        return NITI_NO_ERROR;
+    }
+    ~ResNetModel() override { drop_graph(); }  // (the rest in ~StepDriver)
 };
 
 }  // namespace niti

@@ -1,0 +1,237 @@
+// niti_step_driver.hip -- the logic the two step drivers share (niti_step_driver.hpp).
+#include "niti_step_driver.hpp"
+
+#include <string.h>
+
+#include "niti_map.hpp"
+
+namespace niti {
+
+bool StepDriver::ensure_slab(size_t bytes, bool wgrad) {
+    void*& p = wgrad ? slab_w : slab;
+    size_t& have = wgrad ? slab_w_bytes : slab_bytes;
+    if (have >= bytes) return true;
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    void* s2 = ws.alloc(bytes);
+    if (!s2) return false;
+    p = s2;
+    have = bytes;
+    return true;
+}
+
+StepDriver::~StepDriver() {
+    StepDriver::clear_probe();
+    if (cst) (void)hipStreamSynchronize(cst);
+    for (auto e : ev_bucket) (void)hipEventDestroy(e);
+    if (ev_grads) (void)hipEventDestroy(ev_grads);
+    if (gin) (void)hipEventDestroy(gin);
+    if (gout) (void)hipEventDestroy(gout);
+    if (gstream) (void)hipStreamDestroy(gstream);
+    coll_grad.reset();
+    coll.reset();
+    if (cst) (void)hipStreamDestroy(cst);
+}
+
+// ------------------------------------------------------------------------------ data parallel
+void StepDriver::plan_buckets() {
+    const int nl = (int)grads.size();
+    bucket_lo.assign(nl, 0);
+    closes_bucket.assign(nl, 0);
+    size_t acc = 0;
+    int hi = nl - 1;
+    for (int i = nl - 1; i >= 0; --i) {
+        acc += (size_t)grads[i].elems * 4;
+        if (acc >= bucket_min_bytes || i == 0) {
+            closes_bucket[i] = 1;
+            for (int j = i; j <= hi; ++j) bucket_lo[j] = i;
+            acc = 0;
+            hi = i - 1;
+        }
+    }
+}
+
+int StepDriver::ensure_comm_stream() {
+    if (cst) return NITI_NO_ERROR;
+    if (hipStreamCreateWithFlags(&cst, hipStreamNonBlocking) != hipSuccess) return NITI_NO_EXECUTION;
+    // cross-stream hand-offs on one device need a device-scope release only
+    constexpr unsigned kFlags = hipEventDisableTiming | hipEventReleaseToDevice;
+    ev_bucket.assign(grads.size(), nullptr);
+    for (auto& e : ev_bucket)
+        if (hipEventCreateWithFlags(&e, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
+    if (hipEventCreateWithFlags(&ev_grads, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
+    plan_buckets();
+    return NITI_NO_ERROR;
+}
+
+// Data parallel: the bucket of layers [lo, hi] (contiguous in the gradient bucket; the weight
+// gradients run in descending layer order) is complete once layer lo's weight gradient is in on
+// `wst`: the comm stream waits for it, SUMs the bucket's int32 gradients over the ranks and takes
+// every layer's range of the summed gradient (NITI_RangeEstimate over the global batch,
+// NITI_GradientConv_Int8.cpp:274-296), while the step stream goes on with the input-gradient chain.
+int StepDriver::sum_bucket(int lo, hipStream_t wst) {
+    int hi = lo;
+    while (hi + 1 < (int)grads.size() && bucket_lo[hi + 1] == lo) ++hi;
+    if (hi - lo + 1 > ABSMAX_MAX_JOBS) return NITI_NOT_SUPPORT;
+    size_t elems = 0;
+    for (int j = lo; j <= hi; ++j) elems += (size_t)grads[j].elems;
+    AbsmaxJob jobs[ABSMAX_MAX_JOBS];
+    for (int j = lo; j <= hi; ++j) jobs[j - lo] = AbsmaxJob{grads[j].dwacc, grads[j].elems, grads[j].amax, 0};
+    hipStream_t s = wst;  // one communicator: the SUMs stay in the step's program order
+    if (!shared_comm) {   // own communicator: its own stream, overlapping the rest of the backward pass
+        DTRY(hipEventRecord(ev_bucket[lo], wst));
+        DTRY(hipStreamWaitEvent(cst, ev_bucket[lo], 0));
+        s = cst;
+    }
+    DTRY(coll_grad->allreduce(grads[lo].dwacc, elems, COLL_SUM_I32, s));
+    DTRY(absmax_many(jobs, hi - lo + 1, s));
+    return NITI_NO_ERROR;
+}
+
+void StepDriver::attach(std::unique_ptr<Collective> c, std::unique_ptr<Collective> cg, bool shared, int world_,
+                        int rank_, int exact_) {
+    drop_graph();
+    coll = std::move(c);
+    coll_grad = std::move(cg);
+    shared_comm = shared;
+    world = world_;
+    rank = rank_;
+    exact = exact_ ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------ probe
+void StepDriver::clear_probe() {
+    for (auto e : ev0) (void)hipEventDestroy(e);
+    for (auto e : ev1) (void)hipEventDestroy(e);
+    ev0.clear();
+    ev1.clear();
+    probe_count = 0;
+    probe_layer = probe_phase = -1;
+}
+
+int StepDriver::set_probe(int layer, int phase, int max_launches) {
+    clear_probe();
+    if (layer < 0) return NITI_NO_ERROR;
+    probe_layer = layer;
+    probe_phase = phase;
+    ev0.resize(max_launches);
+    ev1.resize(max_launches);
+    for (int i = 0; i < max_launches; ++i)
+        // timing events without the system-scope cache writeback / invalidate (it delays the
+        // launch after the begin marker and is not needed to read the timestamps)
+        if (hipEventCreateWithFlags(&ev0[i], hipEventDisableSystemFence) != hipSuccess ||
+            hipEventCreateWithFlags(&ev1[i], hipEventDisableSystemFence) != hipSuccess)
+            return NITI_OUT_OF_MEMORY;
+    return probe_alloc(phase, max_launches);
+}
+
+int StepDriver::probe_read(double* total_ms, int* count) {
+    double t = 0;
+    for (int i = 0; i < probe_count; ++i) {
+        float ms = 0.f;
+        if (hipEventSynchronize(ev1[i]) != hipSuccess || hipEventElapsedTime(&ms, ev0[i], ev1[i]) != hipSuccess)
+            return NITI_NO_EXECUTION;
+        t += ms;
+    }
+    *total_ms = t;
+    *count = probe_count;
+    probe_count = 0;
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::probe_read_span(double* total_ms, int* count) {
+    *total_ms = 0;
+    *count = 0;
+    return NITI_NO_ERROR;
+}
+
+// ------------------------------------------------------------------------------ graph stream
+int StepDriver::ensure_graph_stream() {
+    if (gstream) return NITI_NO_ERROR;
+    DTRY(hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking));
+    DTRY(hipEventCreateWithFlags(&gin, hipEventDisableTiming));
+    DTRY(hipEventCreateWithFlags(&gout, hipEventDisableTiming));
+    return NITI_NO_ERROR;
+}
+
+// ------------------------------------------------------------------------------ evaluation
+int StepDriver::alloc_eval() {
+    ev_ws_bytes = head_metrics_workspace(batch);
+    ev_ws = ws.alloc(ev_ws_bytes);
+    ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
+    ev_pred = (int32_t*)ws.alloc((size_t)batch * 4);
+    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
+    if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess ||
+        hipMemset(ev_pred, 0, (size_t)batch * 4) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::eval_reset(hipStream_t st) {
+    DTRY(fill_kernel(ev_totals, 0, sizeof(niti_eval_totals), st));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::eval_read(niti_eval_totals* host_out, hipStream_t st) {
+    DTRY(hipStreamSynchronize(st));
+    DTRY(hipMemcpy(host_out, ev_totals, sizeof(niti_eval_totals), hipMemcpyDeviceToHost));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::get_predictions(int32_t* pred_host, hipStream_t st) {
+    DTRY(hipStreamSynchronize(st));
+    DTRY(hipMemcpy(pred_host, ev_pred, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::rowconv_error() {
+    uint32_t e = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&e, rc_err, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    return (int)e;
+}
+
+// ------------------------------------------------------------------------------ plans
+bool StepDriver::plan_valid(int op, const ConvGeom& g, const int plan[4], bool own_tile) {
+    auto tile_ok = [](int t) { return t == 64 || t == 128 || t == 256; };
+    const bool taps = plan[0] == PLAN_TAPS_TILE && plan[1] == PLAN_TAPS_TILE && op == PLAN_WGRAD && conv_wgrad_taps_ok(g);
+    return !((!taps && !own_tile && (!tile_ok(plan[0]) || !tile_ok(plan[1]))) || plan[2] < 1 || plan[3] < 0 ||
+             plan[3] > 4 || ((taps || own_tile) && plan[3] == 1) || (plan[3] >= 3 && (op == PLAN_WGRAD || plan[2] != 1)));
+}
+
+int StepDriver::plan_commit(const PlanKey& k, int op, const int plan[4], bool gemm_slab) {
+    PlanChoice c;
+    c.bm = plan[0];
+    c.bn = plan[1];
+    c.splits = plan[2];
+    c.strat = plan[3];
+    if (c.strat == 2 && gemm_slab &&
+        !ensure_slab(std::min(plan_slab_bytes(k.M, k.N, c.splits), size_t(1) << 30), op == PLAN_WGRAD))
+        return NITI_OUT_OF_MEMORY;
+    plan_override_set(k, c);
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::plan_out(const PlanChoice& c, int info[4]) {
+    info[0] = c.bm;
+    info[1] = c.bn;
+    info[2] = c.splits;
+    info[3] = c.strat;
+    return NITI_NO_ERROR;
+}
+
+// ------------------------------------------------------------------------------ host helpers
+void cols_from_oihw(const ConvGeom& o, const int8_t* w, int8_t* wc, int kp) {
+    memset(wc, 0, (size_t)o.c_out * kp);
+    for (int co = 0; co < o.c_out; ++co)
+        for (int c = 0; c < o.c_in; ++c)
+            for (int t = 0; t < o.kh * o.kw; ++t)
+                wc[(size_t)co * kp + t * o.c_in + c] = w[((size_t)co * o.c_in + c) * o.kh * o.kw + t];
+}
+void oihw_from_cols(const ConvGeom& o, const int8_t* wc, int8_t* w, int kp) {
+    for (int co = 0; co < o.c_out; ++co)
+        for (int c = 0; c < o.c_in; ++c)
+            for (int t = 0; t < o.kh * o.kw; ++t)
+                w[((size_t)co * o.c_in + c) * o.kh * o.kw + t] = wc[(size_t)co * kp + t * o.c_in + c];
+}
+
+}  // namespace niti

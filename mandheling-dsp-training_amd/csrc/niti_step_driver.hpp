@@ -1,0 +1,242 @@
+// niti_step_driver.hpp -- what the two whole-step training drivers behind the niti_model_* C ABI
+// share: the chain driver (LeNet / VGG, niti_model.hip) and ResNet-18 (niti_resnet_model.hip).
+//
+// StepDriver holds the state and the logic both have in the same form -- split-K slabs, the
+// data-parallel gradient buckets, the event probe, the evaluation totals, the graph stream and its
+// fences, the teardown -- and declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
+// driver.  A virtual is called at most once per ABI call; nothing inside a step (run(), forward(),
+// backward(), the per-layer functions) goes through one.  The base does not know which driver it
+// serves: where the two differ, the difference is the derived class's.
+#pragma once
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "niti_coll.hpp"
+#include "niti_internal.hpp"
+#include "niti_kernels.hpp"
+
+#define DTRY(expr)                                          \
+    do {                                                    \
+        if ((expr) != hipSuccess) return NITI_NO_EXECUTION; \
+    } while (0)
+
+namespace niti {
+
+// one parameter layer's weight gradient as the bucket SUMs see it (filled by the driver's build())
+struct GradSlot {
+    int32_t* dwacc = nullptr;  // int32 gradient, in the contiguous gradient bucket
+    int64_t elems = 0;         // w_elems()
+    uint32_t* amax = nullptr;  // its range word (rng(layer, 2))
+};
+
+struct StepDriver {
+    Workspace ws;  // (first: device memory goes last, after everything below is torn down)
+    int batch = 0;
+    void* slab = nullptr;    // split-K slabs of the forward / input-gradient GEMMs (step stream)
+    size_t slab_bytes = 0;
+    void* slab_w = nullptr;  // split-K slabs of the weight-gradient GEMMs (their own stream)
+    size_t slab_w_bytes = 0;
+    // grow a split-K workspace (the old one stays owned by ws until the model is destroyed)
+    bool ensure_slab(size_t bytes, bool wgrad);
+    uint32_t* rc_err = nullptr;  // set by an in-kernel grid barrier that timed out
+    bool keep_grads = true;      // the int8 weight gradient of the last step kept for get_tap (which = 1)
+    bool use_rowconv = true;     // the register-fed kernels (niti_rowconv.hip) for the layers they take
+    bool tuning = false;         // autotune in progress: no collectives, no probe
+    bool capturing = false;
+    bool in_step = false;        // run(): weight gradients may defer their combine to the update launch
+    // data parallel (niti_coll.hpp, "collectives"): ranges on the step stream through `coll`,
+    // gradient-bucket SUMs on the comm stream `cst` through `coll_grad`.  Attached at any world
+    // size (a world of 1 runs every collective call site on one GPU).
+    std::unique_ptr<Collective> coll, coll_grad;
+    int world = 1, rank = 0, exact = 1;
+    bool dp() const { return coll != nullptr && coll_grad != nullptr && !tuning; }
+    hipStream_t cst = nullptr;
+    // the gradient SUMs share the range communicator (ncclCommSplit unavailable): they then run on
+    // the weight-gradient stream itself, keeping that one communicator in program order
+    bool shared_comm = false;
+    std::vector<GradSlot> grads;
+    std::vector<hipEvent_t> ev_bucket;  // per layer: the bucket closed after this layer's weight gradient
+    hipEvent_t ev_grads = nullptr;      // every bucket summed and ranged (the NITI_SGD join)
+    size_t bucket_min_bytes = grad_bucket_bytes();
+    // the bucket a layer's gradient SUM rides in: layers (backward order) accumulate until the
+    // bucket holds bucket_min_bytes; closes_bucket[i] marks the layer whose weight gradient
+    // completes one (its first layer in memory order is bucket_lo[i])
+    std::vector<int> bucket_lo;
+    std::vector<char> closes_bucket;
+    void plan_buckets();
+    int ensure_comm_stream();
+    int sum_bucket(int lo, hipStream_t wst);
+    void attach(std::unique_ptr<Collective> c, std::unique_ptr<Collective> cg, bool shared, int world_, int rank_,
+                int exact_);
+    // kernel probe: HIP events around one layer phase (0 fwd / 1 dgrad / 2 wgrad), up to ev0.size()
+    // launches; where the events go is the driver's
+    int probe_layer = -1, probe_phase = -1, probe_count = 0;
+    std::vector<hipEvent_t> ev0, ev1;
+    bool probe_paused = false;  // niti_model_probe_pause: the armed probe skips these launches
+    virtual void clear_probe();
+    int set_probe(int layer, int phase, int max_launches);
+    int probe_read(double* total_ms, int* count);
+    // optional hipGraph replay of the single-device step: captured on an internal stream, fenced
+    // against the caller's stream with events (the captured form and its key are the driver's)
+    bool use_graph = false;
+    hipStream_t gstream = nullptr;
+    hipEvent_t gin = nullptr, gout = nullptr;
+    int ensure_graph_stream();
+    // evaluation (niti_model_eval_*): the driver's forward() and the head metrics of its logits, added
+    // to the running totals; everything it needs is allocated in build() (alloc_eval)
+    niti_eval_totals* ev_totals = nullptr;
+    int32_t* ev_pred = nullptr;  // the last evaluation batch's predictions
+    void* ev_ws = nullptr;
+    size_t ev_ws_bytes = 0;
+    int ev_topk = 5;
+    bool eval_pass = false;  // forward() fills / copies by kernel (niti_map.hpp: fill_kernel)
+    int alloc_eval();
+    int eval_reset(hipStream_t st);
+    int eval_read(niti_eval_totals* host_out, hipStream_t st);
+    int get_predictions(int32_t* pred_host, hipStream_t st);
+    int rowconv_error();
+    // the shared half of plan_set: the tile set {64, 128, 256} or the taps tile (own_tile: a tile of
+    // the driver's own, which it vouches for), the strategy range, strategies 3 and 4 only for
+    // unsplit activation GEMMs; then the override, with the split-K slabs it needs (gemm_slab)
+    static int plan_op(int phase) { return phase == 0 ? PLAN_FWD : phase == 1 ? PLAN_DGRAD : PLAN_WGRAD; }
+    static bool plan_valid(int op, const ConvGeom& g, const int plan[4], bool own_tile);
+    int plan_commit(const PlanKey& k, int op, const int plan[4], bool gemm_slab);
+    static int plan_out(const PlanChoice& c, int info[4]);
+
+    // ---- what the C ABI asks of a driver (each validates its layer / phase itself)
+    virtual int num_layers() const = 0;
+    virtual int layer_info(int layer, int info[12]) const = 0;
+    virtual int set_weight(int layer, const int8_t* w_oihw_host, int wscale) = 0;
+    virtual int get_weight(int layer, int8_t* w_oihw_host) = 0;
+    virtual int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) = 0;
+    virtual int get_logits(int8_t* host, int* exp_out, hipStream_t st) = 0;
+    virtual int get_input(int8_t* host, int* ascale, hipStream_t st) = 0;
+    virtual int64_t step_macs() const = 0;
+    virtual int spec_stats(uint32_t* out, int max_layers) = 0;
+    // a layer's row-kernel state (grid barrier words + speculation slots; may be null)
+    virtual int spec_state(int layer, uint32_t** bar) = 0;
+    // x_nchw int8 with exponent exp_in, or (x_nchw == null) uint8 images through the on-device
+    // input quantiser (MnistUtils.cpp:83-93)
+    virtual int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) = 0;
+    virtual int eval(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) = 0;
+    virtual int copy_weights_from(StepDriver& src, hipStream_t st) = 0;  // (another kind of driver: invalid)
+    virtual int autotune(hipStream_t st, int reps) = 0;
+    virtual int run_phase(int layer, int phase, hipStream_t st) = 0;
+    virtual int plan_info(int layer, int phase, int info[4]) = 0;
+    virtual int plan_set(int layer, int phase, const int plan[4]) = 0;
+    virtual int set_rowconv(bool enable) = 0;
+    virtual void set_overlap(bool enable) = 0;
+    virtual void drop_graph() = 0;
+    virtual int probe_alloc(int phase, int max_launches) { return NITI_NO_ERROR; }  // set_probe's extra
+    virtual int probe_read_span(double* total_ms, int* count);  // (none unless the driver has a span probe)
+    // Teardown.  The derived destructor goes first: its graphs, then (after synchronising cst) its own
+    // events and side streams; here the probe events, cst synchronised, the shared events and the
+    // graph stream, coll_grad, then coll, then cst itself; ws (device memory) last.
+    virtual ~StepDriver();
+};
+
+// the concrete drivers (null and *rc set when build() fails)
+std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, int* rc);
+std::unique_ptr<StepDriver> make_resnet_driver(int batch, int in_hw, int classes, int* rc);
+
+// a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
+// zero padded to the column pitch kp <-> OIHW
+void cols_from_oihw(const ConvGeom& o, const int8_t* w, int8_t* wc, int kp);
+void oihw_from_cols(const ConvGeom& o, const int8_t* wc, int8_t* w, int kp);
+
+// ---------------------------------------------------------------------------- autotune harness
+// min over three event-bracketed batches of `reps` back-to-back runs (no host sync inside)
+struct TuneTimer {
+    hipStream_t st = nullptr;
+    int reps = 5;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int init(hipStream_t st_, int reps_) {
+        st = st_;
+        reps = reps_;
+        for (auto& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) return NITI_NO_EXECUTION;
+        return NITI_NO_ERROR;
+    }
+    ~TuneTimer() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    template <class Run>
+    int time(Run&& run, float* us) {
+        int r = run();
+        float best = 1e30f;
+        for (int t = 0; t < 3 && r == NITI_NO_ERROR; ++t) {
+            if (hipEventRecord(ev[0], st) != hipSuccess) return NITI_NO_EXECUTION;
+            for (int k = 0; k < reps && r == NITI_NO_ERROR; ++k) r = run();
+            if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess)
+                return NITI_NO_EXECUTION;
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return NITI_NO_EXECUTION;
+            best = std::min(best, ms * 1000.f / reps);
+        }
+        *us = best;
+        return r;
+    }
+};
+
+// Every GEMM-tile candidate of one plan key -- the tap-sharing weight-gradient kernel where it
+// applies and 6 GEMM tile shapes, each x {store acc, recompute / the optional speculative pair /
+// fused (activation GEMMs), split-K within steps / 2 and the workspace wsb} -- timed through
+// `time(&us)` with the candidate set as the key's override, reported to `note(cand, us)`; a faster
+// one replaces *best / *best_us.
+template <class Time, class Note>
+int tune_gemm_tiles(int op, const ConvGeom& g, size_t wsb, Time&& time, Note&& note, PlanChoice* best, float* best_us) {
+    static const int tiles[7][2] = {{PLAN_TAPS_TILE, PLAN_TAPS_TILE}, {128, 128}, {128, 64}, {64, 128}, {64, 64},
+                                    {256, 128}, {128, 256}};
+    static const int split_opts[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
+    const PlanKey key = conv_plan_key(op, g);
+    const int k_step = conv_plan_k_step(op, g);
+    const int steps = (key.K + k_step - 1) / k_step;
+    const bool act = op != PLAN_WGRAD;
+    const bool taps = op == PLAN_WGRAD && conv_wgrad_taps_ok(g);
+    for (const auto& t : tiles) {
+        if (t[0] == PLAN_TAPS_TILE && !taps) continue;
+        std::vector<PlanChoice> cands;
+        PlanChoice c;
+        c.bm = t[0];
+        c.bn = t[1];
+        c.splits = 1;
+        c.strat = 0;
+        cands.push_back(c);
+        if (act) {
+            c.strat = 1;
+            cands.push_back(c);
+            // the speculative pair only on request (NITI_TUNE_SPEC=1): timed here on one
+            // batch its guess always holds, but over a run of batches 60-80 % of the deep
+            // layers' pairs miss (profiles/r05_gemm_spec.txt) and then cost more than STORE
+            if (tune_spec()) {
+                c.strat = 3;
+                cands.push_back(c);
+            }
+            c.strat = 4;  // one launch, the rescale fused (where every tile is resident)
+            cands.push_back(c);
+        }
+        for (int s : split_opts) {
+            if (s > steps / 2 || plan_slab_bytes(key.M, key.N, s) > wsb) break;
+            c.strat = 2;
+            c.splits = s;
+            cands.push_back(c);
+        }
+        for (const PlanChoice& cand : cands) {
+            plan_override_set(key, cand);
+            float us = 0.f;
+            const int rc = time(&us);
+            note(cand, us);
+            if (rc != NITI_NO_ERROR) return rc;
+            if (us < *best_us) {
+                *best_us = us;
+                *best = cand;
+            }
+        }
+    }
+    return NITI_NO_ERROR;
+}
+
+}  // namespace niti

@@ -255,6 +255,9 @@ def test_copy_weights_from(T):
     with pytest.raises(NitiError) as err:
         res.copy_weights_from(dst)
     assert err.value.code == 5
+    with pytest.raises(NitiError) as err:  # (and the other way round: the two step drivers never mix)
+        dst.copy_weights_from(res)
+    assert err.value.code == 5
 
 
 def test_resnet18_copy_weights_from(T):

@@ -177,7 +177,7 @@ def test_vgg11_step_autotuned(T):
     finally:
         NitiModel.reset_plans()
     assert len(seen) == 3 * 9 - 1
-    # The plan contract niti_model_plan_set enforces (niti_model.hip), not which plan won the
+    # The plan contract niti_model_plan_set enforces (niti_step_driver.hip plan_valid, niti_model.hip plan_set), not which plan won the
     # timing: GEMM tiles are 64..256 wide; the tap-sharing weight-gradient kernel reports 32x32
     # and the P16 weight-gradient kernel 16x16, both unsplit (strategy 0) or split-K (strategy 2),
     # never recompute (strategy 1); the speculative pair (strategy 3) only on forward / input-gradient
