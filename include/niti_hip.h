@@ -570,6 +570,63 @@ int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream)
  * size and class count (hence the same layer shapes); the batch may differ -- how a batch-64
  * training model feeds a batch-20 evaluation model.  NITI_INVALID_VALUE otherwise.  Asynchronous. */
 int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream);
+/* ---- device-resident dataset ----------------------------------------------------------- */
+/* A training or test set kept in device memory, and the batches of an epoch gathered out of it on
+ * the device: shuffled, and with the pad-and-crop / horizontal-flip augmentation of CIFAR-class
+ * data.  images_nchw uint8 [count][c][h][w] and labels int32 [count] may be host or device
+ * pointers; both are copied (synchronously), so the caller's arrays can go.  The images must
+ * already have the model's input size. */
+typedef struct niti_dataset* niti_dataset_t;
+int niti_dataset_create(const uint8_t* images_nchw, const int32_t* labels, int64_t count, int c, int h, int w,
+                        niti_dataset_t* out);
+/* (synchronises the device when an order was set: a gather in flight reads the dataset) */
+void niti_dataset_destroy(niti_dataset_t ds);
+/* An order: index[len] (int32: which image each entry is; -1 = a padding entry, a zero image with
+ * label -1, as niti_model_eval_step excludes it) and optionally xform[len] (int32), the entry's
+ * transform: dx = (int8)(xform & 0xff), dy = (int8)(xform >> 8 & 0xff), flip = xform >> 16 & 1, all
+ * 0 without xform.  Entry i with s = index[i] >= 0 is the image
+ *   out[ch][y][x] = data[s][ch][y + dy][(flip ? w - 1 - x : x) + dx], 0 where that lies outside
+ * -- zero-pad by P, crop at offset (P + dy, P + dx), then mirror; |dx| >= w or |dy| >= h is legal
+ * and gives a zero image -- with the label labels[s].  Batch k of an order is its entries
+ * [k * batch, (k + 1) * batch).
+ * niti_dataset_order_check (host only, no device call) returns NITI_INVALID_VALUE for a NULL index,
+ * len <= 0, len % batch != 0, an index outside [-1, count), an index of -1 while allow_pad is 0,
+ * and an xform with any bit above 16 set. */
+int niti_dataset_order_check(const int32_t* index, const int32_t* xform, int64_t len, int64_t count, int batch,
+                             int allow_pad);
+/* Checks the order (allow_pad = 1, batch = 1) and copies it to the device (host pointers; xform
+ * may be NULL).  Replacing a previous order SYNCHRONISES THE DEVICE first -- steps enqueued earlier
+ * may still read it -- which is one synchronisation per epoch.  NITI_NO_EXECUTION if a copy fails
+ * (the dataset then has no order). */
+int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host, int64_t len);
+/* The primitive: entries [first, first + n) of the order into images_out (uint8 [n][c][h][w],
+ * device) and labels_out (int32 [n], device).  One launch, asynchronous, no atomics; nothing outside
+ * the dataset is read.  16-byte copies when no xform is set and c*h*w % 16 == 0; with an xform and
+ * w % 4 == 0 aligned dword loads, a byte funnel shift and a byte reverse, dword (w % 16 == 0:
+ * 16-byte) stores; otherwise a byte per lane. */
+int niti_batch_gather(niti_dataset_t ds, int64_t first, int n, uint8_t* images_out, int32_t* labels_out,
+                      void* stream);
+/* n_steps training steps, step s (first_step <= s < first_step + n_steps) on batch s of the
+ * dataset's order: the batch is gathered into a staging batch the model owns (allocated at the
+ * first call), then runs as niti_model_train_step_images does -- the same launches; under
+ * niti_model_set_graph(1) one captured step is replayed for every batch, as the staging pointers
+ * never change.  Asynchronous: nothing on the host waits, a whole epoch can be enqueued.
+ * NITI_INVALID_VALUE, before any launch, for a dataset whose c, h, w are not the model's input,
+ * first_step / n_steps outside the order, and a -1 entry in the slice.  With a communicator or a
+ * local group attached every rank owns its dataset and order (its share of each global batch) and
+ * all ranks call together. */
+int niti_model_train_steps_dataset(niti_model_t m, niti_dataset_t ds, int64_t first_step, int n_steps, void* stream);
+/* The same through niti_model_eval_step_images; -1 entries are allowed (and counted nowhere). */
+int niti_model_eval_steps_dataset(niti_model_t m, niti_dataset_t ds, int64_t first_step, int n_steps, void* stream);
+/* Training metrics (default 0): when enabled every dataset training step is followed, on the same
+ * stream, by niti_head_metrics on the step's logits (what niti_model_get_logits returns after it)
+ * and its labels, added to running totals separate from the evaluation's; top-k follows
+ * niti_model_eval_topk.  The loss the reference prints every step (NITI_LOSS_Int8), without a
+ * synchronisation per step.  Disabled, nothing is launched.  _reset: the totals <- 0
+ * (asynchronous); _read synchronises `stream`. */
+int niti_model_train_metrics(niti_model_t m, int enable);
+int niti_model_train_metrics_reset(niti_model_t m, void* stream);
+int niti_model_train_metrics_read(niti_model_t m, niti_eval_totals* host_out, void* stream);
 /* Read back (synchronising): the step's quantised input x (NCHW int8) and its exponent. */
 int niti_model_get_input(niti_model_t m, int8_t* x_nchw_host, int* ascale, void* stream);
 /* Read back (synchronising `stream`): logits [batch][classes] int8 and their exponent. */

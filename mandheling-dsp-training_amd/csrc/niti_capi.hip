@@ -1,5 +1,6 @@
 // niti_capi.hip -- extern "C" entry points of sections 1 and 2 of include/niti_hip.h.
 #include "../../include/niti_hip.h"
+#include <memory>
 #include <vector>
 
 #include "niti_internal.hpp"
@@ -682,6 +683,78 @@ int niti_head_metrics(const int8_t* logits, int batch, int classes, int ld, cons
     if (!workspace || workspace_bytes < niti::head_metrics_workspace(batch)) return NITI_INVALID_VALUE;
     return code(niti::head_metrics(logits, batch, classes, ld, ascale, labels, topk, pred, loss_per_image, totals,
                                    workspace, workspace_bytes, S(stream)));
+}
+
+// ---- device-resident dataset
+int niti_dataset_create(const uint8_t* images_nchw, const int32_t* labels, int64_t count, int c, int h, int w,
+                        niti_dataset_t* out) {
+    if (!images_nchw || !labels || !out || count <= 0 || count > INT32_MAX || c <= 0 || h <= 0 || w <= 0 ||
+        (int64_t)c * h * w > INT32_MAX)
+        return NITI_INVALID_VALUE;
+    auto ds = std::make_unique<niti_dataset>();
+    const size_t bytes = (size_t)count * c * h * w;
+    if (hipMalloc(&ds->data, bytes) != hipSuccess || hipMalloc(&ds->labels, (size_t)count * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return NITI_OUT_OF_MEMORY;
+    }
+    if (hipMemcpy(ds->data, images_nchw, bytes, hipMemcpyDefault) != hipSuccess ||
+        hipMemcpy(ds->labels, labels, (size_t)count * 4, hipMemcpyDefault) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    ds->count = count;
+    ds->c = c;
+    ds->h = h;
+    ds->w = w;
+    *out = ds.release();
+    return NITI_NO_ERROR;
+}
+
+void niti_dataset_destroy(niti_dataset_t ds) {
+    if (ds && ds->index) (void)hipDeviceSynchronize();  // (a gather in flight reads the order and the data)
+    delete ds;
+}
+
+int niti_dataset_order_check(const int32_t* index, const int32_t* xform, int64_t len, int64_t count, int batch,
+                             int allow_pad) {
+    if (!index || len <= 0 || count <= 0 || batch <= 0 || len % batch != 0) return NITI_INVALID_VALUE;
+    for (int64_t i = 0; i < len; ++i) {
+        if (index[i] < (allow_pad ? -1 : 0) || index[i] >= count) return NITI_INVALID_VALUE;
+        if (xform && ((uint32_t)xform[i] >> 17) != 0) return NITI_INVALID_VALUE;
+    }
+    return NITI_NO_ERROR;
+}
+
+int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host, int64_t len) {
+    if (!ds) return NITI_INVALID_VALUE;
+    if (const int rc = niti_dataset_order_check(index_host, xform_host, len, ds->count, 1, 1)) return rc;
+    // launches enqueued earlier may still read the previous order: one device synchronisation per
+    // order, i.e. per epoch
+    if (ds->index && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+    if (len > ds->order_cap) {
+        for (void* p : {(void*)ds->index, (void*)ds->xform_buf})
+            if (p) (void)hipFree(p);
+        ds->index = ds->xform = ds->xform_buf = nullptr;
+        ds->order_cap = 0;
+        ds->index_host.clear();
+        if (hipMalloc(&ds->index, (size_t)len * 4) != hipSuccess || hipMalloc(&ds->xform_buf, (size_t)len * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return NITI_OUT_OF_MEMORY;
+        }
+        ds->order_cap = len;
+    }
+    ds->index_host.clear();  // (no order until both copies are in)
+    ds->xform = nullptr;
+    if (hipMemcpy(ds->index, index_host, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        (xform_host && hipMemcpy(ds->xform_buf, xform_host, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return NITI_NO_EXECUTION;
+    ds->xform = xform_host ? ds->xform_buf : nullptr;
+    ds->index_host.assign(index_host, index_host + len);
+    return NITI_NO_ERROR;
+}
+
+int niti_batch_gather(niti_dataset_t ds, int64_t first, int n, uint8_t* images_out, int32_t* labels_out, void* stream) {
+    if (!ds || !images_out || !labels_out || first < 0 || n <= 0 || first > ds->len() - n) return NITI_INVALID_VALUE;
+    return code(niti::batch_gather(ds->data, ds->labels, ds->count, ds->c, ds->h, ds->w, ds->index + first,
+                                   ds->xform ? ds->xform + first : nullptr, n, images_out, labels_out, S(stream)));
 }
 
 }  // extern "C"

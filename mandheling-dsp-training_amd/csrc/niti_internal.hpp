@@ -9,6 +9,26 @@
 #include "../../include/niti_hip.h"
 #include "niti_kernels.hpp"
 
+// A dataset resident in device memory (niti_dataset_*): the images and labels, and the order the
+// batch gather (niti_dataset.hip) walks -- on the device, with the index's host copy the step calls
+// validate their slice against without a device read.
+struct niti_dataset {
+    uint8_t* data = nullptr;    // [count][c][h][w]
+    int32_t* labels = nullptr;  // [count]
+    int64_t count = 0;
+    int c = 0, h = 0, w = 0;
+    int32_t* index = nullptr;  // [len] (device; capacity order_cap entries)
+    int32_t* xform = nullptr;  // [len] or null: no entry is transformed
+    int32_t* xform_buf = nullptr;
+    int64_t order_cap = 0;
+    std::vector<int32_t> index_host;
+    int64_t len() const { return (int64_t)index_host.size(); }
+    ~niti_dataset() {
+        for (void* p : {(void*)data, (void*)labels, (void*)index, (void*)xform_buf})
+            if (p) (void)hipFree(p);
+    }
+};
+
 namespace niti {
 
 // Device memory owned by a handle; acquired in onResize, freed on re-resize / destroy

@@ -571,6 +571,15 @@ hipError_t head_metrics(const int8_t* logits, int batch, int classes, int ld, co
                         const int32_t* labels, int topk, int32_t* pred, double* loss_per_image,
                         niti_eval_totals* totals, void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// Batch gather of a device-resident dataset (niti_dataset.hip): entry i of the order (s = index[i],
+// t = xform ? xform[i] : 0) -> out[i] uint8 [c][h][w] and labels_out[i].  s outside [0, count): a
+// zero image, label -1.  Else dx = (int8)(t & 0xff), dy = (int8)(t >> 8 & 0xff), flip = t >> 16 & 1:
+// out[i][ch][y][x] = data[s][ch][y + dy][(flip ? w - 1 - x : x) + dx], 0 outside the image.  One
+// launch; nothing outside data[0 .. count) is read.
+hipError_t batch_gather(const uint8_t* data, const int32_t* labels, int64_t count, int c, int h, int w,
+                        const int32_t* index, const int32_t* xform, int n, uint8_t* out, int32_t* labels_out,
+                        hipStream_t st);
+
 // ---- input quantiser (MnistUtils.cpp:83-93; niti_quant.hip states the exact contract) -------
 // stats (4 x u64, device) = {S1 = sum x, S2 = sum x^2, xmax, 255 - xmin} of n uint8 pixels
 hipError_t image_stats(const uint8_t* img, int64_t n, unsigned long long* stats, hipStream_t st);

@@ -515,6 +515,13 @@ struct Model final : StepDriver {
     int get_weight(int layer, int8_t* w_oihw_host) override;
     int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
     int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
+    void logits_view(const int8_t** logits, int* classes, int* ld, const int8_t** exp) const override {
+        const Layer& t = L.back();
+        *logits = t.r;
+        *classes = t.g.c_out;
+        *ld = t.g.cop;
+        *exp = t.exp;
+    }
     int get_input(int8_t* host, int* ascale, hipStream_t st) override;
     int64_t step_macs() const override;
     int spec_stats(uint32_t* out, int max_layers) override;

@@ -93,6 +93,30 @@ int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream)
     return m && pred_host ? m->d->get_predictions(pred_host, (hipStream_t)stream) : NITI_INVALID_VALUE;
 }
 
+int niti_model_train_steps_dataset(niti_model_t m, niti_dataset_t ds, int64_t first_step, int n_steps, void* stream) {
+    if (!m || !ds) return NITI_INVALID_VALUE;
+    return m->d->steps_dataset(*ds, first_step, n_steps, true, (hipStream_t)stream);
+}
+
+int niti_model_eval_steps_dataset(niti_model_t m, niti_dataset_t ds, int64_t first_step, int n_steps, void* stream) {
+    if (!m || !ds) return NITI_INVALID_VALUE;
+    return m->d->steps_dataset(*ds, first_step, n_steps, false, (hipStream_t)stream);
+}
+
+int niti_model_train_metrics(niti_model_t m, int enable) {
+    if (!m) return NITI_INVALID_VALUE;
+    m->d->tm_enabled = enable != 0;
+    return NITI_NO_ERROR;
+}
+
+int niti_model_train_metrics_reset(niti_model_t m, void* stream) {
+    return m ? m->d->train_metrics_reset((hipStream_t)stream) : NITI_INVALID_VALUE;
+}
+
+int niti_model_train_metrics_read(niti_model_t m, niti_eval_totals* host_out, void* stream) {
+    return m && host_out ? m->d->train_metrics_read(host_out, (hipStream_t)stream) : NITI_INVALID_VALUE;
+}
+
 int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream) {
     return dst && src ? dst->d->copy_weights_from(*src->d, (hipStream_t)stream) : NITI_INVALID_VALUE;
 }

@@ -174,6 +174,13 @@ struct ResNetModel final : StepDriver {
     int get_weight(int i, int8_t* w_oihw_host) override;
     int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
     int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
+    void logits_view(const int8_t** logits, int* classes_out, int* ld, const int8_t** exp) const override {
+        const RConv& f = C.back();
+        *logits = f.y;
+        *classes_out = classes;
+        *ld = f.g.cop;
+        *exp = f.y_exp;
+    }
     int get_input(int8_t* host, int* ascale, hipStream_t st) override;
     int64_t step_macs() const override;
     int spec_stats(uint32_t* out, int max_layers) override;

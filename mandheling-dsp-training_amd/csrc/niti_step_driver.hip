@@ -159,8 +159,11 @@ int StepDriver::alloc_eval() {
     ev_ws = ws.alloc(ev_ws_bytes);
     ev_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
     ev_pred = (int32_t*)ws.alloc((size_t)batch * 4);
-    if (!ev_ws || !ev_totals || !ev_pred) return NITI_OUT_OF_MEMORY;
+    tm_ws = ws.alloc(ev_ws_bytes);
+    tm_totals = (niti_eval_totals*)ws.alloc(sizeof(niti_eval_totals));
+    if (!ev_ws || !ev_totals || !ev_pred || !tm_ws || !tm_totals) return NITI_OUT_OF_MEMORY;
     if (hipMemset(ev_totals, 0, sizeof(niti_eval_totals)) != hipSuccess ||
+        hipMemset(tm_totals, 0, sizeof(niti_eval_totals)) != hipSuccess ||
         hipMemset(ev_pred, 0, (size_t)batch * 4) != hipSuccess)
         return NITI_NO_EXECUTION;
     return NITI_NO_ERROR;
@@ -180,6 +183,54 @@ int StepDriver::eval_read(niti_eval_totals* host_out, hipStream_t st) {
 int StepDriver::get_predictions(int32_t* pred_host, hipStream_t st) {
     DTRY(hipStreamSynchronize(st));
     DTRY(hipMemcpy(pred_host, ev_pred, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    return NITI_NO_ERROR;
+}
+
+// ------------------------------------------------------------------------------ dataset steps
+// Steps first_step .. first_step + n_steps - 1 of the dataset's order, each the gather of its `batch`
+// entries into the staging batch (a direct launch on `st`: under set_graph(1) it sits ahead of the
+// replay's fence) and then step() / eval() on the staging pointers.  Everything is refused before
+// the first launch: another geometry than the model's input, a slice past the order's end, a
+// padding entry (-1) in a training slice.
+int StepDriver::steps_dataset(niti_dataset& ds, int64_t first_step, int n_steps, bool train, hipStream_t st) {
+    int info[12];
+    if (layer_info(0, info) != NITI_NO_ERROR) return NITI_INVALID_VALUE;
+    if (ds.c != info[0] || ds.h != info[4] || ds.w != info[5]) return NITI_INVALID_VALUE;
+    if (first_step < 0 || n_steps <= 0 || first_step > ds.len() / batch - n_steps) return NITI_INVALID_VALUE;
+    const int64_t lo = first_step * batch, hi = lo + (int64_t)n_steps * batch;
+    if (train && std::find(ds.index_host.begin() + lo, ds.index_host.begin() + hi, -1) != ds.index_host.begin() + hi)
+        return NITI_INVALID_VALUE;
+    if (st_images == nullptr) {
+        uint8_t* im = (uint8_t*)ws.alloc((size_t)batch * ds.c * ds.h * ds.w);
+        int32_t* lb = (int32_t*)ws.alloc((size_t)batch * 4);
+        if (!im || !lb) return NITI_OUT_OF_MEMORY;
+        st_images = im;
+        st_labels = lb;
+    }
+    const int8_t* logits = nullptr;
+    const int8_t* lexp = nullptr;
+    int classes = 0, ld = 0;
+    logits_view(&logits, &classes, &ld, &lexp);
+    for (int64_t s = first_step; s < first_step + n_steps; ++s) {
+        DTRY(batch_gather(ds.data, ds.labels, ds.count, ds.c, ds.h, ds.w, ds.index + s * batch,
+                          ds.xform ? ds.xform + s * batch : nullptr, batch, st_images, st_labels, st));
+        const int rc = train ? step(nullptr, 0, st_images, st_labels, st) : eval(nullptr, 0, st_images, st_labels, st);
+        if (rc != NITI_NO_ERROR) return rc;
+        if (train && tm_enabled)
+            DTRY(head_metrics(logits, batch, classes, ld, lexp, st_labels, std::min(ev_topk, classes), nullptr, nullptr,
+                              tm_totals, tm_ws, ev_ws_bytes, st));
+    }
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::train_metrics_reset(hipStream_t st) {
+    DTRY(fill_kernel(tm_totals, 0, sizeof(niti_eval_totals), st));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::train_metrics_read(niti_eval_totals* host_out, hipStream_t st) {
+    DTRY(hipStreamSynchronize(st));
+    DTRY(hipMemcpy(host_out, tm_totals, sizeof(niti_eval_totals), hipMemcpyDeviceToHost));
     return NITI_NO_ERROR;
 }
 

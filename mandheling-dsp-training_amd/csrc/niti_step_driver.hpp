@@ -2,8 +2,8 @@
 // share: the chain driver (LeNet / VGG, niti_model.hip) and ResNet-18 (niti_resnet_model.hip).
 //
 // StepDriver holds the state and the logic both have in the same form -- split-K slabs, the
-// data-parallel gradient buckets, the event probe, the evaluation totals, the graph stream and its
-// fences, the teardown -- and declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
+// data-parallel gradient buckets, the event probe, the evaluation totals, the device-resident dataset
+// steps, the graph stream and its fences, the teardown -- and declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
 // driver.  A virtual is called at most once per ABI call; nothing inside a step (run(), forward(),
 // backward(), the per-layer functions) goes through one.  The base does not know which driver it
 // serves: where the two differ, the difference is the derived class's.
@@ -97,6 +97,20 @@ struct StepDriver {
     int eval_read(niti_eval_totals* host_out, hipStream_t st);
     int get_predictions(int32_t* pred_host, hipStream_t st);
     int rowconv_error();
+    // device-resident dataset steps (niti_model_*_steps_dataset): batch s of the dataset's order is
+    // gathered (niti_dataset.hip) into the staging batch below -- allocated on first use, never inside
+    // a step, and never moved, so a captured training step is captured once -- and goes through the
+    // driver's own step() / eval() as any caller's uint8 batch; nothing on the host waits
+    uint8_t* st_images = nullptr;
+    int32_t* st_labels = nullptr;
+    int steps_dataset(niti_dataset& ds, int64_t first_step, int n_steps, bool train, hipStream_t st);
+    // training metrics (opt-in): head_metrics of each dataset training step's logits and staged
+    // labels, added to totals of their own (allocated with the evaluation's, alloc_eval)
+    bool tm_enabled = false;
+    niti_eval_totals* tm_totals = nullptr;
+    void* tm_ws = nullptr;
+    int train_metrics_reset(hipStream_t st);
+    int train_metrics_read(niti_eval_totals* host_out, hipStream_t st);
     // the shared half of plan_set: the tile set {64, 128, 256} or the taps tile (own_tile: a tile of
     // the driver's own, which it vouches for), the strategy range, strategies 3 and 4 only for
     // unsplit activation GEMMs; then the override, with the split-K slabs it needs (gemm_slab)
@@ -113,6 +127,8 @@ struct StepDriver {
     virtual int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) = 0;
     virtual int get_logits(int8_t* host, int* exp_out, hipStream_t st) = 0;
     virtual int get_input(int8_t* host, int* ascale, hipStream_t st) = 0;
+    // the logits as the last step left them on the device: int8 [batch][*ld], their exponent
+    virtual void logits_view(const int8_t** logits, int* classes, int* ld, const int8_t** exp) const = 0;
     virtual int64_t step_macs() const = 0;
     virtual int spec_stats(uint32_t* out, int max_layers) = 0;
     // a layer's row-kernel state (grid barrier words + speculation slots; may be null)

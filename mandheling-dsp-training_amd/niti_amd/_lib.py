@@ -226,6 +226,16 @@ def lib():
         "niti_image_quantize_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, i64, vp, vp, vp]),
         "niti_model_train_step_images": (ci, [vp, vp, vp, vp]),
         "niti_model_get_input": (ci, [vp, vp, C.POINTER(ci), vp]),
+        "niti_dataset_create": (ci, [vp, vp, i64, ci, ci, ci, C.POINTER(vp)]),
+        "niti_dataset_destroy": (None, [vp]),
+        "niti_dataset_order_check": (ci, [vp, vp, i64, i64, ci, ci]),
+        "niti_dataset_set_order": (ci, [vp, vp, vp, i64]),
+        "niti_batch_gather": (ci, [vp, i64, ci, vp, vp, vp]),
+        "niti_model_train_steps_dataset": (ci, [vp, vp, i64, ci, vp]),
+        "niti_model_eval_steps_dataset": (ci, [vp, vp, i64, ci, vp]),
+        "niti_model_train_metrics": (ci, [vp, ci]),
+        "niti_model_train_metrics_reset": (ci, [vp, vp]),
+        "niti_model_train_metrics_read": (ci, [vp, C.POINTER(EvalTotals), vp]),
         "niti_local_group_create": (ci, [ci, C.POINTER(vp)]),
         "niti_local_group_destroy": (None, [vp]),
         "niti_model_attach_local": (ci, [vp, vp, ci, ci]),

@@ -141,6 +141,10 @@ class NitiModel:
         images, accuracy = top1 / images (nan before any image was counted)."""
         t = L.EvalTotals()
         check(self._lib.niti_model_eval_read(self._h, C.byref(t), _stream(stream)), "eval_read")
+        return self._totals_dict(t)
+
+    @staticmethod
+    def _totals_dict(t) -> dict:
         n = int(t.images)
         return {"images": n, "top1": int(t.top1), "topk": int(t.topk), "loss_sum": float(t.loss_sum),
                 "loss": float(t.loss_sum) / n if n else float("nan"),
@@ -182,6 +186,54 @@ class NitiModel:
         for i in range(0, n + pad, b):
             self.eval_step_images(img[i:i + b], lab[i:i + b], stream)
         return self.eval_read(stream)
+
+    # ---- device-resident dataset (niti_amd.dataset)
+    def train_steps(self, ds, first_step: int, n_steps: int, stream=None):
+        """n_steps training steps on batches first_step.. of ds's order, gathered on the device
+        (niti_model_train_steps_dataset).  Asynchronous: nothing waits on the host."""
+        check(self._lib.niti_model_train_steps_dataset(self._h, ds._h, int(first_step), int(n_steps), _stream(stream)),
+              "train_steps_dataset")
+
+    def eval_steps(self, ds, first_step: int, n_steps: int, stream=None):
+        """The same through the evaluation step; entries of index -1 are counted nowhere."""
+        check(self._lib.niti_model_eval_steps_dataset(self._h, ds._h, int(first_step), int(n_steps), _stream(stream)),
+              "eval_steps_dataset")
+
+    def fit_epoch(self, ds, seed: int, epoch: int, pad: int = 0, flip: bool = False, stream=None) -> int:
+        """One epoch over ds: make_order(ds.count, batch, seed, epoch, pad, flip) -- the last partial
+        batch dropped -- set as ds's order (one device synchronisation), then every step enqueued.
+        Returns the number of steps; asynchronous."""
+        from .dataset import make_order
+        index, xform = make_order(ds.count, self.batch, seed, epoch, pad=pad, flip=flip, drop_last=True)
+        ds.set_order(index, xform if (pad or flip) else None)
+        steps = len(index) // self.batch
+        self.train_steps(ds, 0, steps, stream)
+        return steps
+
+    def evaluate_dataset(self, ds, stream=None) -> dict:
+        """evaluate() on a DeviceDataset: a sequential order (which replaces ds's), the last partial
+        batch padded with -1 entries, the totals reset, every batch enqueued, one synchronisation in
+        eval_read."""
+        n, b = ds.count, self.batch
+        index = np.concatenate([np.arange(n, dtype=np.int32), np.full((-n) % b, -1, np.int32)])
+        ds.set_order(index)
+        self.eval_reset(stream)
+        self.eval_steps(ds, 0, len(index) // b, stream)
+        return self.eval_read(stream)
+
+    def train_metrics(self, enable: bool):
+        """Add each dataset training step's loss / top-1 / top-k (of the step's own logits and
+        labels) to running totals on the device (default off: nothing is launched)."""
+        check(self._lib.niti_model_train_metrics(self._h, 1 if enable else 0), "train_metrics")
+
+    def train_metrics_reset(self, stream=None):
+        check(self._lib.niti_model_train_metrics_reset(self._h, _stream(stream)), "train_metrics_reset")
+
+    def train_metrics_read(self, stream=None) -> dict:
+        """The training totals (synchronises), in eval_read's form."""
+        t = L.EvalTotals()
+        check(self._lib.niti_model_train_metrics_read(self._h, C.byref(t), _stream(stream)), "train_metrics_read")
+        return self._totals_dict(t)
 
     def input(self, stream=None):
         """The last step's quantised input x (NCHW int8) and its exponent."""
