@@ -574,8 +574,9 @@ int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream);
 /* A training or test set kept in device memory, and the batches of an epoch gathered out of it on
  * the device: shuffled, and with the pad-and-crop / horizontal-flip augmentation of CIFAR-class
  * data.  images_nchw uint8 [count][c][h][w] and labels int32 [count] may be host or device
- * pointers; both are copied (synchronously), so the caller's arrays can go.  The images must
- * already have the model's input size. */
+ * pointers; both are copied (synchronously), so the caller's arrays can go.  The images either
+ * have the model's input size already, or another size of their own with an output size set
+ * (niti_dataset_set_output) and orders that carry crop windows (niti_dataset_set_order_windows). */
 typedef struct niti_dataset* niti_dataset_t;
 int niti_dataset_create(const uint8_t* images_nchw, const int32_t* labels, int64_t count, int c, int h, int w,
                         niti_dataset_t* out);
@@ -597,13 +598,47 @@ int niti_dataset_order_check(const int32_t* index, const int32_t* xform, int64_t
 /* Checks the order (allow_pad = 1, batch = 1) and copies it to the device (host pointers; xform
  * may be NULL).  Replacing a previous order SYNCHRONISES THE DEVICE first -- steps enqueued earlier
  * may still read it -- which is one synchronisation per epoch.  NITI_NO_EXECUTION if a copy fails
- * (the dataset then has no order). */
+ * (the dataset then has no order).  The order has no crop windows afterwards. */
 int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host, int64_t len);
+/* Crop-and-resize: stored images of another size than the model's input.  A dataset has an output
+ * size (oh, ow), by default its stored (h, w), and an order may carry, besides index and xform,
+ * window[len][4] (int32) = (x0, y0, cw, ch): a rectangle inside the stored image, cw, ch >= 1,
+ * x0, y0 >= 0, x0 + cw <= w, y0 + ch <= h.  With windows the xform words may carry the flip bit 16
+ * only (dx = dy = 0).  Entry i with s = index[i] >= 0 is its window resized bilinearly, corner
+ * pixel to corner pixel, to oh x ow and then mirrored, all in integers (divisions floor):
+ *   pos(o, n_out, cn) = 0 if n_out == 1, else (2*o*(cn-1)*256 + (n_out-1)) / (2*(n_out-1))
+ *   px = pos(flip ? ow-1-x : x, ow, cw);  ix = x0 + (px >> 8);  fx = px & 255;  ix1 = min(ix+1, x0+cw-1)
+ *   py = pos(y, oh, ch);                  iy = y0 + (py >> 8);  fy = py & 255;  iy1 = min(iy+1, y0+ch-1)
+ *   A = data[s][c][iy][ix]  B = data[s][c][iy][ix1]  C = data[s][c][iy1][ix]  D = data[s][c][iy1][ix1]
+ *   out[i][c][y][x] = (((256-fx)*A + fx*B)*(256-fy) + ((256-fx)*C + fx*D)*fy + 32768) >> 16
+ * with the label labels[s]; an index of -1 is a zero image with label -1, as without windows.
+ * Positions are rounded to 1/256 px and the weights are exact 8-bit ones, so the result lies within
+ * 1.5 of the real-valued bilinear value; a window of exactly ow x oh is the plain crop, a 1x1 window
+ * a constant image.  This integer form is the library's own contract (the reference resamples in
+ * float).  Every intermediate fits 32 unsigned bits while (ow-1)*(w-1) < 2^22 and
+ * (oh-1)*(h-1) < 2^22; sizes beyond that are refused.
+ * niti_dataset_set_output: NITI_INVALID_VALUE for a size < 1 or beyond that bound; SYNCHRONISES THE
+ * DEVICE if an order is set, and drops the order.
+ * niti_dataset_windows_check (host only, no device call): NITI_INVALID_VALUE for a NULL window,
+ * len <= 0, h or w <= 0, a window that breaks a rule above, and (xform may be NULL) an xform word
+ * with any bit but 16 set.
+ * niti_dataset_set_order_windows: niti_dataset_set_order's checks plus the window check, the same
+ * synchronise-on-replace rule, NITI_NO_EXECUTION if a copy fails (the dataset then has no order). */
+int niti_dataset_set_output(niti_dataset_t ds, int oh, int ow);
+int niti_dataset_windows_check(const int32_t* window, const int32_t* xform, int64_t len, int h, int w);
+int niti_dataset_set_order_windows(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host,
+                                   const int32_t* window_host, int64_t len);
 /* The primitive: entries [first, first + n) of the order into images_out (uint8 [n][c][h][w],
  * device) and labels_out (int32 [n], device).  One launch, asynchronous, no atomics; nothing outside
  * the dataset is read.  16-byte copies when no xform is set and c*h*w % 16 == 0; with an xform and
  * w % 4 == 0 aligned dword loads, a byte funnel shift and a byte reverse, dword (w % 16 == 0:
- * 16-byte) stores; otherwise a byte per lane. */
+ * 16-byte) stores; otherwise a byte per lane.
+ * When the order has windows images_out is [n][c][oh][ow] and the crop-and-resize kernel runs: a
+ * block builds its entry's column and row positions once (no per-pixel division), a lane produces
+ * 16 adjacent pixels and one 16-byte store (ow % 16 == 0, images_out 16-byte aligned), 4 and one
+ * dword store (ow % 4 == 0, 4-byte aligned) or one byte; the window words are clamped into the
+ * stored image.  Without windows the output size must be the stored size: NITI_INVALID_VALUE
+ * otherwise. */
 int niti_batch_gather(niti_dataset_t ds, int64_t first, int n, uint8_t* images_out, int32_t* labels_out,
                       void* stream);
 /* n_steps training steps, step s (first_step <= s < first_step + n_steps) on batch s of the
@@ -611,7 +646,8 @@ int niti_batch_gather(niti_dataset_t ds, int64_t first, int n, uint8_t* images_o
  * first call), then runs as niti_model_train_step_images does -- the same launches; under
  * niti_model_set_graph(1) one captured step is replayed for every batch, as the staging pointers
  * never change.  Asynchronous: nothing on the host waits, a whole epoch can be enqueued.
- * NITI_INVALID_VALUE, before any launch, for a dataset whose c, h, w are not the model's input,
+ * NITI_INVALID_VALUE, before any launch, for a dataset whose c and output size (oh, ow) are not the
+ * model's input, an output size other than the stored size while the order has no windows,
  * first_step / n_steps outside the order, and a -1 entry in the slice.  With a communicator or a
  * local group attached every rank owns its dataset and order (its share of each global batch) and
  * all ranks call together. */

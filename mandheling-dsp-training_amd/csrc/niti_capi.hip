@@ -702,8 +702,8 @@ int niti_dataset_create(const uint8_t* images_nchw, const int32_t* labels, int64
         return NITI_NO_EXECUTION;
     ds->count = count;
     ds->c = c;
-    ds->h = h;
-    ds->w = w;
+    ds->h = ds->oh = h;
+    ds->w = ds->ow = w;
     *out = ds.release();
     return NITI_NO_ERROR;
 }
@@ -723,9 +723,11 @@ int niti_dataset_order_check(const int32_t* index, const int32_t* xform, int64_t
     return NITI_NO_ERROR;
 }
 
-int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host, int64_t len) {
-    if (!ds) return NITI_INVALID_VALUE;
-    if (const int rc = niti_dataset_order_check(index_host, xform_host, len, ds->count, 1, 1)) return rc;
+namespace {
+
+// niti_dataset_set_order / _set_order_windows: the order is checked by the caller
+int dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host,
+                      const int32_t* window_host, int64_t len) {
     // launches enqueued earlier may still read the previous order: one device synchronisation per
     // order, i.e. per epoch
     if (ds->index && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
@@ -741,20 +743,74 @@ int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const i
         }
         ds->order_cap = len;
     }
-    ds->index_host.clear();  // (no order until both copies are in)
+    ds->index_host.clear();  // (no order until every copy is in)
     ds->xform = nullptr;
+    ds->window = nullptr;
+    if (window_host && len > ds->window_cap) {
+        if (ds->window_buf) (void)hipFree(ds->window_buf);
+        ds->window_buf = nullptr;
+        ds->window_cap = 0;
+        if (hipMalloc(&ds->window_buf, (size_t)len * 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return NITI_OUT_OF_MEMORY;
+        }
+        ds->window_cap = len;
+    }
     if (hipMemcpy(ds->index, index_host, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (xform_host && hipMemcpy(ds->xform_buf, xform_host, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess))
+        (xform_host && hipMemcpy(ds->xform_buf, xform_host, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        (window_host && hipMemcpy(ds->window_buf, window_host, (size_t)len * 16, hipMemcpyHostToDevice) != hipSuccess))
         return NITI_NO_EXECUTION;
     ds->xform = xform_host ? ds->xform_buf : nullptr;
+    ds->window = window_host ? ds->window_buf : nullptr;
     ds->index_host.assign(index_host, index_host + len);
     return NITI_NO_ERROR;
 }
 
+}  // namespace
+
+int niti_dataset_set_order(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host, int64_t len) {
+    if (!ds) return NITI_INVALID_VALUE;
+    if (const int rc = niti_dataset_order_check(index_host, xform_host, len, ds->count, 1, 1)) return rc;
+    return dataset_set_order(ds, index_host, xform_host, nullptr, len);
+}
+
+int niti_dataset_set_output(niti_dataset_t ds, int oh, int ow) {
+    if (!ds || !niti::resize_size_ok(ds->h, oh) || !niti::resize_size_ok(ds->w, ow) ||
+        (int64_t)ds->c * oh * ow > INT32_MAX)
+        return NITI_INVALID_VALUE;
+    // (a gather in flight was sized by the previous output size and reads the order)
+    if (ds->len() > 0 && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+    ds->index_host.clear();
+    ds->xform = nullptr;
+    ds->window = nullptr;
+    ds->oh = oh;
+    ds->ow = ow;
+    return NITI_NO_ERROR;
+}
+
+int niti_dataset_windows_check(const int32_t* window, const int32_t* xform, int64_t len, int h, int w) {
+    if (!window || len <= 0 || h <= 0 || w <= 0) return NITI_INVALID_VALUE;
+    for (int64_t i = 0; i < len; ++i) {
+        const int64_t x0 = window[4 * i], y0 = window[4 * i + 1], cw = window[4 * i + 2], ch = window[4 * i + 3];
+        if (cw < 1 || ch < 1 || x0 < 0 || y0 < 0 || x0 + cw > w || y0 + ch > h) return NITI_INVALID_VALUE;
+        if (xform && ((uint32_t)xform[i] & ~(1u << 16)) != 0) return NITI_INVALID_VALUE;
+    }
+    return NITI_NO_ERROR;
+}
+
+int niti_dataset_set_order_windows(niti_dataset_t ds, const int32_t* index_host, const int32_t* xform_host,
+                                   const int32_t* window_host, int64_t len) {
+    if (!ds) return NITI_INVALID_VALUE;
+    if (const int rc = niti_dataset_order_check(index_host, xform_host, len, ds->count, 1, 1)) return rc;
+    if (const int rc = niti_dataset_windows_check(window_host, xform_host, len, ds->h, ds->w)) return rc;
+    // (a stored size beyond the definition's 32-bit headroom with the default output size)
+    if (!niti::resize_size_ok(ds->h, ds->oh) || !niti::resize_size_ok(ds->w, ds->ow)) return NITI_INVALID_VALUE;
+    return dataset_set_order(ds, index_host, xform_host, window_host, len);
+}
+
 int niti_batch_gather(niti_dataset_t ds, int64_t first, int n, uint8_t* images_out, int32_t* labels_out, void* stream) {
     if (!ds || !images_out || !labels_out || first < 0 || n <= 0 || first > ds->len() - n) return NITI_INVALID_VALUE;
-    return code(niti::batch_gather(ds->data, ds->labels, ds->count, ds->c, ds->h, ds->w, ds->index + first,
-                                   ds->xform ? ds->xform + first : nullptr, n, images_out, labels_out, S(stream)));
+    return code(ds->gather(first, n, images_out, labels_out, S(stream)));
 }
 
 }  // extern "C"

@@ -17,14 +17,27 @@ struct niti_dataset {
     int32_t* labels = nullptr;  // [count]
     int64_t count = 0;
     int c = 0, h = 0, w = 0;
+    int oh = 0, ow = 0;        // the size of a gathered image (niti_dataset_set_output; default h, w)
     int32_t* index = nullptr;  // [len] (device; capacity order_cap entries)
     int32_t* xform = nullptr;  // [len] or null: no entry is transformed
     int32_t* xform_buf = nullptr;
-    int64_t order_cap = 0;
+    int32_t* window = nullptr;  // [len][4] or null: the order has no crop windows
+    int32_t* window_buf = nullptr;
+    int64_t order_cap = 0, window_cap = 0;
     std::vector<int32_t> index_host;
     int64_t len() const { return (int64_t)index_host.size(); }
+    // entries [first, first + n) of the order into out [n][c][oh][ow]: the crop-and-resize gather
+    // when the order has windows, else the plain one, which needs oh, ow == h, w
+    hipError_t gather(int64_t first, int n, uint8_t* out, int32_t* labels_out, hipStream_t st) const {
+        const int32_t* xf = xform ? xform + first : nullptr;
+        if (window)
+            return niti::batch_gather_resize(data, labels, count, c, h, w, index + first, xf, window + first * 4, n, oh,
+                                             ow, out, labels_out, st);
+        if (oh != h || ow != w) return hipErrorInvalidValue;
+        return niti::batch_gather(data, labels, count, c, h, w, index + first, xf, n, out, labels_out, st);
+    }
     ~niti_dataset() {
-        for (void* p : {(void*)data, (void*)labels, (void*)index, (void*)xform_buf})
+        for (void* p : {(void*)data, (void*)labels, (void*)index, (void*)xform_buf, (void*)window_buf})
             if (p) (void)hipFree(p);
     }
 };

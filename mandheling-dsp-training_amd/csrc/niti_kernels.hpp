@@ -579,6 +579,16 @@ hipError_t head_metrics(const int8_t* logits, int batch, int classes, int ld, co
 hipError_t batch_gather(const uint8_t* data, const int32_t* labels, int64_t count, int c, int h, int w,
                         const int32_t* index, const int32_t* xform, int n, uint8_t* out, int32_t* labels_out,
                         hipStream_t st);
+// The same for an order with crop windows (window [n][4] int32 = x0, y0, cw, ch inside the stored
+// image): entry i is its window resized bilinearly to oh x ow and mirrored if xform[i] bit 16 is set
+// (no other xform bit is read), by the integer definition in include/niti_hip.h; out [n][c][oh][ow].
+// One launch, no atomics; the window words are clamped into the image, so nothing outside
+// data[0 .. count) is read.  resize_size_ok: (out - 1) * (in - 1) < 2^22, the definition's 32-bit
+// headroom for one axis.
+bool resize_size_ok(int in, int out);
+hipError_t batch_gather_resize(const uint8_t* data, const int32_t* labels, int64_t count, int c, int h, int w,
+                               const int32_t* index, const int32_t* xform, const int32_t* window, int n, int oh,
+                               int ow, uint8_t* out, int32_t* labels_out, hipStream_t st);
 
 // ---- input quantiser (MnistUtils.cpp:83-93; niti_quant.hip states the exact contract) -------
 // stats (4 x u64, device) = {S1 = sum x, S2 = sum x^2, xmax, 255 - xmin} of n uint8 pixels

@@ -190,18 +190,20 @@ int StepDriver::get_predictions(int32_t* pred_host, hipStream_t st) {
 // Steps first_step .. first_step + n_steps - 1 of the dataset's order, each the gather of its `batch`
 // entries into the staging batch (a direct launch on `st`: under set_graph(1) it sits ahead of the
 // replay's fence) and then step() / eval() on the staging pointers.  Everything is refused before
-// the first launch: another geometry than the model's input, a slice past the order's end, a
-// padding entry (-1) in a training slice.
+// the first launch: an output size (niti_dataset_set_output; the stored size by default) or channel
+// count that is not the model's input, an output size other than the stored one while the order has
+// no crop windows, a slice past the order's end, a padding entry (-1) in a training slice.
 int StepDriver::steps_dataset(niti_dataset& ds, int64_t first_step, int n_steps, bool train, hipStream_t st) {
     int info[12];
     if (layer_info(0, info) != NITI_NO_ERROR) return NITI_INVALID_VALUE;
-    if (ds.c != info[0] || ds.h != info[4] || ds.w != info[5]) return NITI_INVALID_VALUE;
+    if (ds.c != info[0] || ds.oh != info[4] || ds.ow != info[5]) return NITI_INVALID_VALUE;
+    if (ds.window == nullptr && (ds.oh != ds.h || ds.ow != ds.w)) return NITI_INVALID_VALUE;
     if (first_step < 0 || n_steps <= 0 || first_step > ds.len() / batch - n_steps) return NITI_INVALID_VALUE;
     const int64_t lo = first_step * batch, hi = lo + (int64_t)n_steps * batch;
     if (train && std::find(ds.index_host.begin() + lo, ds.index_host.begin() + hi, -1) != ds.index_host.begin() + hi)
         return NITI_INVALID_VALUE;
     if (st_images == nullptr) {
-        uint8_t* im = (uint8_t*)ws.alloc((size_t)batch * ds.c * ds.h * ds.w);
+        uint8_t* im = (uint8_t*)ws.alloc((size_t)batch * ds.c * ds.oh * ds.ow);
         int32_t* lb = (int32_t*)ws.alloc((size_t)batch * 4);
         if (!im || !lb) return NITI_OUT_OF_MEMORY;
         st_images = im;
@@ -212,8 +214,7 @@ int StepDriver::steps_dataset(niti_dataset& ds, int64_t first_step, int n_steps,
     int classes = 0, ld = 0;
     logits_view(&logits, &classes, &ld, &lexp);
     for (int64_t s = first_step; s < first_step + n_steps; ++s) {
-        DTRY(batch_gather(ds.data, ds.labels, ds.count, ds.c, ds.h, ds.w, ds.index + s * batch,
-                          ds.xform ? ds.xform + s * batch : nullptr, batch, st_images, st_labels, st));
+        DTRY(ds.gather(s * batch, batch, st_images, st_labels, st));
         const int rc = train ? step(nullptr, 0, st_images, st_labels, st) : eval(nullptr, 0, st_images, st_labels, st);
         if (rc != NITI_NO_ERROR) return rc;
         if (train && tm_enabled)

@@ -8,6 +8,7 @@ from ._lib import (ARCH_LENET, ARCH_RESNET18, ARCH_VGG11, ARCH_VGG16, FORMAT_NC4
                    OP_DSP_GRADIENT_SPLITBATCHCONV_INT8, OP_DSP_MATMUL_GRADIENT_INT8, OP_DSP_PARALLEL_GRADIENTCONV_INT8,
                    OP_DSP_TRANSPOSEGRADIENT_CONV_INT8, OP_GRADIENT_CONV_INT8,
                    OP_LOSS_GRAD_INT8, OP_LOSS_INT8, OP_MATMUL_INT8, PAD_CAFFE, PAD_SAME, PAD_VALID, NitiError, check, header_functions, lib)
-from .dataset import DeviceDataset, make_order, pack_xform, unpack_xform  # noqa: F401
+from .dataset import (DeviceDataset, center_windows, make_order, make_rrc_order, pack_xform,  # noqa: F401
+                      random_fraction_windows, unpack_xform)
 
 lib()  # fail loudly if the HIP library is missing

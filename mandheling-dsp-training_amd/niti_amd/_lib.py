@@ -230,6 +230,9 @@ def lib():
         "niti_dataset_destroy": (None, [vp]),
         "niti_dataset_order_check": (ci, [vp, vp, i64, i64, ci, ci]),
         "niti_dataset_set_order": (ci, [vp, vp, vp, i64]),
+        "niti_dataset_set_output": (ci, [vp, ci, ci]),
+        "niti_dataset_windows_check": (ci, [vp, vp, i64, ci, ci]),
+        "niti_dataset_set_order_windows": (ci, [vp, vp, vp, vp, i64]),
         "niti_batch_gather": (ci, [vp, i64, ci, vp, vp, vp]),
         "niti_model_train_steps_dataset": (ci, [vp, vp, i64, ci, vp]),
         "niti_model_eval_steps_dataset": (ci, [vp, vp, i64, ci, vp]),

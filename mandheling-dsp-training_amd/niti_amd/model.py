@@ -199,24 +199,43 @@ class NitiModel:
         check(self._lib.niti_model_eval_steps_dataset(self._h, ds._h, int(first_step), int(n_steps), _stream(stream)),
               "eval_steps_dataset")
 
-    def fit_epoch(self, ds, seed: int, epoch: int, pad: int = 0, flip: bool = False, stream=None) -> int:
+    def fit_epoch(self, ds, seed: int, epoch: int, pad: int = 0, flip: bool = False, stream=None, rrc=None) -> int:
         """One epoch over ds: make_order(ds.count, batch, seed, epoch, pad, flip) -- the last partial
         batch dropped -- set as ds's order (one device synchronisation), then every step enqueued.
+        rrc (a dict with `scale` and / or `ratio`, may be empty; needs pad == 0): the order is
+        make_rrc_order's instead, a random-resized crop of every stored image to ds's output size.
         Returns the number of steps; asynchronous."""
-        from .dataset import make_order
-        index, xform = make_order(ds.count, self.batch, seed, epoch, pad=pad, flip=flip, drop_last=True)
-        ds.set_order(index, xform if (pad or flip) else None)
+        from .dataset import make_order, make_rrc_order
+        if rrc is not None:
+            if pad != 0:
+                raise ValueError("rrc needs pad == 0")
+            if set(rrc) - {"scale", "ratio"}:
+                raise ValueError("rrc takes scale and ratio")
+            index, xform, windows = make_rrc_order(ds.count, self.batch, seed, epoch, ds.h, ds.w, flip=flip,
+                                                   drop_last=True, **rrc)
+            ds.set_order(index, xform, windows)
+        else:
+            index, xform = make_order(ds.count, self.batch, seed, epoch, pad=pad, flip=flip, drop_last=True)
+            ds.set_order(index, xform if (pad or flip) else None)
         steps = len(index) // self.batch
         self.train_steps(ds, 0, steps, stream)
         return steps
 
-    def evaluate_dataset(self, ds, stream=None) -> dict:
+    def evaluate_dataset(self, ds, stream=None, windows=None) -> dict:
         """evaluate() on a DeviceDataset: a sequential order (which replaces ds's), the last partial
         batch padded with -1 entries, the totals reset, every batch enqueued, one synchronisation in
-        eval_read."""
+        eval_read.  windows: int32 [ds.count][4], one crop per image; when none are given and ds's
+        stored size is not its output size, center_windows(ds.count, ds.h, ds.w)."""
+        from .dataset import center_windows
         n, b = ds.count, self.batch
-        index = np.concatenate([np.arange(n, dtype=np.int32), np.full((-n) % b, -1, np.int32)])
-        ds.set_order(index)
+        pad = (-n) % b
+        index = np.concatenate([np.arange(n, dtype=np.int32), np.full(pad, -1, np.int32)])
+        if windows is None and (ds.h, ds.w) != (ds.oh, ds.ow):
+            windows = center_windows(n, ds.h, ds.w)
+        if windows is not None:
+            windows = np.asarray(windows, np.int32).reshape(n, 4)
+            windows = np.concatenate([windows, np.tile(np.array([0, 0, 1, 1], np.int32), (pad, 1))])
+        ds.set_order(index, None, windows)
         self.eval_reset(stream)
         self.eval_steps(ds, 0, len(index) // b, stream)
         return self.eval_read(stream)
