@@ -344,6 +344,32 @@ void niti_diag_head_chain(int on);
 void niti_diag_p16_jobs_cap(int cap);
 int niti_conv_wgrad_p16_acc(const niti_geom* g, const int8_t* x_p16, const int8_t* dy_p16, int32_t* acc,
                             uint32_t* amax, void* workspace, size_t workspace_bytes, int splits, void* stream);
+/* Several P16 weight gradients as one persistent launch of `blocks` workgroups: every job is cut into
+ * (32 x 32 tile, K range) items of about t K groups (32 pixels each), the items are packed longest
+ * first into one list per workgroup, and each workgroup runs its list.  Then acc and, if amax, its
+ * range are complete for every job, bit-equal to niti_conv_wgrad_p16_acc (int32 sums are exact).
+ * splits_out (may be NULL) receives the number of K ranges each job was cut into.  The workspace
+ * (niti_conv_wgrad_p16_many_workspace bytes) holds the item table and the split jobs' partials; the
+ * call synchronises the stream once while it uploads the table (the training step keeps its table
+ * on the device instead).  At most 16 jobs. */
+typedef struct niti_wgrad_p16_job {
+    niti_geom g;
+    const int8_t* x_p16;
+    const int8_t* dy_p16;
+    int32_t* acc;
+    uint32_t* amax;
+} niti_wgrad_p16_job;
+int niti_conv_wgrad_p16_many_workspace(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, size_t* bytes);
+int niti_conv_wgrad_p16_many(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, void* workspace,
+                             size_t workspace_bytes, int* splits_out, void* stream);
+/* The training step's 3x3 weight gradients as one such launch after the last input gradient (single
+ * device, one stream, at least two P16 layers; a layer with an armed weight-gradient probe keeps its
+ * own launch), for models' later steps: 0 off (one launch per layer), 1 (default) the autotuner's
+ * choice, which may be off, >= 2 on with items of that many K groups.  Results identical either way. */
+void niti_diag_wgrad_batch(int mode);
+/* diagnostics: batched weight-gradient launches of this process, captured ones counted once (a
+ * graph replay launches without this library) */
+unsigned long long niti_diag_wgrad_batch_launches(void);
 /* acc[m][ldc] = sum_k B[m][k] A[o][k] (columns o..ldc = 0); K zero padded to k16; ldb/lda bytes */
 int niti_matmul_acc(int m, int o, int k16, const int8_t* B, int64_t ldb, const int8_t* A, int64_t lda,
                     int32_t* acc, int64_t ldc, uint32_t* amax, void* workspace, size_t workspace_bytes,

@@ -495,6 +495,66 @@ int niti_conv_wgrad_p16_acc(const niti_geom* g, const int8_t* x, const int8_t* d
     return code(niti::conv_wgrad_p16(r, x, dy, acc, amax, ws, ws_bytes, splits, S(stream)));
 }
 
+// the workspace of niti_conv_wgrad_p16_many: the item table (rounded up to 4 KiB), then every job's
+// room for 8 slabs
+static int p16_many_jobs(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, unsigned char* ws,
+                         niti::WgP16Job* out, niti::WgP16Many* m, size_t* table_room, size_t* bytes) {
+    if (!jobs || n < 1 || n > niti::P16_MANY_MAX_JOBS || blocks < 1 || t < 1) return NITI_INVALID_VALUE;
+    for (int pass = 0; pass < 2; ++pass) {  // the table's size first, then the slabs behind it
+        size_t off = *table_room;
+        for (int j = 0; j < n; ++j) {
+            niti::WgP16Job& o = out[j];
+            if (!to_geom(&jobs[j].g, &o.g)) return NITI_COMPUTE_SIZE_ERROR;
+            if (!niti::conv_wgrad_p16_ok(o.g)) return NITI_NOT_SUPPORT;
+            if (!jobs[j].x_p16 || !jobs[j].dy_p16 || !jobs[j].acc) return NITI_INVALID_VALUE;
+            o.x_p16 = jobs[j].x_p16;
+            o.dy_p16 = jobs[j].dy_p16;
+            o.acc = jobs[j].acc;
+            o.amax = jobs[j].amax;
+            o.slab_bytes = niti::conv_wgrad_p16_workspace(o.g, 8);
+            o.slab = (int32_t*)(ws + off);  // (pass 0: only its being non-null counts)
+            off += o.slab_bytes;
+        }
+        if (niti::conv_wgrad_p16_many_build(out, n, blocks, t, m) != hipSuccess) return NITI_INVALID_VALUE;
+        *bytes = off;
+        if (pass == 0) *table_room = (m->table_bytes + 4095) / 4096 * 4096;
+    }
+    return NITI_NO_ERROR;
+}
+
+int niti_conv_wgrad_p16_many_workspace(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, size_t* bytes) {
+    if (!bytes) return NITI_INVALID_VALUE;
+    niti::WgP16Job r[niti::P16_MANY_MAX_JOBS];
+    niti::WgP16Many m;
+    size_t room = 4096;
+    return p16_many_jobs(jobs, n, blocks, t, (unsigned char*)(uintptr_t)4096, r, &m, &room, bytes);
+}
+
+int niti_conv_wgrad_p16_many(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, void* ws, size_t ws_bytes,
+                             int* splits_out, void* stream) {
+    if (!ws) return NITI_INVALID_VALUE;
+    niti::WgP16Job r[niti::P16_MANY_MAX_JOBS];
+    niti::WgP16Many m;
+    size_t room = 4096, need = 0;
+    if (const int rc = p16_many_jobs(jobs, n, blocks, t, (unsigned char*)ws, r, &m, &room, &need)) return rc;
+    if (ws_bytes < need) return NITI_INVALID_VALUE;
+    hipStream_t st = S(stream);
+    if (hipMemcpyAsync(ws, m.table, m.table_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    hipError_t e = niti::conv_wgrad_p16_many(m, ws, st);
+    for (int j = 0; j < n && e == hipSuccess; ++j) {
+        if (splits_out) splits_out[j] = m.splits[j];
+        if (m.splits[j] > 1)
+            e = niti::splitk_reduce_linear(r[j].slab, m.splits[j], (int64_t)r[j].g.c_out * 9 * r[j].g.cip,
+                                           m.slab_stride[j], r[j].acc, r[j].amax, st);
+    }
+    return code(e);
+}
+
+void niti_diag_wgrad_batch(int mode) { niti::model_wgrad_batch(mode); }
+unsigned long long niti_diag_wgrad_batch_launches(void) { return niti::conv_wgrad_p16_many_launches(); }
+
 int niti_matmul_acc(int m, int o, int k16, const int8_t* B, int64_t ldb, const int8_t* A, int64_t lda, int32_t* acc,
                     int64_t ldc, uint32_t* amax, void* ws, size_t ws_bytes, void* stream) {
     if (k16 % 16 || ldb % 16 || lda % 16 || ldc % 16 || ldc < o) return NITI_INVALID_VALUE;

@@ -4223,6 +4223,26 @@ __global__ void sgd_update_kernel(SgdJobs jobs, int total) {
     }
 }
 
+// the deferred combines of sgd_update_many alone (the autotuner times a weight-gradient set with them)
+hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (n > SGD_MAX_JOBS) return hipErrorInvalidValue;
+    SgdJobs J{};
+    J.n = n;
+    int chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        J.job[i] = jobs[i];
+        J.cstart[i] = chunks;
+        if (jobs[i].slab != nullptr) {
+            if (jobs[i].splits < 1 || jobs[i].slab_stride % 4 != 0 || jobs[i].slab_n % 4 != 0) return hipErrorInvalidValue;
+            chunks += (int)((jobs[i].slab_n + 1023) / 1024);
+        }
+    }
+    J.cstart[n] = chunks;
+    if (chunks > 0) hipLaunchKernelGGL(sgd_combine_kernel, dim3(chunks < 2048 ? chunks : 2048), dim3(256), 0, st, J);
+    return hipGetLastError();
+}
+
 hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (n > SGD_MAX_JOBS) return hipErrorInvalidValue;

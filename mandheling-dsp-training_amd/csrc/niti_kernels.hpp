@@ -178,6 +178,45 @@ hipError_t conv_wgrad_p16(const ConvGeom& g, const int8_t* x_p16, const int8_t* 
                           uint32_t* amax, void* ws, size_t ws_bytes, int splits, hipStream_t st,
                           hipEvent_t ev_b = nullptr, hipEvent_t ev_e = nullptr, unsigned long long* span = nullptr,
                           SgdJob* defer = nullptr);
+// Several layers' P16 weight gradients as one persistent launch (wgrad_p16_many_kernel): a schedule
+// packed on the host once -- every layer cut into (tile, K range) items of about t K groups, the
+// items packed longest first into `blocks` lists -- and a device copy of its table, which the
+// launch only reads.  A job split into splits[j] > 1 K ranges leaves C-shaped partials in its own
+// slabs, slab_stride[j] elements apart (splitk_reduce_linear or sgd_update_many's combine sums
+// them); an unsplit job's tiles go to acc with their max into amax.  A job's split is capped to
+// what its slab bytes hold.  Int32 sums are exact: the result does not depend on the schedule.
+struct WgP16Job {
+    ConvGeom g;
+    const int8_t* x_p16 = nullptr;
+    const int8_t* dy_p16 = nullptr;
+    int32_t* acc = nullptr;
+    uint32_t* amax = nullptr;  // (may be null: no range)
+    int32_t* slab = nullptr;
+    size_t slab_bytes = 0;
+};
+constexpr int P16_MANY_MAX_JOBS = 16;
+struct WgP16Many {
+    unsigned char* table = nullptr;  // host copy (malloc): descriptors | list starts | items
+    size_t table_bytes = 0, starts_off = 0, items_off = 0;
+    int blocks = 0, n_jobs = 0, n_items = 0;
+    int splits[P16_MANY_MAX_JOBS] = {};
+    int64_t slab_stride[P16_MANY_MAX_JOBS] = {};
+    int max_list_kg = 0;  // K groups of the longest list (diagnostics)
+    WgP16Many() = default;
+    WgP16Many(const WgP16Many&) = delete;
+    WgP16Many& operator=(const WgP16Many&) = delete;
+    void clear() {
+        free(table);
+        table = nullptr;
+        table_bytes = 0;
+        n_jobs = n_items = blocks = 0;
+    }
+    ~WgP16Many() { clear(); }
+};
+hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, WgP16Many* out);
+// the launch over `table_dev`, a device copy of m.table
+hipError_t conv_wgrad_p16_many(const WgP16Many& m, const void* table_dev, hipStream_t st);
+unsigned long long conv_wgrad_p16_many_launches();  // of this process (diagnostics)
 // acc[m][o] = sum_k B[m][k] * A[o][k] (NITI_Matmul_Int8); k16 multiple of 16 (zero padded rows),
 // ldb/lda bytes, ldc elements (multiple of 16; columns o..ldc come out 0)
 hipError_t matmul_acc(int M, int O, int k16, const int8_t* B, int64_t ldb, const int8_t* A, int64_t lda,
@@ -392,6 +431,7 @@ void rowconv_speculate(int mode);
 // the speculative pair's miss count of a state buffer (forward / input-gradient slot), device words
 uint32_t* rowconv_spec_slot(uint32_t* bar, bool dg);
 void model_p16_jobs_cap(int cap);  // niti_model.hip, diagnostic
+void model_wgrad_batch(int mode);   // niti_model.hip: niti_diag_wgrad_batch
 hipError_t rowconv_fwd(const ConvGeom& g, const int8_t* x_c32, const int8_t* wf, const RowConvOut& o, int mode,
                        uint32_t* amax, uint32_t* bar, uint32_t epoch, uint32_t* err, hipStream_t st);
 // A 1x1 layer over 1x1 maps (the classifier head) on the same kernel: rows output channels of
@@ -525,6 +565,7 @@ struct SgdJobs {
     int n;
 };
 hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st);
+hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st);  // its deferred combines alone
 // a fully connected layer (1x1 map): its weight gradient's range (pass 0), then the gradient
 // recomputed with job j's NITI_SGD step in the GEMM epilogue (pass 1; j.acc, wf, wft and the
 // slab fields unused) -- no int32 gradient tensor

@@ -29,8 +29,10 @@ namespace niti {
 
 namespace {
 extern int g_p16_jobs_cap;
+extern int g_wgrad_batch;
 }
 void model_p16_jobs_cap(int cap) { g_p16_jobs_cap = cap <= 0 ? P16_MAX_JOBS : cap; }
+void model_wgrad_batch(int mode) { g_wgrad_batch = mode < 0 ? 1 : mode; }
 
 namespace {
 
@@ -83,6 +85,11 @@ struct Im2Col32 {
 
 // diagnostic: jobs per P16 conversion launch (niti_diag_p16_jobs_cap)
 int g_p16_jobs_cap = P16_MAX_JOBS;
+// the step's P16 weight gradients as one launch (niti_diag_wgrad_batch): 0 off, 1 the model's own
+// item size (WGRAD_BATCH_T until autotuned, which may turn it off), >= 2 that item size;
+// NITI_WGRAD_BATCH sets the process's starting mode
+int g_wgrad_batch = getenv("NITI_WGRAD_BATCH") != nullptr ? std::max(0, atoi(getenv("NITI_WGRAD_BATCH"))) : 1;
+constexpr int WGRAD_BATCH_T = 256;
 
 static hipError_t im2col32(const ConvGeom& o, const int8_t* x16, int8_t* out, hipStream_t st) {
     const int64_t px = (int64_t)o.n * o.oh * o.ow;
@@ -451,6 +458,7 @@ struct Model final : StepDriver {
         return !keep && i - 1 >= 1 && next != nullptr && p16 != nullptr && wgrad_p16_splits(i - 1) > 0;
     }
     int autotune(hipStream_t st, int reps) override;
+    int tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log);
     size_t ws_bytes_for(int op) const { return op == PLAN_WGRAD ? slab_w_bytes : slab_bytes; }
     // layer i's own slab buffer for a deferred GEMM weight-gradient combine is big enough for the
     // plan it runs with (false: its plan does not split K into C-shaped slabs, or not sized)
@@ -480,6 +488,96 @@ struct Model final : StepDriver {
             if (!p) return NITI_OUT_OF_MEMORY;
         }
         wslab_epoch = plan_override_epoch();
+        return NITI_NO_ERROR;
+    }
+    // The P16 weight gradients of a step as one persistent launch after the last input gradient
+    // (conv_wgrad_p16_many): single device, one stream.  A weight gradient reads only its layer's
+    // xp16 / dp16, which live until the backward pass ends, so every P16 layer but one with an armed
+    // weight-gradient probe joins; the schedule and its device table are rebuilt outside the step
+    // (and outside a capture) when a plan, the item size or the probe changes.
+    int wgb_tuned = WGRAD_BATCH_T;  // the model's item size (K groups), 0: the autotuner turned the batch off
+    WgP16Many wgb;
+    std::vector<int> wgb_layers;    // the layers of wgb's jobs, in job order (empty: no batch)
+    void* wgb_dev = nullptr;
+    size_t wgb_dev_bytes = 0;
+    unsigned wgb_epoch = 0;
+    int wgb_t = -1, wgb_probe = -2;
+    int wgrad_batch_t() const {
+        if (dp() || g_wgrad_batch == 0) return 0;
+        return g_wgrad_batch == 1 ? wgb_tuned : g_wgrad_batch;
+    }
+    int build_wgrad_batch(int t) {
+        const int pl = probe_phase == 2 ? probe_layer : -1;
+        if (wgb_t == t && wgb_probe == pl && wgb_epoch == plan_override_epoch()) return NITI_NO_ERROR;
+        drop_graph();  // (a captured step launched the old schedule)
+        wgb.clear();
+        wgb_layers.clear();
+        wgb_t = t;
+        wgb_probe = pl;
+        wgb_epoch = plan_override_epoch();
+        if (t <= 0) return NITI_NO_ERROR;
+        WgP16Job jobs[P16_MANY_MAX_JOBS];
+        std::vector<int> layers;
+        for (int i = 0; i < (int)L.size(); ++i) {
+            if (wgrad_p16_splits(i) <= 0 || i == pl) continue;
+            if ((int)layers.size() == P16_MANY_MAX_JOBS) return NITI_NO_ERROR;  // (no such net: per layer)
+            Layer& l = L[i];
+            WgP16Job& j = jobs[layers.size()];
+            j.g = l.g;
+            j.x_p16 = xp16[i];
+            j.dy_p16 = dp16[i];
+            j.acc = l.dwacc;
+            j.amax = rng(i, 2);
+            j.slab = l.slab16;
+            j.slab_bytes = l.slab16_bytes;
+            layers.push_back(i);
+        }
+        if (layers.size() < 2) return NITI_NO_ERROR;
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            return NITI_NO_EXECUTION;
+        if (conv_wgrad_p16_many_build(jobs, (int)layers.size(), cus, t, &wgb) != hipSuccess) return NITI_NO_EXECUTION;
+        // (the previous table may still be read by a step in flight)
+        if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+        if (wgb.table_bytes > wgb_dev_bytes) {
+            wgb_dev = ws.replace(wgb_dev, wgb.table_bytes);
+            wgb_dev_bytes = wgb_dev ? wgb.table_bytes : 0;
+            if (!wgb_dev) {
+                wgb.clear();
+                return NITI_OUT_OF_MEMORY;
+            }
+        }
+        if (hipMemcpy(wgb_dev, wgb.table, wgb.table_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            wgb.clear();
+            return NITI_NO_EXECUTION;
+        }
+        wgb_layers = layers;
+        return NITI_NO_ERROR;
+    }
+    bool wgrad_batched(int i) const {
+        return std::find(wgb_layers.begin(), wgb_layers.end(), i) != wgb_layers.end();
+    }
+    // the batch launch and every member's combine fields (l.defer) or, where the combine is not
+    // deferred to the update launch, its reduce
+    int wgrad_batch_run(bool defer, hipStream_t st) {
+        DTRY(conv_wgrad_p16_many(wgb, wgb_dev, st));
+        for (size_t k = 0; k < wgb_layers.size(); ++k) {
+            Layer& l = L[wgb_layers[k]];
+            l.defer = SgdJob{};
+            l.fc_sgd = false;
+            if (wgb.splits[k] < 2) continue;
+            const int64_t n = (int64_t)l.g.c_out * 9 * l.g.cip;
+            if (defer) {
+                l.defer.slab = l.slab16;
+                l.defer.splits = wgb.splits[k];
+                l.defer.slab_stride = wgb.slab_stride[k];
+                l.defer.slab_n = n;
+            } else {
+                DTRY(splitk_reduce_linear(l.slab16, wgb.splits[k], n, wgb.slab_stride[k], l.dwacc,
+                                          rng(wgb_layers[k], 2), st));
+            }
+        }
         return NITI_NO_ERROR;
     }
     int ensure_streams() {
@@ -760,6 +858,8 @@ int Model::build(int arch_, int batch_, int in_hw) {
 }
 
 int Model::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
+    // (the batched weight gradient's table: rebuilt here, never inside run() or a capture)
+    if (const int rc = build_wgrad_batch(wgrad_batch_t())) return rc;
     if (!use_graph || coll != nullptr) return run(x_nchw, exp_in, images, labels, st);
     Key k;
     k.x = x_nchw ? (const void*)x_nchw : (const void*)images;
@@ -1261,9 +1361,82 @@ int Model::autotune(hipStream_t st, int reps) {
             if (rc != NITI_NO_ERROR) break;
         }
     }
+    if (rc == NITI_NO_ERROR) rc = tune_wgrad_batch(st, timer, log);
     invalidate_xp16();
     tuning = false;
     if (hipStreamSynchronize(st) != hipSuccess) rc = NITI_NO_EXECUTION;
+    return rc;
+}
+
+// The P16 weight gradients as a set, with the per-layer plans settled: the per-layer sequence and
+// the one-launch batch at three item sizes, each with the combine of its slabs (the launch the
+// update does first).  The fastest stays as the model's choice (wgb_tuned; 0: per layer).
+int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
+    if (dp() || g_wgrad_batch == 0) return NITI_NO_ERROR;
+    std::vector<int> set;
+    for (int i = 0; i < (int)L.size(); ++i)
+        if (wgrad_p16_splits(i) > 0 && !(probe_phase == 2 && probe_layer == i)) set.push_back(i);
+    if (set.size() < 2 || set.size() > (size_t)P16_MANY_MAX_JOBS) return NITI_NO_ERROR;
+    // operands as the step leaves them: every input copy, and dy's copy where the last step's input
+    // gradient did not write it
+    if (const int rc = convert_p16_inputs(st)) return rc;
+    for (int i : set)
+        if (!dp16_valid[i]) {
+            const ConvGeom& g = L[i].g;
+            DTRY(nhwc16_to_p16(L[i].dy, (int64_t)g.n * g.oh * g.ow, g.cop, dp16[i], st));
+            dp16_valid[i] = 1;
+        }
+    auto combine = [&]() -> int {
+        SgdJob jobs[SGD_MAX_JOBS];
+        int n = 0;
+        for (int i : set) {
+            Layer& l = L[i];
+            if (l.defer.slab == nullptr) continue;
+            jobs[n] = l.defer;
+            jobs[n].acc = l.dwacc;
+            jobs[n].amax = rng(i, 2);
+            ++n;
+            l.defer = SgdJob{};
+        }
+        return sgd_combine_many(jobs, n, st) == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
+    };
+    auto per_layer = [&]() -> int {
+        for (int i : set) {
+            Layer& l = L[i];
+            const ConvGeom& g = l.g;
+            const int s = wgrad_p16_splits(i);
+            const bool defer = s > 1 && l.slab16 != nullptr && conv_wgrad_p16_workspace(g, s) <= l.slab16_bytes;
+            l.defer = SgdJob{};
+            DTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, rng(i, 2), defer ? l.slab16 : slab_w,
+                                defer ? l.slab16_bytes : slab_w_bytes, s, st, nullptr, nullptr, nullptr,
+                                defer ? &l.defer : nullptr));
+        }
+        return combine();
+    };
+    auto batched = [&]() -> int {
+        if (const int rc = wgrad_batch_run(true, st)) return rc;
+        return combine();
+    };
+    float best_us = 0.f;
+    int best_t = 0;
+    int rc = timer.time(per_layer, &best_us);
+    if (log) fprintf(stderr, "tune wgrad set: per layer %.2f us\n", best_us);
+    for (int t : {128, 256, 512}) {
+        if (rc != NITI_NO_ERROR) break;
+        rc = build_wgrad_batch(t);
+        if (rc != NITI_NO_ERROR || wgb_layers.empty()) break;
+        float us = 0.f;
+        rc = timer.time(batched, &us);
+        if (log)
+            fprintf(stderr, "tune wgrad set: batch t %d (%d items, longest list %d K groups) %.2f us\n", t, wgb.n_items,
+                    wgb.max_list_kg, us);
+        if (rc == NITI_NO_ERROR && us < best_us) {
+            best_us = us;
+            best_t = t;
+        }
+    }
+    if (rc == NITI_NO_ERROR) wgb_tuned = best_t;
+    if (log) fprintf(stderr, "tune wgrad set: keeps %d\n", wgb_tuned);
     return rc;
 }
 
@@ -1433,6 +1606,23 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         if (rc != NITI_NO_ERROR) return rc;
     }
     hipStream_t wst = ov ? side : st;
+    // single device, one stream: the P16 weight gradients wait for the last input gradient and run
+    // as one launch (wgrad_batch_run below)
+    const bool wbatch = !dp && !ov && !tuning && !wgb_layers.empty();
+    auto take_defer = [&](int i) {  // the combine of layer i's split-K slabs, in the update launch
+        const Layer& l = L[i];
+        if (l.defer.slab == nullptr) return;
+        jobs[i].slab = l.defer.slab;
+        jobs[i].splits = l.defer.splits;
+        jobs[i].slab_stride = l.defer.slab_stride;
+        jobs[i].slab_n = l.defer.slab_n;
+        jobs[i].slab_map = l.defer.slab_map;  // (the tap-sharing kernel's tile-blocked slabs)
+        jobs[i].tb_tiles_ci = l.defer.tb_tiles_ci;
+        jobs[i].tb_cip4 = l.defer.tb_cip4;
+        jobs[i].tb_ld4 = l.defer.tb_ld4;
+        jobs[i].tb_m = l.defer.tb_m;
+        jobs[i].tb_s = l.defer.tb_s;
+    };
     for (int i = nl - 1; i >= 0; --i) {
         // (an event record leaves a ~6.5 us bubble before the next launch on the step stream;
         // hipStreamWriteValue64 / WaitValue64 run as blit kernels here and cost more)
@@ -1447,7 +1637,7 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         Layer& l = L[i];
         const ConvGeom& g = l.g;
         const bool in_chain = hc && i == nl - 1;  // (the head chain launch did both)
-        int rc = in_chain ? NITI_NO_ERROR : wgrad_layer(i, wst);
+        int rc = in_chain || (wbatch && wgrad_batched(i)) ? NITI_NO_ERROR : wgrad_layer(i, wst);
         // data parallel: a completed gradient bucket goes to the comm stream right away
         if (rc == NITI_NO_ERROR && dp && closes_bucket[i]) rc = sum_bucket(i, wst);
         if (rc == NITI_NO_ERROR && i > 0 && !in_chain) rc = dgrad_layer(i, st);
@@ -1460,18 +1650,23 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
                          i > 0 && !rowconv_dgrad_layer(i) ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
         jobs[i].wf = l.rc ? l.wf : nullptr;
         jobs[i].wft = l.rcd ? l.wft : nullptr;
-        if (l.defer.slab != nullptr) {  // the combine of this layer's split-K slabs, in the update launch
-            jobs[i].slab = l.defer.slab;
-            jobs[i].splits = l.defer.splits;
-            jobs[i].slab_stride = l.defer.slab_stride;
-            jobs[i].slab_n = l.defer.slab_n;
-            jobs[i].slab_map = l.defer.slab_map;  // (the tap-sharing kernel's tile-blocked slabs)
-            jobs[i].tb_tiles_ci = l.defer.tb_tiles_ci;
-            jobs[i].tb_cip4 = l.defer.tb_cip4;
-            jobs[i].tb_ld4 = l.defer.tb_ld4;
-            jobs[i].tb_m = l.defer.tb_m;
-            jobs[i].tb_s = l.defer.tb_s;
-        }
+        take_defer(i);
+    }
+    if (wbatch) {
+        // dy's P16 copy where no input-gradient epilogue wrote it, all in one launch; then the batch
+        P16Conv cv[P16_MAX_JOBS];
+        int nc = 0;
+        for (int i : wgb_layers)
+            if (!dp16_valid[i]) {
+                const ConvGeom& g = L[i].g;
+                cv[nc++] = P16Conv{L[i].dy, (int64_t)g.n * g.oh * g.ow, g.cop, dp16[i]};
+                dp16_valid[i] = 1;
+            }
+        static_assert(P16_MANY_MAX_JOBS <= P16_MAX_JOBS, "one conversion launch holds every member");
+        if (nc > 0) DTRY(nhwc16_to_p16_many(cv, nc, st));
+        const int rc = wgrad_batch_run(defer_combine(), st);
+        if (rc != NITI_NO_ERROR) return rc;
+        for (int i : wgb_layers) take_defer(i);
     }
     if (dp) {  // every bucket summed and ranged on the comm stream before the update
         DTRY(hipEventRecord(ev_grads, cst));

@@ -37,8 +37,12 @@
 // kernel for conv4; step 0.423 ms against 0.403 ms.)
 #include <hip/hip_ext.h>
 
+#include <string.h>
+
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
+#include <vector>
 
 #include "niti_device.hpp"
 #include "niti_kernels.hpp"
@@ -203,36 +207,37 @@ __device__ __forceinline__ v4i asm_load16(__amdgpu_buffer_rsrc_t r, uint32_t vof
     return v;
 }
 
+// LDS of a block: merge 0: one row-major tile every wave ds_adds into; merge 1: quarter slots
+// [src wave][dst wave][tap][lane] (16 x 9 KiB, the 4 diagonal slots unused); plus the block-max scratch
+constexpr int P16_SMEM = (NITI_WG_MERGE ? 4 * P16_TILE * 4 : P16_TILE * 4) + 64;
+
+// One item: tile `tile` of the layer over the K groups [kg_begin, kg_end) (whole images), each wave a
+// contiguous run of kg_per_wave of them.  slab < 0: the item is the tile's whole K range -- it goes
+// to C and its block max into amax; else a partial tile into slab `slab`.  The per-layer kernel
+// runs one item per block, wgrad_p16_many_kernel a list of them; the caller synchronises the
+// block before the next item touches lds4 again.
 template <int OW, int NW, int D>
-__global__ void __launch_bounds__(NW * 64) wgrad_p16_kernel(WgP16 g) {
+__device__ __forceinline__ void wgrad_p16_item(const WgP16& g, int tile, int slab, int kg_begin, int kg_end,
+                                               int kg_per_wave, v4i* lds4) {
     static_assert(D >= 2 && D % 2 == 0, "the next K group's window must be resident; operand buffers alternate");
     // the block's tile, row-major [co 32][tap 9][ci 32] int32 (every wave adds its partial into it),
     // plus the block-max scratch
-    // merge 0: one row-major LDS tile every wave ds_adds into; merge 1: quarter slots
-    // [src wave][dst wave][tap][lane] (16 x 9 KiB, the 4 diagonal slots unused)
-    constexpr int SMEM = (NITI_WG_MERGE ? 4 * P16_TILE * 4 : P16_TILE * 4) + 64;
+    constexpr int SMEM = P16_SMEM;
     // typed as 16-byte vectors: the exchange stores / loads go through lds4 itself (byte-array
     // storage accessed as v4i is an aliasing violation the optimiser is free to act on)
-    __shared__ v4i lds4[SMEM / 16];
     int8_t* smem = (int8_t*)lds4;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned long long span_t0 = span_begin(g.span);
     WG_STAMP(0);
     WG_WSTAMP(0);
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int split = (int)fdiv(g.fTiles, (uint32_t)logical);
-    const int tile = logical - split * g.tiles;
     const int tco = (int)fdiv(g.fTci, (uint32_t)tile), tci = tile - tco * g.tiles_ci;
     const int co0 = tco * 32, ci0 = tci * 32;
-    // the wave's K groups: a contiguous run [kb, kb + n_w) of the block's split, whole images
-    // (kg_per_split and kg_per_wave are multiples of the K groups per image)
-    const int kg_begin = split * g.kg_per_split;
-    const int kg_end = min(g.kg_total, kg_begin + g.kg_per_split);
-    const int kb = kg_begin + wid * g.kg_per_wave;
-    const int n_w = max(0, min(kg_end, kb + g.kg_per_wave) - kb);
+    // the wave's K groups: a contiguous run [kb, kb + n_w) of the item's range, whole images
+    // (the range and kg_per_wave are multiples of the K groups per image)
+    const int kb = kg_begin + wid * kg_per_wave;
+    const int n_w = max(0, min(kg_end, kb + kg_per_wave) - kb);
 
     const __amdgpu_buffer_rsrc_t rX = make_rsrc(g.x, g.xbytes);
     const __amdgpu_buffer_rsrc_t rD = make_rsrc(g.dy, g.dybytes);
@@ -381,8 +386,8 @@ __global__ void __launch_bounds__(NW * 64) wgrad_p16_kernel(WgP16 g) {
     WG_WSTAMP(1);
 
     constexpr int THREADS = NW * 64;
-    const bool partial = g.splits > 1;
-    int32_t* dst = partial ? g.slab + (int64_t)split * g.slab_stride : g.C;
+    const bool partial = slab >= 0;
+    int32_t* dst = partial ? g.slab + (int64_t)slab * g.slab_stride : g.C;
     uint32_t lmax = 0;
     uint32_t* red = (uint32_t*)(smem + SMEM - 64);
     if constexpr (NITI_WG_MERGE) {
@@ -535,7 +540,56 @@ __global__ void __launch_bounds__(NW * 64) wgrad_p16_kernel(WgP16 g) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         WG_STAMP(5);
     }
+}
+
+// one layer per launch: block = (split, tile), one item
+template <int OW, int NW, int D>
+__global__ void __launch_bounds__(NW * 64) wgrad_p16_kernel(WgP16 g) {
+    __shared__ v4i lds4[P16_SMEM / 16];
+    const unsigned long long span_t0 = span_begin(g.span);
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
+    const int split = (int)fdiv(g.fTiles, (uint32_t)logical);
+    const int tile = logical - split * g.tiles;
+    const int kg_begin = split * g.kg_per_split;
+    const int kg_end = min(g.kg_total, kg_begin + g.kg_per_split);
+    wgrad_p16_item<OW, NW, D>(g, tile, g.splits > 1 ? split : -1, kg_begin, kg_end, g.kg_per_wave, lds4);
     span_end(g.span, span_t0);
+}
+
+// Every P16 weight gradient of a step as one persistent launch: block b runs the items
+// [starts[b], starts[b + 1]) of a table the host packed (wgrad_p16_many_build), one after another.
+// An item names its layer's descriptor, a tile and a K range; the block reads them through uniform
+// addresses, dispatches on the layer's image width and synchronises before the next item reuses
+// the LDS merge buffer.  No ticket, no atomics but the range word of unsplit layers.
+struct WgP16Desc {
+    WgP16 g;
+    int ow, pad;
+};
+struct WgP16Item {
+    int job, tile, slab, kg_begin, kg_end, kg_per_wave, pad0, pad1;
+};
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) wgrad_p16_many_kernel(const WgP16Desc* __restrict__ descs,
+                                                                  const int* __restrict__ starts,
+                                                                  const WgP16Item* __restrict__ items) {
+    __shared__ v4i lds4[P16_SMEM / 16];
+    const int i0 = starts[blockIdx.x], i1 = starts[blockIdx.x + 1];
+    for (int i = i0; i < i1; ++i) {
+        const int job = __builtin_amdgcn_readfirstlane(items[i].job);
+        const int tile = __builtin_amdgcn_readfirstlane(items[i].tile);
+        const int slab = __builtin_amdgcn_readfirstlane(items[i].slab);
+        const int kg_begin = __builtin_amdgcn_readfirstlane(items[i].kg_begin);
+        const int kg_end = __builtin_amdgcn_readfirstlane(items[i].kg_end);
+        const int kpw = __builtin_amdgcn_readfirstlane(items[i].kg_per_wave);
+        const WgP16 g = descs[job].g;
+        switch (__builtin_amdgcn_readfirstlane(descs[job].ow)) {
+            case 8: wgrad_p16_item<8, NW, NITI_WG_D8>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
+            case 16: wgrad_p16_item<16, NW, 8>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
+            case 4: wgrad_p16_item<4, NW, NITI_WG_D4>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
+            default: wgrad_p16_item<2, NW, NITI_WG_D4>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
+        }
+        __syncthreads();  // every wave has read its part of the merge buffer and the block-max scratch
+    }
 }
 
 // NHWC16 [P][CP] -> P16 [P/16][CP][16].  A 16-pixel block is 16 * CP contiguous bytes on both
@@ -726,6 +780,108 @@ hipError_t conv_wgrad_p16(const ConvGeom& g, const int8_t* x_p16, const int8_t* 
         }
     }
     return e;
+}
+
+// The schedule of wgrad_p16_many_kernel.  A layer's K range is cut into whole-image runs of about
+// t K groups (conv_wgrad_p16's rounding; at most what its slab bytes hold), every (tile, run) is an
+// item, and the items go longest first into the list with the least work so far.  An item's cost
+// is its K groups plus P16_ITEM_FIXED: the prologue, merge and output of an item are about 6.8k
+// cycles against 346 per K group.
+constexpr int P16_ITEM_FIXED = 20;
+
+hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, WgP16Many* out) {
+    out->clear();
+    if (jobs == nullptr || n < 1 || n > P16_MANY_MAX_JOBS || blocks < 1 || blocks > 4096 || t < 1)
+        return hipErrorInvalidValue;
+    std::vector<WgP16Desc> descs((size_t)n);
+    std::vector<WgP16Item> items;
+    for (int j = 0; j < n; ++j) {
+        const WgP16Job& jb = jobs[j];
+        const ConvGeom& g = jb.g;
+        WgP16 w;
+        if (!p16_geom(g, &w) || !jb.x_p16 || !jb.dy_p16 || !jb.acc) return hipErrorInvalidValue;
+        const int kpi = g.ow == 8 ? 2 : g.ow == 16 ? 8 : 1;
+        auto round_kpi = [&](int v) { return (v + kpi - 1) / kpi * kpi; };
+        const int64_t stride = p16_slab_stride(g);
+        const int64_t room = jb.slab != nullptr ? (int64_t)(jb.slab_bytes / ((size_t)stride * 4)) : 0;
+        int s = std::max(1, (w.kg_total + t / 2) / t);
+        s = std::min(s, std::max(1, w.kg_total / kpi));
+        s = (int)std::min<int64_t>(std::min(s, 64), room >= 2 ? room : 1);
+        const int kg_per_split = round_kpi((w.kg_total + s - 1) / s);
+        s = (w.kg_total + kg_per_split - 1) / kg_per_split;  // no empty split
+        w.x = jb.x_p16;
+        w.dy = jb.dy_p16;
+        w.kg_per_split = kg_per_split;
+        w.kg_per_wave = round_kpi((kg_per_split + P16_WAVES - 1) / P16_WAVES);
+        w.splits = s;
+        w.fTiles = make_fastdiv((uint32_t)w.tiles);
+        w.C = jb.acc;
+        w.amax = jb.amax;
+        w.slab = s > 1 ? jb.slab : nullptr;
+        w.slab_stride = stride;
+        w.span = nullptr;
+        w.stamps = nullptr;
+        descs[j] = WgP16Desc{w, g.ow, 0};
+        out->splits[j] = s;
+        out->slab_stride[j] = stride;
+        for (int sp = 0; sp < s; ++sp) {
+            const int kb = sp * kg_per_split, ke = std::min(w.kg_total, kb + kg_per_split);
+            const int kpw = round_kpi((ke - kb + P16_WAVES - 1) / P16_WAVES);
+            for (int tile = 0; tile < w.tiles; ++tile)
+                items.push_back(WgP16Item{j, tile, s > 1 ? sp : -1, kb, ke, kpw, 0, 0});
+        }
+    }
+    // longest first (ties: table order, which keeps a layer's tiles together), each into the
+    // lightest list so far (ties: the lowest block)
+    std::vector<int> order(items.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    auto len = [&](int i) { return items[i].kg_end - items[i].kg_begin; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len(a) > len(b); });
+    std::vector<int64_t> load((size_t)blocks, 0);
+    std::vector<int> kg((size_t)blocks, 0);
+    std::vector<std::vector<int>> lists((size_t)blocks);
+    for (int i : order) {
+        const int b = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        lists[b].push_back(i);
+        load[b] += len(i) + P16_ITEM_FIXED;
+        kg[b] += len(i);
+    }
+    const size_t starts_off = (descs.size() * sizeof(WgP16Desc) + 63) / 64 * 64;
+    const size_t items_off = (starts_off + (size_t)(blocks + 1) * sizeof(int) + 63) / 64 * 64;
+    const size_t bytes = items_off + items.size() * sizeof(WgP16Item);
+    unsigned char* tb = (unsigned char*)calloc(bytes, 1);
+    if (tb == nullptr) return hipErrorOutOfMemory;
+    memcpy(tb, descs.data(), descs.size() * sizeof(WgP16Desc));
+    int* starts = (int*)(tb + starts_off);
+    WgP16Item* it = (WgP16Item*)(tb + items_off);
+    int k = 0;
+    for (int b = 0; b < blocks; ++b) {
+        starts[b] = k;
+        for (int i : lists[b]) it[k++] = items[i];
+    }
+    starts[blocks] = k;
+    out->table = tb;
+    out->table_bytes = bytes;
+    out->starts_off = starts_off;
+    out->items_off = items_off;
+    out->blocks = blocks;
+    out->n_jobs = n;
+    out->n_items = k;
+    out->max_list_kg = *std::max_element(kg.begin(), kg.end());
+    return hipSuccess;
+}
+
+static std::atomic<unsigned long long> g_many_launches{0};
+unsigned long long conv_wgrad_p16_many_launches() { return g_many_launches.load(); }
+
+hipError_t conv_wgrad_p16_many(const WgP16Many& m, const void* table_dev, hipStream_t st) {
+    if (m.table == nullptr || table_dev == nullptr || m.blocks < 1) return hipErrorInvalidValue;
+    ++g_many_launches;
+    const unsigned char* base = (const unsigned char*)table_dev;
+    hipLaunchKernelGGL(wgrad_p16_many_kernel<P16_WAVES>, dim3((unsigned)m.blocks), dim3(P16_WAVES * 64), 0, st,
+                       (const WgP16Desc*)base, (const int*)(base + m.starts_off),
+                       (const WgP16Item*)(base + m.items_off));
+    return hipGetLastError();
 }
 
 }  // namespace niti

@@ -75,6 +75,12 @@ class Geom(C.Structure):
         "pad_r", "dilate_h", "dilate_w", "oh", "ow", "cip", "cop", "np")]
 
 
+class WgradP16Job(C.Structure):
+    """niti_wgrad_p16_job: one weight gradient of niti_conv_wgrad_p16_many."""
+    _fields_ = [("g", Geom), ("x_p16", C.c_void_p), ("dy_p16", C.c_void_p), ("acc", C.c_void_p),
+                ("amax", C.c_void_p)]
+
+
 class EvalTotals(C.Structure):
     """niti_eval_totals: the running totals of an evaluation pass."""
     _fields_ = [("images", C.c_uint64), ("top1", C.c_uint64), ("topk", C.c_uint64), ("loss_sum", C.c_double)]
@@ -128,6 +134,8 @@ def lib():
         "niti_diag_head_chain_launches": (C.c_ulonglong, []),
         "niti_diag_head_chain": (None, [C.c_int]),
         "niti_diag_p16_jobs_cap": (None, [C.c_int]),
+        "niti_diag_wgrad_batch": (None, [C.c_int]),
+        "niti_diag_wgrad_batch_launches": (C.c_ulonglong, []),
         "niti_tensor_convert": (ci, [tp, tp, vp]),
         "niti_geom_finalize": (ci, [C.POINTER(Geom)]),
         "niti_conv_workspace_bytes": (ci, [C.POINTER(Geom), ci, C.POINTER(C.c_size_t)]),
@@ -152,6 +160,8 @@ def lib():
         "niti_diag_rowconv_stamps": (None, [vp]),
         "niti_conv_wgrad_p16_workspace": (ci, [C.POINTER(Geom), ci, C.POINTER(C.c_size_t)]),
         "niti_conv_wgrad_p16_acc": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, C.c_size_t, ci, vp]),
+        "niti_conv_wgrad_p16_many_workspace": (ci, [C.POINTER(WgradP16Job), ci, ci, ci, C.POINTER(C.c_size_t)]),
+        "niti_conv_wgrad_p16_many": (ci, [C.POINTER(WgradP16Job), ci, ci, ci, vp, C.c_size_t, C.POINTER(ci), vp]),
         "niti_matmul_acc": (ci, [ci, ci, ci, vp, i64, vp, i64, vp, i64, vp, vp, C.c_size_t, vp]),
         "niti_absmax_i32": (ci, [vp, i64, vp, vp]),
         "niti_requant_act": (ci, [vp, i64, ci, vp, vp, vp, vp, ci, vp, vp, vp]),

@@ -390,6 +390,26 @@ def conv_wgrad_p16_acc(g: L.Geom, xP, dyP, amax=None, splits: int = 0, ws=None, 
     return acc
 
 
+def conv_wgrad_p16_many(jobs, blocks: int, t: int, stream=None):
+    """Several P16 weight gradients as one persistent launch of `blocks` workgroups, cut into items of
+    about t K groups.  jobs: (geom, xP, dyP, amax or None) each.  Returns ([acc per job], [K ranges
+    each job was cut into])."""
+    n = len(jobs)
+    accs = [torch.zeros((g.c_out, g.kh, g.kw, g.cip), dtype=torch.int32, device=xP.device) for g, xP, _, _ in jobs]
+    arr = (L.WgradP16Job * n)()
+    for j, ((g, xP, dyP, amax), acc) in enumerate(zip(jobs, accs)):
+        arr[j].g = g
+        arr[j].x_p16, arr[j].dy_p16, arr[j].acc = xP.data_ptr(), dyP.data_ptr(), acc.data_ptr()
+        arr[j].amax = None if amax is None else amax.data_ptr()
+    nb = C.c_size_t()
+    check(L.lib().niti_conv_wgrad_p16_many_workspace(arr, n, blocks, t, C.byref(nb)), "p16 many workspace")
+    ws = torch.zeros(int(nb.value), dtype=torch.uint8, device=accs[0].device)
+    splits = (C.c_int * n)()
+    check(L.lib().niti_conv_wgrad_p16_many(arr, n, blocks, t, _ptr(ws), int(nb.value), splits, _stream(stream)),
+          "conv_wgrad_p16_many")
+    return accs, list(splits)
+
+
 def matmul_acc(B16, A16, ldc, amax=None, use_workspace=True, stream=None):
     m, k16 = B16.shape
     o = A16.shape[0]
