@@ -534,7 +534,8 @@ int niti_image_quantize_nhwc16(const uint8_t* images_nchw, int n, int c, int hw,
                                int64_t count, int8_t* out_nhwc16, int8_t* ascale, void* stream);
 
 /* ============================ 3. device-resident training step ========================= */
-/* LeNet on MNIST 1x28x28 (cfg 1/2); VGG-11 on CIFAR 3x32x32 (cfg 3); VGG-16 on ImageNet 3x224x224
+/* The built-in networks, and any chain of conv / relu / 2x2 max-pool / flatten layers given as a list
+ * (niti_chain_layer, niti_model_create_chain below).  LeNet on MNIST 1x28x28 (cfg 1/2); VGG-11 on CIFAR 3x32x32 (cfg 3); VGG-16 on ImageNet 3x224x224
  * with the 4096-4096-1000 head (cfg 4; niti_model_create2 takes another input size, a multiple
  * of 32, e.g. 32 for the oracle-checked tests); ResNet-18 on ImageNet 3x224x224 (cfg 5: 21
  * parameter layers in the order conv1, per basic block conv a / conv b / [1x1 projection], fc; the
@@ -542,6 +543,55 @@ int niti_image_quantize_nhwc16(const uint8_t* images_nchw, int n, int c, int hw,
  * NITI_Eltwise_Int8.cpp:20-28 -- stated in csrc/niti_resnet.hip and oracle/niti_resnet_ref.py). */
 enum niti_arch { NITI_ARCH_LENET = 1, NITI_ARCH_VGG11 = 2, NITI_ARCH_VGG16 = 3, NITI_ARCH_RESNET18 = 4 };
 typedef struct niti_model* niti_model_t;
+
+/* A chain network of the caller's own (niti_model_create_chain): a list of NITI_Conv_Int8 layers,
+ * each optionally followed by NITI_Relu_Int8, a 2x2 / stride-2 NITI_Maxpool_Int8 and a flatten, over
+ * square in_c x in_hw x in_hw inputs.  Fully connected layers are kernel-1 layers over the 1x1 map a
+ * flatten (or the pooling) leaves.  LeNet, VGG-11 and VGG-16 are such lists (csrc/niti_model.hip);
+ * a model made from a list reports arch NITI_ARCH_CHAIN, whatever the list. */
+enum { NITI_ARCH_CHAIN = 5 };
+typedef struct niti_chain_layer {
+    int c_out;    /* output channels; the last layer's is the class count */
+    int kernel;   /* square kernel size */
+    int stride;   /* must be 1 (reserved) */
+    int pad;      /* symmetric zero padding */
+    int relu;     /* NITI_Relu_Int8 after the conv */
+    int pool;     /* 2x2 / stride-2 max pool after it (floor, as NITI_Maxpool_Int8) */
+    int flatten;  /* the (pooled) output becomes [c*h*w] channels of a 1x1 map, index (c*h + y)*w + x */
+} niti_chain_layer;
+/* Host only, no device call: validates the list and, if shapes != NULL, writes per layer
+ * {c_in, c_out, k, pad, h_in, oh (pre-pool), out_h (after pool / flatten), flat_c (the channels the
+ * next layer sees: c_out, or c_out * h * w after a flatten)}.  c_in is derived: in_c for layer 0,
+ * else the previous layer's flat_c.
+ * NITI_INVALID_VALUE (malformed): layers == NULL, n < 1, in_c < 1, in_hw < 1, and per layer
+ *   c_out < 1, kernel < 1, pad < 0, pad >= kernel, a conv output smaller than 1x1
+ *   (h + 2 pad < kernel), a pool on a map smaller than 2x2.
+ * NITI_NOT_SUPPORT (well formed, not run by this library):
+ *   - n > 24: the update launch takes at most that many layers;
+ *   - stride != 1;
+ *   - kernel > 7: the implicit GEMM's tap loop is generic in the kernel size (above 32 taps the
+ *     per-lane loaders serve it); 7 is the largest this library's tests run;
+ *   - last layer: c_out > 2048 (the loss and metrics kernels keep a row of logits per thread), a
+ *     pool or a flatten, or an output map other than 1x1 (the logits are [batch][classes]);
+ *   - a layer after a flatten with kernel != 1 or pad != 0 (its input is a 1x1 map);
+ *   - a 3-channel 3x3 or 1-channel 5x5 first layer with 2 pad < kernel (the fused input pass takes
+ *     it; with a wider pad the layer runs from the unfused quantiser and is not bound by this) on an
+ *     input wider than 32768 / (4 kernel) - kernel + 1 pixels (2728 / 1634): its staged rows would
+ *     not fit in LDS;
+ *   - any tensor of a layer -- input [b][h][w][c_in up to 32], output [b][oh][ow][c_out up to 16],
+ *     flattened output, weights [c_out up to 16][k][k][c_in up to 16] -- above 2^29 elements at batch b
+ *     (the GEMM loaders address int8 operands with 31-bit byte offsets and their int32
+ *     accumulators are four times the size); niti_model_chain_check tests b = 1,
+ *     niti_model_create_chain its own batch.  The products are formed saturating, so sizes past
+ *     64 bits are refused like any other.
+ * Every list that passes runs: each fast path of the step (csrc/niti_model.hip) is taken per layer
+ * by its own shape predicate, with the implicit GEMM + requantise pass and the unfused
+ * pool / flatten kernels, which take every shape above, as the fall-back. */
+int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int shapes[][8]);
+/* The model of a list (batch >= 1).  Runs the check first -- at this batch -- and on a refusal returns
+ * its code with nothing allocated and *out untouched.  Every other niti_model_* call takes the
+ * handle; niti_model_copy_weights needs the same list and input on both sides. */
+int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* batch = this rank's images per step.  Weights start zero; load them with
  * niti_model_set_weight (OIHW int8, host memory) -- the reference initialises them with a

@@ -12,12 +12,15 @@
 // MAX), every forward / input-gradient range with MAX and every int32 weight-gradient
 // accumulator with SUM before it is requantised, so N ranks of batch b reproduce one device of
 // batch N*b bit for bit.
+// The network is a layer list (niti_chain_layer): LeNet, VGG-11 and VGG-16 are build()'s own tables,
+// niti_model_create_chain brings the caller's, checked by chain_check before anything is allocated.
 // What this driver shares with the ResNet-18 one (niti_resnet_model.hip) is its base, StepDriver
 // (niti_step_driver.hpp); the C ABI over both is niti_model_capi.hip.
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <memory>
 #include <vector>
 
@@ -189,12 +192,16 @@ struct Layer {
     uint32_t* gspec = nullptr;  // 2 x GEMM_SPEC_SLOT_WORDS
     int8_t* wft = nullptr;
     int8_t* dyc32 = nullptr;
+    // what a flatten reads and its gradient writes: the pooled map, or the conv (+relu) output itself
+    int fh() const { return pool ? ph : g.oh; }
+    int fw() const { return pool ? pw : g.ow; }
+    const int8_t* fsrc() const { return pool ? p : r; }
     int64_t w_elems() const { return (int64_t)g.c_out * g.kh * g.kw * g.cip; }
     int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * og.c_in * og.kh * og.kw; }
 };
 
 struct Model final : StepDriver {
-    int arch = 0, in_c = 0, in_h = 0, in_w = 0, classes = 10;
+    int arch = 0, in_c = 0, in_h = 0, in_w = 0;
     std::vector<Layer> L;
     int8_t* x0 = nullptr;   // NHWC16 input
     int8_t* exp0 = nullptr; // input exponent
@@ -235,6 +242,14 @@ struct Model final : StepDriver {
     size_t gspec_alt_bytes = 0;
     // the first layer's range came with its im2col copy (input_im2col's Conv0Range) this step
     bool conv0_ranged = false;
+    // the first layer's im2col copy comes straight from the batch (input_im2col).  That kernel stages
+    // rows of w + kw - 1 pixels, which hold every tap only while 2 pad < kernel; a wider pad goes
+    // through x0 and im2col32, which bounds-checks each tap.
+    static bool input_fused_ok(int c_in, int k, int pad) { return input_im2col_ok(c_in, k, k) && 2 * pad < k; }
+    static bool input_fused(const Layer& f) {
+        const ConvGeom& o = f.og;
+        return f.col && o.kh == o.kw && o.pt == o.pl && input_fused_ok(o.c_in, o.kh, o.pt) && o.sh == 1 && o.sw == 1;
+    }
     bool rowconv_layer(int i) const { return use_rowconv && L[i].rc; }
     // dyc32_valid[i]: L[i].dyc32 holds L[i].dy as it is now (written by the next layer's input
     // gradient epilogue, else converted)
@@ -437,6 +452,9 @@ struct Model final : StepDriver {
     int probe_read_span(double* total_ms, int* count) override;
 
     int build(int arch_, int batch_, int in_hw = 0);
+    // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
+    // built-in networks are build()'s own lists
+    int build_chain(int arch_, int batch_, const niti_chain_layer* layers, int n, int in_c_, int in_hw);
     int fwd_layer(int i, hipStream_t st);
     int wgrad_layer(int i, hipStream_t st);
     int dgrad_layer(int i, hipStream_t st);
@@ -520,7 +538,7 @@ struct Model final : StepDriver {
         std::vector<int> layers;
         for (int i = 0; i < (int)L.size(); ++i) {
             if (wgrad_p16_splits(i) <= 0 || i == pl) continue;
-            if ((int)layers.size() == P16_MANY_MAX_JOBS) return NITI_NO_ERROR;  // (no such net: per layer)
+            if ((int)layers.size() == P16_MANY_MAX_JOBS) return NITI_NO_ERROR;  // (more than one launch holds: per layer)
             Layer& l = L[i];
             WgP16Job& j = jobs[layers.size()];
             j.g = l.g;
@@ -660,48 +678,106 @@ static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, 
     m.L.push_back(l);
 }
 
+// the largest tensor of a list's layer (elements, at the model's batch): the GEMM loaders address
+// int8 operands with 31-bit byte offsets and the int32 accumulator of a tensor is four times its size
+constexpr int64_t CHAIN_MAX_ELEMS = int64_t(1) << 29;
+constexpr int CHAIN_MAX_KERNEL = 7;
+// a * b, or CHAIN_MAX_ELEMS + 1 once it passes the bound (operands >= 0; no product overflows int64)
+static int64_t chain_mul(int64_t a, int64_t b) {
+    if (a > CHAIN_MAX_ELEMS || b > CHAIN_MAX_ELEMS) return CHAIN_MAX_ELEMS + 1;
+    return std::min(a * b, CHAIN_MAX_ELEMS + 1);
+}
+
+// The shapes a layer list derives (the one rule niti_model_chain_check, niti_model_create_chain and
+// build_chain share): per layer {c_in, c_out, k, pad, h_in, oh, out_h, flat_c}.  Refuses malformed
+// lists and counts that do not fit an int; what else the library does not run is chain_check's.
+static int chain_shapes(const niti_chain_layer* layers, int n, int in_c, int in_hw, std::vector<std::array<int, 8>>* out) {
+    if (layers == nullptr || n < 1 || in_c < 1 || in_hw < 1) return NITI_INVALID_VALUE;
+    int64_t c = in_c, h = in_hw;
+    for (int i = 0; i < n; ++i) {
+        const niti_chain_layer& l = layers[i];
+        if (l.c_out < 1 || l.kernel < 1 || l.pad < 0 || l.pad >= l.kernel) return NITI_INVALID_VALUE;
+        if (h + 2 * (int64_t)l.pad < l.kernel) return NITI_INVALID_VALUE;
+        const int64_t oh = h + 2 * (int64_t)l.pad - l.kernel + 1;
+        if (l.pool && oh < 2) return NITI_INVALID_VALUE;
+        const int64_t ph = l.pool ? (oh - 2) / 2 + 1 : oh;
+        const int64_t fc = l.flatten ? chain_mul(chain_mul(l.c_out, ph), ph) : l.c_out;
+        // (a count past int never reaches a buffer: refused here as a size no tensor of it fits)
+        if (c > CHAIN_MAX_ELEMS || fc > CHAIN_MAX_ELEMS || oh > CHAIN_MAX_ELEMS) return NITI_NOT_SUPPORT;
+        if (out) out->push_back({(int)c, l.c_out, l.kernel, l.pad, (int)h, (int)oh, (int)(l.flatten ? 1 : ph), (int)fc});
+        c = fc;
+        h = l.flatten ? 1 : ph;
+    }
+    return NITI_NO_ERROR;
+}
+
+int chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]) {
+    std::vector<std::array<int, 8>> sh;
+    if (batch < 1) return NITI_INVALID_VALUE;
+    if (const int rc = chain_shapes(layers, n, in_c, in_hw, &sh)) return rc;
+    if (n > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;  // (sgd_update_many's job table)
+    for (int i = 0; i < n; ++i) {
+        const niti_chain_layer& l = layers[i];
+        const std::array<int, 8>& s = sh[i];
+        if (l.stride != 1) return NITI_NOT_SUPPORT;
+        if (l.kernel > CHAIN_MAX_KERNEL) return NITI_NOT_SUPPORT;
+        if (i > 0 && layers[i - 1].flatten && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
+        // a first layer the fused input pass takes (input_im2col) stages kernel + band - 1 image rows
+        // of 4 bytes a pixel in LDS: one output row must fit in half of a workgroup's 64 KiB
+        if (i == 0 && Model::input_fused_ok(s[0], l.kernel, l.pad) && (int64_t)l.kernel * (s[4] + l.kernel - 1) * 4 > 32768)
+            return NITI_NOT_SUPPORT;
+        if (i == n - 1 && (l.c_out > 2048 || l.pool || l.flatten || s[5] != 1)) return NITI_NOT_SUPPORT;
+        // every tensor of the layer, in the padded layouts build_chain allocates
+        const int64_t b = batch, k2 = (int64_t)l.kernel * l.kernel;
+        const int64_t cip32 = round_up(s[0], 32), cop32 = round_up(s[1], 32);
+        const int64_t in_e = chain_mul(chain_mul(chain_mul(b, s[4]), s[4]), cip32);
+        const int64_t out_e = chain_mul(chain_mul(chain_mul(b, s[5]), s[5]), cop32);
+        const int64_t w_e = chain_mul(chain_mul(cop32, k2), cip32), flat_e = chain_mul(b, round_up(s[7], 16));
+        if (in_e > CHAIN_MAX_ELEMS || out_e > CHAIN_MAX_ELEMS || w_e > CHAIN_MAX_ELEMS || flat_e > CHAIN_MAX_ELEMS)
+            return NITI_NOT_SUPPORT;
+    }
+    if (shapes)
+        for (int i = 0; i < n; ++i) std::copy(sh[i].begin(), sh[i].end(), shapes[i]);
+    return NITI_NO_ERROR;
+}
+
 int Model::build(int arch_, int batch_, int in_hw) {
-    arch = arch_;
-    batch = batch_;
-    if (arch == NITI_ARCH_LENET) {  // mnistTrain.cpp:131-181
-        in_c = 1;
-        in_h = in_w = 28;
-        add_conv(*this, 1, 20, 5, 0, 28, 1, 1);
-        add_conv(*this, 20, 52, 5, 0, 12, 1, 1, /*flatten=*/1);
-        add_conv(*this, 832, 500, 1, 0, 1, 1, 0);
-        add_conv(*this, 500, 12, 1, 0, 1, 0, 0);
-    } else if (arch == NITI_ARCH_VGG11) {  // VGG-11 for 32x32 inputs, NITI layers (BASELINE cfg 3)
-        in_c = 3;
-        in_h = in_w = 32;
-        add_conv(*this, 3, 64, 3, 1, 32, 1, 1);
-        add_conv(*this, 64, 128, 3, 1, 16, 1, 1);
-        add_conv(*this, 128, 256, 3, 1, 8, 1, 0);
-        add_conv(*this, 256, 256, 3, 1, 8, 1, 1);
-        add_conv(*this, 256, 512, 3, 1, 4, 1, 0);
-        add_conv(*this, 512, 512, 3, 1, 4, 1, 1);
-        add_conv(*this, 512, 512, 3, 1, 2, 1, 0);
-        add_conv(*this, 512, 512, 3, 1, 2, 1, 1);
-        add_conv(*this, 512, 12, 1, 0, 1, 0, 0);
-    } else if (arch == NITI_ARCH_VGG16) {  // VGG-16 (configuration D), NITI layers (BASELINE cfg 4)
-        const int r = in_hw > 0 ? in_hw : 224;
-        if (r % 32 != 0) return NITI_INVALID_VALUE;
-        in_c = 3;
-        in_h = in_w = r;
-        classes = 1000;
-        static const int cfg[13][3] = {{3, 64, 0},    {64, 64, 1},   {64, 128, 0},  {128, 128, 1}, {128, 256, 0},
-                                       {256, 256, 0}, {256, 256, 1}, {256, 512, 0}, {512, 512, 0}, {512, 512, 1},
-                                       {512, 512, 0}, {512, 512, 0}, {512, 512, 1}};
-        int h = r;
-        for (int i = 0; i < 13; ++i) {
-            add_conv(*this, cfg[i][0], cfg[i][1], 3, 1, h, 1, cfg[i][2], /*flatten=*/i == 12);
-            if (cfg[i][2]) h /= 2;
-        }
-        add_conv(*this, 512 * h * h, 4096, 1, 0, 1, 1, 0);
-        add_conv(*this, 4096, 4096, 1, 0, 1, 1, 0);
-        add_conv(*this, 4096, 1000, 1, 0, 1, 0, 0);
+    // {c_out, kernel, stride, pad, relu, pool, flatten}
+    std::vector<niti_chain_layer> t;
+    int ic = 3, hw = 32;
+    if (arch_ == NITI_ARCH_LENET) {  // mnistTrain.cpp:131-181
+        ic = 1;
+        hw = 28;
+        t = {{20, 5, 1, 0, 1, 1, 0}, {52, 5, 1, 0, 1, 1, 1}, {500, 1, 1, 0, 1, 0, 0}, {12, 1, 1, 0, 0, 0, 0}};
+    } else if (arch_ == NITI_ARCH_VGG11) {  // VGG-11 for 32x32 inputs, NITI layers (BASELINE cfg 3)
+        static const int cfg[8][2] = {{64, 1}, {128, 1}, {256, 0}, {256, 1}, {512, 0}, {512, 1}, {512, 0}, {512, 1}};
+        for (int i = 0; i < 8; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], 0});
+        t.push_back({12, 1, 1, 0, 0, 0, 0});
+    } else if (arch_ == NITI_ARCH_VGG16) {  // VGG-16 (configuration D), NITI layers (BASELINE cfg 4)
+        hw = in_hw > 0 ? in_hw : 224;
+        if (hw % 32 != 0) return NITI_INVALID_VALUE;
+        static const int cfg[13][2] = {{64, 0},  {64, 1},  {128, 0}, {128, 1}, {256, 0}, {256, 0}, {256, 1},
+                                       {512, 0}, {512, 0}, {512, 1}, {512, 0}, {512, 0}, {512, 1}};
+        for (int i = 0; i < 13; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], /*flatten=*/i == 12});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0});
+        t.push_back({1000, 1, 1, 0, 0, 0, 0});
     } else {
         return NITI_NOT_SUPPORT;
     }
+    return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw);
+}
+
+int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, int nlayers, int in_c_, int in_hw) {
+    arch = arch_;
+    batch = batch_;
+    std::vector<std::array<int, 8>> sh;
+    if (const int rc = chain_shapes(layers, nlayers, in_c_, in_hw, &sh)) return rc;
+    in_c = in_c_;
+    in_h = in_w = in_hw;
+    for (int i = 0; i < nlayers; ++i)
+        add_conv(*this, sh[i][0], sh[i][1], sh[i][2], sh[i][3], sh[i][4], layers[i].relu != 0, layers[i].pool != 0,
+                 layers[i].flatten != 0);
     const int n = batch;
     {
         Layer& f = L[0];
@@ -755,15 +831,20 @@ int Model::build(int arch_, int batch_, int in_hw) {
         if (l.pool) {
             l.p = (int8_t*)ws.alloc((size_t)n * l.ph * l.pw * g.cop);
             l.dtmp = (int8_t*)ws.alloc((size_t)n * l.ph * l.pw * g.cop);
+            if (!l.p || !l.dtmp) return NITI_OUT_OF_MEMORY;
             if (!l.flatten && l.ph * 2 == g.oh && l.pw * 2 == g.ow) {
                 l.pc = (int8_t*)ws.alloc((size_t)n * l.ph * l.pw * g.cop);
                 if (!l.pc) return NITI_OUT_OF_MEMORY;
             }
         }
         if (l.flatten) {
-            const int fc = g.c_out * l.ph * l.pw;
+            const int fc = g.c_out * l.fh() * l.fw();
             l.flat = (int8_t*)ws.alloc((size_t)n * round_up(fc, 16));
             l.dflat = (int8_t*)ws.alloc((size_t)n * round_up(fc, 16));
+            // without a pool the flatten's gradient lands on the conv output's own map, ahead of
+            // the relu gradient
+            if (!l.pool) l.dtmp = (int8_t*)ws.alloc(out_px * g.cop);
+            if (!l.flat || !l.dflat || !l.dtmp) return NITI_OUT_OF_MEMORY;
         }
         l.dy = (int8_t*)ws.alloc(out_px * g.cop);
         l.dwacc = grad_bucket + grad_off;
@@ -997,8 +1078,8 @@ int Model::fwd_layer(int i, hipStream_t st) {
         if (feeds_next) xc32_valid[i + 1] = 1;
         probe(i, 0, false, st);
         if (l.flatten) {
-            const int fc = g.c_out * l.ph * l.pw, ld = round_up(fc, 16);
-            DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
+            const int fc = g.c_out * l.fh() * l.fw(), ld = round_up(fc, 16);
+            DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.fsrc(), l.fh() * l.fw(), g.c_out, g.cop, ld, l.flat}, st));
         }
         return NITI_NO_ERROR;
     }
@@ -1038,8 +1119,8 @@ int Model::fwd_layer(int i, hipStream_t st) {
     probe(i, 0, false, st);
     if (l.pool && !fuse_pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
     if (l.flatten) {
-        const int fc = g.c_out * l.ph * l.pw, ld = round_up(fc, 16);
-        DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.p, l.ph * l.pw, g.c_out, g.cop, ld, l.flat}, st));
+        const int fc = g.c_out * l.fh() * l.fw(), ld = round_up(fc, 16);
+        DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.fsrc(), l.fh() * l.fw(), g.c_out, g.cop, ld, l.flat}, st));
     }
     return NITI_NO_ERROR;
 }
@@ -1264,11 +1345,16 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     }
     probe(i, 1, false, st);
     if (pv.flatten) {
-        const int fc = pg.c_out * pv.ph * pv.pw, ld = round_up(fc, 16);
-        DTRY(launch_map((int64_t)n * pv.ph * pv.pw * pg.cop,
-                        FlattenBwd{pv.dflat, pv.ph * pv.pw, pg.c_out, pg.cop, ld, pv.dtmp}, st));
-        DTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
-                                      pv.dy, st));
+        const int fhw = pv.fh() * pv.fw(), ld = round_up(pg.c_out * fhw, 16);
+        const int64_t elems = (int64_t)n * fhw * pg.cop;
+        // (no pool, no relu: the flatten's gradient is the layer's output gradient as it stands)
+        int8_t* din = pv.pool || pv.relu ? pv.dtmp : pv.dy;
+        DTRY(launch_map(elems, FlattenBwd{pv.dflat, fhw, pg.c_out, pg.cop, ld, din}, st));
+        if (pv.pool)
+            DTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
+                                          pv.dy, st));
+        else if (pv.relu)
+            DTRY(relu_grad_nhwc16(pv.r, pv.dtmp, elems, pv.dy, st));
     } else if (pv.pool && !fuse) {
         DTRY(maxpool_relu_grad_nhwc16(pv.r, pv.p, pv.dtmp, n, pg.oh, pg.ow, pg.cop, 2, 2, 0, pv.ph, pv.pw, pv.relu,
                                       pv.dy, st));
@@ -1483,7 +1569,7 @@ int Model::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool
     if (x_nchw != nullptr || amax_bytes % 16 != 0) DTRY(fill(amax, 0, amax_bytes));
     // the first layer's im2col copy straight from the batch where the fused pass takes the layer
     const ConvGeom& o0 = L[0].og;
-    const bool fused_in = L[0].col && input_im2col_ok(o0.c_in, o0.kh, o0.kw) && o0.sh == 1 && o0.sw == 1;
+    const bool fused_in = input_fused(L[0]);
     x0_nchw_valid = fused_in;
     // the first conv's range pass rides in the im2col launch (its rows are in registers there)
     Conv0Range r0;
@@ -1717,7 +1803,8 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
     for (size_t i = 0; i < L.size(); ++i) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
-            L[i].col != src.L[i].col)
+            L[i].col != src.L[i].col || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
+            L[i].flatten != src.L[i].flatten)
             return NITI_INVALID_VALUE;
     }
     if (&src == this) return NITI_NO_ERROR;
@@ -1995,6 +2082,16 @@ int Model::spec_stats(uint32_t* out, int max_layers) {
         }
     }
     return NITI_NO_ERROR;
+}
+
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch,
+                                                   int* rc) {
+    *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr);  // (nothing allocated on a refusal)
+    if (*rc != NITI_NO_ERROR) return nullptr;
+    auto m = std::make_unique<Model>();
+    *rc = m->build_chain(NITI_ARCH_CHAIN, batch, layers, n, in_c, in_hw);
+    if (*rc != NITI_NO_ERROR) return nullptr;
+    return m;
 }
 
 std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, int* rc) {

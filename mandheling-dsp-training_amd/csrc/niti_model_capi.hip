@@ -1,6 +1,7 @@
 // niti_model_capi.hip -- the niti_model_* C ABI (section 3 of include/niti_hip.h) over a StepDriver
-// (niti_step_driver.hpp): the chain driver (LeNet / VGG-11 / VGG-16, niti_model.hip) or ResNet-18
-// (niti_resnet_model.hip), chosen once in niti_model_create3.  Every entry point checks its handle
+// (niti_step_driver.hpp): the chain driver (LeNet / VGG-11 / VGG-16 or the caller's layer list,
+// niti_model.hip) or ResNet-18 (niti_resnet_model.hip), chosen once in niti_model_create3 /
+// niti_model_create_chain.  Every entry point checks its handle
 // and pointers, then makes one call; layers and phases are the driver's to check.
 #include <rccl/rccl.h>
 #include <stdlib.h>
@@ -34,6 +35,19 @@ int niti_model_create3(int arch, int batch, int in_hw, int classes, niti_model_t
         return NITI_NOT_SUPPORT;
     else
         d = niti::make_chain_driver(arch, batch, in_hw, &rc);
+    if (rc != NITI_NO_ERROR) return rc;
+    *out = new niti_model{std::move(d)};
+    return NITI_NO_ERROR;
+}
+
+int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes);
+}
+
+int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    if (!out || batch <= 0) return NITI_INVALID_VALUE;
+    int rc = NITI_NO_ERROR;
+    std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc);
     if (rc != NITI_NO_ERROR) return rc;
     *out = new niti_model{std::move(d)};
     return NITI_NO_ERROR;

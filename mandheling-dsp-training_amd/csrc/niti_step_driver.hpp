@@ -156,6 +156,11 @@ struct StepDriver {
 // the concrete drivers (null and *rc set when build() fails)
 std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, int* rc);
 std::unique_ptr<StepDriver> make_resnet_driver(int batch, int in_hw, int classes, int* rc);
+// a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch,
+                                                   int* rc);
+// niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
+int chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]);
 
 // a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
 // zero padded to the column pitch kp <-> OIHW

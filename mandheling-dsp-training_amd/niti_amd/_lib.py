@@ -16,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "niti_
 # MNN::ErrorCode names (include/MNN/ErrorCode.hpp:17-30)
 ERROR_NAMES = {0: "NO_ERROR", 1: "OUT_OF_MEMORY", 2: "NOT_SUPPORT", 3: "COMPUTE_SIZE_ERROR",
                4: "NO_EXECUTION", 5: "INVALID_VALUE", 10: "INPUT_DATA_ERROR", 11: "CALL_BACK_STOP"}
+NOT_SUPPORT, INVALID_VALUE = 2, 5  # the two codes niti_model_chain_check refuses a layer list with
 
 OP_CONV_INT8 = 700
 OP_DECONV_INT8 = 701
@@ -50,6 +51,7 @@ OP_DSP_TRANSPOSEGRADIENT_CONV_INT8 = 822
 FORMAT_NCHW, FORMAT_NHWC, FORMAT_NC4HW4 = 0, 1, 2
 PAD_CAFFE, PAD_VALID, PAD_SAME = 0, 1, 2
 ARCH_LENET, ARCH_VGG11, ARCH_VGG16, ARCH_RESNET18 = 1, 2, 3, 4
+ARCH_CHAIN = 5  # a model of the caller's own layer list (niti_model_create_chain)
 
 
 class NitiError(RuntimeError):
@@ -79,6 +81,11 @@ class WgradP16Job(C.Structure):
     """niti_wgrad_p16_job: one weight gradient of niti_conv_wgrad_p16_many."""
     _fields_ = [("g", Geom), ("x_p16", C.c_void_p), ("dy_p16", C.c_void_p), ("acc", C.c_void_p),
                 ("amax", C.c_void_p)]
+
+
+class ChainLayer(C.Structure):
+    """niti_chain_layer: one layer of a user-defined chain network."""
+    _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten")]
 
 
 class EvalTotals(C.Structure):
@@ -204,6 +211,9 @@ def lib():
         "niti_model_create": (ci, [ci, ci, C.POINTER(vp)]),
         "niti_model_create2": (ci, [ci, ci, ci, C.POINTER(vp)]),
         "niti_model_create3": (ci, [ci, ci, ci, ci, C.POINTER(vp)]),
+        # (layers: a ChainLayer array, passed untyped)
+        "niti_model_chain_check": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         "niti_model_destroy": (None, [vp]),
         "niti_model_num_layers": (ci, [vp]),
         "niti_model_layer_info": (ci, [vp, ci, C.POINTER(ci)]),

@@ -9,11 +9,15 @@ NITI_SGD, `NITI_SGD.hpp:20-54`).  A snapshot here holds exactly that state:
     layer{i}.weight  int8 [C_out, C_in, KH, KW]  (OIHW, the reference's parameter layout)
     layer{i}.wscale  int8 [1]                    (the side-car the MNN file does not carry)
 
-stored as safetensors (no code executes on load) with `arch` / `num_layers` metadata.  The
+stored as safetensors (no code executes on load) with `arch` / `num_layers` metadata; the snapshot
+of a user-defined chain network (arch ARCH_CHAIN) also carries its layer list and input as one
+JSON string under the metadata key `chain` (`load_chain`).  The
 MNN flatbuffer container itself is not reproduced: `Variable::load` of that format needs
 the MNN schema, which is outside the hot path; the tensors and their order are the same.
 """
 from __future__ import annotations
+
+import json
 
 import numpy as np
 from safetensors.numpy import load_file, save_file
@@ -21,8 +25,15 @@ from safetensors.numpy import load_file, save_file
 FORMAT = "niti-int8-params-v1"
 
 
-def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0) -> None:
-    """Write per-layer int8 OIHW weights and their int8 wscale side-car."""
+def chain_record(spec, in_c: int, in_hw: int) -> dict:
+    """What a chain model's snapshot stores about its network (compared as a whole on load)."""
+    from .chain import normalize_spec
+    return {"spec": normalize_spec(spec), "in_c": int(in_c), "in_hw": int(in_hw)}
+
+
+def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: dict | None = None) -> None:
+    """Write per-layer int8 OIHW weights and their int8 wscale side-car.  chain: a chain_record()
+    for a user-defined network (None: the file is a built-in network's, as it always was)."""
     if len(weights) != len(wscales):
         raise ValueError(f"{len(weights)} weights but {len(wscales)} wscales")
     tensors = {}
@@ -34,8 +45,34 @@ def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0) -> None:
             raise ValueError(f"layer {i}: wscale {s} does not fit int8")
         tensors[f"layer{i}.weight"] = np.ascontiguousarray(w)
         tensors[f"layer{i}.wscale"] = np.array([int(s)], np.int8)
-    save_file(tensors, path, metadata={"format": FORMAT, "arch": str(int(arch)), "num_layers": str(len(weights)),
-                                       "in_hw": str(int(in_hw))})
+    meta = {"format": FORMAT, "arch": str(int(arch)), "num_layers": str(len(weights)), "in_hw": str(int(in_hw))}
+    if chain is not None:
+        meta["chain"] = json.dumps(chain, sort_keys=True)
+    save_file(tensors, path, metadata=meta)
+
+
+def expect_chain(found, record, path: str) -> None:
+    """Refuse (ValueError) a snapshot whose chain record `found` is not the model's `record`; a
+    built-in model (record None) takes any snapshot its arch check let through."""
+    if record is not None and found != record:
+        raise ValueError(f"{path}: the snapshot's layer list {found} differs from the model's {record}")
+
+
+def load_chain(path: str):
+    """The chain_record() a snapshot carries, or None (a built-in network's snapshot)."""
+    from safetensors import safe_open
+
+    with safe_open(path, framework="numpy") as f:
+        meta = f.metadata() or {}
+    if meta.get("format") != FORMAT:
+        raise ValueError(f"{path}: not a {FORMAT} snapshot (format={meta.get('format')!r})")
+    if "chain" not in meta:
+        return None
+    try:
+        rec = json.loads(meta["chain"])
+        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"])
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"{path}: malformed chain record ({e!r})") from None
 
 
 def load_params(path: str):

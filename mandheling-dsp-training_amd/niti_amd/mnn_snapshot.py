@@ -256,6 +256,19 @@ def save(path: str, weights, wscales, names=None, meta=None):
         json.dump(side, f)
 
 
+def chain_of(meta: dict):
+    """The chain_record() (niti_amd.checkpoint) of a side-car's metadata, or None: the layer list
+    and input of a user-defined chain network, stored under `chain`."""
+    rec = (meta or {}).get("chain")
+    if rec is None:
+        return None
+    from .checkpoint import chain_record
+    try:
+        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"])
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"malformed chain record in the side-car ({e!r})") from None
+
+
 def load(path: str):
     """`Variable::load(path)`: the int8 parameters in file order, their wscales (None without a
     side-car) and the side-car metadata.  ValueError on anything that is not such a snapshot."""

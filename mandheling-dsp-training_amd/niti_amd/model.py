@@ -20,8 +20,13 @@ class NitiModel:
         self._lib = L.lib()
         h = C.c_void_p()
         check(self._lib.niti_model_create3(arch, batch, int(in_hw), int(classes), C.byref(h)), "model_create")
+        self._adopt(h, arch, batch)
+
+    def _adopt(self, h, arch: int, batch: int):
+        """The Python side of a ready handle (niti_model_create3's or niti_model_create_chain's)."""
         self._h = h
         self.arch, self.batch = arch, batch
+        self.chain = None  # from_chain: the normalised layer list
         self._wscale = {}
         self.layers = []
         for i in range(self._lib.niti_model_num_layers(h)):
@@ -29,6 +34,40 @@ class NitiModel:
             check(self._lib.niti_model_layer_info(h, i, info), "layer_info")
             keys = ("c_in", "c_out", "kh", "kw", "h", "w", "oh", "ow", "pad", "stride", "relu", "pool")
             self.layers.append(dict(zip(keys, list(info))))
+
+    @classmethod
+    def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
+        """A model of the caller's own chain network (niti_model_create_chain): spec is a list of
+        dicts (c_out, kernel[, pad, relu, pool, flatten]) or tuples in that order, over
+        in_c x in_hw x in_hw inputs; the last layer's c_out is the class count.  ValueError for a
+        malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
+        allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
+        from .chain import normalize_spec, to_c
+        spec = normalize_spec(spec)
+        arr, n = to_c(spec)
+        m = cls.__new__(cls)
+        m._lib = L.lib()
+        h = C.c_void_p()
+        code = m._lib.niti_model_create_chain(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
+        if code == L.INVALID_VALUE:
+            raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input at batch {batch}: {spec}")
+        check(code, "model_create_chain")
+        m._adopt(h, L.ARCH_CHAIN, batch)
+        m.chain, m.in_c, m.in_hw = spec, int(in_c), int(in_hw)
+        return m
+
+    def _chain_record(self):
+        from .checkpoint import chain_record
+        return None if self.chain is None else chain_record(self.chain, self.in_c, self.in_hw)
+
+    def init_weights(self, seed: int):
+        """Every layer's weights and scale from the reference's initialiser (niti_amd.init.xavier_int8),
+        one default_rng(seed) consumed in layer order."""
+        from .init import xavier_int8
+        rng = np.random.default_rng(seed)
+        for i in range(len(self.layers)):
+            w, s = xavier_int8(self.weight_shape(i), rng)
+            self.set_weight(i, w, s)
 
     def weight_shape(self, i):
         l = self.layers[i]
@@ -52,14 +91,16 @@ class NitiModel:
             raise ValueError("save() before every layer's weight was set")
         save_params(path, [self.get_weight(i) for i in range(len(self.layers))],
                     [self._wscale[i] for i in range(len(self.layers))], self.arch,
-                    in_hw=self.layers[0]["h"])
+                    in_hw=self.layers[0]["h"], chain=self._chain_record())
 
     def load(self, path: str):
         """Restore a snapshot written by save() into this model's device weights."""
-        from .checkpoint import load_params
+        from .checkpoint import expect_chain, load_chain, load_params
         weights, wscales, arch = load_params(path)
         if arch != self.arch or len(weights) != len(self.layers):
             raise ValueError(f"snapshot is arch {arch} with {len(weights)} layers, model is arch {self.arch}")
+        if self.chain is not None:
+            expect_chain(load_chain(path), self._chain_record(), path)
         # every layer's shape before any device write (a VGG-16 snapshot taken at another input
         # size has the same arch and layer count but a different first FC layer)
         for i, w in enumerate(weights):
@@ -78,14 +119,23 @@ class NitiModel:
             raise ValueError("save_mnn() before every layer's weight was set")
         mnn_snapshot.save(path, [self.get_weight(i) for i in range(len(self.layers))],
                           [self._wscale[i] for i in range(len(self.layers))],
-                          meta={"arch": int(self.arch), "in_hw": int(self.layers[0]["h"])})
+                          meta=self._mnn_meta())
+
+    def _mnn_meta(self):
+        meta = {"arch": int(self.arch), "in_hw": int(self.layers[0]["h"])}
+        if self.chain is not None:
+            meta["chain"] = self._chain_record()
+        return meta
 
     def load_mnn(self, path: str):
         """`Module::loadParameters(Variable::load(path))` (mnistTrain.cpp:375-376): the weights in
         file order; the wscales from the side-car when there is one, otherwise the model keeps its
         own (as the reference's modules do).  Every shape is checked before any device write."""
         from . import mnn_snapshot
-        weights, wscales, _ = mnn_snapshot.load(path)
+        weights, wscales, meta = mnn_snapshot.load(path)
+        if self.chain is not None:
+            from .checkpoint import expect_chain
+            expect_chain(mnn_snapshot.chain_of(meta), self._chain_record(), path)
         if len(weights) != len(self.layers):
             raise ValueError(f"{path}: {len(weights)} parameters, model has {len(self.layers)} layers")
         for i, w in enumerate(weights):
