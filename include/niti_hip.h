@@ -432,6 +432,20 @@ int niti_sgd_update(const int32_t* acc, const uint32_t* amax, int rule, int co, 
  * pass -- no separate weights_to_wf launches after the update */
 int niti_sgd_update_wf(const int32_t* acc, const uint32_t* amax, int rule, int co, int ci, int kk, int cip, int cop,
                        int8_t* w_ohwi16, int8_t* wt_ihwo16, int8_t* g_out, int8_t* wf, int8_t* wft, void* stream);
+/* The combine the training step's update launch does first, alone: for every job, acc[i] = the sum
+ * over z < splits of slab[z * stride + i] for i < n, and max|acc| into amax (NITI_MAX_WORDS words,
+ * zeroed by the caller), all jobs in one launch.  n and stride are multiples of 4, every pointer
+ * 16-byte aligned, at most 24 jobs.  A job of few elements over many splits is summed by several
+ * lanes per element group; int32 sums are exact in any order. */
+typedef struct niti_sgd_combine_job {
+    const int32_t* slab;
+    int splits;
+    int64_t stride;
+    int64_t n;
+    int32_t* acc;
+    uint32_t* amax;
+} niti_sgd_combine_job;
+int niti_sgd_combine(const niti_sgd_combine_job* jobs, int n_jobs, void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);

@@ -638,6 +638,25 @@ int niti_sgd_update_wf(const int32_t* acc, const uint32_t* amax, int rule, int c
     return code(niti::sgd_update_many(&j, 1, S(stream)));
 }
 
+int niti_sgd_combine(const niti_sgd_combine_job* jobs, int n_jobs, void* stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > niti::SGD_MAX_JOBS) return NITI_INVALID_VALUE;
+    niti::SgdJob r[niti::SGD_MAX_JOBS];
+    for (int j = 0; j < n_jobs; ++j) {
+        const niti_sgd_combine_job& s = jobs[j];
+        if (!s.slab || !s.acc || !s.amax || s.splits < 1 || s.n < 4 || s.n % 4 || s.stride % 4 || s.stride < s.n)
+            return NITI_INVALID_VALUE;
+        if (((uintptr_t)s.slab | (uintptr_t)s.acc) & 15) return NITI_INVALID_VALUE;
+        r[j] = niti::SgdJob{};
+        r[j].acc = s.acc;
+        r[j].amax = s.amax;
+        r[j].slab = s.slab;
+        r[j].splits = s.splits;
+        r[j].slab_stride = s.stride;
+        r[j].slab_n = s.n;
+    }
+    return code(niti::sgd_combine_many(r, n_jobs, S(stream)));
+}
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

@@ -2004,10 +2004,9 @@ static hipError_t gemm_acc_plan(const GemmPlan& p, const LA& la, const LB& lb, i
         hipError_t r = launch_mode<LA, LB, EPI_SLAB, KT>(p, la, lb, M, N, kc_total, e, st);
         if (r == hipSuccess && after_gemm != nullptr) r = hipEventRecord(after_gemm, st);
         if (r != hipSuccess) return r;
-        // the NITI_SGD launch combines the slabs -- where each split has a few 1024-element chunks;
-        // a small gradient over many splits (VGG-11 conv0: 2048 elements x 256 splits) reduces faster
-        // here, splitk_reduce spreading the splits over blocks (the combine sums them serially)
-        if (defer != nullptr && ((int64_t)M * N) % 4 == 0 && (int64_t)M * N >= (int64_t)p.splits * 4096) {
+        // the NITI_SGD launch combines the slabs; a small gradient over many splits (VGG-11 conv0:
+        // 2048 elements x 256 splits) in the combine's lanes-per-group form (sgd_combine_lanes)
+        if (defer != nullptr && ((int64_t)M * N) % 4 == 0) {
             defer->slab = ws;
             defer->splits = p.splits;
             defer->slab_stride = e.slab_stride;
@@ -4100,7 +4099,10 @@ hipError_t requant_grad(const int32_t* acc, int64_t n, const uint32_t* amax, int
 // The deferred split-K combines of a step's P16 weight gradients, all layers in one launch ahead
 // of the update (one launch instead of one reduce per layer, each of which left the chip mostly
 // idle: 576 blocks of a few loads each): chunk c (1024 elements of one job's acc, 4 per thread) =
-// the sum of the job's slabs, its max into the job's range.  (A grid barrier inside the update
+// the sum of the job's slabs, its max into the job's range.  A small gradient over many splits
+// takes splitk_reduce's form instead: G lanes per 16-byte group, each summing every G-th split,
+// a shuffle tree to finish (a chunk is then 1024 / G elements; sgd_combine_lanes).
+// (A grid barrier inside the update
 // launch instead measured +275 us per VGG-11 step: 1536-2048 arrivals on one counter.)
 __global__ void __launch_bounds__(256) sgd_combine_kernel(SgdJobs jobs) {
     const int chunks = jobs.cstart[jobs.n];
@@ -4121,7 +4123,11 @@ __global__ void __launch_bounds__(256) sgd_combine_kernel(SgdJobs jobs) {
             m = 0;
         }
         const SgdJob& J = jobs.job[j];
-        const int64_t e = (int64_t)(c - jobs.cstart[j]) * 1024 + threadIdx.x * 4;
+        // G lanes share an element group and split its slabs among them (sgd_combine_lanes: 1 for
+        // a job with a few chunks per split; block-uniform, so every lane reaches the shuffles)
+        const int G = sgd_combine_lanes(J.splits, J.slab_n);
+        const int g = threadIdx.x & (G - 1);
+        const int64_t e = ((int64_t)(c - jobs.cstart[j]) * (256 / G) + threadIdx.x / G) * 4;
         int64_t de = e;  // the acc element this slab element sums into
         bool live = J.slab != nullptr && e < J.slab_n;
         if (live && J.slab_map == 1) {  // SlabTapsBlocked (splitk_reduce's map), on 16-byte units
@@ -4137,18 +4143,26 @@ __global__ void __launch_bounds__(256) sgd_combine_kernel(SgdJobs jobs) {
             live = co < J.co;
             de = ((int64_t)co * J.tb_ld4 + t * J.tb_cip4 + tci * 8u + part) * 4;
         }
+        v4i s = {0, 0, 0, 0};
         if (live) {
             const v4i* base = (const v4i*)(J.slab + e);
             const int64_t st4 = J.slab_stride / 4;
-            v4i s = {0, 0, 0, 0};
-            for (int z0 = 0; z0 < J.splits; z0 += 8) {  // up to 8 independent loads in flight
+            for (int z0 = g; z0 < J.splits; z0 += 8 * G) {  // up to 8 independent loads in flight
                 v4i v[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    v[q] = z0 + q < J.splits ? __builtin_nontemporal_load(base + (int64_t)(z0 + q) * st4) : v4i{0, 0, 0, 0};
+                for (int q = 0; q < 8; ++q) {
+                    const int z = z0 + q * G;
+                    v[q] = z < J.splits ? __builtin_nontemporal_load(base + (int64_t)z * st4) : v4i{0, 0, 0, 0};
+                }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) s += v[q];
             }
+        }
+        for (int o = G >> 1; o > 0; o >>= 1) {  // (the lanes of a group are live together)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[q] += __shfl_xor(s[q], o, 64);
+        }
+        if (live && g == 0) {
             *(v4i*)(const_cast<int32_t*>(J.acc) + de) = s;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -4235,7 +4249,7 @@ hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st) {
         J.cstart[i] = chunks;
         if (jobs[i].slab != nullptr) {
             if (jobs[i].splits < 1 || jobs[i].slab_stride % 4 != 0 || jobs[i].slab_n % 4 != 0) return hipErrorInvalidValue;
-            chunks += (int)((jobs[i].slab_n + 1023) / 1024);
+            chunks += sgd_combine_chunks(jobs[i].splits, jobs[i].slab_n);
         }
     }
     J.cstart[n] = chunks;
@@ -4256,7 +4270,7 @@ hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st) {
         total += ((jobs[i].cip + 63) / 64) * ((jobs[i].cop + 63) / 64) * jobs[i].kk;
         if (jobs[i].slab != nullptr) {
             if (jobs[i].splits < 1 || jobs[i].slab_stride % 4 != 0 || jobs[i].slab_n % 4 != 0) return hipErrorInvalidValue;
-            chunks += (int)((jobs[i].slab_n + 1023) / 1024);
+            chunks += sgd_combine_chunks(jobs[i].splits, jobs[i].slab_n);
         }
     }
     J.cstart[n] = chunks;

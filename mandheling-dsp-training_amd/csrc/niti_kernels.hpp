@@ -561,9 +561,26 @@ constexpr int SGD_MAX_JOBS = 24;
 struct SgdJobs {
     SgdJob job[SGD_MAX_JOBS];
     int start[SGD_MAX_JOBS];
-    int cstart[SGD_MAX_JOBS + 1];  // combine chunks (1024 elements) per job, prefix sums
+    int cstart[SGD_MAX_JOBS + 1];  // combine chunks (256 lanes) per job, prefix sums
     int n;
 };
+static_assert(sizeof(SgdJobs) <= 4096, "SgdJobs is passed by value: the kernel-argument limit");
+// The combine's chunk form for a job, from its split count and slab size (host chunk count and
+// kernel alike; no field of its own: SgdJobs has no room).  G lanes share one 16-byte element
+// group and take the splits g, g + G, ...: 1 where every split has a few 1024-element chunks (a
+// thread sums all splits of its group), else splitk_reduce's rule -- a small gradient over many
+// splits (VGG-11 conv0: 2048 elements x 256 splits, 2 chunks at G = 1) spreads its splits over
+// lanes until the output alone fills the chip.  A chunk is 256 / G element groups.
+__host__ __device__ inline int sgd_combine_lanes(int splits, int64_t slab_n) {
+    if (slab_n >= (int64_t)splits * 4096) return 1;
+    int G = 1;
+    while (G < 16 && G * 2 <= splits && (slab_n / 4) * G < 131072) G <<= 1;
+    return G;
+}
+inline int sgd_combine_chunks(int splits, int64_t slab_n) {
+    const int per = 256 / sgd_combine_lanes(splits, slab_n);
+    return (int)((slab_n / 4 + per - 1) / per);
+}
 hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st);
 hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st);  // its deferred combines alone
 // a fully connected layer (1x1 map): its weight gradient's range (pass 0), then the gradient

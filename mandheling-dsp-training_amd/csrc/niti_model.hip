@@ -232,6 +232,11 @@ struct Model final : StepDriver {
         static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
         return in_step && !off && !dp() && !capturing && !tuning;
     }
+    // whether a step of this model defers its combines at all (what the autotuner times against)
+    bool in_step_combine() const {
+        static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
+        return !off && !dp();
+    }
     // the row kernels' accumulator store for their two-launch form (data parallel, graph capture):
     // the range launch keeps its int32 accumulators here, the requantise launch reads them back
     int32_t* rc_acc = nullptr;
@@ -1178,10 +1183,23 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     // single device: a split-K plan leaves its slabs (this layer's own) to the NITI_SGD launch's
     // combine, which sums them and takes the range (no reduce launch, no int32 round trip)
     const bool defer = defer_combine() && ensure_wslab(i);
+    // the autotuner times a split plan of the generic GEMM with the combine it will run with in
+    // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
+    // step never makes; the tap-sharing kernel's plans are timed as they were (its slabs keep their
+    // reduce launch where a split has under 4096 elements)
+    const bool tune_defer = tuning && in_step_combine() &&
+                            conv_plan_query(PLAN_WGRAD, g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
     l.defer = SgdJob{};
     DTRY(conv_wgrad_acc(g, l.in, l.dy, l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.wslab : slab_w,
                         defer ? l.wslab_bytes : slab_w_bytes, st, capturing ? probe_end_event(i, 2) : nullptr,
-                        defer ? &l.defer : nullptr));
+                        defer || tune_defer ? &l.defer : nullptr));
+    if (tune_defer && l.defer.slab != nullptr) {
+        SgdJob j = l.defer;
+        j.acc = l.dwacc;
+        j.amax = rng(i, 2);
+        l.defer = SgdJob{};
+        if (sgd_combine_many(&j, 1, st) != hipSuccess) return NITI_NO_EXECUTION;
+    }
     return NITI_NO_ERROR;
 }
 

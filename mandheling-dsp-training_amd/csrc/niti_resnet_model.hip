@@ -420,9 +420,21 @@ int ResNetModel::wgrad_conv(int i, hipStream_t st) {
     probe(i, 2, true, st);
     // single device, in the step: a split-K plan leaves its (own) slabs to the update's combine
     const bool defer = in_step && !dp() && !capturing && !tuning && ensure_wslab(i);
+    // the autotuner times a split plan of the generic GEMM with the combine it will run with in
+    // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
+    // step never makes; the tap-sharing kernel's plans are timed as they were
+    const bool tune_defer = tuning && !dp() &&
+                            conv_plan_query(PLAN_WGRAD, c.g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
     c.defer = SgdJob{};
     DTRY(conv_wgrad_acc(c.g, c.in, c.dy, c.dwacc, dp() ? nullptr : rng(i, 2), defer ? c.wslab : slab_w,
-                        defer ? c.wslab_bytes : slab_w_bytes, st, nullptr, defer ? &c.defer : nullptr));
+                        defer ? c.wslab_bytes : slab_w_bytes, st, nullptr, defer || tune_defer ? &c.defer : nullptr));
+    if (tune_defer && c.defer.slab != nullptr) {
+        SgdJob j = c.defer;
+        j.acc = c.dwacc;
+        j.amax = rng(i, 2);
+        c.defer = SgdJob{};
+        if (sgd_combine_many(&j, 1, st) != hipSuccess) return NITI_NO_EXECUTION;
+    }
     probe(i, 2, false, st);
     return NITI_NO_ERROR;
 }

@@ -633,16 +633,19 @@ __device__ __forceinline__ void epi_prefetch(const RowConvArgs& a, const RowUnit
 // (image, row, column) of the wave's pixels), leaves in the weight gradient's P16 layout: per 16-lane
 // group, two ds_read_b64_tr_b8 give lane j the 16 pixels of channel j (8 rows each), one 16-byte
 // store.  A round covers two 16-pixel blocks x 32 channels (the four groups).  ROWS: the wave's
-// band rows at the tile's resolution (R, or 2R through the pool), WD its image width.
-template <int ROWS, int WD, int G>
+// band rows at the tile's resolution (R, or 2R through the pool), WD its image width.  NQ rounds
+// from round q0 on: all of them, or a wave's share of a tile two waves staged (p16_pair_store).
+template <int ROWS, int WD, int G, int NQ = G * ROWS * WD / 32>
 __device__ __forceinline__ void p16_store(const RowConvArgs& a, int lane, const int8_t* tile, int img0, int y0, int hd,
-                                          int cob) {
+                                          int cob, int q0 = 0) {
     constexpr int PPI = ROWS * WD;  // the tile's pixels per image (G images)
     constexpr int NROWS = G * PPI;
     static_assert(NROWS % 32 == 0 && NROWS * 32 <= RC_P16_WAVE_BYTES, "whole rounds in the wave's slot");
+    static_assert(NQ >= 1 && NQ <= NROWS / 32, "rounds of the tile");
     const int gi = lane >> 4, j = lane & 15, chalf = gi & 1;
 #pragma unroll
-    for (int q = 0; q < NROWS / 32; ++q) {
+    for (int qq = 0; qq < NQ; ++qq) {
+        const int q = q0 + qq;
         const int r0 = 16 * (2 * q + (gi >> 1));
         const int8_t* t = tile + (r0 + (j >> 1)) * 32 + 16 * chalf + 8 * (j & 1);
         const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i*)(t));
@@ -652,6 +655,24 @@ __device__ __forceinline__ void p16_store(const RowConvArgs& a, int lane, const 
         if (P < a.p16_pixels)
             *(v4i*)(a.p16 + ((P >> 4) * a.cop + cob * 32 + 16 * chalf + j) * 16) = v4i{lo[0], lo[1], hi[0], hi[1]};
     }
+}
+
+// A 4x4 map at R = 2 (no pool): a wave holds half of each of its 8 images, 8 pixels, no whole
+// 16-pixel block.  The two bands of an image group are waves 2k and 2k + 1 of one workgroup
+// (gb = 4 x + wid with nbands = 2, so b = wid & 1; ngb is even, so the two are valid together): both
+// stage into the even wave's slot, rows in (image, row, column) order (8 x 16 x 32 bytes = 4 KiB),
+// and after a workgroup barrier -- the caller's, outside `if (U.valid && owner)`: a wave without a
+// unit must reach it -- each stores two of the tile's four rounds.
+template <int W, int R, bool DG>
+constexpr bool RC_P16_PAIR = DG && W == 4 && R == 2;
+// the pair's tile, from the wave's own slot
+template <int W, int R>
+__device__ __forceinline__ int8_t* p16_pair_tile(const RowUnit<W, R>& U, int8_t* own) {
+    return own - U.b * RC_P16_WAVE_BYTES;
+}
+template <int W, int R>
+__device__ __forceinline__ void p16_pair_store(const RowConvArgs& a, const RowUnit<W, R>& U, int lane, int8_t* own) {
+    p16_store<4, 4, 8, 2>(a, lane, p16_pair_tile<W, R>(U, own), U.img - (lane & 31) / W, 0, 4, U.cob, 2 * U.b);
 }
 
 template <int W, int R, bool DG>
@@ -733,10 +754,15 @@ __device__ __forceinline__ void rowconv_epilogue(const RowConvArgs& a, const Row
             if (a.out != nullptr && (W > 1 || cb16 < a.cop)) *(v4i*)(a.out + po) = v;  // (a 1x1 head: 16 channels)
             if (a.next != nullptr && a.pool_out == nullptr)
                 *(v4i*)(a.next + (((img * a.COB + U.cob) * H + oy) * W + ox) * 32 + 16 * h) = v;
-            if (DG && a.p16 != nullptr) *(v4i*)(tile + (((c / W) * R + r) * W + ox) * 32 + 16 * h) = v;
+            if constexpr (RC_P16_PAIR<W, R, DG>) {  // whole images in the pair's tile; the caller stores it
+                if (a.p16 != nullptr)
+                    *(v4i*)(p16_pair_tile<W, R>(U, tile) + (((c / W) * H + oy) * W + ox) * 32 + 16 * h) = v;
+            } else {
+                if (DG && a.p16 != nullptr) *(v4i*)(tile + (((c / W) * R + r) * W + ox) * 32 + 16 * h) = v;
+            }
         }
     }
-    if constexpr (DG && (R * W >= 16 || W == 2))
+    if constexpr (DG && !RC_P16_PAIR<W, R, DG> && (R * W >= 16 || W == 2))
         if (a.p16 != nullptr) p16_store<R, W, 32 / W>(a, lane, tile, U.img - c / W, U.b * R, H, U.cob);
     if (a.pool_out != nullptr) {
         constexpr int HO = H / 2, WO = W / 2;
@@ -1352,7 +1378,16 @@ __global__ void __launch_bounds__(256, (RC_EXP & 16) ? 2 : 1) rowconv_fwd_kernel
         }
         __syncthreads();
         RC_STAMP(4);
-        if (U.valid && owner && (!spec || gm != g_guess)) unit_epilogue<W, R, DG>(a, U, lane, acc, gm, ein, tile);
+        const bool redo = !spec || gm != g_guess;  // workgroup-uniform: every wave read the same hint, red and gm
+        if (U.valid && owner && redo) unit_epilogue<W, R, DG>(a, U, lane, acc, gm, ein, tile);
+        if constexpr (RC_P16_PAIR<W, R, DG>) {
+            // the pair's tile is whole after a barrier: the one above where the speculative epilogue
+            // staged it, else one more (all four waves, with or without a unit)
+            if (a.p16 != nullptr && a.pool_dx == nullptr) {
+                if (redo) __syncthreads();
+                if (U.valid) p16_pair_store<W, R>(a, U, lane, tile);
+            }
+        }
         RC_STAMP(5);
     } else if constexpr (MODE == RC_RANGE && W == 0) {
         uint32_t m = 0;
@@ -1441,6 +1476,13 @@ __global__ void __launch_bounds__(256, (RC_EXP & 16) ? 2 : 1) rowconv_fwd_kernel
             }
             if (U.valid && owner) unit_epilogue<W, R, DG>(a, U, lane, acc, g, ein, smem + wid * RC_P16_WAVE_BYTES);
             if (DG && a.p16 != nullptr) __syncthreads();  // the P16 tiles sit in the next unit's ring
+            if constexpr (RC_P16_PAIR<W, R, DG>) {
+                // the pair's tile is whole after that barrier; its stores end before the next unit's ring
+                if (a.p16 != nullptr && a.pool_dx == nullptr) {
+                    if (U.valid) p16_pair_store<W, R>(a, U, lane, smem + wid * RC_P16_WAVE_BYTES);
+                    __syncthreads();
+                }
+            }
         }
         if (a.spec2 == 1) {
             m = wave_max(m);
@@ -1669,7 +1711,8 @@ bool rowconv_p16_ok(const ConvGeom& d, bool pool) {
     const int R = rowconv_rows(d, true, &u), W = d.w;
     const int64_t px = (int64_t)d.n * d.h * d.w * (pool ? 4 : 1);
     if (px % 16 != 0) return false;
-    return pool || R * W >= 16 || (W == 2 && R == 2);
+    // whole 16-pixel blocks per wave, or per pair of waves (4x4 at R = 2: p16_pair_store)
+    return pool || R * W >= 16 || (W == 2 && R == 2) || (W == 4 && R == 2);
 }
 
 // the K-split form (rowconv_compute_ks): chunks per wave, or 0.  Whole-image 2-row units whose

@@ -83,6 +83,12 @@ class WgradP16Job(C.Structure):
                 ("amax", C.c_void_p)]
 
 
+class SgdCombineJob(C.Structure):
+    """niti_sgd_combine_job: one split-K slab sum of niti_sgd_combine."""
+    _fields_ = [("slab", C.c_void_p), ("splits", C.c_int), ("stride", C.c_int64), ("n", C.c_int64),
+                ("acc", C.c_void_p), ("amax", C.c_void_p)]
+
+
 class ChainLayer(C.Structure):
     """niti_chain_layer: one layer of a user-defined chain network."""
     _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten")]
@@ -175,6 +181,7 @@ def lib():
         "niti_requant_act_fused": (ci, [vp, i64, ci, vp, C.POINTER(RequantFused), vp]),
         "niti_requant_grad": (ci, [vp, i64, vp, ci, vp, vp, vp]),
         "niti_sgd_update": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+        "niti_sgd_combine": (ci, [C.POINTER(SgdCombineJob), ci, vp]),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),

@@ -497,6 +497,18 @@ def sgd_update(acc, amax, w16, ci, rule=2, stream=None, wT=None, g=None, wf=None
     return wT, g
 
 
+def sgd_combine(jobs, stream=None):
+    """The update launch's split-K combine alone (niti_sgd_combine), every job in one launch.
+    jobs: (slab int32 [splits][stride], n, acc int32 [>= n], amax range buffer) each; acc[:n] = the sum
+    of the slabs' first n elements, its max|.| into amax (zeroed by the caller)."""
+    arr = (L.SgdCombineJob * len(jobs))()
+    for j, (slab, n, acc, amax) in enumerate(jobs):
+        assert slab.dtype == torch.int32 and slab.dim() == 2 and slab.is_contiguous() and acc.numel() >= n
+        arr[j].slab, arr[j].splits, arr[j].stride, arr[j].n = slab.data_ptr(), slab.shape[0], slab.shape[1], n
+        arr[j].acc, arr[j].amax = acc.data_ptr(), amax.data_ptr()
+    check(L.lib().niti_sgd_combine(arr, len(jobs), _stream(stream)), "sgd_combine")
+
+
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
     """Exponent-aligned int32 sum of two int8 tensors (niti_resnet.hip) -> (z int32, ez int8 [1])."""
     assert a.shape == b.shape and a.dtype == b.dtype == torch.int8
