@@ -556,6 +556,19 @@ struct SgdJob {
     int slab_map = 0;
     int tb_tiles_ci = 0, tb_cip4 = 0, tb_ld4 = 0;
     uint32_t tb_m = 0, tb_s = 0;
+    // the deferred combine a weight gradient left in d (its slab fields), into this update job
+    void take_combine(const SgdJob& d) {
+        slab = d.slab;
+        splits = d.splits;
+        slab_stride = d.slab_stride;
+        slab_n = d.slab_n;
+        slab_map = d.slab_map;
+        tb_tiles_ci = d.tb_tiles_ci;
+        tb_cip4 = d.tb_cip4;
+        tb_ld4 = d.tb_ld4;
+        tb_m = d.tb_m;
+        tb_s = d.tb_s;
+    }
 };
 constexpr int SGD_MAX_JOBS = 24;
 struct SgdJobs {

@@ -157,14 +157,9 @@ struct Layer {
     int8_t* dflat = nullptr;
     int32_t* dwacc = nullptr;  // [co][kk][cip]
     // the P16 weight gradient's own split-K slabs when its combine is deferred to the NITI_SGD
-    // launch (sgd_update_many), and this step's deferred combine (slab == null: none)
+    // launch (sgd_update_many); the deferred combine itself is grads[i].defer, as the GEMM path's
     int32_t* slab16 = nullptr;
     size_t slab16_bytes = 0;
-    // the GEMM-path weight gradient's own split-K slabs when its combine is deferred the same way
-    // (sized for the current plans at the head of run(), size_wslabs)
-    int32_t* wslab = nullptr;
-    size_t wslab_bytes = 0;
-    SgdJob defer{};
     bool fc_sgd = false;  // this step's weight gradient took the fused NITI_SGD form (pass 1 in run())
     int8_t* g8 = nullptr;    // int8 weight gradient OHWI16
     int8_t* exp = nullptr;   // exponent of this layer's output
@@ -228,19 +223,6 @@ struct Model final : StepDriver {
         return in_step && !off && !dp() && !tuning && conv_wgrad_fc_sgd_ok(g) &&
                !(head_layer(i) && g.c_out <= 32 && g.cip % 32 == 0) && wgrad_p16_splits(i) == 0;
     }
-    bool defer_combine() const {
-        static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
-        return in_step && !off && !dp() && !capturing && !tuning;
-    }
-    // whether a step of this model defers its combines at all (what the autotuner times against)
-    bool in_step_combine() const {
-        static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
-        return !off && !dp();
-    }
-    // the row kernels' accumulator store for their two-launch form (data parallel, graph capture):
-    // the range launch keeps its int32 accumulators here, the requantise launch reads them back
-    int32_t* rc_acc = nullptr;
-    size_t rc_acc_size = 0;
     // the GEMM speculative pairs' alternates (one bit width below / above A's guess), shared by every
     // layer phase: a pair's B consumes them before the next pair's A writes them
     int8_t* gspec_alt = nullptr;
@@ -351,7 +333,7 @@ struct Model final : StepDriver {
     void probe_launch(int layer, int phase, hipEvent_t* b, hipEvent_t* e, unsigned long long** sp) {
         *b = *e = nullptr;
         *sp = nullptr;
-        if (layer != probe_layer || phase != probe_phase || probe_paused || tuning || capturing) return;
+        if (!probe_armed(layer, phase)) return;
         if (probe_count < (int)ev0.size()) {
             *b = ev0[probe_count];
             *e = ev1[probe_count];
@@ -415,15 +397,12 @@ struct Model final : StepDriver {
     unsigned long long* span = nullptr;
     int span_cap = 0, span_count = 0;
     void arm_kernel_events(int layer, int phase) {
-        if (layer != probe_layer || phase != probe_phase || probe_paused || tuning || capturing || probe_count >= (int)ev0.size())
-            return;
+        if (!probe_armed(layer, phase) || probe_count >= (int)ev0.size()) return;
         probe_events_arm(ev0[probe_count], ev1[probe_count]);
         ++probe_count;
     }
     void arm_span(int layer, int phase) {
-        if (layer != probe_layer || phase != probe_phase || probe_paused || tuning || capturing || span == nullptr ||
-            span_count >= span_cap)
-            return;
+        if (!probe_armed(layer, phase) || span == nullptr || span_count >= span_cap) return;
         probe_span_arm(span + 2 * SPAN_MAX_BLOCKS * span_count++);
     }
     void probe(int layer, int phase, bool begin, hipStream_t st) {
@@ -443,8 +422,7 @@ struct Model final : StepDriver {
     }
     // the end event of a probe that the callee records itself (right after the GEMM launch)
     hipEvent_t probe_end_event(int layer, int phase) {
-        if (layer != probe_layer || phase != probe_phase || probe_paused || capturing || tuning || probe_count >= (int)ev0.size())
-            return nullptr;
+        if (!probe_armed(layer, phase) || probe_count >= (int)ev0.size()) return nullptr;
         return ev1[probe_count++];
     }
     void clear_probe() override {
@@ -483,36 +461,6 @@ struct Model final : StepDriver {
     int autotune(hipStream_t st, int reps) override;
     int tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log);
     size_t ws_bytes_for(int op) const { return op == PLAN_WGRAD ? slab_w_bytes : slab_bytes; }
-    // layer i's own slab buffer for a deferred GEMM weight-gradient combine is big enough for the
-    // plan it runs with (false: its plan does not split K into C-shaped slabs, or not sized)
-    bool ensure_wslab(int i) const {
-        const Layer& l = L[i];
-        const PlanChoice c = conv_plan_query(PLAN_WGRAD, l.g, false, slab_w_bytes);
-        if (c.strat != 2 || c.splits < 2 || c.bm == PLAN_P16_TILE) return false;
-        return l.wslab_bytes >= conv_wgrad_slab_bytes(l.g, c);  // (GEMM or tap-sharing slabs)
-    }
-    // size every layer's deferred-combine slab for the current plans, at the head of run() whenever a
-    // plan override changed since the last sizing (one device sync, the old buffer freed): no
-    // allocation or sync inside the step
-    unsigned wslab_epoch = 0;
-    int size_wslabs() {
-        if (wslab_epoch == plan_override_epoch()) return NITI_NO_ERROR;
-        bool synced = false;
-        for (Layer& l : L) {
-            const PlanChoice c = conv_plan_query(PLAN_WGRAD, l.g, false, slab_w_bytes);
-            if (c.strat != 2 || c.splits < 2 || c.bm == PLAN_P16_TILE) continue;
-            const size_t need = conv_wgrad_slab_bytes(l.g, c);
-            if (l.wslab_bytes >= need) continue;
-            if (!synced && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-            synced = true;
-            void* p = ws.replace(l.wslab, need);
-            l.wslab = (int32_t*)p;
-            l.wslab_bytes = p ? need : 0;
-            if (!p) return NITI_OUT_OF_MEMORY;
-        }
-        wslab_epoch = plan_override_epoch();
-        return NITI_NO_ERROR;
-    }
     // The P16 weight gradients of a step as one persistent launch after the last input gradient
     // (conv_wgrad_p16_many): single device, one stream.  A weight gradient reads only its layer's
     // xp16 / dp16, which live until the backward pass ends, so every P16 layer but one with an armed
@@ -581,21 +529,22 @@ struct Model final : StepDriver {
     bool wgrad_batched(int i) const {
         return std::find(wgb_layers.begin(), wgb_layers.end(), i) != wgb_layers.end();
     }
-    // the batch launch and every member's combine fields (l.defer) or, where the combine is not
+    // the batch launch and every member's combine fields (grads[i].defer) or, where the combine is not
     // deferred to the update launch, its reduce
     int wgrad_batch_run(bool defer, hipStream_t st) {
         DTRY(conv_wgrad_p16_many(wgb, wgb_dev, st));
         for (size_t k = 0; k < wgb_layers.size(); ++k) {
             Layer& l = L[wgb_layers[k]];
-            l.defer = SgdJob{};
+            SgdJob& d = grads[wgb_layers[k]].defer;
+            d = SgdJob{};
             l.fc_sgd = false;
             if (wgb.splits[k] < 2) continue;
             const int64_t n = (int64_t)l.g.c_out * 9 * l.g.cip;
             if (defer) {
-                l.defer.slab = l.slab16;
-                l.defer.splits = wgb.splits[k];
-                l.defer.slab_stride = wgb.slab_stride[k];
-                l.defer.slab_n = n;
+                d.slab = l.slab16;
+                d.splits = wgb.splits[k];
+                d.slab_stride = wgb.slab_stride[k];
+                d.slab_n = n;
             } else {
                 DTRY(splitk_reduce_linear(l.slab16, wgb.splits[k], n, wgb.slab_stride[k], l.dwacc,
                                           rng(wgb_layers[k], 2), st));
@@ -938,7 +887,8 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (const int rc = alloc_eval()) return rc;
     if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
-    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{L[i].dwacc, L[i].w_elems(), rng(i, 2)});  // (the bucket SUMs)
+    // (the bucket SUMs, the GEMM weight gradients)
+    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{L[i].dwacc, L[i].w_elems(), rng(i, 2), L[i].g});
     if (hipMemset(x0, 0, (size_t)n * in_h * in_w * round_up(in_c, 16)) != hipSuccess) return NITI_NO_EXECUTION;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
@@ -995,6 +945,10 @@ int Model::fwd_layer(int i, hipStream_t st) {
     const bool dp = this->dp();
     Layer& l = L[i];
     const ConvGeom& g = l.g;
+    auto flatten_fwd = [&] {  // the NCHW flatten of the (pooled) output
+        const int ld = round_up(g.c_out * l.fh() * l.fw(), 16);
+        return launch_map((int64_t)n * ld, FlattenFwd{l.fsrc(), l.fh() * l.fw(), g.c_out, g.cop, ld, l.flat}, st);
+    };
     probe(i, 0, true, st);
     l.r_written = true;
     if (l.col && conv0_ok(g) && !l.flatten) {
@@ -1012,7 +966,7 @@ int Model::fwd_layer(int i, hipStream_t st) {
         const bool next_c32 = i + 1 < (int)L.size() && rowconv_layer(i + 1) && !rowconv_nhwc_pref(L[i + 1].g);
         if (!conv0_ranged) DTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 0, st));
         conv0_ranged = false;
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
+        DTRY(range_max(rng(i, 0), st));
         DTRY(conv0_fwd(g, l.in, l.w, rng(i, 0), o, 1, st, next_c32 && l.pool ? L[i + 1].xc32 : nullptr,
                        next_c32 && !l.pool ? L[i + 1].xc32 : nullptr, code ? l.pc : nullptr));
         if (next_c32) xc32_valid[i + 1] = 1;
@@ -1028,17 +982,12 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.exp_out = l.exp;
         o.relu = l.relu;
         const int K = g.c_in, rows = g.c_out;
-        if (!dp && !capturing && rowconv_fc_ok(n, K, rows, true)) {
-            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {  // the speculative pair: one GEMM pass while the bit width holds
-            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
-        } else {
-            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fc_ok(n, K, rows, true), false, o, rng(i, 0), l.bar, l.epoch, st,
+                                      [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fc(n, K, rows, l.in, g.cip, l.w, g.cip, ro, mode, rng(i, 0), bar,
+                                                            epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         probe(i, 0, false, st);
         return NITI_NO_ERROR;
     }
@@ -1067,25 +1016,14 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.wscale = l.ws_dev;
         o.exp_out = l.exp;
         o.relu = l.relu;
-        if (!dp && !capturing && rowconv_fused_ok(g)) {
-            DTRY(rowconv_fwd(g, xin, l.wf, o, 0, rng(i, 0), l.bar, ++l.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {  // the speculative pair: one GEMM pass while the bit width holds
-            o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;  // its store mode after a change
-            DTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_A, rng(i, 0), l.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(g, xin, l.wf, o, RC_SPEC_B, rng(i, 0), l.bar, 0, nullptr, st));
-        } else {
-            o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;  // else the requantise launch recomputes
-            DTRY(rowconv_fwd(g, xin, l.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(g, xin, l.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fused_ok(g), rowconv_acc_bytes(g, false) != 0, o, rng(i, 0), l.bar, l.epoch,
+                                      st, [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fwd(g, xin, l.wf, ro, mode, rng(i, 0), bar, epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         if (feeds_next) xc32_valid[i + 1] = 1;
         probe(i, 0, false, st);
-        if (l.flatten) {
-            const int fc = g.c_out * l.fh() * l.fw(), ld = round_up(fc, 16);
-            DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.fsrc(), l.fh() * l.fw(), g.c_out, g.cop, ld, l.flat}, st));
-        }
+        if (l.flatten) DTRY(flatten_fwd());
         return NITI_NO_ERROR;
     }
     ActOut o;
@@ -1102,31 +1040,22 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.pool.H = g.oh;
         o.pool.W = g.ow;
     }
-    hipError_t fe = hipErrorNotSupported;
-    if (!dp && !capturing && !fuse_pool) {  // one launch with the rescale fused (plan strategy 4)
-        fe = conv_fwd_fused(g, l.in, l.w, o, FusedBar{l.bar, l.epoch + 1, rc_err}, st);
-        if (fe != hipErrorNotSupported) {
-            ++l.epoch;
-            DTRY(fe);
-        }
-    }
-    if (fe != hipErrorNotSupported) {
-    } else if (spec) {  // the speculative pair: one GEMM pass while the bit width holds, no int32 tensor
-        int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        DTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 0, st, alt));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_fwd_spec(g, l.in, l.w, rng(i, 0), o, l.gspec, 1, st, alt));
-    } else {
-        DTRY(conv_fwd_phase1(g, l.in, l.w, acc, rng(i, 0), slab, slab_bytes, st));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_fwd_phase2(g, l.in, l.w, acc, rng(i, 0), o, slab_bytes, st));
-    }
+    // (the pair: one GEMM pass while the bit width holds, no int32 tensor)
+    const int rc = gemm_ranged(
+        !dp && !capturing && !fuse_pool, spec, o, rng(i, 0), l.bar, l.epoch, st,
+        [&](const ActOut& ao, const FusedBar& fb) { return conv_fwd_fused(g, l.in, l.w, ao, fb, st); },
+        [&](const ActOut& ao, int ph) {
+            int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
+            return conv_fwd_spec(g, l.in, l.w, rng(i, 0), ao, l.gspec, ph, st, alt);
+        },
+        [&](const ActOut& ao, int ph) {
+            return ph == 1 ? conv_fwd_phase1(g, l.in, l.w, acc, rng(i, 0), slab, slab_bytes, st)
+                           : conv_fwd_phase2(g, l.in, l.w, acc, rng(i, 0), ao, slab_bytes, st);
+        });
+    if (rc != NITI_NO_ERROR) return rc;
     probe(i, 0, false, st);
     if (l.pool && !fuse_pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
-    if (l.flatten) {
-        const int fc = g.c_out * l.fh() * l.fw(), ld = round_up(fc, 16);
-        DTRY(launch_map((int64_t)n * ld, FlattenFwd{l.fsrc(), l.fh() * l.fw(), g.c_out, g.cop, ld, l.flat}, st));
-    }
+    if (l.flatten) DTRY(flatten_fwd());
     return NITI_NO_ERROR;
 }
 
@@ -1144,8 +1073,9 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         return NITI_NO_ERROR;
     }
     l.fc_sgd = fc_sgd_layer(i);
+    SgdJob& defer_job = grads[i].defer;
     if (l.fc_sgd) {  // its range now; the recompute with the update after the backward pass
-        l.defer = SgdJob{};
+        defer_job = SgdJob{};
         DTRY(conv_wgrad_fc_sgd(g, l.in, l.dy, rng(i, 2), SgdJob{}, 0, st));
         return NITI_NO_ERROR;
     }
@@ -1169,9 +1099,9 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         // next layer)
         const bool defer = defer_combine() && s > 1 && l.slab16 != nullptr &&
                            conv_wgrad_p16_workspace(g, s) <= l.slab16_bytes;
-        l.defer = SgdJob{};
+        defer_job = SgdJob{};
         DTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.slab16 : slab_w,
-                            defer ? l.slab16_bytes : slab_w_bytes, s, st, eb, ee, sp, defer ? &l.defer : nullptr));
+                            defer ? l.slab16_bytes : slab_w_bytes, s, st, eb, ee, sp, defer ? &defer_job : nullptr));
         return NITI_NO_ERROR;
     }
     // the weight-gradient probe is the GEMM launch's own begin / end (its split-K reduce excluded)
@@ -1180,27 +1110,7 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     else
         arm_kernel_events(i, 2);
     arm_span(i, 2);
-    // single device: a split-K plan leaves its slabs (this layer's own) to the NITI_SGD launch's
-    // combine, which sums them and takes the range (no reduce launch, no int32 round trip)
-    const bool defer = defer_combine() && ensure_wslab(i);
-    // the autotuner times a split plan of the generic GEMM with the combine it will run with in
-    // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
-    // step never makes; the tap-sharing kernel's plans are timed as they were (its slabs keep their
-    // reduce launch where a split has under 4096 elements)
-    const bool tune_defer = tuning && in_step_combine() &&
-                            conv_plan_query(PLAN_WGRAD, g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
-    l.defer = SgdJob{};
-    DTRY(conv_wgrad_acc(g, l.in, l.dy, l.dwacc, dp ? nullptr : rng(i, 2), defer ? l.wslab : slab_w,
-                        defer ? l.wslab_bytes : slab_w_bytes, st, capturing ? probe_end_event(i, 2) : nullptr,
-                        defer || tune_defer ? &l.defer : nullptr));
-    if (tune_defer && l.defer.slab != nullptr) {
-        SgdJob j = l.defer;
-        j.acc = l.dwacc;
-        j.amax = rng(i, 2);
-        l.defer = SgdJob{};
-        if (sgd_combine_many(&j, 1, st) != hipSuccess) return NITI_NO_EXECUTION;
-    }
-    return NITI_NO_ERROR;
+    return wgrad_gemm(i, l.in, l.dy, capturing ? probe_end_event(i, 2) : nullptr, st);
 }
 
 // Input gradient of layer i (i > 0) into the previous layer's output gradient, with the
@@ -1237,17 +1147,12 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         }
         dy16_valid[i - 1] = !(pv.pool && o.pool_dx_nhwc == 0);
         const int K = g.c_out, rows = g.c_in;
-        if (!dp && !capturing && rowconv_fc_ok(n, K, rows, true)) {
-            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {
-            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
-        } else {
-            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fc_ok(n, K, rows, true), false, o, rng(i, 1), l.bar, l.epoch, st,
+                                      [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fc(n, K, rows, l.dy, g.cop, l.wT, g.cop, ro, mode, rng(i, 1), bar,
+                                                            epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         probe(i, 1, false, st);
         dp16_valid[i - 1] = o.p16 != nullptr ? 1 : 0;
         dyc32_valid[i - 1] = next != nullptr ? 1 : 0;
@@ -1290,19 +1195,12 @@ int Model::dgrad_layer(int i, hipStream_t st) {
             o.relu_mask = pv.relu ? pv.r : nullptr;
         }
         dy16_valid[i - 1] = !skip16;
-        if (!dp && !capturing && rowconv_fused_ok(d, true)) {
-            DTRY(rowconv_fwd(d, dyin, l.wft, o, 0, rng(i, 1), l.bar, ++l.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {
-            o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_A, rng(i, 1), l.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(d, dyin, l.wft, o, RC_SPEC_B, rng(i, 1), l.bar, 0, nullptr, st));
-        } else {
-            o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(d, dyin, l.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(d, dyin, l.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fused_ok(d, true), rowconv_acc_bytes(d, true) != 0, o, rng(i, 1), l.bar,
+                                      l.epoch, st,
+                                      [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fwd(d, dyin, l.wft, ro, mode, rng(i, 1), bar, epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         probe(i, 1, false, st);
         dp16_valid[i - 1] = o.p16 != nullptr ? 1 : 0;
         dyc32_valid[i - 1] = next != nullptr ? 1 : 0;
@@ -1342,25 +1240,19 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         o.out = pv.dy;
         if (conv_dgrad_phase2_separate(g, slab_bytes)) o.out_p16 = p16_out;
     }
-    hipError_t fe = hipErrorNotSupported;
-    if (!dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr) {  // one launch, the rescale fused
-        fe = conv_dgrad_fused(g, l.dy, l.wT, o, FusedBar{l.bar, l.epoch + 1, rc_err}, st);
-        if (fe != hipErrorNotSupported) {
-            ++l.epoch;
-            DTRY(fe);
-        }
-    }
-    if (fe != hipErrorNotSupported) {
-    } else if (spec) {  // the speculative pair (no int32 tensor while the bit width holds)
-        int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        DTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 0, st, alt));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), o, l.gspec + GEMM_SPEC_SLOT_WORDS, 1, st, alt));
-    } else {
-        DTRY(conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), o, slab_bytes, st));
-    }
+    // (the pair: no int32 tensor while the bit width holds)
+    const int rc = gemm_ranged(
+        !dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr, spec, o, rng(i, 1), l.bar, l.epoch, st,
+        [&](const ActOut& ao, const FusedBar& fb) { return conv_dgrad_fused(g, l.dy, l.wT, ao, fb, st); },
+        [&](const ActOut& ao, int ph) {
+            int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
+            return conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), ao, l.gspec + GEMM_SPEC_SLOT_WORDS, ph, st, alt);
+        },
+        [&](const ActOut& ao, int ph) {
+            return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st)
+                           : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st);
+        });
+    if (rc != NITI_NO_ERROR) return rc;
     probe(i, 1, false, st);
     if (pv.flatten) {
         const int fhw = pv.fh() * pv.fw(), ld = round_up(pg.c_out * fhw, 16);
@@ -1494,13 +1386,13 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
         SgdJob jobs[SGD_MAX_JOBS];
         int n = 0;
         for (int i : set) {
-            Layer& l = L[i];
-            if (l.defer.slab == nullptr) continue;
-            jobs[n] = l.defer;
-            jobs[n].acc = l.dwacc;
+            SgdJob& d = grads[i].defer;
+            if (d.slab == nullptr) continue;
+            jobs[n] = d;
+            jobs[n].acc = L[i].dwacc;
             jobs[n].amax = rng(i, 2);
             ++n;
-            l.defer = SgdJob{};
+            d = SgdJob{};
         }
         return sgd_combine_many(jobs, n, st) == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
     };
@@ -1510,10 +1402,10 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
             const ConvGeom& g = l.g;
             const int s = wgrad_p16_splits(i);
             const bool defer = s > 1 && l.slab16 != nullptr && conv_wgrad_p16_workspace(g, s) <= l.slab16_bytes;
-            l.defer = SgdJob{};
+            grads[i].defer = SgdJob{};
             DTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, rng(i, 2), defer ? l.slab16 : slab_w,
                                 defer ? l.slab16_bytes : slab_w_bytes, s, st, nullptr, nullptr, nullptr,
-                                defer ? &l.defer : nullptr));
+                                defer ? &grads[i].defer : nullptr));
         }
         return combine();
     };
@@ -1549,12 +1441,8 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
     const bool dp = this->dp();
     SgdJob jobs[SGD_MAX_JOBS];
     if (nl > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;
-    struct InStep {  // weight gradients inside this step may defer their combine (defer_combine)
-        bool& f;
-        explicit InStep(bool& x) : f(x) { f = true; }
-        ~InStep() { f = false; }
-    } in_step_guard(in_step);
-    for (auto& l : L) l.defer = SgdJob{};
+    InStep in_step_guard(in_step);  // weight gradients inside this step may defer their combine (defer_combine)
+    for (GradSlot& s : grads) s.defer = SgdJob{};
     if (dp) {
         const int rc = ensure_comm_stream();
         if (rc != NITI_NO_ERROR) return rc;
@@ -1713,20 +1601,6 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
     // single device, one stream: the P16 weight gradients wait for the last input gradient and run
     // as one launch (wgrad_batch_run below)
     const bool wbatch = !dp && !ov && !tuning && !wgb_layers.empty();
-    auto take_defer = [&](int i) {  // the combine of layer i's split-K slabs, in the update launch
-        const Layer& l = L[i];
-        if (l.defer.slab == nullptr) return;
-        jobs[i].slab = l.defer.slab;
-        jobs[i].splits = l.defer.splits;
-        jobs[i].slab_stride = l.defer.slab_stride;
-        jobs[i].slab_n = l.defer.slab_n;
-        jobs[i].slab_map = l.defer.slab_map;  // (the tap-sharing kernel's tile-blocked slabs)
-        jobs[i].tb_tiles_ci = l.defer.tb_tiles_ci;
-        jobs[i].tb_cip4 = l.defer.tb_cip4;
-        jobs[i].tb_ld4 = l.defer.tb_ld4;
-        jobs[i].tb_m = l.defer.tb_m;
-        jobs[i].tb_s = l.defer.tb_s;
-    };
     for (int i = nl - 1; i >= 0; --i) {
         // (an event record leaves a ~6.5 us bubble before the next launch on the step stream;
         // hipStreamWriteValue64 / WaitValue64 run as blit kernels here and cost more)
@@ -1754,7 +1628,8 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
                          i > 0 && !rowconv_dgrad_layer(i) ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
         jobs[i].wf = l.rc ? l.wf : nullptr;
         jobs[i].wft = l.rcd ? l.wft : nullptr;
-        take_defer(i);
+        // the combine of this layer's split-K slabs, in the update launch
+        if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
     if (wbatch) {
         // dy's P16 copy where no input-gradient epilogue wrote it, all in one launch; then the batch
@@ -1770,7 +1645,8 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         if (nc > 0) DTRY(nhwc16_to_p16_many(cv, nc, st));
         const int rc = wgrad_batch_run(defer_combine(), st);
         if (rc != NITI_NO_ERROR) return rc;
-        for (int i : wgb_layers) take_defer(i);
+        for (int i : wgb_layers)
+            if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
     if (dp) {  // every bucket summed and ranged on the comm stream before the update
         DTRY(hipEventRecord(ev_grads, cst));

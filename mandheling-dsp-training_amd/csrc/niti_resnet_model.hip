@@ -247,13 +247,14 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     amax_bytes = (3 * C.size() + 2 * B.size() + 1) * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (!amax) return NITI_OUT_OF_MEMORY;
-    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2)});  // (the bucket SUMs)
+    // (the bucket SUMs, the GEMM weight gradients)
+    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2), C[i].g});
     if (const int rc = alloc_eval()) return rc;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
 
 void ResNetModel::probe(int layer, int phase, bool begin, hipStream_t st) {
-    if (layer != probe_layer || phase != probe_phase || probe_paused || tuning || capturing || probe_count >= (int)ev0.size()) return;
+    if (!probe_armed(layer, phase) || probe_count >= (int)ev0.size()) return;
     if (begin) {
         (void)hipEventRecord(ev0[probe_count], st);
     } else {
@@ -287,19 +288,11 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
         o.wscale = c.ws_dev;
         o.exp_out = c.y_exp;
         o.relu = c.relu;
-        if (!dp && !capturing && rowconv_fused_ok(g)) {
-            DTRY(rowconv_fwd(g, xin, c.wf, o, 0, rng(i, 0), c.bar, ++c.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {
-            o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_A, rng(i, 0), c.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(g, xin, c.wf, o, RC_SPEC_B, rng(i, 0), c.bar, 0, nullptr, st));
-        } else {
-            o.acc_store = rowconv_acc_bytes(g, false) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(g, xin, c.wf, o, 1, rng(i, 0), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(g, xin, c.wf, o, 2, rng(i, 0), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fused_ok(g), rowconv_acc_bytes(g, false) != 0, o, rng(i, 0), c.bar, c.epoch,
+                                      st, [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fwd(g, xin, c.wf, ro, mode, rng(i, 0), bar, epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         probe(i, 0, false, st);
         return NITI_NO_ERROR;
     }
@@ -322,25 +315,18 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
         }
         stem_y_written = o.out != nullptr;
     }
-    if (!dp && !capturing) {  // one launch with the rescale fused (plan strategy 4, every tile resident)
-        const hipError_t e = conv_fwd_fused(g, c.in, c.w, o, FusedBar{c.bar, c.epoch + 1, rc_err}, st);
-        if (e != hipErrorNotSupported) {
-            ++c.epoch;
-            DTRY(e);
-            probe(i, 0, false, st);
-            return NITI_NO_ERROR;
-        }
-    }
-    if (conv_fwd_spec_ok(g)) {  // the GEMM's speculative pair (plan strategy 3)
-        int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        DTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 0, st, alt));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_fwd_spec(g, c.in, c.w, rng(i, 0), o, c.gspec, 1, st, alt));
-    } else {
-        DTRY(conv_fwd_phase1(g, c.in, c.w, acc, rng(i, 0), slab, slab_bytes, st));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 0), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_fwd_phase2(g, c.in, c.w, acc, rng(i, 0), o, slab_bytes, st));
-    }
+    const int rc = gemm_ranged(
+        !dp && !capturing, conv_fwd_spec_ok(g), o, rng(i, 0), c.bar, c.epoch, st,
+        [&](const ActOut& ao, const FusedBar& fb) { return conv_fwd_fused(g, c.in, c.w, ao, fb, st); },
+        [&](const ActOut& ao, int ph) {
+            int8_t* alt = conv_fwd_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
+            return conv_fwd_spec(g, c.in, c.w, rng(i, 0), ao, c.gspec, ph, st, alt);
+        },
+        [&](const ActOut& ao, int ph) {
+            return ph == 1 ? conv_fwd_phase1(g, c.in, c.w, acc, rng(i, 0), slab, slab_bytes, st)
+                           : conv_fwd_phase2(g, c.in, c.w, acc, rng(i, 0), ao, slab_bytes, st);
+        });
+    if (rc != NITI_NO_ERROR) return rc;
     probe(i, 0, false, st);
     return NITI_NO_ERROR;
 }
@@ -350,7 +336,6 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
 int ResNetModel::dgrad_conv(int i, hipStream_t st) {
     RConv& c = C[i];
     const ConvGeom& g = c.g;
-    const bool dp = this->dp();
     if (c.dx == nullptr) return NITI_NO_ERROR;
     probe(i, 1, true, st);
     if (rows_dg_on(i)) {
@@ -366,19 +351,12 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
         o.wscale = c.ws_dev;
         o.exp_out = c.dx_exp;
         o.dgrad_slot = 1;
-        if (!dp && !capturing && rowconv_fused_ok(d, true)) {
-            DTRY(rowconv_fwd(d, dyin, c.wft, o, 0, rng(i, 1), c.bar, ++c.epoch, rc_err, st));
-        } else if (rowconv_spec2_on()) {
-            o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_A, rng(i, 1), c.bar, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(d, dyin, c.wft, o, RC_SPEC_B, rng(i, 1), c.bar, 0, nullptr, st));
-        } else {
-            o.acc_store = rowconv_acc_bytes(d, true) ? rc_acc : nullptr;
-            DTRY(rowconv_fwd(d, dyin, c.wft, o, 1, rng(i, 1), nullptr, 0, nullptr, st));
-            if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-            DTRY(rowconv_fwd(d, dyin, c.wft, o, 2, rng(i, 1), nullptr, 0, nullptr, st));
-        }
+        const int rc = rowconv_ranged(rowconv_fused_ok(d, true), rowconv_acc_bytes(d, true) != 0, o, rng(i, 1), c.bar,
+                                      c.epoch, st,
+                                      [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
+                                          return rowconv_fwd(d, dyin, c.wft, ro, mode, rng(i, 1), bar, epoch, err, st);
+                                      });
+        if (rc != NITI_NO_ERROR) return rc;
         probe(i, 1, false, st);
         return NITI_NO_ERROR;
     }
@@ -388,27 +366,20 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
     o.exp_in = c.dy_exp;
     o.wscale = c.ws_dev;
     o.exp_out = c.dx_exp;
-    uint32_t* slot = c.gspec + GEMM_SPEC_SLOT_WORDS;
-    if (!dp && !capturing) {  // one launch with the rescale fused (plan strategy 4; stride 1)
-        const hipError_t e = conv_dgrad_fused(g, c.dy, c.wT, o, FusedBar{c.bar, c.epoch + 1, rc_err}, st);
-        if (e != hipErrorNotSupported) {
-            ++c.epoch;
-            DTRY(e);
-            probe(i, 1, false, st);
-            return NITI_NO_ERROR;
-        }
-    }
-    if (conv_dgrad_spec_ok(g)) {
-        int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
-        DTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 0, st, alt));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), o, slot, 1, st, alt));
-    } else {
-        const int8_t* subw = subpix_on() ? c.subw : nullptr;  // stride 2: four sub-pixel class GEMMs
-        DTRY(conv_dgrad_phase1(g, c.dy, c.wT, acc, rng(i, 1), slab, slab_bytes, st, subw));
-        if (dp && exact) DTRY(coll->allreduce(rng(i, 1), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(conv_dgrad_phase2(g, c.dy, c.wT, acc, rng(i, 1), o, slab_bytes, st, subw));
-    }
+    // (the fused launch: stride 1)
+    const int rc = gemm_ranged(
+        !dp() && !capturing, conv_dgrad_spec_ok(g), o, rng(i, 1), c.bar, c.epoch, st,
+        [&](const ActOut& ao, const FusedBar& fb) { return conv_dgrad_fused(g, c.dy, c.wT, ao, fb, st); },
+        [&](const ActOut& ao, int ph) {
+            int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
+            return conv_dgrad_spec(g, c.dy, c.wT, rng(i, 1), ao, c.gspec + GEMM_SPEC_SLOT_WORDS, ph, st, alt);
+        },
+        [&](const ActOut& ao, int ph) {
+            const int8_t* subw = subpix_on() ? c.subw : nullptr;  // stride 2: four sub-pixel class GEMMs
+            return ph == 1 ? conv_dgrad_phase1(g, c.dy, c.wT, acc, rng(i, 1), slab, slab_bytes, st, subw)
+                           : conv_dgrad_phase2(g, c.dy, c.wT, acc, rng(i, 1), ao, slab_bytes, st, subw);
+        });
+    if (rc != NITI_NO_ERROR) return rc;
     probe(i, 1, false, st);
     return NITI_NO_ERROR;
 }
@@ -416,120 +387,51 @@ int ResNetModel::dgrad_conv(int i, hipStream_t st) {
 // Weight gradient of conv i (int32, and on one device its range; data parallel, the bucket SUM and
 // the range follow on the comm stream)
 int ResNetModel::wgrad_conv(int i, hipStream_t st) {
-    RConv& c = C[i];
     probe(i, 2, true, st);
-    // single device, in the step: a split-K plan leaves its (own) slabs to the update's combine
-    const bool defer = in_step && !dp() && !capturing && !tuning && ensure_wslab(i);
-    // the autotuner times a split plan of the generic GEMM with the combine it will run with in
-    // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
-    // step never makes; the tap-sharing kernel's plans are timed as they were
-    const bool tune_defer = tuning && !dp() &&
-                            conv_plan_query(PLAN_WGRAD, c.g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
-    c.defer = SgdJob{};
-    DTRY(conv_wgrad_acc(c.g, c.in, c.dy, c.dwacc, dp() ? nullptr : rng(i, 2), defer ? c.wslab : slab_w,
-                        defer ? c.wslab_bytes : slab_w_bytes, st, nullptr, defer || tune_defer ? &c.defer : nullptr));
-    if (tune_defer && c.defer.slab != nullptr) {
-        SgdJob j = c.defer;
-        j.acc = c.dwacc;
-        j.amax = rng(i, 2);
-        c.defer = SgdJob{};
-        if (sgd_combine_many(&j, 1, st) != hipSuccess) return NITI_NO_EXECUTION;
-    }
+    const int rc = wgrad_gemm(i, C[i].in, C[i].dy, nullptr, st);
+    if (rc != NITI_NO_ERROR) return rc;
     probe(i, 2, false, st);
     return NITI_NO_ERROR;
 }
 
-// conv i's own slab buffer for a deferred weight-gradient combine is big enough for the plan it
-// runs with (false: the plan does not split K into C-shaped slabs, or the buffer was not sized)
-bool ResNetModel::ensure_wslab(int i) {
-    const RConv& c = C[i];
-    const PlanChoice p = conv_plan_query(PLAN_WGRAD, c.g, false, slab_w_bytes);
-    if (p.strat != 2 || p.splits < 2 || p.bm == PLAN_P16_TILE) return false;
-    return c.wslab_bytes >= conv_wgrad_slab_bytes(c.g, p);  // (GEMM or tap-sharing slabs)
-}
-
-// Size every conv's deferred-combine slab for the current plans: at the head of run(), before
-// anything is enqueued, whenever a plan override changed since the last sizing (one device sync,
-// the old buffer freed).  Inside the step ensure_wslab only checks.
-int ResNetModel::size_wslabs() {
-    if (wslab_epoch == plan_override_epoch()) return NITI_NO_ERROR;
-    bool synced = false;
-    for (RConv& c : C) {
-        const PlanChoice p = conv_plan_query(PLAN_WGRAD, c.g, false, slab_w_bytes);
-        if (p.strat != 2 || p.splits < 2 || p.bm == PLAN_P16_TILE) continue;
-        const size_t need = conv_wgrad_slab_bytes(c.g, p);
-        if (c.wslab_bytes >= need) continue;
-        if (!synced && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-        synced = true;
-        void* q = ws.replace(c.wslab, need);
-        c.wslab = (int32_t*)q;
-        c.wslab_bytes = q ? need : 0;
-        if (!q) return NITI_OUT_OF_MEMORY;
-    }
-    wslab_epoch = plan_override_epoch();
-    return NITI_NO_ERROR;
-}
-
-// Block k's output: relu(requant(aligned y_b + shortcut)) -- range pass (the sum not stored),
-// [MAX], the sum recomputed and requantised (niti_resnet.hip)
-int ResNetModel::residual_fwd(int k, hipStream_t st) {
+// Block k's residual sum (niti_resnet.hip) in one of the three forms of the range / rescale protocol:
+// the sum is never stored, the requantise launch recomputes it from the int8 operands.
+//   forward   the block's output: relu(requant(aligned y_b + shortcut))
+//   backward  the gradient at the block's input: requant(aligned dx_a + shortcut gradient), the
+//             previous block output's relu gradient fused (block 0: the stem's max-pool gradient
+//             takes it)
+int ResNetModel::residual_sum(int k, bool bwd, hipStream_t st) {
     RBlock& b = B[k];
-    const RConv& cb = C[b.b];
-    const int8_t* sc = b.p >= 0 ? C[b.p].y : b.u;
-    const int8_t* es = b.p >= 0 ? C[b.p].y_exp : b.u_exp;
+    const bool proj = b.p >= 0;
+    const int8_t* a = bwd ? b.dua : C[b.b].y;
+    const int8_t* ea = bwd ? C[b.a].dx_exp : C[b.b].y_exp;
+    const int8_t* s = bwd ? (proj ? b.dus : b.dz) : (proj ? C[b.p].y : b.u);
+    const int8_t* es = bwd ? (proj ? C[b.p].dx_exp : b.dz_exp) : (proj ? C[b.p].y_exp : b.u_exp);
+    const int64_t n = bwd ? b.in_elems : b.out_elems;
+    int8_t* ez = bwd ? b.ezb : b.ez;
+    int8_t* eo = bwd ? b.du_exp : b.out_exp;
+    int8_t* out = bwd ? b.du : b.out;
+    const int relu = bwd ? 0 : 1;
+    const int8_t* mask = bwd && k > 0 ? B[k - 1].out : nullptr;
+    uint32_t* amax = rng_blk(k, bwd ? 1 : 0);
     if (res_fused_on()) {  // one launch: the range through the in-kernel grid barrier
-        const hipError_t e = residual_fused(cb.y, cb.y_exp, sc, es, b.out_elems, b.ez, b.out_exp, 1, b.out, res_bar,
-                                            ++res_epoch, rc_err, st);
+        const hipError_t e = residual_fused(a, ea, s, es, n, ez, eo, relu, out, res_bar, ++res_epoch, rc_err, st, mask);
         if (e != hipErrorNotSupported) {
             DTRY(e);
             return NITI_NO_ERROR;
         }
         --res_epoch;
     }
-    if (res_spec_on()) {  // the speculative pair: one pass of the sum while its bit width holds
-        uint32_t* slot = res_slot + (2 * k) * RES_SPEC_SLOT_WORDS;
-        DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
-                              nullptr, 1, slot));
-        if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st,
-                              nullptr, 2, slot));
-        return NITI_NO_ERROR;
-    }
-    DTRY(residual_add(cb.y, cb.y_exp, sc, es, b.out_elems, nullptr, nullptr, rng_blk(k, 0), st));
-    if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 0), MAX_WORDS, COLL_MAX_U32, st));
-    DTRY(residual_requant(cb.y, cb.y_exp, sc, es, b.out_elems, rng_blk(k, 0), b.ez, b.out_exp, 1, b.out, st));
-    return NITI_NO_ERROR;
-}
-
-// The gradient at block k's input: requant(aligned dx_a + shortcut gradient), the previous block
-// output's relu gradient fused (block 0: the stem's max-pool gradient takes it)
-int ResNetModel::residual_bwd(int k, hipStream_t st) {
-    RBlock& b = B[k];
-    const RConv& ca = C[b.a];
-    const int8_t* s = b.p >= 0 ? b.dus : b.dz;
-    const int8_t* es = b.p >= 0 ? C[b.p].dx_exp : b.dz_exp;
-    if (res_fused_on()) {
-        const hipError_t e = residual_fused(b.dua, ca.dx_exp, s, es, b.in_elems, b.ezb, b.du_exp, 0, b.du, res_bar,
-                                            ++res_epoch, rc_err, st, k > 0 ? B[k - 1].out : nullptr);
-        if (e != hipErrorNotSupported) {
-            DTRY(e);
-            return NITI_NO_ERROR;
-        }
-        --res_epoch;
-    }
-    const int8_t* mask = k > 0 ? B[k - 1].out : nullptr;
-    if (res_spec_on()) {  // the speculative pair (residual_fwd)
-        uint32_t* slot = res_slot + (2 * k + 1) * RES_SPEC_SLOT_WORDS;
-        DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
-                              1, slot));
-        if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
-        DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask,
-                              2, slot));
-        return NITI_NO_ERROR;
-    }
-    DTRY(residual_add(b.dua, ca.dx_exp, s, es, b.in_elems, nullptr, nullptr, rng_blk(k, 1), st));
-    if (dp() && exact) DTRY(coll->allreduce(rng_blk(k, 1), MAX_WORDS, COLL_MAX_U32, st));
-    DTRY(residual_requant(b.dua, ca.dx_exp, s, es, b.in_elems, rng_blk(k, 1), b.ezb, b.du_exp, 0, b.du, st, mask));
+    // the speculative pair (one pass of the sum while its bit width holds; one slot per block and
+    // direction), else the range pass and the requantise pass
+    const bool spec = res_spec_on();
+    uint32_t* slot = spec ? res_slot + (2 * k + (bwd ? 1 : 0)) * RES_SPEC_SLOT_WORDS : nullptr;
+    if (spec)
+        DTRY(residual_requant(a, ea, s, es, n, amax, ez, eo, relu, out, st, mask, 1, slot));
+    else
+        DTRY(residual_add(a, ea, s, es, n, nullptr, nullptr, amax, st));
+    DTRY(range_max(amax, st));
+    DTRY(residual_requant(a, ea, s, es, n, amax, ez, eo, relu, out, st, mask, spec ? 2 : 0, slot));
     return NITI_NO_ERROR;
 }
 
@@ -543,12 +445,8 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         const int rc = ensure_comm_stream();
         if (rc != NITI_NO_ERROR) return rc;
     }
-    struct InStep {  // weight gradients inside this step may defer their combine
-        bool& f;
-        explicit InStep(bool& x) : f(x) { f = true; }
-        ~InStep() { f = false; }
-    } in_step_guard(in_step);
-    for (RConv& c : C) c.defer = SgdJob{};
+    InStep in_step_guard(in_step);  // weight gradients inside this step may defer their combine
+    for (GradSlot& s : grads) s.defer = SgdJob{};
     if (!dp && !capturing && !tuning) {
         const int rc = size_wslabs();  // (plan changes: no allocation or sync inside the step)
         if (rc != NITI_NO_ERROR) return rc;
@@ -575,7 +473,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         if ((rc = dgrad_conv(b.b, st)) != NITI_NO_ERROR || (rc = wg(b.b)) != NITI_NO_ERROR) return rc;
         if ((rc = dgrad_conv(b.a, st)) != NITI_NO_ERROR || (rc = wg(b.a)) != NITI_NO_ERROR) return rc;
         if (b.p >= 0 && (rc = dgrad_conv(b.p, st)) != NITI_NO_ERROR) return rc;
-        if ((rc = residual_bwd(k, st)) != NITI_NO_ERROR) return rc;
+        if ((rc = residual_sum(k, true, st)) != NITI_NO_ERROR) return rc;
     }
     // the stem: overlapping 3x3 / 2 max-pool gradient (first max wins) with the relu gradient, then
     // its weight gradient over the im2col
@@ -607,18 +505,8 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
             jobs[i].sub_pt = g.pt;
             jobs[i].sub_pl = g.pl;
         }
-        if (c.defer.slab != nullptr) {  // this conv's split-K slabs, combined in the update launch
-            jobs[i].slab = c.defer.slab;
-            jobs[i].splits = c.defer.splits;
-            jobs[i].slab_stride = c.defer.slab_stride;
-            jobs[i].slab_n = c.defer.slab_n;
-            jobs[i].slab_map = c.defer.slab_map;  // (the tap-sharing kernel's tile-blocked slabs)
-            jobs[i].tb_tiles_ci = c.defer.tb_tiles_ci;
-            jobs[i].tb_cip4 = c.defer.tb_cip4;
-            jobs[i].tb_ld4 = c.defer.tb_ld4;
-            jobs[i].tb_m = c.defer.tb_m;
-            jobs[i].tb_s = c.defer.tb_s;
-        }
+        // this conv's split-K slabs, combined in the update launch
+        if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
     DTRY(sgd_update_many(jobs, nl, st));
     g8_written = keep_grads;
@@ -668,13 +556,13 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
         if ((rc = fwd_conv(b.a, st)) != NITI_NO_ERROR) return rc;
         if ((rc = fwd_conv(b.b, st)) != NITI_NO_ERROR) return rc;
         if (b.p >= 0 && (rc = fwd_conv(b.p, st)) != NITI_NO_ERROR) return rc;
-        if ((rc = residual_fwd(k, st)) != NITI_NO_ERROR) return rc;
+        if ((rc = residual_sum(k, false, st)) != NITI_NO_ERROR) return rc;
     }
     // global sum pool + requantisation, the fc head
     const RBlock& bl = B.back();
     const ConvGeom& gl = C[bl.b].g;
     DTRY(sum_pool(bl.out, n, gl.oh * gl.ow, gl.cop, gsum, rng_pool(), st));
-    if (dp && exact) DTRY(coll->allreduce(rng_pool(), MAX_WORDS, COLL_MAX_U32, st));
+    DTRY(range_max(rng_pool(), st));
     {
         ActRequant r;
         r.acc = gsum;

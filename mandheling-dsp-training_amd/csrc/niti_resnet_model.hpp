@@ -48,10 +48,6 @@ struct RConv {
     int8_t* dx_exp = nullptr;
     const int8_t* dx_mask = nullptr; // the previous op's relu gradient fused into the input gradient
     int32_t* dwacc = nullptr;        // int32 weight gradient (in the contiguous gradient bucket)
-    // single device: a split-K weight gradient's own slabs, combined by the NITI_SGD launch
-    int32_t* wslab = nullptr;
-    size_t wslab_bytes = 0;
-    SgdJob defer{};
     int64_t w_elems() const { return (int64_t)g.c_out * g.kh * g.kw * g.cip; }
     int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * og.c_in * og.kh * og.kw; }
 };
@@ -102,8 +98,6 @@ struct ResNetModel final : StepDriver {
     int n_exps = 0;
     int32_t* acc = nullptr;       // shared int32 accumulator of the GEMM paths
     size_t acc_bytes = 0;
-    int32_t* rc_acc = nullptr;    // the row kernels' accumulator store (two-launch store mode)
-    size_t rc_acc_size = 0;
     int8_t* gspec_alt = nullptr;  // the GEMM speculative pairs' alternates (shared)
     size_t gspec_alt_bytes = 0;
     // the residual sums' single-launch form (residual_fused, NITI_RES_FUSED=1: measured slower than
@@ -145,11 +139,8 @@ struct ResNetModel final : StepDriver {
     int fwd_conv(int i, hipStream_t st);
     int dgrad_conv(int i, hipStream_t st);
     int wgrad_conv(int i, hipStream_t st);
-    bool ensure_wslab(int i);
-    int size_wslabs();
-    unsigned wslab_epoch = 0;  // plan_override_epoch() the slabs were last sized for
-    int residual_fwd(int k, hipStream_t st);
-    int residual_bwd(int k, hipStream_t st);
+    // block k's residual sum: its output (forward) or the gradient at its input (bwd)
+    int residual_sum(int k, bool bwd, hipStream_t st);
     int run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st);
     int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) override;
     // the step's forward half (input, every conv and residual sum, the pool, the fc head)

@@ -32,6 +32,60 @@ StepDriver::~StepDriver() {
     if (cst) (void)hipStreamDestroy(cst);
 }
 
+// ------------------------------------------------------------------------------ weight gradient
+// the plan layer i's GEMM weight gradient runs with, where it splits K into slabs a combine can sum
+static bool wslab_plan(const ConvGeom& g, size_t slab_w_bytes, PlanChoice* c) {
+    *c = conv_plan_query(PLAN_WGRAD, g, false, slab_w_bytes);
+    return c->strat == 2 && c->splits >= 2 && c->bm != PLAN_P16_TILE;
+}
+
+bool StepDriver::ensure_wslab(int i) const {
+    PlanChoice c;
+    if (!wslab_plan(grads[i].g, slab_w_bytes, &c)) return false;
+    return grads[i].wslab_bytes >= conv_wgrad_slab_bytes(grads[i].g, c);  // (GEMM or tap-sharing slabs)
+}
+
+int StepDriver::size_wslabs() {
+    if (wslab_epoch == plan_override_epoch()) return NITI_NO_ERROR;
+    bool synced = false;
+    for (GradSlot& s : grads) {
+        PlanChoice c;
+        if (!wslab_plan(s.g, slab_w_bytes, &c)) continue;
+        const size_t need = conv_wgrad_slab_bytes(s.g, c);
+        if (s.wslab_bytes >= need) continue;
+        if (!synced && hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+        synced = true;
+        void* p = ws.replace(s.wslab, need);
+        s.wslab = (int32_t*)p;
+        s.wslab_bytes = p ? need : 0;
+        if (!p) return NITI_OUT_OF_MEMORY;
+    }
+    wslab_epoch = plan_override_epoch();
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::wgrad_gemm(int i, const int8_t* x, const int8_t* dy, hipEvent_t after_gemm, hipStream_t st) {
+    GradSlot& s = grads[i];
+    const bool defer = defer_combine() && ensure_wslab(i);
+    // the autotuner times a split plan of the generic GEMM with the combine it will run with in
+    // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
+    // step never makes; the tap-sharing kernel's plans are timed as they were (its slabs keep their
+    // reduce launch where a split has under 4096 elements)
+    const bool tune_defer = tuning && in_step_combine() &&
+                            conv_plan_query(PLAN_WGRAD, s.g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
+    s.defer = SgdJob{};
+    DTRY(conv_wgrad_acc(s.g, x, dy, s.dwacc, dp() ? nullptr : s.amax, defer ? s.wslab : slab_w,
+                        defer ? s.wslab_bytes : slab_w_bytes, st, after_gemm, defer || tune_defer ? &s.defer : nullptr));
+    if (tune_defer && s.defer.slab != nullptr) {
+        SgdJob j = s.defer;
+        j.acc = s.dwacc;
+        j.amax = s.amax;
+        s.defer = SgdJob{};
+        DTRY(sgd_combine_many(&j, 1, st));
+    }
+    return NITI_NO_ERROR;
+}
+
 // ------------------------------------------------------------------------------ data parallel
 void StepDriver::plan_buckets() {
     const int nl = (int)grads.size();

@@ -2,12 +2,16 @@
 // share: the chain driver (LeNet / VGG, niti_model.hip) and ResNet-18 (niti_resnet_model.hip).
 //
 // StepDriver holds the state and the logic both have in the same form -- split-K slabs, the
-// data-parallel gradient buckets, the event probe, the evaluation totals, the device-resident dataset
-// steps, the graph stream and its fences, the teardown -- and declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
+// data-parallel gradient buckets, the range / rescale launch protocol (range_max, rowconv_ranged,
+// gemm_ranged), the GEMM weight gradient with its deferred combine, the event probe, the evaluation
+// totals, the device-resident dataset steps, the graph stream and its fences, the teardown -- and
+// declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
 // driver.  A virtual is called at most once per ABI call; nothing inside a step (run(), forward(),
 // backward(), the per-layer functions) goes through one.  The base does not know which driver it
 // serves: where the two differ, the difference is the derived class's.
 #pragma once
+
+#include <stdlib.h>
 
 #include <algorithm>
 #include <memory>
@@ -24,11 +28,20 @@
 
 namespace niti {
 
-// one parameter layer's weight gradient as the bucket SUMs see it (filled by the driver's build())
+// one parameter layer's weight gradient as the base sees it (filled by the driver's build()): what the
+// bucket SUMs and the GEMM weight gradient (wgrad_gemm) need of it
 struct GradSlot {
     int32_t* dwacc = nullptr;  // int32 gradient, in the contiguous gradient bucket
     int64_t elems = 0;         // w_elems()
     uint32_t* amax = nullptr;  // its range word (rng(layer, 2))
+    ConvGeom g{};              // the layer's conv as it runs
+    // single device: a split-K GEMM weight gradient's own slabs (sized for the current plans at the
+    // head of run(), size_wslabs), and this step's combine deferred to the NITI_SGD launch
+    // (sgd_update_many; slab == null: none -- the chain driver's P16 weight gradients leave theirs
+    // here too)
+    int32_t* wslab = nullptr;
+    size_t wslab_bytes = 0;
+    SgdJob defer{};
 };
 
 struct StepDriver {
@@ -46,6 +59,11 @@ struct StepDriver {
     bool tuning = false;         // autotune in progress: no collectives, no probe
     bool capturing = false;
     bool in_step = false;        // run(): weight gradients may defer their combine to the update launch
+    struct InStep {              // run()'s guard over in_step
+        bool& f;
+        explicit InStep(bool& x) : f(x) { f = true; }
+        ~InStep() { f = false; }
+    };
     // data parallel (niti_coll.hpp, "collectives"): ranges on the step stream through `coll`,
     // gradient-bucket SUMs on the comm stream `cst` through `coll_grad`.  Attached at any world
     // size (a world of 1 runs every collective call site on one GPU).
@@ -70,11 +88,90 @@ struct StepDriver {
     int sum_bucket(int lo, hipStream_t wst);
     void attach(std::unique_ptr<Collective> c, std::unique_ptr<Collective> cg, bool shared, int world_, int rank_,
                 int exact_);
+
+    // ---- the range / rescale launch protocol.  An int8 output needs its whole tensor's range before
+    // it is written, so every conv phase and residual sum of a step takes one of three forms: fused
+    // (one launch, the range through an in-kernel grid barrier: single device, outside a capture,
+    // where the kernel says its grid is resident), the speculative pair (launch A, [MAX], launch B)
+    // or range launch, [MAX], requantise launch.  The choice is made here, once; the callables are
+    // the site's own kernel calls (template parameters: inlined, nothing on the heap).
+    // [MAX]: one range estimate all-reduced over the ranks (exact data parallelism)
+    hipError_t range_max(uint32_t* amax, hipStream_t st) {
+        return dp() && exact ? coll->allreduce(amax, MAX_WORDS, COLL_MAX_U32, st) : hipSuccess;
+    }
+    // A row kernel (niti_rowconv.hip).  fused_ok: the site's rowconv_fused_ok / rowconv_fc_ok; stores:
+    // its two-launch forms keep their accumulators in rc_acc (rowconv_acc_bytes != 0; never the
+    // head); launch(o, mode, bar, epoch, err) is its rowconv_fwd / rowconv_fc call.  The pair runs on
+    // `bar` (its speculation slots); the plain form passes none, which is how the kernels tell them
+    // apart.
+    int32_t* rc_acc = nullptr;  // the row kernels' accumulator store (two-launch store mode)
+    size_t rc_acc_size = 0;
+    template <class Launch>
+    int rowconv_ranged(bool fused_ok, bool stores, RowConvOut& o, uint32_t* amax, uint32_t* bar, uint32_t& epoch,
+                       hipStream_t st, Launch&& launch) {
+        if (!dp() && !capturing && fused_ok) {
+            DTRY(launch(o, 0, bar, ++epoch, rc_err));
+            return NITI_NO_ERROR;
+        }
+        if (stores) o.acc_store = rc_acc;  // (else the second launch recomputes)
+        const bool pair = rowconv_spec2_on();  // one GEMM pass while the bit width holds
+        uint32_t* b = pair ? bar : nullptr;
+        DTRY(launch(o, pair ? RC_SPEC_A : 1, b, 0, nullptr));
+        DTRY(range_max(amax, st));
+        DTRY(launch(o, pair ? RC_SPEC_B : 2, b, 0, nullptr));
+        return NITI_NO_ERROR;
+    }
+    // An implicit GEMM (niti_kernels.hip).  allow_fused: the site's own gate for the fused launch
+    // (plan strategy 4), which may still decline with hipErrorNotSupported -- its barrier epoch
+    // counts only the launches made; spec: the site's conv_*_spec_ok (plan strategy 3).
+    // fused(o, FusedBar), pair(o, 0 | 1) and phase(o, 1 | 2) are the site's conv_* calls.
+    template <class Fused, class Pair, class Phase>
+    int gemm_ranged(bool allow_fused, bool spec, const ActOut& o, uint32_t* amax, uint32_t* bar, uint32_t& epoch,
+                    hipStream_t st, Fused&& fused, Pair&& pair, Phase&& phase) {
+        if (allow_fused) {
+            const hipError_t e = fused(o, FusedBar{bar, epoch + 1, rc_err});
+            if (e != hipErrorNotSupported) {
+                ++epoch;
+                DTRY(e);
+                return NITI_NO_ERROR;
+            }
+        }
+        DTRY(spec ? pair(o, 0) : phase(o, 1));
+        DTRY(range_max(amax, st));
+        DTRY(spec ? pair(o, 1) : phase(o, 2));
+        return NITI_NO_ERROR;
+    }
+
+    // ---- the GEMM-path weight gradient.  Single device, inside run(): a split-K plan leaves its
+    // slabs (the layer's own, GradSlot::wslab) to the NITI_SGD launch's combine, which sums them and
+    // takes the range -- no reduce launch, no int32 round trip (NITI_DIAG_SGD_COMBINE=0: off)
+    static bool sgd_combine_on() {
+        static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
+        return !off;
+    }
+    bool defer_combine() const { return in_step && sgd_combine_on() && !dp() && !capturing && !tuning; }
+    // whether a step of this model defers its combines at all (what the autotuner times against)
+    bool in_step_combine() const { return sgd_combine_on() && !dp(); }
+    // layer i's own slab buffer is big enough for the plan it runs with (false: its plan does not
+    // split K into C-shaped slabs, or the buffer was not sized)
+    bool ensure_wslab(int i) const;
+    // size every layer's slab buffer for the current plans: at the head of run(), before anything is
+    // enqueued, whenever a plan override changed since the last sizing (one device sync, the old
+    // buffer freed) -- no allocation or sync inside the step
+    int size_wslabs();
+    unsigned wslab_epoch = 0;  // plan_override_epoch() the slabs were last sized for
+    // conv_wgrad_acc of layer i over its input and output gradient (after_gemm: recorded right
+    // behind the GEMM launch), its combine deferred where defer_combine() holds and the slabs fit
+    int wgrad_gemm(int i, const int8_t* x, const int8_t* dy, hipEvent_t after_gemm, hipStream_t st);
+
     // kernel probe: HIP events around one layer phase (0 fwd / 1 dgrad / 2 wgrad), up to ev0.size()
     // launches; where the events go is the driver's
     int probe_layer = -1, probe_phase = -1, probe_count = 0;
     std::vector<hipEvent_t> ev0, ev1;
     bool probe_paused = false;  // niti_model_probe_pause: the armed probe skips these launches
+    bool probe_armed(int layer, int phase) const {
+        return layer == probe_layer && phase == probe_phase && !probe_paused && !tuning && !capturing;
+    }
     virtual void clear_probe();
     int set_probe(int layer, int phase, int max_launches);
     int probe_read(double* total_ms, int* count);
