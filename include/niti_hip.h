@@ -446,6 +446,48 @@ typedef struct niti_sgd_combine_job {
     uint32_t* amax;
 } niti_sgd_combine_job;
 int niti_sgd_combine(const niti_sgd_combine_job* jobs, int n_jobs, void* stream);
+/* Several layers' NITI_SGD steps in one launch (the training step's update launch; at most 24 jobs):
+ * per job niti_sgd_update_wf's arguments.  A workgroup walks tiles of consecutive jobs, each job
+ * with its own range and rule. */
+typedef struct niti_sgd_job {
+    const int32_t* acc;
+    const uint32_t* amax;
+    int rule, co, ci, kk, cip, cop;
+    int8_t* w_ohwi16;
+    int8_t* wt_ihwo16;
+    int8_t* g_out;
+    int8_t* wf;
+    int8_t* wft;
+} niti_sgd_job;
+int niti_sgd_update_many(const niti_sgd_job* jobs, int n_jobs, void* stream);
+/* The training step's first layer, alone.  niti_input_im2col: the batch (uint8 images quantised
+ * with stats = niti_image_stats' four words over `count` pixels when quant, else int8 pixels as
+ * they are) into xcol [n * oh * ow][32], the K = 32 im2col copy (stride 1; c / kh / kw = 3/3/3 or
+ * 1/5/5), x_nchw (may be NULL) the int8 input, *ascale its exponent (quant only); with w0 (the
+ * first conv's weights [co0][32], cop0 = 32 or 64) its range max|y| goes into amax0 as well.
+ * niti_conv0_fwd: that conv on xcol (g: 1x1, c_in 32, n / h / w the output's, w % 32 == 0, h even,
+ * c_out rounded up to 16 a multiple of 32, else NITI_NOT_SUPPORT): pass 0 the range into amax, pass 1 requantise with
+ * it (+ relu) into out (NHWC, may be NULL with pool_out and pool_code) and, with pool_out, the 2x2
+ * max pool, its gradient route pool_code and the row kernels' C32 copies (all optional).
+ * niti_diag_conv0_blocks: the workgroups of niti_conv0_fwd's launch (0: the default; results do
+ * not depend on it). */
+int niti_input_im2col(const void* in, int quant, int n, int c, int h, int w, int kh, int kw, int pad_t, int pad_l,
+                      const uint64_t* stats, int64_t count, int8_t* x_nchw, int8_t* xcol, int8_t* ascale,
+                      const int8_t* w0, int co0, int cop0, uint32_t* amax0, void* stream);
+typedef struct niti_conv0_out {
+    int8_t* out;
+    int8_t* pool_out;
+    int8_t* pool_code;
+    int8_t* pool_c32;
+    int8_t* out_c32;
+    const int8_t* exp_in;
+    const int8_t* wscale;
+    int8_t* exp_out;
+    int relu;
+} niti_conv0_out;
+int niti_conv0_fwd(const niti_geom* g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const niti_conv0_out* o,
+                   int pass, void* stream);
+void niti_diag_conv0_blocks(int n);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);

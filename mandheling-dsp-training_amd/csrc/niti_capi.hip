@@ -657,6 +657,56 @@ int niti_sgd_combine(const niti_sgd_combine_job* jobs, int n_jobs, void* stream)
     return code(niti::sgd_combine_many(r, n_jobs, S(stream)));
 }
 
+int niti_sgd_update_many(const niti_sgd_job* jobs, int n_jobs, void* stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > niti::SGD_MAX_JOBS) return NITI_INVALID_VALUE;
+    niti::SgdJob r[niti::SGD_MAX_JOBS];
+    for (int j = 0; j < n_jobs; ++j) {
+        const niti_sgd_job& s = jobs[j];
+        if (!s.acc || !s.amax || !s.w_ohwi16 || (s.rule != 2 && s.rule != 3)) return NITI_INVALID_VALUE;
+        if (s.co < 1 || s.ci < 1 || s.kk < 1 || s.cip < s.ci || s.cop < s.co || s.cip % 16 || s.cop % 16)
+            return NITI_INVALID_VALUE;
+        if ((s.wf || s.wft) && (s.kk != 9 || s.ci % 32 != 0 || s.co % 32 != 0)) return NITI_NOT_SUPPORT;
+        r[j] = niti::SgdJob{s.acc, s.amax, s.rule, s.co, s.ci, s.kk, s.cip, s.cop, s.w_ohwi16, s.wt_ihwo16, s.g_out};
+        r[j].wf = s.wf;
+        r[j].wft = s.wft;
+    }
+    return code(niti::sgd_update_many(r, n_jobs, S(stream)));
+}
+
+int niti_input_im2col(const void* in, int quant, int n, int c, int h, int w, int kh, int kw, int pad_t, int pad_l,
+                      const uint64_t* stats, int64_t count, int8_t* x_nchw, int8_t* xcol, int8_t* ascale,
+                      const int8_t* w0, int co0, int cop0, uint32_t* amax0, void* stream) {
+    if (!in || !xcol || n <= 0 || h <= 0 || w <= 0 || pad_t < 0 || pad_l < 0) return NITI_INVALID_VALUE;
+    if (!niti::input_im2col_ok(c, kh, kw)) return NITI_NOT_SUPPORT;
+    if (quant && (!stats || count <= 0)) return NITI_INVALID_VALUE;
+    niti::Conv0Range r0;
+    if (w0 != nullptr) {
+        r0.w = w0;
+        r0.co = co0;
+        r0.cop = cop0;
+        r0.amax = amax0;
+    }
+    return code(niti::input_im2col(in, quant != 0, n, c, h, w, kh, kw, pad_t, pad_l,
+                                   (const unsigned long long*)stats, quant ? 1 : 0, count, x_nchw, xcol, ascale,
+                                   S(stream), r0));
+}
+
+int niti_conv0_fwd(const niti_geom* g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const niti_conv0_out* o,
+                   int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!g || !xcol || !w || !amax || !o || pass < 0 || pass > 1 || !to_geom(g, &r)) return NITI_INVALID_VALUE;
+    if (!niti::conv0_ok(r)) return NITI_NOT_SUPPORT;
+    niti::ActOut a;
+    a.out = o->out;
+    a.relu = o->relu;
+    a.exp_in = o->exp_in;
+    a.wscale = o->wscale;
+    a.exp_out = o->exp_out;
+    a.pool.pool_out = o->pool_out;
+    return code(niti::conv0_fwd(r, xcol, w, amax, a, pass, S(stream), o->pool_c32, o->out_c32, o->pool_code));
+}
+void niti_diag_conv0_blocks(int n) { niti::diag_conv0_blocks(n); }
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

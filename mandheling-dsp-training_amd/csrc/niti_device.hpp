@@ -26,6 +26,12 @@ __device__ __forceinline__ v4i buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t off
     return __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
 }
 
+// (an offset at or past the resource's size stores nothing)
+__device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t r, uint32_t off, v4i v) {
+    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)off, 0, 0);
+}
+
 // multiply-shift division for 0 <= n < 2^31 (Granlund-Montgomery, round-up variant)
 struct FastDiv {
     uint32_t m = 1, s = 0, d = 1;

@@ -278,6 +278,7 @@ bool conv0_ok(const ConvGeom& g);
 hipError_t conv0_fwd(const ConvGeom& g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const ActOut& o,
                      int pass, hipStream_t st,
                      int8_t* pool_c32 = nullptr, int8_t* out_c32 = nullptr, int8_t* pool_code = nullptr);
+void diag_conv0_blocks(int n);  // conv0_fwd's grid (0: its default), diagnostic
 bool conv_dgrad_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // The speculative pair on the implicit GEMM (plan strategy 3 = STRAT_SPEC, forward / input
 // gradient, no K split; NITI_Conv_Int8.cpp:260-307, NITI_DeConv_Int8.cpp:294-329): pass 0 (launch A)

@@ -76,7 +76,11 @@ __device__ __forceinline__ void sgd_tile_load(const SgdJob& J, int ci0, int co0,
 __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0, int co0, int k, const SgdTileIn& in,
                                                 int8_t (*T)[64 + 4]) {
     const int t = threadIdx.x;
-    const int sh = bw - J.rule;
+    // the rule's class is the tile's (bw and rule are per job): chosen once, wave-uniformly, each
+    // class a straight-line body over the 16 elements -- a zero gradient (bw == 0), psto_fast
+    // (0 <= sh <= 30), psto_generic (its divisions only where a shift needs them)
+    const int ubw = __builtin_amdgcn_readfirstlane(bw);
+    const int sh = ubw - __builtin_amdgcn_readfirstlane(J.rule);
     {
         const int r = t >> 2, c = (t & 3) * 16;
         v16c wn;
@@ -85,11 +89,15 @@ __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0
         if (co0 + r < J.co && ci0 + c < J.cip) {
             const int64_t idx = ((int64_t)(co0 + r) * J.kk + k) * J.cip + ci0 + c;
             v16c g;
+            if (ubw == 0) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4i v = in.a[q];
+                for (int j = 0; j < 16; ++j) g[j] = 0;
+            } else if (sh >= 0 && sh <= 30) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) g[q * 4 + e] = (signed char)(bw == 0 ? 0 : psto_any(v[e], sh));
+                for (int j = 0; j < 16; ++j) g[j] = (signed char)psto_fast(in.a[j >> 2][j & 3], sh);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) g[j] = (signed char)psto_generic(in.a[j >> 2][j & 3], sh);
             }
 #pragma unroll
             for (int j = 0; j < 16; ++j) wn[j] = (signed char)clip127((int32_t)in.w[j] - (int32_t)g[j]);

@@ -89,6 +89,19 @@ class SgdCombineJob(C.Structure):
                 ("acc", C.c_void_p), ("amax", C.c_void_p)]
 
 
+class SgdJob(C.Structure):
+    """niti_sgd_job: one layer's update of niti_sgd_update_many."""
+    _fields_ = ([("acc", C.c_void_p), ("amax", C.c_void_p)] +
+                [(n, C.c_int) for n in ("rule", "co", "ci", "kk", "cip", "cop")] +
+                [(n, C.c_void_p) for n in ("w_ohwi16", "wt_ihwo16", "g_out", "wf", "wft")])
+
+
+class Conv0Out(C.Structure):
+    """niti_conv0_out: the outputs and options of niti_conv0_fwd."""
+    _fields_ = ([(n, C.c_void_p) for n in ("out", "pool_out", "pool_code", "pool_c32", "out_c32", "exp_in",
+                                           "wscale", "exp_out")] + [("relu", C.c_int)])
+
+
 class ChainLayer(C.Structure):
     """niti_chain_layer: one layer of a user-defined chain network."""
     _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten")]
@@ -182,6 +195,10 @@ def lib():
         "niti_requant_grad": (ci, [vp, i64, vp, ci, vp, vp, vp]),
         "niti_sgd_update": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "niti_sgd_combine": (ci, [C.POINTER(SgdCombineJob), ci, vp]),
+        "niti_sgd_update_many": (ci, [C.POINTER(SgdJob), ci, vp]),
+        "niti_input_im2col": (ci, [vp] + [ci] * 9 + [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp]),
+        "niti_conv0_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(Conv0Out), ci, vp]),
+        "niti_diag_conv0_blocks": (None, [C.c_int]),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),

@@ -509,6 +509,57 @@ def sgd_combine(jobs, stream=None):
     check(L.lib().niti_sgd_combine(arr, len(jobs), _stream(stream)), "sgd_combine")
 
 
+def sgd_update_many(jobs, stream=None):
+    """Several layers' updates in one launch (niti_sgd_update_many).  jobs: dicts of sgd_update's
+    arguments -- acc, amax, w16, ci, rule and the optional wT / g / wf / wft, every buffer the
+    caller's and written in place."""
+    arr = (L.SgdJob * len(jobs))()
+    for j, job in enumerate(jobs):
+        acc, w16 = job["acc"], job["w16"]
+        co, kh, kw, cip = acc.shape
+        assert acc.dtype == torch.int32 and w16.shape == acc.shape and acc.is_contiguous() and w16.is_contiguous()
+        arr[j].acc, arr[j].amax = acc.data_ptr(), job["amax"].data_ptr()
+        arr[j].rule, arr[j].co, arr[j].ci, arr[j].kk = job.get("rule", 2), co, job["ci"], kh * kw
+        arr[j].cip, arr[j].cop = cip, r16(co)
+        arr[j].w_ohwi16 = w16.data_ptr()
+        for name, key in (("wt_ihwo16", "wT"), ("g_out", "g"), ("wf", "wf"), ("wft", "wft")):
+            t = job.get(key)
+            setattr(arr[j], name, None if t is None else t.data_ptr())
+    check(L.lib().niti_sgd_update_many(arr, len(jobs), _stream(stream)), "sgd_update_many")
+
+
+def input_im2col(x, kernel, pad, stats=None, count=None, w0=None, co0=0, amax0=None, stream=None):
+    """The first layer's im2col copy straight from the batch (niti_input_im2col): x uint8 images
+    (quantised with `stats`, image_stats' words over `count` pixels) or int8 pixels, NCHW ->
+    (xcol int8 [n * oh * ow][32], x int8 NCHW, ascale int8 [1]).  With w0 (the first conv's weights
+    [cop0][32], co0 of them real) the conv's range goes into amax0."""
+    assert x.dim() == 4 and x.is_contiguous() and x.dtype in (torch.uint8, torch.int8)
+    quant = x.dtype == torch.uint8
+    assert not quant or stats is not None
+    n, c, h, w = x.shape
+    oh, ow = h + 2 * pad - kernel + 1, w + 2 * pad - kernel + 1
+    xcol = torch.empty((n * oh * ow, 32), dtype=torch.int8, device=x.device)
+    x8 = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    ascale = torch.zeros(1, dtype=torch.int8, device=x.device)
+    check(L.lib().niti_input_im2col(_ptr(x), 1 if quant else 0, n, c, h, w, kernel, kernel, pad, pad, _ptr(stats),
+                                    int(count or x.numel()), _ptr(x8), _ptr(xcol), _ptr(ascale), _ptr(w0), co0,
+                                    0 if w0 is None else w0.shape[0], _ptr(amax0), _stream(stream)), "input_im2col")
+    return xcol, x8, ascale
+
+
+def conv0_fwd(g, xcol, w, amax, pass_, *, out=None, pool_out=None, pool_code=None, pool_c32=None, out_c32=None,
+              exp_in=None, wscale=None, exp_out=None, relu=False, stream=None):
+    """The first layer's K = 32 conv on its im2col copy (niti_conv0_fwd): pass 0 the range into amax,
+    pass 1 the requantised output (and pool) into the caller's buffers.  g: geom(n, 32, oh, ow, c_out, 1)."""
+    o = L.Conv0Out()
+    for name, t in (("out", out), ("pool_out", pool_out), ("pool_code", pool_code), ("pool_c32", pool_c32),
+                    ("out_c32", out_c32), ("exp_in", exp_in), ("wscale", wscale), ("exp_out", exp_out)):
+        setattr(o, name, None if t is None else t.data_ptr())
+    o.relu = 1 if relu else 0
+    check(L.lib().niti_conv0_fwd(C.byref(g), _ptr(xcol), _ptr(w), _ptr(amax), C.byref(o), pass_, _stream(stream)),
+          "conv0_fwd")
+
+
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
     """Exponent-aligned int32 sum of two int8 tensors (niti_resnet.hip) -> (z int32, ez int8 [1])."""
     assert a.shape == b.shape and a.dtype == b.dtype == torch.int8
