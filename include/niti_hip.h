@@ -370,6 +370,19 @@ void niti_diag_wgrad_batch(int mode);
 /* diagnostics: batched weight-gradient launches of this process, captured ones counted once (a
  * graph replay launches without this library) */
 unsigned long long niti_diag_wgrad_batch_launches(void);
+/* Quad items of that launch: an unsplit job of 2x2 / 4x4 maps whose whole K range is at most kg K
+ * groups runs four consecutive tiles per item, one per wave, with no cross-wave sum.  Process-wide:
+ * -1 (default) the caller's own threshold (the model's autotuned choice; 32 for
+ * niti_conv_wgrad_p16_many), 0 no quad items, kg > 0 that threshold.  Results identical either way. */
+void niti_diag_wgrad_quad(int kg);
+/* The schedule niti_conv_wgrad_p16_many(jobs, n, blocks, t) would run, copied out without any device
+ * call (the jobs' pointers only have to be non-null).  items8: 8 ints per item {job, first tile,
+ * tiles of a quad item (0: the merged form, one tile), slab (-1: unsplit), kg_begin, kg_end,
+ * kg_per_wave, form (0 merged, 1 quad)}; starts: blocks + 1 list starts (workgroup b runs the items
+ * [starts[b], starts[b + 1])).  cap_items / cap_starts: the room, in items and in ints; too little is
+ * NITI_INVALID_VALUE. */
+int niti_conv_wgrad_p16_many_items(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, int* items8,
+                                   int cap_items, int* starts, int cap_starts, int* n_items);
 /* acc[m][ldc] = sum_k B[m][k] A[o][k] (columns o..ldc = 0); K zero padded to k16; ldb/lda bytes */
 int niti_matmul_acc(int m, int o, int k16, const int8_t* B, int64_t ldb, const int8_t* A, int64_t lda,
                     int32_t* acc, int64_t ldc, uint32_t* amax, void* workspace, size_t workspace_bytes,

@@ -515,7 +515,8 @@ static int p16_many_jobs(const niti_wgrad_p16_job* jobs, int n, int blocks, int 
             o.slab = (int32_t*)(ws + off);  // (pass 0: only its being non-null counts)
             off += o.slab_bytes;
         }
-        if (niti::conv_wgrad_p16_many_build(out, n, blocks, t, m) != hipSuccess) return NITI_INVALID_VALUE;
+        if (niti::conv_wgrad_p16_many_build(out, n, blocks, t, niti::wgrad_quad_kg(niti::P16_QUAD_KG), m) != hipSuccess)
+            return NITI_INVALID_VALUE;
         *bytes = off;
         if (pass == 0) *table_room = (m->table_bytes + 4095) / 4096 * 4096;
     }
@@ -552,7 +553,23 @@ int niti_conv_wgrad_p16_many(const niti_wgrad_p16_job* jobs, int n, int blocks, 
     return code(e);
 }
 
+// the schedule niti_conv_wgrad_p16_many would run, copied out; no device call (the jobs' pointers
+// only have to be non-null)
+int niti_conv_wgrad_p16_many_items(const niti_wgrad_p16_job* jobs, int n, int blocks, int t, int* items8,
+                                   int cap_items, int* starts, int cap_starts, int* n_items) {
+    if (!items8 || !starts || !n_items || cap_items < 0 || cap_starts < 0) return NITI_INVALID_VALUE;
+    niti::WgP16Job r[niti::P16_MANY_MAX_JOBS];
+    niti::WgP16Many m;
+    size_t room = 4096, need = 0;
+    if (const int rc = p16_many_jobs(jobs, n, blocks, t, (unsigned char*)(uintptr_t)4096, r, &m, &room, &need)) return rc;
+    const int k = niti::conv_wgrad_p16_many_items(m, items8, cap_items, starts, cap_starts);
+    if (k < 0) return NITI_INVALID_VALUE;
+    *n_items = k;
+    return NITI_NO_ERROR;
+}
+
 void niti_diag_wgrad_batch(int mode) { niti::model_wgrad_batch(mode); }
+void niti_diag_wgrad_quad(int kg) { niti::model_wgrad_quad(kg); }
 unsigned long long niti_diag_wgrad_batch_launches(void) { return niti::conv_wgrad_p16_many_launches(); }
 
 int niti_matmul_acc(int m, int o, int k16, const int8_t* B, int64_t ldb, const int8_t* A, int64_t lda, int32_t* acc,

@@ -202,6 +202,7 @@ struct WgP16Many {
     int splits[P16_MANY_MAX_JOBS] = {};
     int64_t slab_stride[P16_MANY_MAX_JOBS] = {};
     int max_list_kg = 0;  // K groups of the longest list (diagnostics)
+    int n_quads = 0;      // items of the quad form
     WgP16Many() = default;
     WgP16Many(const WgP16Many&) = delete;
     WgP16Many& operator=(const WgP16Many&) = delete;
@@ -209,11 +210,18 @@ struct WgP16Many {
         free(table);
         table = nullptr;
         table_bytes = 0;
-        n_jobs = n_items = blocks = 0;
+        n_jobs = n_items = blocks = n_quads = 0;
     }
     ~WgP16Many() { clear(); }
 };
-hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, WgP16Many* out);
+// quad_kg: an unsplit 2x2 / 4x4-map job of at most that many K groups runs as quad items -- four
+// consecutive tiles per item, one per wave, no cross-wave sum (0: none)
+constexpr int P16_QUAD_KG = 32;  // the default threshold: VGG-11's 2x2 layers at batch 256
+hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, int quad_kg, WgP16Many* out);
+// the built schedule copied out (no device call): 8 ints per item {job, first tile, tiles of a quad
+// item (0: the merged form), slab, kg_begin, kg_end, kg_per_wave, form} and the blocks + 1 list
+// starts; returns the item count, -1 where the room is too small
+int conv_wgrad_p16_many_items(const WgP16Many& m, int* items8, int cap_items, int* starts, int cap_starts);
 // the launch over `table_dev`, a device copy of m.table
 hipError_t conv_wgrad_p16_many(const WgP16Many& m, const void* table_dev, hipStream_t st);
 unsigned long long conv_wgrad_p16_many_launches();  // of this process (diagnostics)
@@ -433,6 +441,8 @@ void rowconv_speculate(int mode);
 uint32_t* rowconv_spec_slot(uint32_t* bar, bool dg);
 void model_p16_jobs_cap(int cap);  // niti_model.hip, diagnostic
 void model_wgrad_batch(int mode);   // niti_model.hip: niti_diag_wgrad_batch
+void model_wgrad_quad(int kg);      // niti_diag_wgrad_quad
+int wgrad_quad_kg(int own);         // the forced threshold, or `own` where none is forced
 hipError_t rowconv_fwd(const ConvGeom& g, const int8_t* x_c32, const int8_t* wf, const RowConvOut& o, int mode,
                        uint32_t* amax, uint32_t* bar, uint32_t epoch, uint32_t* err, hipStream_t st);
 // A 1x1 layer over 1x1 maps (the classifier head) on the same kernel: rows output channels of

@@ -33,9 +33,12 @@ namespace niti {
 namespace {
 extern int g_p16_jobs_cap;
 extern int g_wgrad_batch;
+extern int g_wgrad_quad;
 }
 void model_p16_jobs_cap(int cap) { g_p16_jobs_cap = cap <= 0 ? P16_MAX_JOBS : cap; }
 void model_wgrad_batch(int mode) { g_wgrad_batch = mode < 0 ? 1 : mode; }
+void model_wgrad_quad(int kg) { g_wgrad_quad = kg < 0 ? -1 : kg; }
+int wgrad_quad_kg(int own) { return g_wgrad_quad >= 0 ? g_wgrad_quad : own; }
 
 namespace {
 
@@ -93,6 +96,10 @@ int g_p16_jobs_cap = P16_MAX_JOBS;
 // NITI_WGRAD_BATCH sets the process's starting mode
 int g_wgrad_batch = getenv("NITI_WGRAD_BATCH") != nullptr ? std::max(0, atoi(getenv("NITI_WGRAD_BATCH"))) : 1;
 constexpr int WGRAD_BATCH_T = 256;
+// the batch's quad threshold (niti_diag_wgrad_quad): -1 the schedule owner's own (the model's
+// wgb_quad, the op entry's P16_QUAD_KG), 0 no quad items, k > 0 that many K groups; NITI_WGRAD_QUAD
+// sets the process's starting value
+int g_wgrad_quad = getenv("NITI_WGRAD_QUAD") != nullptr ? std::max(-1, atoi(getenv("NITI_WGRAD_QUAD"))) : -1;
 
 static hipError_t im2col32(const ConvGeom& o, const int8_t* x16, int8_t* out, hipStream_t st) {
     const int64_t px = (int64_t)o.n * o.oh * o.ow;
@@ -467,23 +474,26 @@ struct Model final : StepDriver {
     // weight-gradient probe joins; the schedule and its device table are rebuilt outside the step
     // (and outside a capture) when a plan, the item size or the probe changes.
     int wgb_tuned = WGRAD_BATCH_T;  // the model's item size (K groups), 0: the autotuner turned the batch off
+    int wgb_quad = P16_QUAD_KG;     // the model's quad threshold (K groups), 0: the autotuner turned quads off
     WgP16Many wgb;
     std::vector<int> wgb_layers;    // the layers of wgb's jobs, in job order (empty: no batch)
     void* wgb_dev = nullptr;
     size_t wgb_dev_bytes = 0;
     unsigned wgb_epoch = 0;
-    int wgb_t = -1, wgb_probe = -2;
+    int wgb_t = -1, wgb_q = -1, wgb_probe = -2;
     int wgrad_batch_t() const {
         if (dp() || g_wgrad_batch == 0) return 0;
         return g_wgrad_batch == 1 ? wgb_tuned : g_wgrad_batch;
     }
-    int build_wgrad_batch(int t) {
+    int build_wgrad_batch(int t) { return build_wgrad_batch(t, wgrad_quad_kg(wgb_quad)); }
+    int build_wgrad_batch(int t, int q) {
         const int pl = probe_phase == 2 ? probe_layer : -1;
-        if (wgb_t == t && wgb_probe == pl && wgb_epoch == plan_override_epoch()) return NITI_NO_ERROR;
+        if (wgb_t == t && wgb_q == q && wgb_probe == pl && wgb_epoch == plan_override_epoch()) return NITI_NO_ERROR;
         drop_graph();  // (a captured step launched the old schedule)
         wgb.clear();
         wgb_layers.clear();
         wgb_t = t;
+        wgb_q = q;
         wgb_probe = pl;
         wgb_epoch = plan_override_epoch();
         if (t <= 0) return NITI_NO_ERROR;
@@ -508,7 +518,7 @@ struct Model final : StepDriver {
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
             return NITI_NO_EXECUTION;
-        if (conv_wgrad_p16_many_build(jobs, (int)layers.size(), cus, t, &wgb) != hipSuccess) return NITI_NO_EXECUTION;
+        if (conv_wgrad_p16_many_build(jobs, (int)layers.size(), cus, t, q, &wgb) != hipSuccess) return NITI_NO_EXECUTION;
         // (the previous table may still be read by a step in flight)
         if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
         if (wgb.table_bytes > wgb_dev_bytes) {
@@ -1366,7 +1376,10 @@ int Model::autotune(hipStream_t st, int reps) {
 
 // The P16 weight gradients as a set, with the per-layer plans settled: the per-layer sequence and
 // the one-launch batch at three item sizes, each with the combine of its slabs (the launch the
-// update does first).  The fastest stays as the model's choice (wgb_tuned; 0: per layer).
+// update does first).  The fastest stays as the model's choice (wgb_tuned; 0: per layer).  The item
+// sizes are timed with the merged form only; the winner is then timed with its short-K layers as
+// quad items (P16_QUAD_KG), and the faster of the two stays (wgb_quad; 0: no quads).  A quad
+// threshold forced through niti_diag_wgrad_quad is used as it is.
 int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
     if (dp() || g_wgrad_batch == 0) return NITI_NO_ERROR;
     std::vector<int> set;
@@ -1417,9 +1430,11 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
     int best_t = 0;
     int rc = timer.time(per_layer, &best_us);
     if (log) fprintf(stderr, "tune wgrad set: per layer %.2f us\n", best_us);
+    const int q_forced = wgrad_quad_kg(-1);
+    const int q_base = q_forced >= 0 ? q_forced : 0;
     for (int t : {128, 256, 512}) {
         if (rc != NITI_NO_ERROR) break;
-        rc = build_wgrad_batch(t);
+        rc = build_wgrad_batch(t, q_base);
         if (rc != NITI_NO_ERROR || wgb_layers.empty()) break;
         float us = 0.f;
         rc = timer.time(batched, &us);
@@ -1431,8 +1446,26 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
             best_t = t;
         }
     }
-    if (rc == NITI_NO_ERROR) wgb_tuned = best_t;
-    if (log) fprintf(stderr, "tune wgrad set: keeps %d\n", wgb_tuned);
+    int best_q = 0;
+    if (rc == NITI_NO_ERROR && best_t > 0 && q_forced < 0) {
+        rc = build_wgrad_batch(best_t, P16_QUAD_KG);
+        if (rc == NITI_NO_ERROR && wgb.n_quads > 0) {
+            float us = 0.f;
+            rc = timer.time(batched, &us);
+            if (log)
+                fprintf(stderr, "tune wgrad set: batch t %d quad %d (%d items, %d quads) %.2f us against %.2f us\n", best_t,
+                        P16_QUAD_KG, wgb.n_items, wgb.n_quads, us, best_us);
+            if (rc == NITI_NO_ERROR && us < best_us) {
+                best_us = us;
+                best_q = P16_QUAD_KG;
+            }
+        }
+    }
+    if (rc == NITI_NO_ERROR) {
+        wgb_tuned = best_t;
+        if (q_forced < 0) wgb_quad = best_q;
+    }
+    if (log) fprintf(stderr, "tune wgrad set: keeps %d, quad %d\n", wgb_tuned, wgrad_quad_kg(wgb_quad));
     return rc;
 }
 

@@ -216,9 +216,14 @@ constexpr int P16_SMEM = (NITI_WG_MERGE ? 4 * P16_TILE * 4 : P16_TILE * 4) + 64;
 // to C and its block max into amax; else a partial tile into slab `slab`.  The per-layer kernel
 // runs one item per block, wgrad_p16_many_kernel a list of them; the caller synchronises the
 // block before the next item touches lds4 again.
-template <int OW, int NW, int D>
+//
+// QUAD (wgrad_p16_many_kernel, short-K unsplit layers): the item is quad_n <= NW consecutive tiles
+// from `tile` on, one per wave, each wave running the whole K range [kg_begin, kg_end) of its own
+// tile -- no cross-wave sum.  A wave beyond quad_n runs as a wave without K groups does: dy pushed
+// out of range, no stores, no contribution to the range.
+template <int OW, int NW, int D, bool QUAD = false>
 __device__ __forceinline__ void wgrad_p16_item(const WgP16& g, int tile, int slab, int kg_begin, int kg_end,
-                                               int kg_per_wave, v4i* lds4) {
+                                               int kg_per_wave, v4i* lds4, int quad_n = 0) {
     static_assert(D >= 2 && D % 2 == 0, "the next K group's window must be resident; operand buffers alternate");
     // the block's tile, row-major [co 32][tap 9][ci 32] int32 (every wave adds its partial into it),
     // plus the block-max scratch
@@ -232,12 +237,13 @@ __device__ __forceinline__ void wgrad_p16_item(const WgP16& g, int tile, int sla
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     WG_STAMP(0);
     WG_WSTAMP(0);
+    if constexpr (QUAD) tile += wid;  // (a wave beyond quad_n: any tile, it only reads)
     const int tco = (int)fdiv(g.fTci, (uint32_t)tile), tci = tile - tco * g.tiles_ci;
     const int co0 = tco * 32, ci0 = tci * 32;
     // the wave's K groups: a contiguous run [kb, kb + n_w) of the item's range, whole images
-    // (the range and kg_per_wave are multiples of the K groups per image)
-    const int kb = kg_begin + wid * kg_per_wave;
-    const int n_w = max(0, min(kg_end, kb + kg_per_wave) - kb);
+    // (the range and kg_per_wave are multiples of the K groups per image); QUAD: the whole range
+    const int kb = QUAD ? kg_begin : kg_begin + wid * kg_per_wave;
+    const int n_w = QUAD ? (wid < quad_n ? kg_end - kg_begin : 0) : max(0, min(kg_end, kb + kg_per_wave) - kb);
 
     const __amdgpu_buffer_rsrc_t rX = make_rsrc(g.x, g.xbytes);
     const __amdgpu_buffer_rsrc_t rD = make_rsrc(g.dy, g.dybytes);
@@ -390,7 +396,49 @@ __device__ __forceinline__ void wgrad_p16_item(const WgP16& g, int tile, int sla
     int32_t* dst = partial ? g.slab + (int64_t)slab * g.slab_stride : g.C;
     uint32_t lmax = 0;
     uint32_t* red = (uint32_t*)(smem + SMEM - 64);
-    if constexpr (NITI_WG_MERGE) {
+    if constexpr (QUAD) {
+        // The wave's tile is whole: nothing to sum.  Stores straight from the accumulator layout
+        // cover 32 bytes per row per instruction (round 2: output 9.5k cycles against 2.9k), so the
+        // wave turns its tile through its own quarter of the merge buffer -- the slots
+        // [wid][q][tap] and the swizzle of the merged form below -- and reads it back in four
+        // passes of 8 rows (co = 8 p + r), each the merged form's 9 ds_read_b128 and 9 stores of
+        // 8 rows x 128 bytes.  Only this wave touches its quarter and a wave's LDS accesses
+        // execute in order, so no workgroup barrier: a wave-scope fence keeps the compiler's order.
+        static_assert(NITI_WG_MERGE && NITI_WG_SWAP && NW == 4, "the transposed tile's slots, a quarter per wave");
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+                lds4[((wid * 4 + q) * 9 + t) * 64 + (lane ^ (2 * q + (lane >> 5) + 8 * (q & 1)))] =
+                    v4i{acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        WG_STAMP(3);
+        WG_STAMP(4);
+        const int r = lane >> 3, c = lane & 7, q = c >> 1;
+        const bool live = wid < quad_n;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int co = 8 * p + r;
+            const int pos = (co + 32 * (c & 1)) ^ (c + 8 * ((c >> 1) & 1));
+            v4i sum[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) sum[t] = lds4[((wid * 4 + q) * 9 + t) * 64 + pos];
+            if (live && co0 + co < g.c_out && NITI_WG_ABLATE != 5) {
+                int32_t* o = dst + (int64_t)(co0 + co) * g.ldc + ci0 + 4 * c;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    __builtin_nontemporal_store(sum[t], (v4i*)(o + t * g.CIP));
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t u = uabs32(sum[t][j]);
+                        lmax = lmax > u ? lmax : u;
+                    }
+                }
+            }
+        }
+    } else if constexpr (NITI_WG_MERGE) {
         static_assert(NW == 4, "one accumulator row quarter per wave");
         if constexpr (NITI_WG_SWAP) {
             // The tile is C^T: lane (co = lane & 31, h = lane >> 5) holds, in accumulator registers
@@ -565,9 +613,13 @@ struct WgP16Desc {
     WgP16 g;
     int ow, pad;
 };
+// quad > 0: the quad form -- `quad` (1..4) consecutive tiles from `tile` on, one per wave, each over
+// the whole range [kg_begin, kg_end) (slab -1: quads are cut from unsplit layers only)
 struct WgP16Item {
-    int job, tile, slab, kg_begin, kg_end, kg_per_wave, pad0, pad1;
+    int job, tile, slab, kg_begin, kg_end, kg_per_wave, quad, pad1;
 };
+// the quad form needs the transposed tile's LDS slots (diagnostic builds may turn them off)
+constexpr bool P16_QUAD_OK = NITI_WG_MERGE && NITI_WG_SWAP;
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) wgrad_p16_many_kernel(const WgP16Desc* __restrict__ descs,
                                                                   const int* __restrict__ starts,
@@ -581,8 +633,20 @@ __global__ void __launch_bounds__(NW * 64) wgrad_p16_many_kernel(const WgP16Desc
         const int kg_begin = __builtin_amdgcn_readfirstlane(items[i].kg_begin);
         const int kg_end = __builtin_amdgcn_readfirstlane(items[i].kg_end);
         const int kpw = __builtin_amdgcn_readfirstlane(items[i].kg_per_wave);
+        const int quad = __builtin_amdgcn_readfirstlane(items[i].quad);
         const WgP16 g = descs[job].g;
-        switch (__builtin_amdgcn_readfirstlane(descs[job].ow)) {
+        const int ow = __builtin_amdgcn_readfirstlane(descs[job].ow);
+        if constexpr (P16_QUAD_OK) {
+            if (quad > 0) {  // (the schedule cuts quads from 2x2 / 4x4 layers only: short K is small maps)
+                if (ow == 4)
+                    wgrad_p16_item<4, NW, NITI_WG_D4, true>(g, tile, -1, kg_begin, kg_end, kpw, lds4, quad);
+                else
+                    wgrad_p16_item<2, NW, NITI_WG_D4, true>(g, tile, -1, kg_begin, kg_end, kpw, lds4, quad);
+                __syncthreads();  // (the next item may be of the merged form: all four quarters)
+                continue;
+            }
+        }
+        switch (ow) {
             case 8: wgrad_p16_item<8, NW, NITI_WG_D8>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
             case 16: wgrad_p16_item<16, NW, 8>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
             case 4: wgrad_p16_item<4, NW, NITI_WG_D4>(g, tile, slab, kg_begin, kg_end, kpw, lds4); break;
@@ -787,12 +851,25 @@ hipError_t conv_wgrad_p16(const ConvGeom& g, const int8_t* x_p16, const int8_t* 
 // item, and the items go longest first into the list with the least work so far.  An item's cost
 // is its K groups plus P16_ITEM_FIXED: the prologue, merge and output of an item are about 6.8k
 // cycles against 346 per K group.
+//
+// Quad items (quad_kg > 0): an unsplit layer of 2x2 / 4x4 maps whose whole K range is at most
+// quad_kg K groups is cut into items of four consecutive tiles (the last may hold fewer), one tile
+// per wave.  Such an item's K time is one wave's -- the layer's kg_total, not four times it -- and
+// its fixed phases are the prologue, one wave's LDS write and the four output passes.  Stamps of
+// one item per workgroup on a 512 -> 512 layer of 2x2 maps at batch 256 (tools/wg_quad_diag.py,
+// cycles): merged form prologue 712, K loop 4438, LDS write and the wait for the slowest wave 1812,
+// sum 657, output 2851 -- 6.0k outside the K loop (6.8k inside a step's launch, above: 20 K groups);
+// quad form prologue 696, K loop 12640 (32 K groups), LDS write 1900, output 6922 -- 9.6k outside
+// the K loop: 28 K groups at 346 cycles.  (Weights of 24 to 48 gave the same launch time, 40.1-40.5
+// us per VGG-11 batch-256 step.)
 constexpr int P16_ITEM_FIXED = 20;
+constexpr int P16_QUAD_FIXED = 28;
 
-hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, WgP16Many* out) {
+hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, int t, int quad_kg, WgP16Many* out) {
     out->clear();
-    if (jobs == nullptr || n < 1 || n > P16_MANY_MAX_JOBS || blocks < 1 || blocks > 4096 || t < 1)
+    if (jobs == nullptr || n < 1 || n > P16_MANY_MAX_JOBS || blocks < 1 || blocks > 4096 || t < 1 || quad_kg < 0)
         return hipErrorInvalidValue;
+    if (!P16_QUAD_OK) quad_kg = 0;
     std::vector<WgP16Desc> descs((size_t)n);
     std::vector<WgP16Item> items;
     for (int j = 0; j < n; ++j) {
@@ -820,10 +897,15 @@ hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, in
         w.slab = s > 1 ? jb.slab : nullptr;
         w.slab_stride = stride;
         w.span = nullptr;
-        w.stamps = nullptr;
+        w.stamps = g_wg_stamps;  // (diagnostic builds: the block's last item leaves its marks)
         descs[j] = WgP16Desc{w, g.ow, 0};
         out->splits[j] = s;
         out->slab_stride[j] = stride;
+        if (s == 1 && g.ow <= 4 && w.kg_total <= quad_kg) {
+            for (int t0 = 0; t0 < w.tiles; t0 += P16_WAVES)
+                items.push_back(WgP16Item{j, t0, -1, 0, w.kg_total, w.kg_total, std::min(P16_WAVES, w.tiles - t0), 0});
+            continue;
+        }
         for (int sp = 0; sp < s; ++sp) {
             const int kb = sp * kg_per_split, ke = std::min(w.kg_total, kb + kg_per_split);
             const int kpw = round_kpi((ke - kb + P16_WAVES - 1) / P16_WAVES);
@@ -843,8 +925,9 @@ hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, in
     for (int i : order) {
         const int b = (int)(std::min_element(load.begin(), load.end()) - load.begin());
         lists[b].push_back(i);
-        load[b] += len(i) + P16_ITEM_FIXED;
+        load[b] += len(i) + (items[i].quad > 0 ? P16_QUAD_FIXED : P16_ITEM_FIXED);
         kg[b] += len(i);
+        out->n_quads += items[i].quad > 0;
     }
     const size_t starts_off = (descs.size() * sizeof(WgP16Desc) + 63) / 64 * 64;
     const size_t items_off = (starts_off + (size_t)(blocks + 1) * sizeof(int) + 63) / 64 * 64;
@@ -869,6 +952,20 @@ hipError_t conv_wgrad_p16_many_build(const WgP16Job* jobs, int n, int blocks, in
     out->n_items = k;
     out->max_list_kg = *std::max_element(kg.begin(), kg.end());
     return hipSuccess;
+}
+
+// the schedule as plain integers, for host-side checks: per item {job, first tile, tiles (0: the
+// merged form, one tile), slab, kg_begin, kg_end, kg_per_wave, form (1: quad)}
+int conv_wgrad_p16_many_items(const WgP16Many& m, int* items8, int cap_items, int* starts, int cap_starts) {
+    if (m.table == nullptr || cap_items < m.n_items || cap_starts < m.blocks + 1) return -1;
+    const WgP16Item* it = (const WgP16Item*)(m.table + m.items_off);
+    for (int i = 0; i < m.n_items; ++i) {
+        const int row[8] = {it[i].job,      it[i].tile,   it[i].quad,        it[i].slab,
+                            it[i].kg_begin, it[i].kg_end, it[i].kg_per_wave, it[i].quad > 0};
+        memcpy(items8 + 8 * i, row, sizeof row);
+    }
+    memcpy(starts, m.table + m.starts_off, (size_t)(m.blocks + 1) * sizeof(int));
+    return m.n_items;
 }
 
 static std::atomic<unsigned long long> g_many_launches{0};

@@ -162,6 +162,9 @@ def lib():
         "niti_diag_p16_jobs_cap": (None, [C.c_int]),
         "niti_diag_wgrad_batch": (None, [C.c_int]),
         "niti_diag_wgrad_batch_launches": (C.c_ulonglong, []),
+        "niti_diag_wgrad_quad": (None, [C.c_int]),
+        "niti_conv_wgrad_p16_many_items": (ci, [C.POINTER(WgradP16Job), ci, ci, ci, C.POINTER(ci), ci, C.POINTER(ci),
+                                                ci, C.POINTER(ci)]),
         "niti_tensor_convert": (ci, [tp, tp, vp]),
         "niti_geom_finalize": (ci, [C.POINTER(Geom)]),
         "niti_conv_workspace_bytes": (ci, [C.POINTER(Geom), ci, C.POINTER(C.c_size_t)]),

@@ -410,6 +410,27 @@ def conv_wgrad_p16_many(jobs, blocks: int, t: int, stream=None):
     return accs, list(splits)
 
 
+def conv_wgrad_p16_many_schedule(jobs, blocks: int, t: int):
+    """The item lists conv_wgrad_p16_many(jobs, blocks, t) would run, without any device call: per
+    workgroup a list of (job, first tile, tiles of a quad item or 0, slab, kg_begin, kg_end, kg_per_wave,
+    form) with form 0 the merged item (one tile, its K range split over the waves) and 1 the quad item."""
+    n = len(jobs)
+    arr = (L.WgradP16Job * n)()
+    for j, (g, xP, dyP, _) in enumerate(jobs):
+        arr[j].g = g
+        arr[j].x_p16, arr[j].dy_p16, arr[j].acc = xP.data_ptr(), dyP.data_ptr(), xP.data_ptr()  # (non-null is enough)
+    cap = 1024
+    while True:
+        items, starts, k = (C.c_int * (8 * cap))(), (C.c_int * (blocks + 1))(), C.c_int()
+        rc = L.lib().niti_conv_wgrad_p16_many_items(arr, n, blocks, t, items, cap, starts, blocks + 1, C.byref(k))
+        if rc == 0 or cap >= 1 << 20:
+            break
+        cap *= 8
+    check(rc, "conv_wgrad_p16_many_items")
+    rows = [tuple(items[8 * i:8 * i + 8]) for i in range(k.value)]
+    return [rows[starts[b]:starts[b + 1]] for b in range(blocks)]
+
+
 def matmul_acc(B16, A16, ldc, amax=None, use_workspace=True, stream=None):
     m, k16 = B16.shape
     o = A16.shape[0]
