@@ -609,7 +609,9 @@ int niti_image_quantize_nhwc16(const uint8_t* images_nchw, int n, int c, int hw,
  * of 32, e.g. 32 for the oracle-checked tests); ResNet-18 on ImageNet 3x224x224 (cfg 5: 21
  * parameter layers in the order conv1, per basic block conv a / conv b / [1x1 projection], fc; the
  * residual and global-pool rules are this library's -- the reference's NITI_Eltwise_Int8 is a stub,
- * NITI_Eltwise_Int8.cpp:20-28 -- stated in csrc/niti_resnet.hip and oracle/niti_resnet_ref.py). */
+ * NITI_Eltwise_Int8.cpp:20-28 -- stated in csrc/niti_resnet.hip and oracle/niti_resnet_ref.py), and
+ * any residual network of basic blocks given as a stage list (niti_resnet_spec,
+ * niti_model_create_resnet below; ResNet-18 is one, and is built through it). */
 enum niti_arch { NITI_ARCH_LENET = 1, NITI_ARCH_VGG11 = 2, NITI_ARCH_VGG16 = 3, NITI_ARCH_RESNET18 = 4 };
 typedef struct niti_model* niti_model_t;
 
@@ -662,6 +664,70 @@ int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int 
  * handle; niti_model_copy_weights needs the same list and input on both sides. */
 int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
+/* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
+ * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and
+ * the fc head, over square in_c x in_hw x in_hw inputs.  ResNet-10 / 18 / 34, narrow or short
+ * variants and the CIFAR ResNets (3x3 / 1 stem, no pool, three stages of 16 / 32 / 64) are such
+ * specs.  The rule:
+ *   - stage s (from 0) has width << s channels and depths[s] basic blocks; conv1 has width;
+ *   - a basic block is conv a (3x3, pad 1, relu) and conv b (3x3 / 1, pad 1); conv a has stride 2
+ *     on the first block of stages 1 and up, stride 1 elsewhere;
+ *   - a block has a 1x1 projection (conv a's stride, pad 0) on its shortcut exactly when its stride
+ *     or its channel count differs from its input's; else the shortcut is the block input;
+ *   - parameter layers in the order conv1, per block conv a, conv b, [projection], then fc (a 1x1
+ *     conv over the global sum pool of the last block: c_in = width << (n_stages - 1));
+ *   - the residual sum, the pool and the gradient exponents are ResNet-18's (csrc/niti_resnet.hip,
+ *     oracle/niti_resnet_ref.py); without the stem pool block 0 reads relu(conv1) and conv1's output
+ *     gradient is the relu gradient of block 0's input gradient.
+ * A model made from a spec reports arch NITI_ARCH_RESNET, whatever the spec;
+ * niti_model_create3(NITI_ARCH_RESNET18) is the spec {3, 7, 2, 3, 1, 64, 4, {2, 2, 2, 2}, classes}. */
+enum { NITI_ARCH_RESNET = 6 };
+#define NITI_RESNET_MAX_STAGES 8
+/* Parameter layers of a spec model at most.  The caller sizes the check's `shapes` by it; each step
+ * updates the layers in ceil(n / 24) launches (at most 11) and keeps three range words and an event
+ * per layer.  256 holds every basic-block ResNet in use (ResNet-34: 37, CIFAR ResNet-110: 112,
+ * ResNet-1202's 603 is left out on purpose: no test runs past this size). */
+#define NITI_RESNET_MAX_LAYERS 256
+typedef struct niti_resnet_spec {
+    int in_c;                               /* input channels, 1..4 */
+    int stem_kernel, stem_stride, stem_pad; /* conv1 (square, symmetric pad), followed by relu */
+    int stem_pool;                          /* 1: the 3x3 / 2 pad-1 max pool after it; 0: none */
+    int width;                              /* stage s has width << s channels; conv1 has width */
+    int n_stages;                           /* 1..NITI_RESNET_MAX_STAGES */
+    int depths[NITI_RESNET_MAX_STAGES];     /* basic blocks per stage, each >= 1 (beyond n_stages: ignored) */
+    int classes;                            /* <= 2048 */
+} niti_resnet_spec;
+/* Host only, no device call: validates the spec and writes *n_layers (if not NULL) and, if
+ * shapes != NULL, per parameter layer {c_in, c_out, k, stride, pad, h_in, oh, relu} (room for
+ * NITI_RESNET_MAX_LAYERS rows is always enough).
+ * NITI_INVALID_VALUE (malformed): spec == NULL, in_hw < 1, in_c < 1, stem_kernel < 1,
+ *   stem_stride < 1, stem_pad < 0, stem_pad >= stem_kernel, stem_pool other than 0 or 1, width < 1,
+ *   n_stages < 1 or > NITI_RESNET_MAX_STAGES, a depth < 1, classes < 1, a stem output below 1x1
+ *   (in_hw + 2 stem_pad < stem_kernel; no later layer can drop below 1x1).
+ * NITI_NOT_SUPPORT (well formed, not run by this library):
+ *   - in_c > 4: the stem's im2col packs a pixel's channels into one dword;
+ *   - the stem's im2col columns, stem_kernel^2 in_c rounded up to 32, above 4096 (a thread of the
+ *     im2col keeps one 16-byte chunk of a pixel's columns);
+ *   - stem_kernel ((ow - 1) stem_stride + stem_kernel) in_c > 16384, ow the stem's output width: the
+ *     input rows one output row reads are staged in 16 KiB of LDS;
+ *   - classes > 2048 (the loss and metrics kernels keep a row of logits per thread);
+ *   - more than NITI_RESNET_MAX_LAYERS parameter layers;
+ *   - any tensor -- the input [b][in_c][h][w], a layer's output [b][oh][ow][c_out up to 32], a
+ *     layer's input after the stem [b][h][w][c_in up to 32] or weights
+ *     [c_out up to 32][k][k][c_in up to 32] -- above 2^29 elements at batch b (31-bit byte offsets,
+ *     int32 accumulators of four times the size), or the stem's im2col [b][oh][ow][columns], an int8
+ *     operand only, of 2^31 bytes or more; niti_model_resnet_check tests b = 1,
+ *     niti_model_create_resnet its own batch.  Products and width << s are formed saturating.
+ * Every spec that passes runs, odd map sizes included (a stride-2 conv a and its 1x1 projection
+ * agree on them): each layer takes its fast path by its own shape predicate -- stride-1 3x3 layers
+ * the register-fed row kernels, stride-2 3x3 input gradients the sub-pixel classes, the rest the
+ * implicit GEMM with autotunable plans -- and the implicit GEMM + requantise pass is the fall-back. */
+int niti_model_resnet_check(const niti_resnet_spec* spec, int in_hw, int* n_layers, int shapes[][8]);
+/* The model of a spec (batch >= 1).  Runs the check first -- at this batch -- and on a refusal returns
+ * its code with nothing allocated and *out untouched.  niti_model_copy_weights between two such
+ * models needs equal specs and equal in_hw. */
+int niti_model_create_resnet(const niti_resnet_spec* spec, int in_hw, int batch, niti_model_t* out);
+
 /* batch = this rank's images per step.  Weights start zero; load them with
  * niti_model_set_weight (OIHW int8, host memory) -- the reference initialises them with a
  * time-seeded RNG (nn/Distributions.cpp:26-51), so callers supply their own. */
@@ -712,8 +778,9 @@ int niti_model_eval_topk(niti_model_t m, int k);
 int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream);
 /* Device-to-device weight hand-over: every layer's weights and weight scale of src into dst on
  * `stream`, dst's derived copies refreshed.  Both models must have the same architecture, input
- * size and class count (hence the same layer shapes); the batch may differ -- how a batch-64
- * training model feeds a batch-20 evaluation model.  NITI_INVALID_VALUE otherwise.  Asynchronous. */
+ * size and class count (hence the same layer shapes; two chain models the same list, two residual
+ * models equal specs); the batch may differ -- how a batch-64 training model feeds a batch-20
+ * evaluation model.  NITI_INVALID_VALUE otherwise.  Asynchronous. */
 int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream);
 /* ---- device-resident dataset ----------------------------------------------------------- */
 /* A training or test set kept in device memory, and the batches of an epoch gathered out of it on

@@ -29,9 +29,11 @@ int niti_model_create3(int arch, int batch, int in_hw, int classes, niti_model_t
     if (!out || batch <= 0 || in_hw < 0 || classes < 0) return NITI_INVALID_VALUE;
     int rc = NITI_NO_ERROR;
     std::unique_ptr<niti::StepDriver> d;
-    if (arch == NITI_ARCH_RESNET18)
-        d = niti::make_resnet_driver(batch, in_hw, classes, &rc);
-    else if (classes != 0)  // the LeNet / VGG heads are fixed (10 or 1000 classes)
+    if (arch == NITI_ARCH_RESNET18) {  // the stage list of ResNet-18, built as any other
+        if (classes > 2048) return NITI_INVALID_VALUE;
+        const niti_resnet_spec spec = {3, 7, 2, 3, 1, 64, 4, {2, 2, 2, 2}, classes > 0 ? classes : 1000};
+        d = niti::make_resnet_driver(&spec, in_hw > 0 ? in_hw : 224, batch, &rc);
+    } else if (classes != 0)  // the LeNet / VGG heads are fixed (10 or 1000 classes)
         return NITI_NOT_SUPPORT;
     else
         d = niti::make_chain_driver(arch, batch, in_hw, &rc);
@@ -48,6 +50,19 @@ int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int
     if (!out || batch <= 0) return NITI_INVALID_VALUE;
     int rc = NITI_NO_ERROR;
     std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc);
+    if (rc != NITI_NO_ERROR) return rc;
+    *out = new niti_model{std::move(d)};
+    return NITI_NO_ERROR;
+}
+
+int niti_model_resnet_check(const niti_resnet_spec* spec, int in_hw, int* n_layers, int shapes[][8]) {
+    return niti::resnet_check(spec, in_hw, 1, n_layers, shapes);
+}
+
+int niti_model_create_resnet(const niti_resnet_spec* spec, int in_hw, int batch, niti_model_t* out) {
+    if (!out || batch <= 0) return NITI_INVALID_VALUE;
+    int rc = NITI_NO_ERROR;
+    std::unique_ptr<niti::StepDriver> d = niti::make_resnet_driver(spec, in_hw, batch, &rc);
     if (rc != NITI_NO_ERROR) return rc;
     *out = new niti_model{std::move(d)};
     return NITI_NO_ERROR;

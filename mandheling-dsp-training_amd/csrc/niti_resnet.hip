@@ -348,6 +348,11 @@ hipError_t im2col_small(const ConvGeom& g, const int8_t* x, int kp, int8_t* xcol
             hipLaunchKernelGGL((im2col_small_kernel<7, 7, 3, true>), grid, dim3(256), 0, st, x, g, kp, xcol);
         else
             hipLaunchKernelGGL((im2col_small_kernel<7, 7, 3, false>), grid, dim3(256), 0, st, x, g, kp, xcol);
+    } else if (g.kh == 3 && g.kw == 3 && g.c_in == 3) {  // the CIFAR ResNets' stem
+        if (nchw)
+            hipLaunchKernelGGL((im2col_small_kernel<3, 3, 3, true>), grid, dim3(256), 0, st, x, g, kp, xcol);
+        else
+            hipLaunchKernelGGL((im2col_small_kernel<3, 3, 3, false>), grid, dim3(256), 0, st, x, g, kp, xcol);
     } else if (nchw) {
         hipLaunchKernelGGL((im2col_small_kernel<0, 0, 0, true>), grid, dim3(256), 0, st, x, g, kp, xcol);
     } else {

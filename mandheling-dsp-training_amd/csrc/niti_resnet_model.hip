@@ -1,5 +1,6 @@
-// niti_resnet_model.hip -- ResNet-18 NITI int8 training step on the device, driven from C++
-// (BASELINE config 5; declarations and the rules' provenance in niti_resnet_model.hpp).
+// niti_resnet_model.hip -- the NITI int8 training step of a residual network on the device, driven
+// from C++: ResNet-18 (BASELINE config 5) or any stage list of basic blocks (niti_resnet_spec;
+// declarations and the rules' provenance in niti_resnet_model.hpp).  Described for ResNet-18:
 //
 // One step (uint8 images or int8 x in, NITI_SGD out), every op on the step stream:
 //   input      image statistics -> [SUM / MAX over ranks] -> quantise (NCHW) -> the stem's im2col
@@ -11,7 +12,8 @@
 //              memory order) and the input gradient with the previous relu gradient fused; the
 //              residual gradient sums with the next block-output relu gradient fused; the stem's
 //              overlapping max-pool gradient (first max wins) with its relu gradient
-//   update     one NITI_SGD launch over all 21 layers (+ the row kernels' weight copies)
+//   update     one NITI_SGD launch over all 21 layers (+ the row kernels' weight copies); a deeper
+//              network's in consecutive launches of at most SGD_MAX_JOBS layers
 // Every forward / input-gradient conv is one of the two forms the VGG driver uses: the register-fed
 // row kernels with the rescale fused (stride-1 3x3 layers, niti_rowconv.hip) or the implicit-GEMM
 // range + requantise phases (strided / 1x1 / deep layers, niti_kernels.hip).  Data parallel: the
@@ -21,6 +23,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <set>
 
 #include "../../include/niti_hip.h"
@@ -43,41 +46,121 @@ static ConvGeom make_geom(int n, int ci, int h, int co, int k, int s, int p) {
     return g;
 }
 
-int ResNetModel::build(int batch_, int in_hw_, int classes_) {
-    batch = batch_;
-    in_hw = in_hw_ > 0 ? in_hw_ : 224;
-    classes = classes_ > 0 ? classes_ : 1000;
-    // every stage halves the map (stride-2 convs and the 1x1 projections agree on odd sizes too)
-    if (in_hw % 16 != 0 || classes > 2048) return NITI_INVALID_VALUE;
-    const int n = batch;
-    // the 21 parameter layers in parameter order (oracle/niti_resnet_ref.py resnet18_convs)
-    auto add = [&](int ci, int co, int k, int s, int p, int h, int relu) {
-        RConv c;
-        c.og = c.g = make_geom(n, ci, h, co, k, s, p);
-        c.relu = relu;
-        C.push_back(c);
-        return (int)C.size() - 1;
+// ------------------------------------------------------------------------------ the stage list
+// The largest tensor of a layer (elements, at the model's batch): the GEMM loaders address int8
+// operands with 31-bit byte offsets and the int32 accumulator of a tensor is four times its size.
+// The stem's im2col is an int8 operand only, never an accumulator: 2^31 - 1 bytes.
+constexpr int64_t RESNET_MAX_ELEMS = int64_t(1) << 29;
+constexpr int64_t RESNET_SAT = int64_t(1) << 31;
+// a * b, or RESNET_SAT once it reaches it (operands >= 0; no product overflows int64)
+static int64_t sat_mul(int64_t a, int64_t b) {
+    if (a >= RESNET_SAT || b >= RESNET_SAT) return RESNET_SAT;
+    return std::min(a * b, RESNET_SAT);
+}
+
+// one derived parameter layer: {c_in, c_out, k, stride, pad, h_in, oh, relu}
+using RShape = std::array<int, 8>;
+
+// The rule of include/niti_hip.h (niti_model_resnet_check), shared by the check, the create call and
+// build(): the parameter layers of a spec in parameter order.
+int resnet_check(const niti_resnet_spec* sp, int in_hw, int batch, int* n_layers, int shapes[][8]) {
+    if (sp == nullptr || in_hw < 1 || batch < 1) return NITI_INVALID_VALUE;
+    const niti_resnet_spec& s = *sp;
+    if (s.in_c < 1 || s.stem_kernel < 1 || s.stem_stride < 1 || s.stem_pad < 0 || s.stem_pad >= s.stem_kernel ||
+        (s.stem_pool != 0 && s.stem_pool != 1) || s.width < 1 || s.n_stages < 1 || s.n_stages > NITI_RESNET_MAX_STAGES ||
+        s.classes < 1)
+        return NITI_INVALID_VALUE;
+    // conv1 and fc, two convs a block, one projection per stage after the first (stage 0 keeps conv1's
+    // width at stride 1; every later stage changes both)
+    int64_t layers = 2 + (s.n_stages - 1);
+    for (int i = 0; i < s.n_stages; ++i) {
+        if (s.depths[i] < 1) return NITI_INVALID_VALUE;
+        layers += 2 * (int64_t)s.depths[i];
+    }
+    if ((int64_t)in_hw + 2 * (int64_t)s.stem_pad < s.stem_kernel) return NITI_INVALID_VALUE;
+    // ---- well formed from here
+    if (s.in_c > 4 || s.classes > 2048) return NITI_NOT_SUPPORT;
+    if (layers > NITI_RESNET_MAX_LAYERS) return NITI_NOT_SUPPORT;  // (before the walk over them)
+    const int64_t kk = sat_mul(sat_mul(s.stem_kernel, s.stem_kernel), s.in_c);
+    if (kk > 4096 - 31) return NITI_NOT_SUPPORT;  // the im2col's column pitch: one 16-byte chunk per thread
+    const int64_t kp = (kk + 31) / 32 * 32;
+    const int64_t b = batch;
+    const int64_t oh0 = ((int64_t)in_hw + 2 * s.stem_pad - s.stem_kernel) / s.stem_stride + 1;
+    // the input rows one output row of the stem reads, staged in the im2col's 16 KiB of LDS
+    if (sat_mul(sat_mul(s.stem_kernel, (oh0 - 1) * s.stem_stride + s.stem_kernel), s.in_c) > 16384) return NITI_NOT_SUPPORT;
+    if (sat_mul(sat_mul(sat_mul(b, s.in_c), in_hw), in_hw) > RESNET_MAX_ELEMS) return NITI_NOT_SUPPORT;
+    if (sat_mul(sat_mul(sat_mul(b, oh0), oh0), kp) >= RESNET_SAT) return NITI_NOT_SUPPORT;
+    std::vector<RShape> sh;
+    bool fits = true;
+    // every tensor of a layer in the padded layouts build() allocates (the row kernels' C32 copies;
+    // the stem's input is the NCHW batch and its im2col, bounded above)
+    auto add = [&](int64_t ci, int64_t co, int k, int st, int p, int64_t h, int relu) {
+        const int64_t oh = (h + 2 * p - k) / st + 1;
+        const int64_t ci32 = (std::min(ci, RESNET_SAT) + 31) / 32 * 32, co32 = (std::min(co, RESNET_SAT) + 31) / 32 * 32;
+        if ((!sh.empty() && sat_mul(sat_mul(sat_mul(b, h), h), ci32) > RESNET_MAX_ELEMS) ||
+            sat_mul(sat_mul(sat_mul(b, oh), oh), co32) > RESNET_MAX_ELEMS ||
+            sat_mul(sat_mul(co32, (int64_t)k * k), ci32) > RESNET_MAX_ELEMS)
+            fits = false;
+        else
+            sh.push_back({(int)ci, (int)co, k, st, p, (int)h, (int)oh, relu});
+        return oh;
     };
-    stem = make_geom(n, 3, in_hw, 64, 7, 2, 3);
-    add(3, 64, 7, 2, 3, in_hw, 1);
-    C[0].g = make_geom(n, STEM_KP, stem.oh, 64, 1, 1, 0);
-    const int ph = (stem.oh + 2 - 3) / 2 + 1;
-    int h = ph, ci = 64;
-    for (int stage = 0; stage < 4; ++stage) {
-        const int co = 64 << stage;
-        for (int blk = 0; blk < 2; ++blk) {
-            const int s = stage > 0 && blk == 0 ? 2 : 1;
-            RBlock b;
-            b.a = add(ci, co, 3, s, 1, h, 1);
-            const int ho = (h + 2 - 3) / s + 1;
-            b.b = add(co, co, 3, 1, 1, ho, 0);
-            if (s != 1 || ci != co) b.p = add(ci, co, 1, s, 0, h, 0);
-            B.push_back(b);
+    int64_t h = add(s.in_c, s.width, s.stem_kernel, s.stem_stride, s.stem_pad, in_hw, 1);
+    if (s.stem_pool) h = (h + 2 - 3) / 2 + 1;
+    int64_t ci = s.width;
+    for (int stage = 0; stage < s.n_stages && fits; ++stage) {
+        const int64_t co = sat_mul(s.width, int64_t(1) << stage);  // width << stage, saturating
+        for (int blk = 0; blk < s.depths[stage] && fits; ++blk) {
+            const int st = stage > 0 && blk == 0 ? 2 : 1;
+            const int64_t ho = add(ci, co, 3, st, 1, h, 1);
+            add(co, co, 3, 1, 1, ho, 0);
+            if (st != 1 || ci != co) add(ci, co, 1, st, 0, h, 0);
             ci = co;
             h = ho;
         }
     }
-    const int fc = add(512, classes, 1, 1, 0, 1, 0);
+    if (fits) add(ci, s.classes, 1, 1, 0, 1, 0);
+    if (!fits) return NITI_NOT_SUPPORT;
+    if (n_layers) *n_layers = (int)sh.size();
+    if (shapes)
+        for (size_t i = 0; i < sh.size(); ++i) std::copy(sh[i].begin(), sh[i].end(), shapes[i]);
+    return NITI_NO_ERROR;
+}
+
+int ResNetModel::build(int batch_, int in_hw_, const niti_resnet_spec& spec_) {
+    batch = batch_;
+    in_hw = in_hw_;
+    spec = spec_;
+    for (int i = spec.n_stages; i < NITI_RESNET_MAX_STAGES; ++i) spec.depths[i] = 0;
+    classes = spec.classes;
+    int n_sh = 0;
+    std::vector<RShape> sh(NITI_RESNET_MAX_LAYERS);
+    if (const int rc = resnet_check(&spec, in_hw, batch, &n_sh, (int(*)[8])sh.data())) return rc;
+    const int n = batch;
+    // the parameter layers in parameter order (oracle/niti_resnet_ref.py resnet18_convs for
+    // ResNet-18); every stage after the first halves the map (stride-2 convs and the 1x1 projections
+    // agree on odd sizes too)
+    auto add = [&](const RShape& v) {
+        RConv c;
+        c.og = c.g = make_geom(n, v[0], v[5], v[1], v[2], v[3], v[4]);
+        c.relu = v[7];
+        C.push_back(c);
+        return (int)C.size() - 1;
+    };
+    stem_kp = stem_cols(spec);
+    add(sh[0]);
+    stem = C[0].og;
+    C[0].g = make_geom(n, stem_kp, stem.oh, spec.width, 1, 1, 0);
+    const int ph = spec.stem_pool ? (stem.oh + 2 - 3) / 2 + 1 : stem.oh;  // block 0's input size
+    for (int i = 1; i + 1 < n_sh;) {  // a block: conv a, conv b, [the 1x1 projection]
+        RBlock b;
+        b.a = add(sh[i++]);
+        b.b = add(sh[i++]);
+        if (i + 1 < n_sh && sh[i][2] == 1) b.p = add(sh[i++]);
+        B.push_back(b);
+    }
+    const int fc = add(sh[n_sh - 1]);
+    const int cpool = C[B.back().b].g.cop;  // the pooled channels as stored (the last stage's width, padded)
     const int nl = (int)C.size();
     // device exponents: 2 per conv, 4 per block, pool, loss gradient, input
     n_exps = 2 * nl + 4 * (int)B.size() + 3;
@@ -90,12 +173,16 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     ed = exp_slot();  // the loss gradient's exponent: 0, never written
     auto A8 = [&](size_t bytes) { return (int8_t*)ws.alloc(bytes); };
     // the input and the stem
-    x0n = A8((size_t)n * 3 * in_hw * in_hw);
-    xcol = A8((size_t)n * stem.oh * stem.ow * STEM_KP);
-    p0 = A8((size_t)n * ph * ph * 64);
-    pool_ws = A8((size_t)n * ph * ph * 64);
-    d0 = A8((size_t)n * stem.oh * stem.ow * 64);
-    if (!x0n || !xcol || !p0 || !pool_ws || !d0) return NITI_OUT_OF_MEMORY;
+    const int cop0 = C[0].g.cop;
+    x0n = A8((size_t)n * spec.in_c * in_hw * in_hw);
+    xcol = A8((size_t)n * stem.oh * stem.ow * stem_kp);
+    if (spec.stem_pool) {
+        p0 = A8((size_t)n * ph * ph * cop0);
+        pool_ws = A8((size_t)n * ph * ph * cop0);
+        if (!p0 || !pool_ws) return NITI_OUT_OF_MEMORY;
+    }
+    d0 = A8((size_t)n * stem.oh * stem.ow * cop0);
+    if (!x0n || !xcol || !d0) return NITI_OUT_OF_MEMORY;
     size_t acc_elems = 0, grad_elems = 0;
     rc_err = (uint32_t*)ws.alloc(64);
     if (!rc_err || hipMemset(rc_err, 0, 64) != hipSuccess) return NITI_OUT_OF_MEMORY;
@@ -165,8 +252,8 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     C[0].in_exp = exp0;
     C[0].dy = d0;
     C[0].dy_exp = ed;  // (the stem's weight gradient reads no exponent)
-    const int8_t* u = p0;
-    const int8_t* u_exp = C[0].y_exp;  // max pooling keeps the exponent
+    const int8_t* u = spec.stem_pool ? p0 : C[0].y;  // (no pool: the stem's relu'd output, always written)
+    const int8_t* u_exp = C[0].y_exp;                // max pooling keeps the exponent
     for (size_t k = 0; k < B.size(); ++k) {
         RBlock& b = B[k];
         RConv& ca = C[b.a];
@@ -220,9 +307,9 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
             C[b.p].dy_exp = b.dz_exp;
         }
     }
-    gsum = (int32_t*)ws.alloc((size_t)n * 512 * 4);
-    g8pool = A8((size_t)n * 512);
-    dg = A8((size_t)n * 512);
+    gsum = (int32_t*)ws.alloc((size_t)n * cpool * 4);
+    g8pool = A8((size_t)n * cpool);
+    dg = A8((size_t)n * cpool);
     RConv& f = C[fc];
     f.in = g8pool;
     f.in_exp = eg;
@@ -249,6 +336,7 @@ int ResNetModel::build(int batch_, int in_hw_, int classes_) {
     if (!amax) return NITI_OUT_OF_MEMORY;
     // (the bucket SUMs, the GEMM weight gradients)
     for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2), C[i].g});
+    sgd_jobs.resize(nl);
     if (const int rc = alloc_eval()) return rc;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
@@ -303,7 +391,7 @@ int ResNetModel::fwd_conv(int i, hipStream_t st) {
     o.wscale = c.ws_dev;
     o.exp_out = c.y_exp;
     if (i == 0) {  // the stem: its 3x3 / 2 max pool in the requantise pass when there is one
-        stem_pooled = !conv_fwd_spec_ok(g) && conv_fwd_phase2_separate(g, slab_bytes);
+        stem_pooled = spec.stem_pool && !conv_fwd_spec_ok(g) && conv_fwd_phase2_separate(g, slab_bytes);
         if (stem_pooled) {
             const int ph = C[B[0].a].g.h;
             o.pool3.out = p0;
@@ -454,7 +542,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     int rc = forward(x_nchw, exp_in, images, st);
     if (rc != NITI_NO_ERROR) return rc;
     // the loss gradient, then the backward pass
-    const int ph = C[B[0].a].g.h;  // the stem's pooled size
+    const int ph = C[B[0].a].g.h;  // block 0's input size (the stem's pooled size)
     const RBlock& bl = B.back();
     const ConvGeom& gl = C[bl.b].g;
     RConv& f = C[fc];
@@ -466,7 +554,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         return r;
     };
     if ((rc = dgrad_conv(fc, st)) != NITI_NO_ERROR || (rc = wg(fc)) != NITI_NO_ERROR) return rc;
-    DTRY(sum_pool_grad(dg, n, gl.oh * gl.ow, 512, bl.dz, st, bl.out));  // + the last block's relu gradient
+    DTRY(sum_pool_grad(dg, n, gl.oh * gl.ow, gl.cop, bl.dz, st, bl.out));  // + the last block's relu gradient
     for (int k = (int)B.size() - 1; k >= 0; --k) {
         const RBlock& b = B[k];
         if (b.p >= 0 && (rc = wg(b.p)) != NITI_NO_ERROR) return rc;
@@ -478,7 +566,11 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     // the stem: overlapping 3x3 / 2 max-pool gradient (first max wins) with the relu gradient, then
     // its weight gradient over the im2col
     // (the relu mask from the pooled output: the pre-pool output may not exist)
-    DTRY(maxpool_relu_grad_arg(nullptr, pool_ws, B[0].du, n, stem.oh, stem.ow, 64, 3, 2, 1, ph, ph, 1, d0, st, p0));
+    // (no pool: the relu gradient alone, the stem's relu'd output as its mask)
+    if (spec.stem_pool)
+        DTRY(maxpool_relu_grad_arg(nullptr, pool_ws, B[0].du, n, stem.oh, stem.ow, C[0].g.cop, 3, 2, 1, ph, ph, 1, d0, st, p0));
+    else
+        DTRY(relu_grad_nhwc16(C[0].y, B[0].du, (int64_t)n * stem.oh * stem.ow * C[0].g.cop, d0, st));
     if ((rc = wg(0)) != NITI_NO_ERROR) return rc;
     if (dp) {  // every bucket summed and ranged before the update
         if (!shared_comm) {
@@ -486,11 +578,11 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
             DTRY(hipStreamWaitEvent(st, ev_grads, 0));
         }
     }
-    // NITI_SGD (NITI_SGD.hpp:20-54) for every layer in one launch, after every input gradient read the
-    // old weights; it also rewrites the row kernels' fragment-major copies and the GEMM input
-    // gradient's transposed copy
-    SgdJob jobs[SGD_MAX_JOBS];
-    if (nl > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;
+    // NITI_SGD (NITI_SGD.hpp:20-54) for every layer in one launch (more than SGD_MAX_JOBS layers: in
+    // consecutive launches, each group's deferred combines ahead of its update), after every input
+    // gradient read the old weights; it also rewrites the row kernels' fragment-major copies and the
+    // GEMM input gradient's transposed copy
+    SgdJob* jobs = sgd_jobs.data();
     for (int i = 0; i < nl; ++i) {
         RConv& c = C[i];
         const ConvGeom& g = c.g;
@@ -508,7 +600,8 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         // this conv's split-K slabs, combined in the update launch
         if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
-    DTRY(sgd_update_many(jobs, nl, st));
+    rc = in_job_groups(nl, SGD_MAX_JOBS, [&](int first, int count) { return sgd_update_many(jobs + first, count, st); });
+    if (rc != NITI_NO_ERROR) return rc;
     g8_written = keep_grads;
     return NITI_NO_ERROR;
 }
@@ -526,7 +619,7 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
     };
     if (images == nullptr || amax_bytes % 16 != 0) DTRY(fill(amax, 0, amax_bytes));
     // input: NITIInt8Train's quantiser (MnistUtils.cpp:83-93) on uint8 images, or int8 x as given
-    const int64_t px = (int64_t)n * 3 * in_hw * in_hw;
+    const int64_t px = (int64_t)n * spec.in_c * in_hw * in_hw;
     const int8_t* xq = x_nchw;
     if (images != nullptr) {
         int ns = 0;
@@ -537,20 +630,20 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
             DTRY(coll->allreduce(qstats, 2, COLL_SUM_U64, st));
             DTRY(coll->allreduce(qstats + 2, 2, COLL_MAX_U64, st));
         }
-        DTRY(image_quantize(images, n, 3, in_hw * in_hw, 3, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
+        DTRY(image_quantize(images, n, spec.in_c, in_hw * in_hw, spec.in_c, qstats, dp && exact ? px * world : px, x0n, exp0, false, st));
         xq = x0n;
     } else {
         DTRY(fill(exp0, exp_in, 1));
         DTRY(by_kernel ? copy_kernel(x0n, x_nchw, (size_t)px, st)
                        : hipMemcpyAsync(x0n, x_nchw, (size_t)px, hipMemcpyDeviceToDevice, st));
     }
-    DTRY(im2col_small(stem, xq, STEM_KP, xcol, st, true));
+    DTRY(im2col_small(stem, xq, stem_kp, xcol, st, true));
     // forward
     int rc = fwd_conv(0, st);
     if (rc != NITI_NO_ERROR) return rc;
     const int ph = C[B[0].a].g.h;  // the stem's pooled size
-    if (!stem_pooled)  // (else fused into the stem's requantise pass)
-        DTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, 64, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
+    if (spec.stem_pool && !stem_pooled)  // (else fused into the stem's requantise pass, or none)
+        DTRY(maxpool_nhwc16(C[0].y, n, stem.oh, stem.ow, C[0].g.cop, 3, 2, 1, p0, ph, ph, st, pool_ws));  // + first-max positions
     for (int k = 0; k < (int)B.size(); ++k) {
         const RBlock& b = B[k];
         if ((rc = fwd_conv(b.a, st)) != NITI_NO_ERROR) return rc;
@@ -567,7 +660,7 @@ int ResNetModel::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images
         ActRequant r;
         r.acc = gsum;
         r.rows = n;
-        r.ldc = 512;
+        r.ldc = gl.cop;
         r.amax = rng_pool();
         r.exp_in = bl.out_exp;
         r.exp_out = eg;
@@ -607,7 +700,8 @@ int ResNetModel::copy_weights_from(StepDriver& other, hipStream_t st) {
     ResNetModel* sp = dynamic_cast<ResNetModel*>(&other);
     if (sp == nullptr) return NITI_INVALID_VALUE;
     ResNetModel& src = *sp;
-    if (src.in_hw != in_hw || src.classes != classes || src.C.size() != C.size()) return NITI_INVALID_VALUE;
+    // (equal stage lists: the same layers)
+    if (src.in_hw != in_hw || memcmp(&src.spec, &spec, sizeof(spec)) != 0 || src.C.size() != C.size()) return NITI_INVALID_VALUE;
     for (size_t i = 0; i < C.size(); ++i)
         if (C[i].w_elems() != src.C[i].w_elems()) return NITI_INVALID_VALUE;
     if (&src == this) return NITI_NO_ERROR;
@@ -678,8 +772,8 @@ int ResNetModel::autotune(hipStream_t st, int reps) {
     auto run_op = [&](int i, int op) {
         if (op == PLAN_FWD && i == 0) {  // the stem with its max pool (fused into a separate requantise pass)
             int r = fwd_conv(0, st);
-            if (r == NITI_NO_ERROR && !stem_pooled &&
-                maxpool_nhwc16(C[0].y, batch, stem.oh, stem.ow, 64, 3, 2, 1, p0, C[B[0].a].g.h, C[B[0].a].g.w, st,
+            if (r == NITI_NO_ERROR && spec.stem_pool && !stem_pooled &&
+                maxpool_nhwc16(C[0].y, batch, stem.oh, stem.ow, C[0].g.cop, 3, 2, 1, p0, C[B[0].a].g.h, C[B[0].a].g.w, st,
                                pool_ws) != hipSuccess)
                 r = NITI_NO_EXECUTION;
             return r;
@@ -741,8 +835,8 @@ int ResNetModel::set_weight(int i, const int8_t* w_host, int wscale) {
     const ConvGeom& g = c.g;
     std::vector<int8_t> colw;
     if (i == 0) {
-        colw.resize((size_t)g.c_out * STEM_KP);
-        cols_from_oihw(c.og, w_host, colw.data(), STEM_KP);
+        colw.resize((size_t)g.c_out * stem_kp);
+        cols_from_oihw(c.og, w_host, colw.data(), stem_kp);
         w_host = colw.data();
     }
     const size_t nb = (size_t)g.c_out * g.c_in * g.kh * g.kw;
@@ -773,7 +867,7 @@ int ResNetModel::get_weight(int i, int8_t* w_host) {
     if (ohwi16_to_oihw(c.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr) != hipSuccess ||
         hipMemcpy(i == 0 ? colw.data() : w_host, tmp, nb, hipMemcpyDeviceToHost) != hipSuccess)
         rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR && i == 0) oihw_from_cols(c.og, colw.data(), w_host, STEM_KP);
+    if (rc == NITI_NO_ERROR && i == 0) oihw_from_cols(c.og, colw.data(), w_host, stem_kp);
     (void)hipFree(tmp);
     return rc;
 }
@@ -806,7 +900,7 @@ int ResNetModel::get_tap(int layer, int which, int8_t* host, size_t bytes, hipSt
     if (which == 1 && layer == 0) {
         std::vector<int8_t> colw(need);
         if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) oihw_from_cols(c.og, colw.data(), host, STEM_KP);
+        if (e == hipSuccess) oihw_from_cols(c.og, colw.data(), host, stem_kp);
     } else if (e == hipSuccess) {
         e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
     }
@@ -831,7 +925,7 @@ int ResNetModel::get_logits(int8_t* host, int* exp_out, hipStream_t st) {
 int ResNetModel::get_input(int8_t* host, int* ascale, hipStream_t st) {
     if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
     int8_t e = 0;
-    if (hipMemcpy(host, x0n, (size_t)batch * 3 * in_hw * in_hw, hipMemcpyDeviceToHost) != hipSuccess ||
+    if (hipMemcpy(host, x0n, (size_t)batch * spec.in_c * in_hw * in_hw, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(&e, exp0, 1, hipMemcpyDeviceToHost) != hipSuccess)
         return NITI_NO_EXECUTION;
     if (ascale) *ascale = e;
@@ -904,9 +998,11 @@ int ResNetModel::set_rowconv(bool enable) {
     return NITI_NO_ERROR;
 }
 
-std::unique_ptr<StepDriver> make_resnet_driver(int batch, int in_hw, int classes, int* rc) {
+std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int in_hw, int batch, int* rc) {
+    *rc = resnet_check(spec, in_hw, batch, nullptr, nullptr);  // (nothing allocated on a refusal)
+    if (*rc != NITI_NO_ERROR) return nullptr;
     auto m = std::make_unique<ResNetModel>();
-    *rc = m->build(batch, in_hw, classes);
+    *rc = m->build(batch, in_hw, *spec);
     if (*rc != NITI_NO_ERROR) return nullptr;
     return m;
 }

@@ -1,5 +1,5 @@
-// niti_resnet_model.hpp -- the ResNet-18 NITI training step driven from C++ (BASELINE config 5),
-// behind the same niti_model_* C ABI (niti_model_capi.hip) as the LeNet / VGG driver (niti_model.hip),
+// niti_resnet_model.hpp -- the NITI training step of a residual network of basic blocks driven from
+// C++: ResNet-18 (BASELINE config 5) or the caller's own stage list (niti_resnet_spec), behind the same niti_model_* C ABI (niti_model_capi.hip) as the LeNet / VGG driver (niti_model.hip),
 // on the same base (niti_step_driver.hpp).
 //
 // The reference has no ResNet NITI model: its graph builder would chain NITI_Conv_Int8_Module
@@ -71,14 +71,19 @@ struct RBlock {
 };
 
 struct ResNetModel final : StepDriver {
-    static constexpr int STEM_KP = 160;  // the stem's im2col columns: 7 * 7 * 3 = 147, padded
+    niti_resnet_spec spec{};      // what build() made (unused depths zero: compared as a whole)
+    // the stem's im2col columns: kernel^2 * in_c, padded to whole 32-column GEMM steps (7 * 7 * 3 =
+    // 147 -> 160)
+    static int stem_cols(const niti_resnet_spec& s) { return round_up(s.stem_kernel * s.stem_kernel * s.in_c, 32); }
+    int stem_kp = 0;
     int in_hw = 0, classes = 1000;
     std::vector<RConv> C;
     std::vector<RBlock> B;
     ConvGeom stem{};              // conv1 as defined (the im2col's geometry)
     int8_t* x0n = nullptr;        // the quantised input, NCHW int8
     int8_t* exp0 = nullptr;
-    int8_t* xcol = nullptr;       // the stem's im2col [n * oh * ow][STEM_KP]
+    int8_t* xcol = nullptr;       // the stem's im2col [n * oh * ow][stem_kp]
+    // (both null without the stem pool: block 0 then reads the stem's relu'd output itself)
     int8_t* p0 = nullptr;         // 3x3 / 2 max pool of the stem output
     int8_t* pool_ws = nullptr;    // each pool window's first-max position (the pool gradient's)
     // the stem's requantise pass also max-pooled (Pool3) this step; with keep_grads off its pre-pool
@@ -89,10 +94,10 @@ struct ResNetModel final : StepDriver {
     bool stem_y_written = false;
     bool g8_written = false;
     int8_t* d0 = nullptr;         // the stem's output gradient
-    int32_t* gsum = nullptr;      // global sum pool [n][512]
+    int32_t* gsum = nullptr;      // global sum pool [n][the last stage's width, padded]
     int8_t* g8pool = nullptr;     // its requantisation (the fc input)
     int8_t* eg = nullptr;
-    int8_t* dg = nullptr;         // the fc head's input gradient [n][512]
+    int8_t* dg = nullptr;         // the fc head's input gradient (as gsum)
     int8_t* ed = nullptr;         // the loss gradient's exponent (0)
     int8_t* exps = nullptr;       // device int8 exponents, handed out in build()
     int n_exps = 0;
@@ -133,7 +138,9 @@ struct ResNetModel final : StepDriver {
     const void* gkey_l = nullptr;
     int gkey_e = 0;
 
-    int build(int batch_, int in_hw_, int classes_);
+    std::vector<SgdJob> sgd_jobs;  // the update's job table (sized in build(): no allocation in a step)
+
+    int build(int batch_, int in_hw_, const niti_resnet_spec& spec_);
     bool rows_on(int i) const { return use_rowconv && C[i].rows; }
     bool rows_dg_on(int i) const { return use_rowconv && C[i].rows_dg; }
     int fwd_conv(int i, hipStream_t st);

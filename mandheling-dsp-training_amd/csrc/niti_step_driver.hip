@@ -125,11 +125,10 @@ int StepDriver::ensure_comm_stream() {
 int StepDriver::sum_bucket(int lo, hipStream_t wst) {
     int hi = lo;
     while (hi + 1 < (int)grads.size() && bucket_lo[hi + 1] == lo) ++hi;
-    if (hi - lo + 1 > ABSMAX_MAX_JOBS) return NITI_NOT_SUPPORT;
     size_t elems = 0;
     for (int j = lo; j <= hi; ++j) elems += (size_t)grads[j].elems;
-    AbsmaxJob jobs[ABSMAX_MAX_JOBS];
-    for (int j = lo; j <= hi; ++j) jobs[j - lo] = AbsmaxJob{grads[j].dwacc, grads[j].elems, grads[j].amax, 0};
+    bucket_jobs.resize(hi - lo + 1);
+    for (int j = lo; j <= hi; ++j) bucket_jobs[j - lo] = AbsmaxJob{grads[j].dwacc, grads[j].elems, grads[j].amax, 0};
     hipStream_t s = wst;  // one communicator: the SUMs stay in the step's program order
     if (!shared_comm) {   // own communicator: its own stream, overlapping the rest of the backward pass
         DTRY(hipEventRecord(ev_bucket[lo], wst));
@@ -137,8 +136,9 @@ int StepDriver::sum_bucket(int lo, hipStream_t wst) {
         s = cst;
     }
     DTRY(coll_grad->allreduce(grads[lo].dwacc, elems, COLL_SUM_I32, s));
-    DTRY(absmax_many(jobs, hi - lo + 1, s));
-    return NITI_NO_ERROR;
+    // (a narrow deep network's bucket can hold more layers than one range launch takes)
+    return in_job_groups(hi - lo + 1, ABSMAX_MAX_JOBS,
+                         [&](int first, int count) { return absmax_many(bucket_jobs.data() + first, count, s); });
 }
 
 void StepDriver::attach(std::unique_ptr<Collective> c, std::unique_ptr<Collective> cg, bool shared, int world_,

@@ -1,5 +1,6 @@
 // niti_step_driver.hpp -- what the two whole-step training drivers behind the niti_model_* C ABI
-// share: the chain driver (LeNet / VGG, niti_model.hip) and ResNet-18 (niti_resnet_model.hip).
+// share: the chain driver (LeNet / VGG, niti_model.hip) and the residual driver (ResNet-18 and the
+// stage lists, niti_resnet_model.hip).
 //
 // StepDriver holds the state and the logic both have in the same form -- split-K slabs, the
 // data-parallel gradient buckets, the range / rescale launch protocol (range_max, rowconv_ranged,
@@ -84,6 +85,16 @@ struct StepDriver {
     std::vector<int> bucket_lo;
     std::vector<char> closes_bucket;
     void plan_buckets();
+    // A job table of any length through a launch that takes at most max_jobs of them (the tables
+    // travel as kernel arguments: sgd_update_many's SGD_MAX_JOBS, absmax_many's ABSMAX_MAX_JOBS):
+    // launch(first, count) over consecutive groups, in order, on the caller's stream.  n <= max_jobs
+    // is the one launch it always was.
+    template <class Launch>
+    static int in_job_groups(int n, int max_jobs, Launch&& launch) {
+        for (int lo = 0; lo < n; lo += max_jobs) DTRY(launch(lo, std::min(max_jobs, n - lo)));
+        return NITI_NO_ERROR;
+    }
+    std::vector<AbsmaxJob> bucket_jobs;  // sum_bucket's table (kept: no allocation once it has grown)
     int ensure_comm_stream();
     int sum_bucket(int lo, hipStream_t wst);
     void attach(std::unique_ptr<Collective> c, std::unique_ptr<Collective> cg, bool shared, int world_, int rank_,
@@ -252,7 +263,10 @@ struct StepDriver {
 
 // the concrete drivers (null and *rc set when build() fails)
 std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, int* rc);
-std::unique_ptr<StepDriver> make_resnet_driver(int batch, int in_hw, int classes, int* rc);
+// a residual network of a stage list (ResNet-18's or the caller's), after resnet_check at its batch
+std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int in_hw, int batch, int* rc);
+// niti_model_resnet_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
+int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_layers, int shapes[][8]);
 // a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc);

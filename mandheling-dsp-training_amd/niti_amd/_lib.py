@@ -52,6 +52,8 @@ FORMAT_NCHW, FORMAT_NHWC, FORMAT_NC4HW4 = 0, 1, 2
 PAD_CAFFE, PAD_VALID, PAD_SAME = 0, 1, 2
 ARCH_LENET, ARCH_VGG11, ARCH_VGG16, ARCH_RESNET18 = 1, 2, 3, 4
 ARCH_CHAIN = 5  # a model of the caller's own layer list (niti_model_create_chain)
+ARCH_RESNET = 6  # a residual network of the caller's own stage list (niti_model_create_resnet)
+RESNET_MAX_STAGES, RESNET_MAX_LAYERS = 8, 256  # NITI_RESNET_MAX_STAGES / _LAYERS
 
 
 class NitiError(RuntimeError):
@@ -105,6 +107,13 @@ class Conv0Out(C.Structure):
 class ChainLayer(C.Structure):
     """niti_chain_layer: one layer of a user-defined chain network."""
     _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten")]
+
+
+class ResnetSpec(C.Structure):
+    """niti_resnet_spec: the stage list of a user-defined residual network."""
+    _fields_ = ([(n, C.c_int) for n in ("in_c", "stem_kernel", "stem_stride", "stem_pad", "stem_pool", "width",
+                                        "n_stages")] +
+                [("depths", C.c_int * RESNET_MAX_STAGES), ("classes", C.c_int)])
 
 
 class EvalTotals(C.Structure):
@@ -241,6 +250,9 @@ def lib():
         # (layers: a ChainLayer array, passed untyped)
         "niti_model_chain_check": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        # (spec: a ResnetSpec, passed untyped)
+        "niti_model_resnet_check": (ci, [vp, ci, C.POINTER(ci), vp]),
+        "niti_model_create_resnet": (ci, [vp, ci, ci, C.POINTER(vp)]),
         "niti_model_destroy": (None, [vp]),
         "niti_model_num_layers": (ci, [vp]),
         "niti_model_layer_info": (ci, [vp, ci, C.POINTER(ci)]),

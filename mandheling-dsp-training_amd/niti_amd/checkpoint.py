@@ -11,7 +11,8 @@ NITI_SGD, `NITI_SGD.hpp:20-54`).  A snapshot here holds exactly that state:
 
 stored as safetensors (no code executes on load) with `arch` / `num_layers` metadata; the snapshot
 of a user-defined chain network (arch ARCH_CHAIN) also carries its layer list and input as one
-JSON string under the metadata key `chain` (`load_chain`).  The
+JSON string under the metadata key `chain` (`load_chain`), that of a user-defined residual network
+(arch ARCH_RESNET) its stage list and input size under `resnet` (`load_resnet`).  The
 MNN flatbuffer container itself is not reproduced: `Variable::load` of that format needs
 the MNN schema, which is outside the hot path; the tensors and their order are the same.
 """
@@ -31,9 +32,17 @@ def chain_record(spec, in_c: int, in_hw: int) -> dict:
     return {"spec": normalize_spec(spec), "in_c": int(in_c), "in_hw": int(in_hw)}
 
 
-def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: dict | None = None) -> None:
+def resnet_record(spec, in_hw: int) -> dict:
+    """What a stage-list model's snapshot stores about its network (compared as a whole on load)."""
+    from .resnet import normalize_resnet_spec
+    return {"spec": normalize_resnet_spec(spec), "in_hw": int(in_hw)}
+
+
+def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: dict | None = None,
+                resnet: dict | None = None) -> None:
     """Write per-layer int8 OIHW weights and their int8 wscale side-car.  chain: a chain_record()
-    for a user-defined network (None: the file is a built-in network's, as it always was)."""
+    for a user-defined chain, resnet: a resnet_record() for a user-defined residual network (both
+    None: the file is a built-in network's, as it always was)."""
     if len(weights) != len(wscales):
         raise ValueError(f"{len(weights)} weights but {len(wscales)} wscales")
     tensors = {}
@@ -48,12 +57,14 @@ def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: d
     meta = {"format": FORMAT, "arch": str(int(arch)), "num_layers": str(len(weights)), "in_hw": str(int(in_hw))}
     if chain is not None:
         meta["chain"] = json.dumps(chain, sort_keys=True)
+    if resnet is not None:
+        meta["resnet"] = json.dumps(resnet, sort_keys=True)
     save_file(tensors, path, metadata=meta)
 
 
 def expect_chain(found, record, path: str) -> None:
-    """Refuse (ValueError) a snapshot whose chain record `found` is not the model's `record`; a
-    built-in model (record None) takes any snapshot its arch check let through."""
+    """Refuse (ValueError) a snapshot whose chain (or resnet) record `found` is not the model's
+    `record`; a built-in model (record None) takes any snapshot its arch check let through."""
     if record is not None and found != record:
         raise ValueError(f"{path}: the snapshot's layer list {found} differs from the model's {record}")
 
@@ -73,6 +84,23 @@ def load_chain(path: str):
         return chain_record(rec["spec"], rec["in_c"], rec["in_hw"])
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f"{path}: malformed chain record ({e!r})") from None
+
+
+def load_resnet(path: str):
+    """The resnet_record() a snapshot carries, or None."""
+    from safetensors import safe_open
+
+    with safe_open(path, framework="numpy") as f:
+        meta = f.metadata() or {}
+    if meta.get("format") != FORMAT:
+        raise ValueError(f"{path}: not a {FORMAT} snapshot (format={meta.get('format')!r})")
+    if "resnet" not in meta:
+        return None
+    try:
+        rec = json.loads(meta["resnet"])
+        return resnet_record(rec["spec"], rec["in_hw"])
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"{path}: malformed resnet record ({e!r})") from None
 
 
 def load_params(path: str):

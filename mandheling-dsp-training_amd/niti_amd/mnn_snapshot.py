@@ -269,6 +269,19 @@ def chain_of(meta: dict):
         raise ValueError(f"malformed chain record in the side-car ({e!r})") from None
 
 
+def resnet_of(meta: dict):
+    """The resnet_record() (niti_amd.checkpoint) of a side-car's metadata, or None: the stage list
+    and input size of a user-defined residual network, stored under `resnet`."""
+    rec = (meta or {}).get("resnet")
+    if rec is None:
+        return None
+    from .checkpoint import resnet_record
+    try:
+        return resnet_record(rec["spec"], rec["in_hw"])
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"malformed resnet record in the side-car ({e!r})") from None
+
+
 def load(path: str):
     """`Variable::load(path)`: the int8 parameters in file order, their wscales (None without a
     side-car) and the side-car metadata.  ValueError on anything that is not such a snapshot."""

@@ -27,6 +27,7 @@ class NitiModel:
         self._h = h
         self.arch, self.batch = arch, batch
         self.chain = None  # from_chain: the normalised layer list
+        self.resnet = None  # from_resnet: the normalised stage list
         self._wscale = {}
         self.layers = []
         for i in range(self._lib.niti_model_num_layers(h)):
@@ -55,6 +56,32 @@ class NitiModel:
         m._adopt(h, L.ARCH_CHAIN, batch)
         m.chain, m.in_c, m.in_hw = spec, int(in_c), int(in_hw)
         return m
+
+    @classmethod
+    def from_resnet(cls, spec, in_hw: int, batch: int, **kw) -> "NitiModel":
+        """A residual network of the caller's own stage list (niti_model_create_resnet): spec is a
+        dict as niti_amd.normalize_resnet_spec takes (keywords override its entries), over
+        in_c x in_hw x in_hw inputs.
+        ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one the library does not run --
+        nothing is allocated then.  The model reports arch ARCH_RESNET; .resnet holds the normalised
+        spec."""
+        from .resnet import normalize_resnet_spec, to_c
+        spec = normalize_resnet_spec(spec, **kw)
+        cs = to_c(spec)
+        m = cls.__new__(cls)
+        m._lib = L.lib()
+        h = C.c_void_p()
+        code = m._lib.niti_model_create_resnet(C.byref(cs), int(in_hw), int(batch), C.byref(h))
+        if code == L.INVALID_VALUE:
+            raise ValueError(f"malformed residual network for a {in_hw} x {in_hw} input at batch {batch}: {spec}")
+        check(code, "model_create_resnet")
+        m._adopt(h, L.ARCH_RESNET, batch)
+        m.resnet, m.in_hw = spec, int(in_hw)
+        return m
+
+    def _resnet_record(self):
+        from .checkpoint import resnet_record
+        return None if self.resnet is None else resnet_record(self.resnet, self.in_hw)
 
     def _chain_record(self):
         from .checkpoint import chain_record
@@ -91,7 +118,7 @@ class NitiModel:
             raise ValueError("save() before every layer's weight was set")
         save_params(path, [self.get_weight(i) for i in range(len(self.layers))],
                     [self._wscale[i] for i in range(len(self.layers))], self.arch,
-                    in_hw=self.layers[0]["h"], chain=self._chain_record())
+                    in_hw=self.layers[0]["h"], chain=self._chain_record(), resnet=self._resnet_record())
 
     def load(self, path: str):
         """Restore a snapshot written by save() into this model's device weights."""
@@ -101,6 +128,9 @@ class NitiModel:
             raise ValueError(f"snapshot is arch {arch} with {len(weights)} layers, model is arch {self.arch}")
         if self.chain is not None:
             expect_chain(load_chain(path), self._chain_record(), path)
+        if self.resnet is not None:
+            from .checkpoint import load_resnet
+            expect_chain(load_resnet(path), self._resnet_record(), path)
         # every layer's shape before any device write (a VGG-16 snapshot taken at another input
         # size has the same arch and layer count but a different first FC layer)
         for i, w in enumerate(weights):
@@ -125,6 +155,8 @@ class NitiModel:
         meta = {"arch": int(self.arch), "in_hw": int(self.layers[0]["h"])}
         if self.chain is not None:
             meta["chain"] = self._chain_record()
+        if self.resnet is not None:
+            meta["resnet"] = self._resnet_record()
         return meta
 
     def load_mnn(self, path: str):
@@ -136,6 +168,9 @@ class NitiModel:
         if self.chain is not None:
             from .checkpoint import expect_chain
             expect_chain(mnn_snapshot.chain_of(meta), self._chain_record(), path)
+        if self.resnet is not None:
+            from .checkpoint import expect_chain
+            expect_chain(mnn_snapshot.resnet_of(meta), self._resnet_record(), path)
         if len(weights) != len(self.layers):
             raise ValueError(f"{path}: {len(weights)} parameters, model has {len(self.layers)} layers")
         for i, w in enumerate(weights):
