@@ -268,6 +268,12 @@ int niti_conv_dgrad_phase2(const niti_geom* g, const int8_t* dy_nhwc16, const in
  * last mode-3 call used, [2] the mode-4 calls that redid */
 uint32_t* niti_rows_spec_slot(uint32_t* state, int dgrad);
 int niti_conv_rows_ok(const niti_geom* g);
+/* Which row-kernel instantiation a launch of g runs, by host arithmetic alone (no device call): W the
+ * image-row width the kernel is built for (0: the row-segment form), R its output rows per band, ks the
+ * channel chunks per wave of the K-split form (0: the general form), workgroups the launch's tiles.
+ * g is the LAYER's geometry; dgrad != 0 asks for its input gradient with a fused relu / pool
+ * gradient (niti_conv_dgrad_rows).  Returns 1, or 0 where niti_conv_rows_ok refuses the geometry. */
+int niti_conv_rows_plan(const niti_geom* g, int dgrad, int* W, int* R, int* ks, int* workgroups);
 int niti_nhwc16_to_c32(const int8_t* in_nhwc16, int n, int hw, int cp, int c, int8_t* out_c32, void* stream);
 int niti_weights_to_wf(const int8_t* w_ohwi16, int co, int ci, int cip, int transpose, int8_t* out_wf,
                        void* stream);

@@ -313,6 +313,13 @@ int niti_conv_rows_ok(const niti_geom* g) {
     return g && to_geom(g, &r) && niti::rowconv_ok(r) ? 1 : 0;
 }
 
+int niti_conv_rows_plan(const niti_geom* g, int dgrad, int* W, int* R, int* ks, int* workgroups) {
+    niti::ConvGeom r, d;
+    if (!g || !W || !R || !ks || !workgroups || !to_geom(g, &r)) return 0;
+    if (dgrad && !niti::rowconv_dgrad_geom(r, &d)) return 0;
+    return niti::rowconv_plan(dgrad ? d : r, dgrad != 0, W, R, ks, workgroups) ? 1 : 0;
+}
+
 int niti_nhwc16_to_c32(const int8_t* in, int n, int hw, int cp, int c, int8_t* out, void* stream) {
     if (!in || !out || n <= 0 || hw <= 0 || c <= 0 || cp < c || cp % 16) return NITI_INVALID_VALUE;
     return code(niti::nhwc16_to_c32(in, n, hw, cp, c, out, S(stream)));

@@ -413,6 +413,10 @@ bool rowconv_p16_ok(const ConvGeom& d, bool pool);
 // dg: for the input-gradient epilogues (at most 4 rows per unit)
 bool rowconv_fused_ok(const ConvGeom& g, bool dg = false);
 int rowconv_units(const ConvGeom& g, bool dg = false);
+// the instantiation and grid a launch of g runs (host arithmetic only, no device call): the kernel's W
+// (0: the row-segment form), rows per band R, chunks per wave of the K-split form (0: not K-split)
+// and the launch's workgroup tiles; false if rowconv_ok(g) is
+bool rowconv_plan(const ConvGeom& g, bool dg, int* W, int* R, int* ks, int* wgs);
 size_t rowconv_wf_bytes(int co, int ci);
 hipError_t nhwc16_to_c32(const int8_t* in, int n, int hw, int cp, int c, int8_t* out, hipStream_t st);
 // C32 [n][cb][hw][32] -> NHWC16 [n][hw][cp] (channels >= c written as zero)

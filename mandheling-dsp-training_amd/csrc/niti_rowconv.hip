@@ -155,7 +155,8 @@ struct RowConvArgs {
 
 // diagnostic stamps, 16 per wave: [0] start, [1] prologue issued, [2] cycles issuing loads, [3] K
 // loop done, [4] max reduced (+ grid barrier), [5] end, [6] cycles in the per-step waits +
-// barriers, [7] cycles in the per-step fragment reads (s_memtime, per-XCD clock); wave 0 of each
+// barriers, [7] cycles in the per-step fragment reads (s_memtime, per-XCD clock; [2] and [7] are 0
+// for W > 0, whose loads and reads are issued among the MFMAs: no phases to time); wave 0 of each
 // workgroup: [8] / [9] s_memrealtime (chip-wide 100 MHz) at the grid barrier's arrival / release
 #define RC_STAMP(k)                                                                                  \
     do {                                                                                             \
@@ -292,7 +293,13 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     // this wave's three DMA pieces of a chunk's 9 fragments (pieces 9..11 are dummies: OOB source)
     const uint32_t dv2 = wid == 0 ? (uint32_t)lane * 16u : OOB;
     const int cb = a.CB;
-    const uint32_t wbase = (uint32_t)(U.cob * cb * 9) * 1024u;
+    // (readfirstlane: the co block is the same for the whole workgroup, but hipcc cannot tell and
+    // would wrap each DMA, whose scalar offset this feeds, in a readfirstlane loop over the lanes.
+    // ONE_BLOCK is off for the row-segment form's fused launches, W = 0: VGG-16's steps measured
+    // 0.02 ms slower with them as one block, so they keep round 3's code)
+    constexpr bool ONE_BLOCK = W != 0;
+    const uint32_t wbase =
+        (uint32_t)(ONE_BLOCK ? __builtin_amdgcn_readfirstlane(U.cob * cb * 9) : U.cob * cb * 9) * 1024u;
     v4i X[S][KXL][NR];
     auto issue = [&](auto st_c, int cc) {
         constexpr int ST = decltype(st_c)::value;
@@ -310,7 +317,7 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
                 X[ST][kx][j] = buf_load16(rX, off[DPPX ? 1 : kx][j] + (uint32_t)cc * CHUNK);
     };
     const uint32_t lds_lane = lds_addr(smem) + (uint32_t)lane * 16u;
-    unsigned long long t_wait = 0, t_read = 0, t_issue = 0;
+    unsigned long long t_wait = 0, t_read = 0, t_issue = 0;  // (the last two: W = 0 only)
     const bool stamp = a.stamps != nullptr;
     // Software pipeline, per step c: wait for chunk c + 1's own loads (c + 2 stays in flight) and
     // meet at the barrier (chunk c + 1's weights are in LDS, chunk c - 1's stage is free), refill
@@ -335,34 +342,50 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
+    // A whole-image unit (one band: R == W) has the zero padding row above the image as its row 0
+    // and the one below it as its row NR - 1: their shifts and their three MFMAs each are left out
+    // (the rows are still loaded -- out of range, no data moves -- so L and the counted waits
+    // hold).  With more bands per image the kind of band differs between the waves of a
+    // workgroup; a wave-uniform branch round those MFMAs made hipcc carry the accumulator tile
+    // through VGPRs at every merge (48 v_accvgpr moves per step, what the 3 MFMAs save), and one
+    // copy of the loop per kind of band cost up to 60 more registers and scratch at R = 8, so
+    // those units multiply the zeros.
+    constexpr bool SKIP = W > 0 && R == W && !(RC_EXP & 32);
     auto step = [&](auto st_c, int cc) {
         constexpr int ST = decltype(st_c)::value, WB = ST & 1;
         const unsigned long long s0 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
         const bool more = UNC || cc + 1 < cb;
         if (more && !(RC_EXP & 2)) arrive(UNC || cc + 2 < cb ? 1 : 0);
+        // (ONE_BLOCK: the only stamp inside a step, beside the barrier -- a branch anywhere after it
+        // would cut the block in which hipcc places the loads and fragment reads among the MFMAs)
         const unsigned long long s1 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
+        if constexpr (ONE_BLOCK)
+            if (stamp) t_wait += s1 - s0;
         if ((UNC || cc + 3 < cb) && !(RC_EXP & 8)) issue(std::integral_constant<int, (ST + 3) % S>(), cc + 3);
-        if (stamp) {
-            asm volatile("" ::: "memory");
-            t_issue += __builtin_amdgcn_s_memtime() - s1;
-        }
+        if constexpr (!ONE_BLOCK)
+            if (stamp) {
+                asm volatile("" ::: "memory");
+                t_issue += __builtin_amdgcn_s_memtime() - s1;
+            }
         if (more && !(RC_EXP & 4)) read_w(std::integral_constant<int, (ST + 1) % S>(), wreg[1 - WB]);
         const v4i (&w)[9] = wreg[(RC_EXP & 4) ? 0 : WB];
         if constexpr (DPPX) {
             v4i XL[NR], XR[NR];
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
+            auto taps = [&](int j) {
                 XL[j] = (RC_EXP & 1) ? X[ST][0][j] : shift_in_left<WS>(X[ST][0][j], ox == 0);
                 XR[j] = (RC_EXP & 1) ? X[ST][0][j] : shift_in_right<WS>(X[ST][0][j], ox == WS - 1);
-            }
+            };
+            auto mfma3 = [&](int r, int ky) {
+                acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky], XL[r + ky], acc[r], 0, 0, 0);
+                acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + 1], X[ST][0][r + ky], acc[r], 0, 0, 0);
+                acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + 2], XR[r + ky], acc[r], 0, 0, 0);
+            };
+#pragma unroll
+            for (int j = SKIP ? 1 : 0; j < (SKIP ? NR - 1 : NR); ++j) taps(j);
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky], XL[r + ky], acc[r], 0, 0, 0);
-                    acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + 1], X[ST][0][r + ky], acc[r], 0, 0, 0);
-                    acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + 2], XR[r + ky], acc[r], 0, 0, 0);
-                }
+                for (int ky = SKIP && r == 0 ? 1 : 0; ky < (SKIP && r == R - 1 ? 2 : 3); ++ky) mfma3(r, ky);
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r)
@@ -372,11 +395,15 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
                     for (int kx = 0; kx < 3; ++kx)
                         acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + kx], X[ST][kx][r + ky], acc[r], 0, 0, 0);
         }
-        const unsigned long long s2 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
-        if (more) fence_w(wreg[1 - WB]);
-        if (stamp) {
-            t_wait += s1 - s0;
-            t_read += __builtin_amdgcn_s_memtime() - s2;
+        if constexpr (ONE_BLOCK) {
+            if (more) fence_w(wreg[1 - WB]);
+        } else {
+            const unsigned long long s2 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
+            if (more) fence_w(wreg[1 - WB]);
+            if (stamp) {
+                t_wait += s1 - s0;
+                t_read += __builtin_amdgcn_s_memtime() - s2;
+            }
         }
     };
 #pragma unroll
@@ -436,7 +463,8 @@ __device__ __forceinline__ void rowconv_compute_ks(const RowConvArgs& a, const R
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(a.wf, a.wbytes);
     const uint32_t xl = U.img_ok ? (uint32_t)((((int64_t)U.img * a.CB * H) * W + ox) * 32 + 16 * h) : OOB;
     constexpr uint32_t CHUNK = (uint32_t)H * W * 32;
-    const uint32_t wbase = (uint32_t)(U.cob * a.CB * 9) * 1024u;
+    // (readfirstlane: as in rowconv_compute, so each DMA's scalar offset is one to hipcc as well)
+    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(U.cob * a.CB * 9) * 1024u;
     int8_t* ring = smem + wid * (RC_KS_MAX_NS * 9 * 1024);
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -1318,8 +1346,14 @@ __device__ __forceinline__ void seg_run(const RowConvArgs& a, int lane, int wid,
 }
 
 // DG: the input-gradient epilogues (relu mask / pool gradient), their operands prefetched
+// Two instantiations that fit two workgroups per CU only just (253 / 255 registers) are held to it:
+// with the K-loop step one block, hipcc's freer schedule would take 8 / 16 registers more
 template <int W, int R, int MODE, bool DG, bool UNC, int KS>
-__global__ void __launch_bounds__(256, (RC_EXP & 16) ? 2 : 1) rowconv_fwd_kernel(RowConvArgs a) {
+constexpr bool RC_TWO_BLOCKS = (W == 16 || W == 4) && R == 4 && MODE == RC_REQUANT && !DG && UNC && KS == 0;
+
+template <int W, int R, int MODE, bool DG, bool UNC, int KS>
+__global__ void __launch_bounds__(256, ((RC_EXP & 16) || RC_TWO_BLOCKS<W, R, MODE, DG, UNC, KS>) ? 2 : 1)
+    rowconv_fwd_kernel(RowConvArgs a) {
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: DMA bases stay scalar
     const int c = lane & 31;
@@ -1818,6 +1852,13 @@ static int rowconv_wgs(const ConvGeom& g, bool dg, int* R_out, int* ks_out) {
     *R_out = R;
     *ks_out = ks;
     return ks > 0 ? COB * ngb : COB * ngb4 / 4;
+}
+
+bool rowconv_plan(const ConvGeom& g, bool dg, int* W, int* R, int* ks, int* wgs) {
+    if (!rowconv_ok(g)) return false;
+    *wgs = rowconv_wgs(g, dg, R, ks);
+    *W = rowconv_seg(g) ? 0 : g.w;
+    return true;
 }
 
 // FUSED needs every workgroup resident (one unit per wave, the grid barrier inside the kernel)

@@ -184,6 +184,7 @@ def lib():
         "niti_conv_wgrad_acc": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, C.c_size_t, vp]),
         "niti_conv_fwd_phase1": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, C.c_size_t, vp]),
         "niti_conv_rows_ok": (ci, [C.POINTER(Geom)]),
+        "niti_conv_rows_plan": (ci, [C.POINTER(Geom), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
         "niti_nhwc16_to_c32": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_weights_to_wf": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_conv_fwd_rows": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, C.c_uint32, vp,

@@ -211,6 +211,17 @@ def conv_rows_ok(g: L.Geom) -> bool:
     return bool(L.lib().niti_conv_rows_ok(C.byref(g)))
 
 
+def conv_rows_plan(g: L.Geom, dgrad=False):
+    """(W, R, ks, workgroups) of the row-kernel launch the layer of geometry g runs (dgrad: its input
+    gradient with a fused relu / pool gradient): rowconv_fwd_kernel<W, R, ...>, W = 0 the row-segment
+    form, ks > 0 the K-split form.  Host arithmetic only.  None where conv_rows_ok refuses g."""
+    w, r, ks, wgs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    if not L.lib().niti_conv_rows_plan(C.byref(g), 1 if dgrad else 0, C.byref(w), C.byref(r), C.byref(ks),
+                                       C.byref(wgs)):
+        return None
+    return w.value, r.value, ks.value, wgs.value
+
+
 def nhwc16_to_c32(x16: torch.Tensor, c: int, stream=None, out=None):
     """NHWC16 [n][h][w][cp] -> C32 [n][ceil(c/32)][h][w][32] (the register-fed conv's activations)."""
     n, h, w, cp = x16.shape
