@@ -479,6 +479,44 @@ typedef struct niti_sgd_job {
     int8_t* wft;
 } niti_sgd_job;
 int niti_sgd_update_many(const niti_sgd_job* jobs, int n_jobs, void* stream);
+/* Update bits: the learning rate of a training step, per parameter layer.
+ *
+ * In NITI the number of bits kept of the int32 weight gradient is the step size.  The reference
+ * froze it at 2 (NITI_GradientConv_Int8.cpp:274-296; 3 in its matmul op): rules 2 and 3 above.  A
+ * model keeps one int32 word per parameter layer in device memory, `update_bits` in 0..7, 2 from
+ * creation; the launches that apply a step's update (the update launch and the fully connected
+ * layers' fused update) read the layer's word.  With bw the bit width of the layer's gradient range
+ * (NITI_RangeEstimate) and acc its int32 gradient, w <- clip(w - g, +-127) with
+ *   bits == 2       exactly rule 2: bw == 0 gives g = 0, else g = PSTO(acc, bw - 2) -- including
+ *                   bw == 1, where the shift -1 goes through the reference's PSTO as its x86 build
+ *                   executes it.  This negative-shift case deliberately keeps the reference's
+ *                   behaviour.
+ *   bits 1, 3..7    this library's own extension, as the residual rule is (the reference has no such
+ *                   setting): bw == 0 gives g = 0; else sh = bw - bits; sh >= 0 gives
+ *                   g = PSTO(acc, sh); sh < 0 gives g = clip(acc, +-127) -- the gradient already
+ *                   fits in the bits asked for and is applied as it is.
+ *   bits == 0       the layer is frozen: its weights and every derived copy (the transposed, the
+ *                   fragment-major and the sub-pixel class weights) are neither changed nor
+ *                   rewritten; the kept int8 gradient (niti_model_get_tap which = 1) reads zero.  The
+ *                   weight gradient is still computed: no time is saved.
+ * The gradient exponent the drop-in DSP Executions report (bw - rule) is no part of a model step
+ * and is unchanged.
+ *
+ * niti_sgd_update_many_bits: the update launch alone under this rule, job k with bits_dev[k] (device
+ * memory, n_jobs words, each 0..7); the jobs' rule fields are ignored.  Beside niti_sgd_job's fields a
+ * job may carry subw, a stride-2 layer's sub-pixel class weights (the input gradient's layout), with
+ * the conv's kernel sub_kh x sub_kw (= kk) and top / left pads, and a deferred split-K combine: slab,
+ * `splits` [co][kk][cip] slabs slab_stride elements apart, summed into acc with their range into
+ * amax (zeroed by the caller) ahead of the update, as the training step does.  Either may be NULL. */
+typedef struct niti_sgd_bits_job {
+    niti_sgd_job job;
+    int8_t* subw;
+    int sub_kh, sub_kw, sub_pt, sub_pl;
+    const int32_t* slab;
+    int splits;
+    int64_t slab_stride;
+} niti_sgd_bits_job;
+int niti_sgd_update_many_bits(const niti_sgd_bits_job* jobs, int n_jobs, const int32_t* bits_dev, void* stream);
 /* The training step's first layer, alone.  niti_input_im2col: the batch (uint8 images quantised
  * with stats = niti_image_stats' four words over `count` pixels when quant, else int8 pixels as
  * they are) into xcol [n * oh * ow][32], the K = 32 im2col copy (stride 1; c / kh / kw = 3/3/3 or
@@ -788,6 +826,18 @@ int niti_model_get_predictions(niti_model_t m, int32_t* pred_host, void* stream)
  * models equal specs); the batch may differ -- how a batch-64 training model feeds a batch-20
  * evaluation model.  NITI_INVALID_VALUE otherwise.  Asynchronous. */
 int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream);
+/* The model's update bits (the rule: "Update bits" at niti_sgd_update_many_bits).
+ * niti_model_set_update_bits: layer's word <- bits (layer == -1: every layer), by a kernel on `stream`:
+ * asynchronous, in effect for the steps enqueued after it on that stream -- replays of an already
+ * captured step (niti_model_set_graph) included, which is neither re-captured nor dropped -- and
+ * for the dataset steps of niti_model_train_steps_dataset enqueued after it.  NITI_INVALID_VALUE
+ * for bits outside 0..7 or a layer out of range (nothing is written).
+ * niti_model_get_update_bits: synchronises `stream` and reads niti_model_num_layers words back.
+ * niti_model_copy_weights does not copy the words.  Data parallel: every rank holds its own words
+ * and the caller sets them on every rank; ranks that differ are the caller's error and are not
+ * detected (the ranks' weights then drift apart). */
+int niti_model_set_update_bits(niti_model_t m, int layer, int bits, void* stream);
+int niti_model_get_update_bits(niti_model_t m, int32_t* bits_host, void* stream);
 /* ---- device-resident dataset ----------------------------------------------------------- */
 /* A training or test set kept in device memory, and the batches of an epoch gathered out of it on
  * the device: shuffled, and with the pad-and-crop / horizontal-flip augmentation of CIFAR-class

@@ -697,6 +697,42 @@ int niti_sgd_update_many(const niti_sgd_job* jobs, int n_jobs, void* stream) {
     return code(niti::sgd_update_many(r, n_jobs, S(stream)));
 }
 
+int niti_sgd_update_many_bits(const niti_sgd_bits_job* jobs, int n_jobs, const int32_t* bits_dev, void* stream) {
+    if (!jobs || !bits_dev || n_jobs < 1 || n_jobs > niti::SGD_MAX_JOBS) return NITI_INVALID_VALUE;
+    niti::SgdJob r[niti::SGD_MAX_JOBS];
+    for (int j = 0; j < n_jobs; ++j) {
+        const niti_sgd_bits_job& b = jobs[j];
+        const niti_sgd_job& s = b.job;
+        if (!s.acc || !s.amax || !s.w_ohwi16) return NITI_INVALID_VALUE;
+        if (s.co < 1 || s.ci < 1 || s.kk < 1 || s.cip < s.ci || s.cop < s.co || s.cip % 16 || s.cop % 16)
+            return NITI_INVALID_VALUE;
+        if ((s.wf || s.wft) && (s.kk != 9 || s.ci % 32 != 0 || s.co % 32 != 0)) return NITI_NOT_SUPPORT;
+        if (b.subw && (b.sub_kh < 1 || b.sub_kw < 1 || b.sub_kh * b.sub_kw != s.kk || b.sub_pt < 0 || b.sub_pl < 0))
+            return NITI_INVALID_VALUE;
+        if (b.slab && (b.splits < 1 || b.slab_stride % 4 || b.slab_stride < (int64_t)s.co * s.kk * s.cip ||
+                       (((uintptr_t)b.slab | (uintptr_t)s.acc) & 15)))
+            return NITI_INVALID_VALUE;
+        // (the rule field is ignored: job j reads bits_dev[j])
+        r[j] = niti::SgdJob{s.acc, s.amax, -(1 + j), s.co, s.ci, s.kk, s.cip, s.cop, s.w_ohwi16, s.wt_ihwo16, s.g_out};
+        r[j].wf = s.wf;
+        r[j].wft = s.wft;
+        if (b.subw) {
+            r[j].subw = b.subw;
+            r[j].sub_kh = b.sub_kh;
+            r[j].sub_kw = b.sub_kw;
+            r[j].sub_pt = b.sub_pt;
+            r[j].sub_pl = b.sub_pl;
+        }
+        if (b.slab) {  // C-shaped slabs, summed into acc (and ranged into amax) ahead of the update
+            r[j].slab = b.slab;
+            r[j].splits = b.splits;
+            r[j].slab_stride = b.slab_stride;
+            r[j].slab_n = (int64_t)s.co * s.kk * s.cip;
+        }
+    }
+    return code(niti::sgd_update_many(r, n_jobs, S(stream), bits_dev));
+}
+
 int niti_input_im2col(const void* in, int quant, int n, int c, int h, int w, int kh, int kw, int pad_t, int pad_l,
                       const uint64_t* stats, int64_t count, int8_t* x_nchw, int8_t* xcol, int8_t* ascale,
                       const int8_t* w0, int co0, int cop0, uint32_t* amax0, void* stream) {

@@ -243,6 +243,7 @@ struct Epi {
     int8_t* sgd_g = nullptr;
     int sgd_rule = 0, sgd_ci = 0;
     int64_t sgd_ldt = 0;
+    const int32_t* sgd_bits = nullptr;  // EPI_SGD: the layer's update-bits word (read when sgd_rule < 1)
     RowMap rmap;  // STORE / REQUANT: where GEMM row m lands (sub-pixel classes)
     // REQUANT with the rescale fused (plan strategy STRAT_FUSED, every tile resident): each block
     // keeps its accumulators in registers across the row kernels' in-kernel grid barrier, which
@@ -461,8 +462,18 @@ __device__ __forceinline__ void gemm_epilogue(v16i (&acc)[TM][TN], int r0, int c
         // through an LDS tile, leaving as 16-byte row chunks.  Every weight of the tile is loaded
         // before the first store (the stores to w could alias later loads: issued in between, each
         // load would wait for a memory round trip of its own).
+        // The rule's class is the launch's: an immediate sgd_rule (>= 1), or the layer's update-bits
+        // word (one uniform load, issued ahead of the range read so the two are in flight together;
+        // sgd_bits is always a readable word): 2 is the immediate 2; any other value is the library's
+        // extension (a negative shift applies the gradient as it is: PSTO at shift 0), 0 a frozen
+        // layer -- no weight or transposed weight stored, the kept gradient zero.
+        const int word = *epi.sgd_bits;
         const int bw = bitwidth_of(read_max(epi.amax));
-        const int sh = bw - epi.sgd_rule;
+        const int ubits = epi.sgd_rule >= 1 ? epi.sgd_rule : (__builtin_amdgcn_readfirstlane(word) & 7);
+        const bool ext = epi.sgd_rule < 1 && ubits != 2;
+        const bool frozen = ext && ubits == 0;
+        const int sh = ext && bw - ubits < 0 ? 0 : bw - ubits;
+        const bool gzero = bw == 0 || frozen;
         const int j = lane & 3;
         const int col4 = c0 + 4 * ((lane & 31) >> 2);
         uint32_t wv[TM][TN][4];
@@ -486,7 +497,7 @@ __device__ __forceinline__ void gemm_epilogue(v16i (&acc)[TM][TN], int r0, int c
                     uint32_t gd = 0;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int32_t q = bw == 0 ? 0 : psto_any(acc[a][b][4 * gq + r], sh);
+                        const int32_t q = gzero ? 0 : psto_any(acc[a][b][4 * gq + r], sh);
                         gd |= ((uint32_t)q & 0xffu) << (8 * r);
                     }
                     gd = quad_transpose(gd, j);
@@ -501,7 +512,7 @@ __device__ __forceinline__ void gemm_epilogue(v16i (&acc)[TM][TN], int r0, int c
                             wn |= ((uint32_t)clip127((int32_t)(int8_t)(wo >> (8 * k)) - (int32_t)(int8_t)(gd >> (8 * k))) &
                                    0xffu)
                                   << (8 * k);
-                        *(uint32_t*)(epi.sgd_w + o) = wn;
+                        if (!frozen) *(uint32_t*)(epi.sgd_w + o) = wn;
                         if (epi.sgd_g != nullptr) *(uint32_t*)(epi.sgd_g + o) = gd;
                     }
                     // back to 4 rows of one column: a dword of the transposed tile
@@ -510,7 +521,7 @@ __device__ __forceinline__ void gemm_epilogue(v16i (&acc)[TM][TN], int r0, int c
                     *(uint32_t*)(smem + tcol * TP + trow) = wt;
                 }
         __syncthreads();
-        if (epi.sgd_wT != nullptr) {
+        if (epi.sgd_wT != nullptr && !frozen) {
             constexpr int CPR = BM / 16;  // 16-byte chunks per transposed row
             for (int t = tid; t < BN * CPR; t += NW * 64) {
                 const int cl = t / CPR, rl = (t - cl * CPR) * 16;
@@ -2679,8 +2690,9 @@ bool conv_wgrad_fc_sgd_ok(const ConvGeom& g) {
     return g.kh == 1 && g.kw == 1 && g.h == 1 && g.w == 1 && g.oh == 1 && g.ow == 1 && plain_1x1(g);
 }
 hipError_t conv_wgrad_fc_sgd(const ConvGeom& g, const int8_t* x, const int8_t* dy, uint32_t* amax, const SgdJob& j,
-                             int pass, hipStream_t st) {
+                             int pass, hipStream_t st, const int32_t* bits) {
     if (!conv_wgrad_fc_sgd_ok(g) || amax == nullptr || (pass == 1 && j.w == nullptr)) return hipErrorInvalidValue;
+    if (pass == 1 && j.rule < 1 && bits == nullptr) return hipErrorInvalidValue;
     // the EPI_SGD epilogue writes w, wT and the int8 gradient only: a job carrying the row kernels'
     // fragment-major copies, sub-pixel class weights or deferred slabs would leave them stale
     if (pass == 1 && (j.wf != nullptr || j.wft != nullptr || j.subw != nullptr || j.slab != nullptr))
@@ -2707,6 +2719,8 @@ hipError_t conv_wgrad_fc_sgd(const ConvGeom& g, const int8_t* x, const int8_t* d
     e.sgd_wT = j.wT;
     e.sgd_g = j.g_out;
     e.sgd_rule = j.rule;
+    // (as sgd_rule_word: the job names a table word; an immediate rule gets a readable word it ignores)
+    e.sgd_bits = j.rule < 1 ? bits + (-j.rule - 1) : (const int32_t*)amax;
     e.sgd_ci = j.ci;
     e.sgd_ldt = j.cop;
     return launch_mode<KtRowsU, KtRowsU, EPI_SGD, true>(p, la, lx, M, N, lg.K, e, st);
@@ -4359,7 +4373,9 @@ __global__ void __launch_bounds__(256) sgd_combine_kernel(SgdJobs jobs) {
     }
 }
 
-__global__ void sgd_update_kernel(SgdJobs jobs, int total) {
+// bits: the update-bits table the jobs with rule < 0 name a word of (sgd_rule_word; a launch without
+// one passes any readable word: word 0 is loaded, and ignored, for a job with an immediate rule)
+__global__ void sgd_update_kernel(SgdJobs jobs, int total, const int32_t* __restrict__ bits) {
     __shared__ int8_t T[64][64 + 4];
     // a block takes tiles b, b + gridDim, ...: one resident wave of blocks instead of a full
     // wave plus a straggling partial one.  The next tile's operands are loaded before this one is
@@ -4385,22 +4401,24 @@ __global__ void sgd_update_kernel(SgdJobs jobs, int total) {
     int bb = blockIdx.x;
     if (bb >= total) return;
     if (!NITI_SGD_PREFETCH) {  // one tile at a time
-        int last_j = -1, bw = 0;
+        int last_j = -1, bw = 0, rule = 0;
         for (; bb < total; bb += gridDim.x) {
             const Tile t = locate(bb);
             if (t.j != last_j) {
+                const int word = sgd_rule_word(jobs.job[t.j], bits);
                 bw = bitwidth_of(read_max(jobs.job[t.j].amax));
+                rule = sgd_rule_of(jobs.job[t.j], word);
                 last_j = t.j;
             }
             if (bb != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed reads are done
-            sgd_tile(jobs.job[t.j], bw, t.ci0, t.co0, t.k, T);
+            sgd_tile(jobs.job[t.j], bw, rule, t.ci0, t.co0, t.k, T);
         }
         return;
     }
     Tile cur = locate(bb);
     SgdTileIn cin, nin;  // (named, not an indexed pair: a dynamically indexed array would live in scratch)
     sgd_tile_load(jobs.job[cur.j], cur.ci0, cur.co0, cur.k, cin);
-    int last_j = -1, bw = 0;
+    int last_j = -1, bw = 0, rule = 0;
     for (; bb < total; bb += gridDim.x) {
         const int nb = bb + gridDim.x;
         Tile nxt = cur;
@@ -4409,11 +4427,13 @@ __global__ void sgd_update_kernel(SgdJobs jobs, int total) {
             sgd_tile_load(jobs.job[nxt.j], nxt.ci0, nxt.co0, nxt.k, nin);
         }
         if (cur.j != last_j) {
+            const int word = sgd_rule_word(jobs.job[cur.j], bits);
             bw = bitwidth_of(read_max(jobs.job[cur.j].amax));
+            rule = sgd_rule_of(jobs.job[cur.j], word);
             last_j = cur.j;
         }
         if (bb != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed reads are done
-        sgd_tile_finish(jobs.job[cur.j], bw, cur.ci0, cur.co0, cur.k, cin, T);
+        sgd_tile_finish(jobs.job[cur.j], bw, rule, cur.ci0, cur.co0, cur.k, cin, T);
         cur = nxt;
         cin = nin;
     }
@@ -4439,9 +4459,11 @@ hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st) {
+hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st, const int32_t* bits) {
     if (n <= 0) return hipSuccess;
     if (n > SGD_MAX_JOBS) return hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i)  // a job that names a table word needs the table
+        if (jobs[i].rule < 1 && bits == nullptr) return hipErrorInvalidValue;
     SgdJobs J{};
     J.n = n;
     int total = 0, chunks = 0;
@@ -4461,7 +4483,10 @@ hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st) {
         hipLaunchKernelGGL(sgd_combine_kernel, dim3(cgrid), dim3(256), 0, st, J);
     }
     const int grid = total < 1536 ? total : 1536;  // 6 blocks per CU
-    hipLaunchKernelGGL(sgd_update_kernel, dim3(grid), dim3(256), 0, st, J, total);
+    // (no table: the first job's range word stands in as the readable word no job uses)
+    const int32_t* table = bits != nullptr ? bits : (const int32_t*)jobs[0].amax;
+    if (table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sgd_update_kernel, dim3(grid), dim3(256), 0, st, J, total, table);
     return hipGetLastError();
 }
 
@@ -4469,6 +4494,24 @@ hipError_t sgd_update(const int32_t* acc, const uint32_t* amax, int rule, int co
                       int8_t* w, int8_t* wT, int8_t* g_out, hipStream_t st) {
     SgdJob j{acc, amax, rule, co, ci, kk, cip, cop, w, wT, g_out};
     return sgd_update_many(&j, 1, st);
+}
+
+// The update-bits words (include/niti_hip.h): word first + t <- v[t], the values travelling as kernel
+// arguments so the change is an ordinary launch on the caller's stream (ordered between steps, and
+// ahead of a replayed graph's update launches, which read the words); one thread per word.
+__global__ void update_bits_set_kernel(int32_t* __restrict__ bits, int first, int count, UpdateBitsArgs v) {
+    const int t = (int)threadIdx.x;
+    if (t < count) bits[first + t] = v.b[t];
+}
+hipError_t update_bits_set(int32_t* bits, int first, int count, const int32_t* values, hipStream_t st) {
+    if (bits == nullptr || values == nullptr || first < 0 || count < 0) return hipErrorInvalidValue;
+    for (int lo = 0; lo < count; lo += UPDATE_BITS_PER_LAUNCH) {
+        UpdateBitsArgs v{};
+        const int c = count - lo < UPDATE_BITS_PER_LAUNCH ? count - lo : UPDATE_BITS_PER_LAUNCH;
+        for (int t = 0; t < c; ++t) v.b[t] = values[lo + t];
+        hipLaunchKernelGGL(update_bits_set_kernel, dim3(1), dim3(UPDATE_BITS_PER_LAUNCH), 0, st, bits, first + lo, c, v);
+    }
+    return hipGetLastError();
 }
 
 // =====================================================================================

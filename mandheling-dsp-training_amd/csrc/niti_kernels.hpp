@@ -547,7 +547,7 @@ hipError_t requant_grad(const int32_t* acc, int64_t n, const uint32_t* amax, int
 struct SgdJob {
     const int32_t* acc;
     const uint32_t* amax;
-    int rule, co, ci, kk, cip, cop;
+    int rule, co, ci, kk, cip, cop;  // rule >= 1: immediate; -(1 + k): word k of the launch's update-bits table
     int8_t* w;
     int8_t* wT;
     int8_t* g_out;
@@ -609,14 +609,23 @@ inline int sgd_combine_chunks(int splits, int64_t slab_n) {
     const int per = 256 / sgd_combine_lanes(splits, slab_n);
     return (int)((slab_n / 4 + per - 1) / per);
 }
-hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st);
+// bits: the update-bits table (device, one int32 per layer; include/niti_hip.h) for jobs whose rule
+// is -(1 + k), which take word k of it in place of an immediate rule; may be null when no job does
+hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st, const int32_t* bits = nullptr);
+// words [first, first + count) of an update-bits table <- values (host), by kernel on `st`
+constexpr int UPDATE_BITS_PER_LAUNCH = 64;
+struct UpdateBitsArgs {
+    int32_t b[UPDATE_BITS_PER_LAUNCH];
+};
+hipError_t update_bits_set(int32_t* bits, int first, int count, const int32_t* values, hipStream_t st);
 hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st);  // its deferred combines alone
 // a fully connected layer (1x1 map): its weight gradient's range (pass 0), then the gradient
 // recomputed with job j's NITI_SGD step in the GEMM epilogue (pass 1; j.acc, wf, wft and the
 // slab fields unused) -- no int32 gradient tensor
 bool conv_wgrad_fc_sgd_ok(const ConvGeom& g);
+// (bits: as sgd_update_many's)
 hipError_t conv_wgrad_fc_sgd(const ConvGeom& g, const int8_t* x, const int8_t* dy, uint32_t* amax, const SgdJob& j,
-                             int pass, hipStream_t st);
+                             int pass, hipStream_t st, const int32_t* bits = nullptr);
 // exponent of a requantised weight gradient: bw - rule (0 for an all-zero gradient)
 hipError_t grad_exponent(const uint32_t* amax, int rule, int8_t* out, hipStream_t st);
 hipError_t sgd_update(const int32_t* acc, const uint32_t* amax, int rule, int co, int ci, int kk, int cip, int cop,

@@ -896,6 +896,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
     amax_bytes = (size_t)3 * nl * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (const int rc = alloc_eval()) return rc;
+    if (const int rc = alloc_update_bits()) return rc;
     if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
     // (the bucket SUMs, the GEMM weight gradients)
     for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{L[i].dwacc, L[i].w_elems(), rng(i, 2), L[i].g});
@@ -1657,7 +1658,8 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         // launch after the backward pass (the input gradients above read the old weights); the IHWO16
         // transpose feeds only the GEMM input gradient, the int8 gradient only the
         // niti_model_get tap (keep_grads)
-        jobs[i] = SgdJob{l.dwacc, rng(i, 2), RULE_WGRAD_BW2, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.w,
+        // (rule: the layer's update-bits word, read by the launch that applies the update)
+        jobs[i] = SgdJob{l.dwacc, rng(i, 2), -(1 + i), g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.w,
                          i > 0 && !rowconv_dgrad_layer(i) ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
         jobs[i].wf = l.rc ? l.wf : nullptr;
         jobs[i].wft = l.rcd ? l.wft : nullptr;
@@ -1693,9 +1695,9 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
     int n_many = 0;
     for (int i = 0; i < nl; ++i)
         if (!L[i].fc_sgd) many[n_many++] = jobs[i];
-    DTRY(sgd_update_many(many, n_many, st));  // (+ the deferred combines) also rewrites the fragment-major weight copies
+    DTRY(sgd_update_many(many, n_many, st, upd_bits));  // (+ the deferred combines) also rewrites the fragment-major weight copies
     for (int i = 0; i < nl; ++i)
-        if (L[i].fc_sgd) DTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st));
+        if (L[i].fc_sgd) DTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st, upd_bits));
     g8_written = keep_grads;
     return NITI_NO_ERROR;
 }

@@ -150,6 +150,14 @@ int niti_model_copy_weights(niti_model_t dst, niti_model_t src, void* stream) {
     return dst && src ? dst->d->copy_weights_from(*src->d, (hipStream_t)stream) : NITI_INVALID_VALUE;
 }
 
+int niti_model_set_update_bits(niti_model_t m, int layer, int bits, void* stream) {
+    return m ? m->d->set_update_bits(layer, bits, (hipStream_t)stream) : NITI_INVALID_VALUE;
+}
+
+int niti_model_get_update_bits(niti_model_t m, int32_t* bits_host, void* stream) {
+    return m && bits_host ? m->d->get_update_bits(bits_host, (hipStream_t)stream) : NITI_INVALID_VALUE;
+}
+
 int niti_model_get_input(niti_model_t m, int8_t* x_nchw_host, int* ascale, void* stream) {
     return m && x_nchw_host ? m->d->get_input(x_nchw_host, ascale, (hipStream_t)stream) : NITI_INVALID_VALUE;
 }

@@ -338,6 +338,7 @@ int ResNetModel::build(int batch_, int in_hw_, const niti_resnet_spec& spec_) {
     for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2), C[i].g});
     sgd_jobs.resize(nl);
     if (const int rc = alloc_eval()) return rc;
+    if (const int rc = alloc_update_bits()) return rc;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
 
@@ -586,7 +587,8 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     for (int i = 0; i < nl; ++i) {
         RConv& c = C[i];
         const ConvGeom& g = c.g;
-        jobs[i] = SgdJob{c.dwacc, rng(i, 2), RULE_WGRAD_BW2, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, c.w,
+        // (rule: the conv's update-bits word, whichever group's launch takes the job)
+        jobs[i] = SgdJob{c.dwacc, rng(i, 2), -(1 + i), g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, c.w,
                          i > 0 && !rows_dg_on(i) ? c.wT : nullptr, keep_grads ? c.g8 : nullptr};
         jobs[i].wf = c.rows ? c.wf : nullptr;
         jobs[i].wft = c.rows_dg ? c.wft : nullptr;
@@ -600,7 +602,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         // this conv's split-K slabs, combined in the update launch
         if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
-    rc = in_job_groups(nl, SGD_MAX_JOBS, [&](int first, int count) { return sgd_update_many(jobs + first, count, st); });
+    rc = in_job_groups(nl, SGD_MAX_JOBS, [&](int first, int count) { return sgd_update_many(jobs + first, count, st, upd_bits); });
     if (rc != NITI_NO_ERROR) return rc;
     g8_written = keep_grads;
     return NITI_NO_ERROR;

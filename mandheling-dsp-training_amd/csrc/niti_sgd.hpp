@@ -62,6 +62,25 @@ struct SgdTileIn {
     v4i a[4];  // this thread's 16 gradient words
     v16c w;    // and its 16 weights
 };
+// A job's update rule as the tile takes it: SgdJob::rule >= 1 is an immediate value (the reference's
+// rule 2 / 3: PSTO at any shift).  rule = -(1 + k) names word k of the launch's update-bits table
+// (include/niti_hip.h, "Update bits"): one uniform load per job; 2 there is the immediate 2, any
+// other value carries SGD_RULE_EXT (the library's extension: a negative shift applies the gradient
+// as it is) and 0 | SGD_RULE_EXT is a frozen layer.
+// In two halves so the word's load is in flight beside the job's range read and not ahead of it
+// (one memory latency per job, as before the table): sgd_rule_word issues the load -- word 0 for
+// an immediate rule, so the table pointer is always readable memory -- and sgd_rule_of decodes.
+constexpr int SGD_RULE_EXT = 0x100;
+constexpr int SGD_RULE_FROZEN = SGD_RULE_EXT;
+__device__ __forceinline__ int sgd_rule_word(const SgdJob& J, const int32_t* __restrict__ bits) {
+    const int r = __builtin_amdgcn_readfirstlane(J.rule);
+    return bits[r < 1 ? -r - 1 : 0];
+}
+__device__ __forceinline__ int sgd_rule_of(const SgdJob& J, int word) {
+    const int r = __builtin_amdgcn_readfirstlane(J.rule);
+    const int b = word & 7;
+    return r >= 1 ? r : (b == 2 ? 2 : (b | SGD_RULE_EXT));
+}
 __device__ __forceinline__ void sgd_tile_load(const SgdJob& J, int ci0, int co0, int k, SgdTileIn& in) {
     const int t = threadIdx.x;
     const int r = t >> 2, c = (t & 3) * 16;
@@ -73,14 +92,21 @@ __device__ __forceinline__ void sgd_tile_load(const SgdJob& J, int ci0, int co0,
         in.w = *(const v16c*)(J.w + idx);
     }
 }
-__device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0, int co0, int k, const SgdTileIn& in,
-                                                int8_t (*T)[64 + 4]) {
+__device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int rule, int ci0, int co0, int k,
+                                                const SgdTileIn& in, int8_t (*T)[64 + 4]) {
     const int t = threadIdx.x;
     // the rule's class is the tile's (bw and rule are per job): chosen once, wave-uniformly, each
     // class a straight-line body over the 16 elements -- a zero gradient (bw == 0), psto_fast
-    // (0 <= sh <= 30), psto_generic (its divisions only where a shift needs them)
+    // (0 <= sh <= 30), psto_generic (its divisions only where a shift needs them).  Under the
+    // update-bits extension (rule: sgd_rule_of's encoding) a negative shift applies the
+    // gradient as it is, clip(acc, +-127): that is psto_fast at shift 0, so no class of its own.  A
+    // frozen layer takes the zero-gradient class with every weight store skipped (uniform tests:
+    // as a branch around the tile it cost 4 VGPRs and an occupancy class of the whole kernel)
     const int ubw = __builtin_amdgcn_readfirstlane(bw);
-    const int sh = ubw - __builtin_amdgcn_readfirstlane(J.rule);
+    const int urule = __builtin_amdgcn_readfirstlane(rule);
+    const int sh0 = ubw - (urule & (SGD_RULE_EXT - 1));
+    const int sh = (urule & SGD_RULE_EXT) != 0 && sh0 < 0 ? 0 : sh0;
+    const bool frozen = urule == SGD_RULE_FROZEN;
     {
         const int r = t >> 2, c = (t & 3) * 16;
         v16c wn;
@@ -89,7 +115,7 @@ __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0
         if (co0 + r < J.co && ci0 + c < J.cip) {
             const int64_t idx = ((int64_t)(co0 + r) * J.kk + k) * J.cip + ci0 + c;
             v16c g;
-            if (ubw == 0) {
+            if (ubw == 0 || frozen) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) g[j] = 0;
             } else if (sh >= 0 && sh <= 30) {
@@ -101,9 +127,9 @@ __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0
             }
 #pragma unroll
             for (int j = 0; j < 16; ++j) wn[j] = (signed char)clip127((int32_t)in.w[j] - (int32_t)g[j]);
-            *(v16c*)(J.w + idx) = wn;
+            if (!frozen) *(v16c*)(J.w + idx) = wn;
             if (J.g_out != nullptr) *(v16c*)(J.g_out + idx) = g;
-            if (J.wf != nullptr) {  // WF [co/32][ci/32][9][2][32][16]: this row's 16 ci of one co
+            if (J.wf != nullptr && !frozen) {  // WF [co/32][ci/32][9][2][32][16]: this row's 16 ci of one co
                 const int o = co0 + r, i0 = ci0 + c, cb = (J.ci + 31) / 32;
                 *(v16c*)(J.wf + (((((int64_t)(o >> 5) * cb + (i0 >> 5)) * 9 + k) * 2 + ((i0 >> 4) & 1)) * 32 + (o & 31)) * 16) = wn;
             }
@@ -112,7 +138,7 @@ __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0
         for (int j = 0; j < 16; ++j) T[r][c + j] = wn[j];
     }
     __syncthreads();
-    if (J.wT != nullptr || J.wft != nullptr || J.subw != nullptr) {
+    if (!frozen && (J.wT != nullptr || J.wft != nullptr || J.subw != nullptr)) {
         const int r = t >> 2, c = (t & 3) * 16;  // r: ci within the tile, c: co offset
         if (ci0 + r < J.ci && co0 + c < J.cop) {
             v16c o;
@@ -139,10 +165,10 @@ __device__ __forceinline__ void sgd_tile_finish(const SgdJob& J, int bw, int ci0
         }
     }
 }
-__device__ __forceinline__ void sgd_tile(const SgdJob& J, int bw, int ci0, int co0, int k, int8_t (*T)[64 + 4]) {
+__device__ __forceinline__ void sgd_tile(const SgdJob& J, int bw, int rule, int ci0, int co0, int k, int8_t (*T)[64 + 4]) {
     SgdTileIn in;
     sgd_tile_load(J, ci0, co0, k, in);
-    sgd_tile_finish(J, bw, ci0, co0, k, in, T);
+    sgd_tile_finish(J, bw, rule, ci0, co0, k, in, T);
 }
 
 // NITI_LOSS_Grad rows (niti_kernels.hip loss_grad*, niti_head.hip): see loss_grad in niti_kernels.hpp

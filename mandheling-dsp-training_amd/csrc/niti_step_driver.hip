@@ -289,6 +289,30 @@ int StepDriver::train_metrics_read(niti_eval_totals* host_out, hipStream_t st) {
     return NITI_NO_ERROR;
 }
 
+// ------------------------------------------------------------------------------ update bits
+int StepDriver::alloc_update_bits() {
+    const int nl = num_layers();
+    upd_bits = (int32_t*)ws.alloc((size_t)std::max(nl, 1) * 4);
+    if (!upd_bits) return NITI_OUT_OF_MEMORY;
+    const std::vector<int32_t> two(nl, 2);
+    DTRY(hipMemcpy(upd_bits, two.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::set_update_bits(int layer, int bits, hipStream_t st) {
+    const int nl = num_layers();
+    if (bits < 0 || bits > 7 || layer < -1 || layer >= nl) return NITI_INVALID_VALUE;
+    const std::vector<int32_t> v(layer < 0 ? nl : 1, bits);
+    DTRY(update_bits_set(upd_bits, layer < 0 ? 0 : layer, (int)v.size(), v.data(), st));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::get_update_bits(int32_t* bits_host, hipStream_t st) {
+    DTRY(hipStreamSynchronize(st));
+    DTRY(hipMemcpy(bits_host, upd_bits, (size_t)num_layers() * 4, hipMemcpyDeviceToHost));
+    return NITI_NO_ERROR;
+}
+
 int StepDriver::rowconv_error() {
     uint32_t e = 0;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&e, rc_err, 4, hipMemcpyDeviceToHost) != hipSuccess)

@@ -219,6 +219,16 @@ struct StepDriver {
     void* tm_ws = nullptr;
     int train_metrics_reset(hipStream_t st);
     int train_metrics_read(niti_eval_totals* host_out, hipStream_t st);
+    // ---- update bits (include/niti_hip.h): one int32 per parameter layer, the bits of the gradient
+    // its update keeps.  An allocation of its own (never among the range words, which every step
+    // zeroes), 2 everywhere from build().  The update launches read it (SgdJob::rule = -(1 + layer)
+    // with this table); only set_update_bits writes it, by kernel on the caller's stream, so a change
+    // is ordered between enqueued steps and holds for replays of a captured step.  Autotuning, the
+    // phase runs and the probe neither read nor write it.
+    int32_t* upd_bits = nullptr;
+    int alloc_update_bits();
+    int set_update_bits(int layer, int bits, hipStream_t st);  // layer -1: every layer
+    int get_update_bits(int32_t* bits_host, hipStream_t st);
     // the shared half of plan_set: the tile set {64, 128, 256} or the taps tile (own_tile: a tile of
     // the driver's own, which it vouches for), the strategy range, strategies 3 and 4 only for
     // unsplit activation GEMMs; then the override, with the split-K slabs it needs (gemm_slab)

@@ -12,5 +12,6 @@ from .dataset import (DeviceDataset, center_windows, make_order, make_rrc_order,
                       random_fraction_windows, unpack_xform)
 from .chain import chain_layers, normalize_spec  # noqa: F401
 from .resnet import normalize_resnet_spec, resnet_layers  # noqa: F401
+from .schedule import bits_schedule  # noqa: F401
 
 lib()  # fail loudly if the HIP library is missing

@@ -98,6 +98,13 @@ class SgdJob(C.Structure):
                 [(n, C.c_void_p) for n in ("w_ohwi16", "wt_ihwo16", "g_out", "wf", "wft")])
 
 
+class SgdBitsJob(C.Structure):
+    """niti_sgd_bits_job: one layer's update of niti_sgd_update_many_bits."""
+    _fields_ = ([("job", SgdJob), ("subw", C.c_void_p)] +
+                [(n, C.c_int) for n in ("sub_kh", "sub_kw", "sub_pt", "sub_pl")] +
+                [("slab", C.c_void_p), ("splits", C.c_int), ("slab_stride", C.c_int64)])
+
+
 class Conv0Out(C.Structure):
     """niti_conv0_out: the outputs and options of niti_conv0_fwd."""
     _fields_ = ([(n, C.c_void_p) for n in ("out", "pool_out", "pool_code", "pool_c32", "out_c32", "exp_in",
@@ -209,6 +216,9 @@ def lib():
         "niti_sgd_update": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "niti_sgd_combine": (ci, [C.POINTER(SgdCombineJob), ci, vp]),
         "niti_sgd_update_many": (ci, [C.POINTER(SgdJob), ci, vp]),
+        "niti_sgd_update_many_bits": (ci, [C.POINTER(SgdBitsJob), ci, vp, vp]),
+        "niti_model_set_update_bits": (ci, [vp, ci, ci, vp]),
+        "niti_model_get_update_bits": (ci, [vp, C.POINTER(i32), vp]),
         "niti_input_im2col": (ci, [vp] + [ci] * 9 + [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp]),
         "niti_conv0_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(Conv0Out), ci, vp]),
         "niti_diag_conv0_blocks": (None, [C.c_int]),

@@ -39,10 +39,11 @@ def resnet_record(spec, in_hw: int) -> dict:
 
 
 def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: dict | None = None,
-                resnet: dict | None = None) -> None:
+                resnet: dict | None = None, update_bits=None) -> None:
     """Write per-layer int8 OIHW weights and their int8 wscale side-car.  chain: a chain_record()
     for a user-defined chain, resnet: a resnet_record() for a user-defined residual network (both
-    None: the file is a built-in network's, as it always was)."""
+    None: the file is a built-in network's, as it always was).  update_bits: the model's per-layer
+    update bits, recorded (metadata key `update_bits`) only when some layer differs from 2."""
     if len(weights) != len(wscales):
         raise ValueError(f"{len(weights)} weights but {len(wscales)} wscales")
     tensors = {}
@@ -59,6 +60,8 @@ def save_params(path: str, weights, wscales, arch: int, in_hw: int = 0, chain: d
         meta["chain"] = json.dumps(chain, sort_keys=True)
     if resnet is not None:
         meta["resnet"] = json.dumps(resnet, sort_keys=True)
+    if update_bits is not None and any(int(b) != 2 for b in update_bits):
+        meta["update_bits"] = json.dumps([int(b) for b in update_bits])
     save_file(tensors, path, metadata=meta)
 
 
@@ -101,6 +104,34 @@ def load_resnet(path: str):
         return resnet_record(rec["spec"], rec["in_hw"])
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f"{path}: malformed resnet record ({e!r})") from None
+
+
+def check_update_bits(bits, n_layers: int, path: str):
+    """The `update_bits` record of a snapshot as a list of n_layers ints in 0..7 (ValueError
+    otherwise); None stays None."""
+    if bits is None:
+        return None
+    try:
+        bits = [int(b) for b in bits]
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"{path}: malformed update_bits ({e!r})") from None
+    if len(bits) != n_layers or any(not 0 <= b <= 7 for b in bits):
+        raise ValueError(f"{path}: update_bits {bits} for a model of {n_layers} layers (one value in 0..7 each)")
+    return bits
+
+
+def load_update_bits(path: str):
+    """The update bits a snapshot carries (a list), or None: a snapshot of a model at the default."""
+    from safetensors import safe_open
+
+    with safe_open(path, framework="numpy") as f:
+        meta = f.metadata() or {}
+    if "update_bits" not in meta:
+        return None
+    try:
+        return list(json.loads(meta["update_bits"]))
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"{path}: malformed update_bits ({e!r})") from None
 
 
 def load_params(path: str):

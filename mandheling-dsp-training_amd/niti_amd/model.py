@@ -118,11 +118,12 @@ class NitiModel:
             raise ValueError("save() before every layer's weight was set")
         save_params(path, [self.get_weight(i) for i in range(len(self.layers))],
                     [self._wscale[i] for i in range(len(self.layers))], self.arch,
-                    in_hw=self.layers[0]["h"], chain=self._chain_record(), resnet=self._resnet_record())
+                    in_hw=self.layers[0]["h"], chain=self._chain_record(), resnet=self._resnet_record(),
+                    update_bits=self.update_bits())
 
     def load(self, path: str):
         """Restore a snapshot written by save() into this model's device weights."""
-        from .checkpoint import expect_chain, load_chain, load_params
+        from .checkpoint import check_update_bits, expect_chain, load_chain, load_params, load_update_bits
         weights, wscales, arch = load_params(path)
         if arch != self.arch or len(weights) != len(self.layers):
             raise ValueError(f"snapshot is arch {arch} with {len(weights)} layers, model is arch {self.arch}")
@@ -136,8 +137,11 @@ class NitiModel:
         for i, w in enumerate(weights):
             if tuple(w.shape) != self.weight_shape(i):
                 raise ValueError(f"snapshot layer {i} is {tuple(w.shape)}, model layer is {self.weight_shape(i)}")
+        bits = check_update_bits(load_update_bits(path), len(self.layers), path)
         for i, (w, s) in enumerate(zip(weights, wscales)):
             self.set_weight(i, w, s)
+        if bits is not None:  # (a snapshot without the key leaves the model's own)
+            self.set_update_bits(bits)
 
     def save_mnn(self, path: str):
         """The reference's own snapshot: `Variable::save(model->parameters(), path)` -- an MNN Net
@@ -157,6 +161,9 @@ class NitiModel:
             meta["chain"] = self._chain_record()
         if self.resnet is not None:
             meta["resnet"] = self._resnet_record()
+        bits = self.update_bits()
+        if any(b != 2 for b in bits):  # (a default model's side-car stays what it always was)
+            meta["update_bits"] = bits
         return meta
 
     def load_mnn(self, path: str):
@@ -180,8 +187,12 @@ class NitiModel:
             if len(self._wscale) != len(self.layers):
                 raise ValueError(f"{path}: no wscale side-car and the model's scales are not set")
             wscales = [self._wscale[i] for i in range(len(self.layers))]
+        from .checkpoint import check_update_bits
+        bits = check_update_bits((meta or {}).get("update_bits"), len(self.layers), path)
         for i, (w, s) in enumerate(zip(weights, wscales)):
             self.set_weight(i, w, s)
+        if bits is not None:
+            self.set_update_bits(bits)
 
     def get_weight(self, i) -> np.ndarray:
         w = np.empty(self.weight_shape(i), np.int8)
@@ -247,9 +258,42 @@ class NitiModel:
               "get_predictions")
         return out
 
+    # ---- update bits: the learning rate (include/niti_hip.h, "Update bits")
+    def set_update_bits(self, bits, stream=None):
+        """How many bits of each layer's weight gradient its update keeps -- NITI's learning rate --
+        set on the device by a launch on `stream`: in effect for the steps enqueued after it (replays
+        of a captured step included).  bits: an int for every layer, a sequence of one value per
+        layer, or a dict {layer: bits}; each in 0..7, 2 the default (the reference's rule), 0 a
+        frozen layer.  Everything is checked before the first launch.  Data parallel: set the same
+        values on every rank (a mismatch is not detected)."""
+        n = len(self.layers)
+        if isinstance(bits, dict):
+            items = [(int(k), v) for k, v in bits.items()]
+        elif isinstance(bits, (int, np.integer)):
+            items = [(-1, bits)]
+        else:
+            bits = list(bits)
+            if len(bits) != n:
+                raise ValueError(f"{len(bits)} update bits for a model of {n} layers")
+            items = list(enumerate(bits))
+        for layer, b in items:
+            if not isinstance(b, (int, np.integer)) or isinstance(b, bool) or not 0 <= int(b) <= 7:
+                raise ValueError(f"update bits {b!r}: an int in 0..7")
+            if not -1 <= layer < n or (layer == -1 and len(items) != 1):
+                raise ValueError(f"layer {layer} out of range (model has {n})")
+        for layer, b in items:
+            check(self._lib.niti_model_set_update_bits(self._h, layer, int(b), _stream(stream)), "set_update_bits")
+
+    def update_bits(self, stream=None) -> list:
+        """Every layer's update bits, read back from the device (synchronises)."""
+        out = (C.c_int32 * len(self.layers))()
+        check(self._lib.niti_model_get_update_bits(self._h, out, _stream(stream)), "get_update_bits")
+        return [int(v) for v in out]
+
     def copy_weights_from(self, other: "NitiModel", stream=None):
         """Device-to-device copy of every layer's weights and weight scale from a model of the same
-        architecture, input size and class count (the batch may differ)."""
+        architecture, input size and class count (the batch may differ).  The update bits are not
+        copied (the copy's use is an evaluation model)."""
         check(self._lib.niti_model_copy_weights(self._h, other._h, _stream(stream)), "copy_weights")
         self._wscale = dict(other._wscale)
 
@@ -284,13 +328,17 @@ class NitiModel:
         check(self._lib.niti_model_eval_steps_dataset(self._h, ds._h, int(first_step), int(n_steps), _stream(stream)),
               "eval_steps_dataset")
 
-    def fit_epoch(self, ds, seed: int, epoch: int, pad: int = 0, flip: bool = False, stream=None, rrc=None) -> int:
+    def fit_epoch(self, ds, seed: int, epoch: int, pad: int = 0, flip: bool = False, stream=None, rrc=None,
+                  update_bits=None) -> int:
         """One epoch over ds: make_order(ds.count, batch, seed, epoch, pad, flip) -- the last partial
         batch dropped -- set as ds's order (one device synchronisation), then every step enqueued.
         rrc (a dict with `scale` and / or `ratio`, may be empty; needs pad == 0): the order is
         make_rrc_order's instead, a random-resized crop of every stored image to ds's output size.
+        update_bits (as set_update_bits takes): set on the stream ahead of the epoch's steps.
         Returns the number of steps; asynchronous."""
         from .dataset import make_order, make_rrc_order
+        if update_bits is not None:
+            self.set_update_bits(update_bits, stream)
         if rrc is not None:
             if pad != 0:
                 raise ValueError("rrc needs pad == 0")

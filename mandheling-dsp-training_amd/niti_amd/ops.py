@@ -560,6 +560,38 @@ def sgd_update_many(jobs, stream=None):
     check(L.lib().niti_sgd_update_many(arr, len(jobs), _stream(stream)), "sgd_update_many")
 
 
+def sgd_update_many_bits(jobs, bits, stream=None):
+    """The update launch under the update-bits rule (niti_sgd_update_many_bits): job k takes
+    bits[k] (an int32 device tensor of len(jobs) values in 0..7; a `rule` entry is ignored).  jobs:
+    sgd_update_many's dicts, optionally with subw (a stride-2 layer's sub-pixel class weights, with
+    sub = (kh, kw, pad_t, pad_l)) and slab (int32 [splits][stride] slabs summed into acc, their
+    range into the zeroed amax, ahead of the update)."""
+    assert bits.dtype == torch.int32 and bits.numel() == len(jobs) and bits.is_cuda
+    arr = (L.SgdBitsJob * len(jobs))()
+    for j, job in enumerate(jobs):
+        acc, w16 = job["acc"], job["w16"]
+        co, kh, kw, cip = acc.shape
+        assert acc.dtype == torch.int32 and w16.shape == acc.shape and acc.is_contiguous() and w16.is_contiguous()
+        a = arr[j].job
+        a.acc, a.amax = acc.data_ptr(), job["amax"].data_ptr()
+        a.rule, a.co, a.ci, a.kk = 0, co, job["ci"], kh * kw
+        a.cip, a.cop = cip, r16(co)
+        a.w_ohwi16 = w16.data_ptr()
+        for name, key in (("wt_ihwo16", "wT"), ("g_out", "g"), ("wf", "wf"), ("wft", "wft")):
+            t = job.get(key)
+            setattr(a, name, None if t is None else t.data_ptr())
+        subw = job.get("subw")
+        if subw is not None:
+            arr[j].subw = subw.data_ptr()
+            arr[j].sub_kh, arr[j].sub_kw, arr[j].sub_pt, arr[j].sub_pl = job["sub"]
+        slab = job.get("slab")
+        if slab is not None:
+            assert slab.dtype == torch.int32 and slab.dim() == 2 and slab.is_contiguous()
+            assert slab.shape[1] >= acc.numel()
+            arr[j].slab, arr[j].splits, arr[j].slab_stride = slab.data_ptr(), slab.shape[0], slab.shape[1]
+    check(L.lib().niti_sgd_update_many_bits(arr, len(jobs), _ptr(bits), _stream(stream)), "sgd_update_many_bits")
+
+
 def input_im2col(x, kernel, pad, stats=None, count=None, w0=None, co0=0, amax0=None, stream=None):
     """The first layer's im2col copy straight from the batch (niti_input_im2col): x uint8 images
     (quantised with `stats`, image_stats' words over `count` pixels) or int8 pixels, NCHW ->
