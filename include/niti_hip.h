@@ -545,6 +545,25 @@ typedef struct niti_conv0_out {
 int niti_conv0_fwd(const niti_geom* g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const niti_conv0_out* o,
                    int pass, void* stream);
 void niti_diag_conv0_blocks(int n);
+/* The first layer's weight gradient from the pooled gradient and the pool codes, alone.
+ * niti_conv0_wgrad_codes: dW0[co][k] = sum over pooled pixels q and window elements t of (g0[q][co]
+ * where bit t of code[q][co] is set, else 0) * xcol[pixel t of q's window][k].  g0 and code:
+ * [n][oh/2][ow/2][cop] int8 (code: the route bytes niti_conv0_fwd's pool_code holds), xcol
+ * [n * oh * ow][32].  The launch leaves *slabs partial sums [cop][32] int32 in slab, cop * 32 elements
+ * apart, for niti_sgd_combine (or any sum); niti_conv0_wgrad_codes_slabs is that count, for sizing.
+ * blocks: 0 the entry's default, else clamped to the number of 64-pixel steps.  NITI_INVALID_VALUE
+ * (nothing launched): oh or ow odd, cop not 32 or 64, k > 32, an operand of 2^31 bytes or more,
+ * slab_bytes too small.
+ * niti_diag_conv0_wgrad_blocks: the block count the training step passes (0: the default).
+ * niti_diag_conv0_wgrad_codes: whether the training step takes this form where it is eligible: -1 the
+ * model's own choice (the autotuner's, else the default), 0 off, 1 on (env NITI_CONV0_WGRAD_CODES
+ * sets the starting value); niti_diag_conv0_wgrad_codes_launches counts its launches by the step. */
+int niti_conv0_wgrad_codes(int n, int oh, int ow, int cop, int k, const int8_t* g0, const int8_t* code,
+                           const int8_t* xcol, int blocks, int32_t* slab, size_t slab_bytes, int* slabs, void* stream);
+int niti_conv0_wgrad_codes_slabs(int n, int oh, int ow, int cop, int k, int blocks);
+void niti_diag_conv0_wgrad_blocks(int n);
+void niti_diag_conv0_wgrad_codes(int mode);
+unsigned long long niti_diag_conv0_wgrad_codes_launches(void);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);

@@ -767,6 +767,18 @@ int niti_conv0_fwd(const niti_geom* g, const int8_t* xcol, const int8_t* w, uint
 }
 void niti_diag_conv0_blocks(int n) { niti::diag_conv0_blocks(n); }
 
+int niti_conv0_wgrad_codes(int n, int oh, int ow, int cop, int k, const int8_t* g0, const int8_t* code_bytes,
+                           const int8_t* xcol, int blocks, int32_t* slab, size_t slab_bytes, int* slabs, void* stream) {
+    return code(niti::conv0_wgrad_codes(n, oh, ow, cop, k, g0, code_bytes, xcol, blocks, slab, slab_bytes, slabs,
+                                        S(stream)));
+}
+int niti_conv0_wgrad_codes_slabs(int n, int oh, int ow, int cop, int k, int blocks) {
+    return niti::conv0_wgrad_codes_ok(n, oh, ow, cop, k) ? niti::conv0_wgrad_codes_blocks(n, oh, ow, blocks) : 0;
+}
+void niti_diag_conv0_wgrad_blocks(int n) { niti::diag_conv0_wgrad_blocks(n); }
+void niti_diag_conv0_wgrad_codes(int mode) { niti::model_conv0_wgrad_codes(mode); }
+unsigned long long niti_diag_conv0_wgrad_codes_launches(void) { return niti::model_conv0_wgrad_codes_launches(); }
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

@@ -287,6 +287,23 @@ hipError_t conv0_fwd(const ConvGeom& g, const int8_t* xcol, const int8_t* w, uin
                      int pass, hipStream_t st,
                      int8_t* pool_c32 = nullptr, int8_t* out_c32 = nullptr, int8_t* pool_code = nullptr);
 void diag_conv0_blocks(int n);  // conv0_fwd's grid (0: its default), diagnostic
+// ---- the first layer's weight gradient from the pooled gradient and the pool codes (niti_conv0_wgrad.hip)
+// dW0[co][k] = sum over pooled pixels q and window elements t of (g0[q][co] where bit t of code[q][co]
+// is set, else 0) * xcol[pixel t of q's window][k]: g0 and code NHWC16-shaped [n][oh/2][ow/2][cop]
+// (code: pool_code4 bytes, as conv0_fwd / a row kernel's forward records them), xcol [n*oh*ow][32].
+// The launch leaves *slabs C-shaped partial sums [cop][32] int32 in slab (cop * 32 elements apart) for
+// splitk_reduce_linear or the update launch's combine.  blocks: 0 the entry's default, else clamped to
+// the number of 64-pixel steps (and to 256).  hipErrorInvalidValue, nothing launched: oh or ow odd,
+// cop not 32 or 64, k > 32, an operand of 2^31 bytes or more, slab_bytes too small.
+bool conv0_wgrad_codes_ok(int n, int oh, int ow, int cop, int k);
+int conv0_wgrad_codes_blocks(int n, int oh, int ow, int blocks);  // the slabs a launch writes
+hipError_t conv0_wgrad_codes(int n, int oh, int ow, int cop, int k, const int8_t* g0, const int8_t* code,
+                             const int8_t* xcol, int blocks, int32_t* slab, size_t slab_bytes, int* slabs,
+                             hipStream_t st);
+void diag_conv0_wgrad_blocks(int n);    // niti_diag_conv0_wgrad_blocks: the model path's block count
+int conv0_wgrad_codes_model_blocks();
+void model_conv0_wgrad_codes(int mode);  // niti_model.hip: niti_diag_conv0_wgrad_codes
+unsigned long long model_conv0_wgrad_codes_launches();
 bool conv_dgrad_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // The speculative pair on the implicit GEMM (plan strategy 3 = STRAT_SPEC, forward / input
 // gradient, no K split; NITI_Conv_Int8.cpp:260-307, NITI_DeConv_Int8.cpp:294-329): pass 0 (launch A)

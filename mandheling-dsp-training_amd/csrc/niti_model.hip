@@ -34,11 +34,15 @@ namespace {
 extern int g_p16_jobs_cap;
 extern int g_wgrad_batch;
 extern int g_wgrad_quad;
+extern int g_c0w_mode;
+extern unsigned long long g_c0w_launches;
 }
 void model_p16_jobs_cap(int cap) { g_p16_jobs_cap = cap <= 0 ? P16_MAX_JOBS : cap; }
 void model_wgrad_batch(int mode) { g_wgrad_batch = mode < 0 ? 1 : mode; }
 void model_wgrad_quad(int kg) { g_wgrad_quad = kg < 0 ? -1 : kg; }
 int wgrad_quad_kg(int own) { return g_wgrad_quad >= 0 ? g_wgrad_quad : own; }
+void model_conv0_wgrad_codes(int mode) { g_c0w_mode = mode < 0 ? -1 : (mode > 0 ? 1 : 0); }
+unsigned long long model_conv0_wgrad_codes_launches() { return g_c0w_launches; }
 
 namespace {
 
@@ -100,6 +104,13 @@ constexpr int WGRAD_BATCH_T = 256;
 // wgb_quad, the op entry's P16_QUAD_KG), 0 no quad items, k > 0 that many K groups; NITI_WGRAD_QUAD
 // sets the process's starting value
 int g_wgrad_quad = getenv("NITI_WGRAD_QUAD") != nullptr ? std::max(-1, atoi(getenv("NITI_WGRAD_QUAD"))) : -1;
+// the first layer's weight gradient from the pooled gradient and the pool codes
+// (niti_diag_conv0_wgrad_codes): -1 the model's choice, 0 off, 1 on where eligible;
+// NITI_CONV0_WGRAD_CODES sets the process's starting value.  g_c0w_launches counts the step's launches.
+int g_c0w_mode = getenv("NITI_CONV0_WGRAD_CODES") != nullptr
+                     ? std::min(1, std::max(-1, atoi(getenv("NITI_CONV0_WGRAD_CODES"))))
+                     : -1;
+unsigned long long g_c0w_launches = 0;
 
 static hipError_t im2col32(const ConvGeom& o, const int8_t* x16, int8_t* out, hipStream_t st) {
     const int64_t px = (int64_t)o.n * o.oh * o.ow;
@@ -136,6 +147,26 @@ struct FlattenBwd {
         const int p = (int)(r % hw);
         const int64_t b = r / hw;
         din[i] = ch < c ? dout[b * ldo + ch * hw + p] : (int8_t)0;
+    }
+};
+
+// The expanded output gradient of a 2x2-pooled layer from its pooled gradient and the recorded route:
+// out[n][y][x][c] = g0[n][y / 2][x / 2][c] where bit 2 (y & 1) + (x & 1) of the code is set, else 0
+// (the first layer's dy tap after a step on the codes route, which never writes that tensor).
+struct ExpandPoolCodes {
+    const int8_t* g0;
+    const int8_t* code;
+    int oh, ow, cop;
+    int8_t* out;
+    __device__ void operator()(int64_t i) const {  // i over [n][oh][ow][cop]
+        const int c = (int)(i % cop);
+        int64_t r = i / cop;
+        const int x = (int)(r % ow);
+        r /= ow;
+        const int y = (int)(r % oh);
+        const int64_t b = r / oh;
+        const int64_t q = ((b * (oh / 2) + (y >> 1)) * (ow / 2) + (x >> 1)) * cop + c;
+        out[i] = ((code[q] >> (2 * (y & 1) + (x & 1))) & 1) ? g0[q] : (int8_t)0;
     }
 };
 
@@ -277,6 +308,33 @@ struct Model final : StepDriver {
         if (pv.flatten || pv.col || pv.g.cop != L[i].g.cip) return false;
         return pv.pool ? (pv.ph == 1 && pv.pw == 1 && pv.g.oh == 2 && pv.g.ow == 2) : (pv.g.oh == 1 && pv.g.ow == 1);
     }
+    // The first layer's expanded output gradient has one reader, its own weight gradient (no input
+    // gradient; no tap under keep_grads(0)).  On this route layer 1's input gradient writes only the
+    // pooled gradient g0 -- the plain `out` epilogue, into the first quarter of L[0].dy -- and the
+    // weight gradient reads g0, the codes and xcol (conv0_wgrad_codes).  Single device, outside a
+    // graph capture (its combine is deferred to the update launch; a captured step keeps the old
+    // launches) and without the side stream, layer 1's input gradient a W > 0 row launch, no probe on
+    // the launch it replaces.
+    int32_t* c0w_slab = nullptr;  // the route's own slabs
+    size_t c0w_slab_bytes = 0;
+    bool c0w_tuned = true;   // the model's choice (mode -1): the autotuner's, else the default
+    int c0w_force = -1;      // the autotuner's own timing: 0 / 1 that way, whatever the mode
+    bool dy0_codes = false;  // the last step left g0 in L[0].dy, not the expanded gradient (get_tap rebuilds it)
+    bool conv0_codes_eligible() const {
+        if (L.size() < 2 || c0w_slab == nullptr) return false;
+        const Layer& l = L[0];
+        if (!l.col || !pool_code_layer(0) || keep_grads || coll != nullptr || coll_grad != nullptr) return false;
+        if (use_graph || capturing || overlap) return false;  // (one stream, direct launches: the bench's step)
+        if (!rowconv_dgrad_layer(1) || rowconv_seg(L[1].dg) || head_dgrad_ok(1)) return false;
+        if (probe_layer == 0 && probe_phase == 2) return false;
+        return conv0_wgrad_codes_ok(l.g.n, l.g.oh, l.g.ow, l.g.cop, l.g.cip);
+    }
+    bool conv0_codes_route() const {
+        if (c0w_force >= 0) return c0w_force == 1 && conv0_codes_eligible();
+        if (tuning || g_c0w_mode == 0 || (g_c0w_mode < 0 && !c0w_tuned)) return false;
+        return conv0_codes_eligible();
+    }
+    int tune_conv0_codes(hipStream_t st, TuneTimer& timer, bool log);
     bool g8_written = false;  // the last step stored the int8 weight gradients (tap(layer, 1))
     // IHWO16 weights of the layers whose input gradient ran on the row kernel (the SGD kernel
     // skips them there) -- rebuilt when the GEMM input gradient takes over again
@@ -887,6 +945,12 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
         rc_acc = (int32_t*)ws.alloc(rc_acc_size);
         if (!rc_acc) return NITI_OUT_OF_MEMORY;
     }
+    if (nl >= 2 && L[0].col && L[0].pc != nullptr &&
+        conv0_wgrad_codes_ok(L[0].g.n, L[0].g.oh, L[0].g.ow, L[0].g.cop, L[0].g.cip)) {
+        c0w_slab_bytes = (size_t)conv0_wgrad_codes_blocks(L[0].g.n, L[0].g.oh, L[0].g.ow, 1 << 30) * L[0].g.cop * 32 * 4;
+        c0w_slab = (int32_t*)ws.alloc(c0w_slab_bytes);
+        if (!c0w_slab) return NITI_OUT_OF_MEMORY;
+    }
     for (int i = 0; i < nl; ++i) {  // the GEMM-path phases that may run the speculative pair
         const Layer& l = L[i];
         if (!(l.col && conv0_ok(l.g)) && !l.rc) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_fwd_spec_alt_bytes(l.g));
@@ -1085,6 +1149,30 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     }
     l.fc_sgd = fc_sgd_layer(i);
     SgdJob& defer_job = grads[i].defer;
+    if (i == 0 && conv0_codes_route()) {
+        // from g0 (the first quarter of dy, left by layer 1's input gradient), the codes and xcol; the
+        // slabs go to the update launch's combine, as the GEMM path's do (wgrad_gemm)
+        int slabs = 0;
+        defer_job = SgdJob{};
+        DTRY(conv0_wgrad_codes(g.n, g.oh, g.ow, g.cop, g.cip, l.dy, l.pc, l.xcol, conv0_wgrad_codes_model_blocks(),
+                               c0w_slab, c0w_slab_bytes, &slabs, st));
+        ++g_c0w_launches;
+        SgdJob d{};
+        d.slab = c0w_slab;
+        d.splits = slabs;
+        d.slab_stride = (int64_t)g.cop * 32;
+        d.slab_n = l.w_elems();
+        if (defer_combine()) {
+            defer_job = d;
+        } else if (tuning && in_step_combine()) {  // (timed with the combine the step runs it with)
+            d.acc = l.dwacc;
+            d.amax = rng(i, 2);
+            DTRY(sgd_combine_many(&d, 1, st));
+        } else {
+            DTRY(splitk_reduce_linear(c0w_slab, slabs, l.w_elems(), d.slab_stride, l.dwacc, dp ? nullptr : rng(i, 2), st));
+        }
+        return NITI_NO_ERROR;
+    }
     if (l.fc_sgd) {  // its range now; the recompute with the update after the backward pass
         defer_job = SgdJob{};
         DTRY(conv_wgrad_fc_sgd(g, l.in, l.dy, rng(i, 2), SgdJob{}, 0, st));
@@ -1189,7 +1277,15 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         // 16-pixel blocks; else wgrad_layer converts
         o.p16 = fuse_dp16 && wgrad_p16_splits(i - 1) > 0 && rowconv_p16_ok(l.dg, pv.pool) ? dp16[i - 1] : nullptr;
         const bool skip16 = skip_dy16(i, next, o.p16);
-        if (pv.pool) {
+        // layer 0 on the codes route: the plain epilogue, q of every pooled pixel into the first
+        // quarter of its dy (the launch then has no input-gradient operand: the forward instantiation)
+        const bool g0_only = i == 1 && conv0_codes_route();
+        if (i == 1) dy0_codes = g0_only;
+        if (g0_only) {
+            o.out = pv.dy;
+            o.p16 = nullptr;
+            next = nullptr;
+        } else if (pv.pool) {
             if (pool_code_layer(i - 1)) {
                 o.pool_code = pv.pc;
             } else {
@@ -1205,8 +1301,9 @@ int Model::dgrad_layer(int i, hipStream_t st) {
             o.next = next;
             o.relu_mask = pv.relu ? pv.r : nullptr;
         }
-        dy16_valid[i - 1] = !skip16;
-        const int rc = rowconv_ranged(rowconv_fused_ok(d, true), rowconv_acc_bytes(d, true) != 0, o, rng(i, 1), l.bar,
+        dy16_valid[i - 1] = !skip16 && !g0_only;
+        const bool dgk = !g0_only;  // (rowconv_fwd's own rule: an operand of the input-gradient epilogues)
+        const int rc = rowconv_ranged(rowconv_fused_ok(d, dgk), rowconv_acc_bytes(d, dgk) != 0, o, rng(i, 1), l.bar,
                                       l.epoch, st,
                                       [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
                                           return rowconv_fwd(d, dyin, l.wft, ro, mode, rng(i, 1), bar, epoch, err, st);
@@ -1369,6 +1466,7 @@ int Model::autotune(hipStream_t st, int reps) {
         }
     }
     if (rc == NITI_NO_ERROR) rc = tune_wgrad_batch(st, timer, log);
+    if (rc == NITI_NO_ERROR) rc = tune_conv0_codes(st, timer, log);
     invalidate_xp16();
     tuning = false;
     if (hipStreamSynchronize(st) != hipSuccess) rc = NITI_NO_EXECUTION;
@@ -1467,6 +1565,31 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
         if (q_forced < 0) wgb_quad = best_q;
     }
     if (log) fprintf(stderr, "tune wgrad set: keeps %d, quad %d\n", wgb_tuned, wgrad_quad_kg(wgb_quad));
+    return rc;
+}
+
+// Layer 0's weight-gradient side both ways, with the plans settled: layer 1's input gradient through
+// the pool epilogue + the GEMM + its combine, against the plain input gradient + conv0_wgrad_codes +
+// its combine.  The faster stays as the model's choice (c0w_tuned); a forced mode is used as it is.
+int Model::tune_conv0_codes(hipStream_t st, TuneTimer& timer, bool log) {
+    c0w_force = 1;
+    const bool can = conv0_codes_route();
+    c0w_force = -1;
+    if (!can) return NITI_NO_ERROR;
+    float us[2] = {0.f, 0.f};
+    int rc = NITI_NO_ERROR;
+    for (int way = 0; way < 2 && rc == NITI_NO_ERROR; ++way) {
+        c0w_force = way;
+        rc = timer.time(
+            [&]() -> int {
+                if (const int r = dgrad_layer(1, st)) return r;
+                return wgrad_layer(0, st);
+            },
+            &us[way]);
+    }
+    c0w_force = -1;
+    if (rc == NITI_NO_ERROR) c0w_tuned = us[1] < us[0];
+    if (log) fprintf(stderr, "tune conv0 wgrad: expanded %.2f us, codes %.2f us, keeps %s\n", us[0], us[1], c0w_tuned ? "codes" : "expanded");
     return rc;
 }
 
@@ -1958,7 +2081,15 @@ int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t
     }
     if (which == 0)
         e = nhwc16_to_nchw(l.r, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else if (which == 2 && !dy16_valid[layer]) {  // rebuilt from the C32 copy the step wrote
+    else if (which == 2 && layer == 0 && dy0_codes) {  // the codes route never wrote it: rebuilt from g0 and the codes
+        int8_t* d16 = nullptr;
+        const int64_t elems = (int64_t)n * g.oh * g.ow * g.cop;
+        e = hipMalloc(&d16, (size_t)elems);
+        if (e == hipSuccess) e = launch_map(elems, ExpandPoolCodes{l.dy, l.pc, g.oh, g.ow, g.cop, d16}, nullptr);
+        if (e == hipSuccess) e = nhwc16_to_nchw(d16, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (d16) (void)hipFree(d16);
+    } else if (which == 2 && !dy16_valid[layer]) {  // rebuilt from the C32 copy the step wrote
         int8_t* d16 = nullptr;
         e = hipMalloc(&d16, (size_t)n * g.oh * g.ow * g.cop);
         if (e == hipSuccess) e = c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, d16, nullptr);

@@ -222,6 +222,11 @@ def lib():
         "niti_input_im2col": (ci, [vp] + [ci] * 9 + [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp]),
         "niti_conv0_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(Conv0Out), ci, vp]),
         "niti_diag_conv0_blocks": (None, [C.c_int]),
+        "niti_conv0_wgrad_codes": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, C.c_size_t, C.POINTER(ci), vp]),
+        "niti_conv0_wgrad_codes_slabs": (ci, [ci, ci, ci, ci, ci, ci]),
+        "niti_diag_conv0_wgrad_blocks": (None, [C.c_int]),
+        "niti_diag_conv0_wgrad_codes": (None, [C.c_int]),
+        "niti_diag_conv0_wgrad_codes_launches": (C.c_ulonglong, []),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),

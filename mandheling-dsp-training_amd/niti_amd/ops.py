@@ -624,6 +624,26 @@ def conv0_fwd(g, xcol, w, amax, pass_, *, out=None, pool_out=None, pool_code=Non
           "conv0_fwd")
 
 
+def conv0_wgrad_codes(g, g0, code, xcol, blocks=0, k=32, cop=None, amax=None, stream=None):
+    """The first layer's weight gradient from the pooled gradient and the pool codes
+    (niti_conv0_wgrad_codes).  g: conv0_fwd's geom(n, 32, oh, ow, c_out, 1); g0 and code int8
+    [n * oh/2 * ow/2][cop] (cop: g.cop unless given), xcol int8 [n * oh * ow][32].  Returns (acc int32 [c_out][32], range): the
+    launch's slabs summed by sgd_combine, the range max|acc| (also left in amax when given, zeroed by
+    the caller).  Raises NitiError(INVALID_VALUE) where the entry refuses the arguments."""
+    n, oh, ow, co = g.n, g.oh, g.ow, g.c_out
+    cop = g.cop if cop is None else cop
+    slabs = L.lib().niti_conv0_wgrad_codes_slabs(n, oh, ow, cop, k, blocks)
+    slab = torch.full((max(slabs, 1), cop * 32), 0x5A5A5A5A, dtype=torch.int32, device=xcol.device)
+    wrote = C.c_int(0)
+    check(L.lib().niti_conv0_wgrad_codes(n, oh, ow, cop, k, _ptr(g0), _ptr(code), _ptr(xcol), blocks, _ptr(slab),
+                                         slab.numel() * 4, C.byref(wrote), _stream(stream)), "conv0_wgrad_codes")
+    assert wrote.value == slabs
+    acc = torch.full((co, 32), 0x5A5A5A5A, dtype=torch.int32, device=xcol.device)
+    amax = new_range(xcol.device) if amax is None else amax
+    sgd_combine([(slab, co * 32, acc, amax)], stream=stream)
+    return acc, range_max(amax)
+
+
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
     """Exponent-aligned int32 sum of two int8 tensors (niti_resnet.hip) -> (z int32, ez int8 [1])."""
     assert a.shape == b.shape and a.dtype == b.dtype == torch.int8
