@@ -564,6 +564,46 @@ int niti_conv0_wgrad_codes_slabs(int n, int oh, int ow, int cop, int k, int bloc
 void niti_diag_conv0_wgrad_blocks(int n);
 void niti_diag_conv0_wgrad_codes(int mode);
 unsigned long long niti_diag_conv0_wgrad_codes_launches(void);
+/* Depthwise conv layers, alone (csrc/niti_depthwise.hip).  g: c_out == c_in == C, a square 3x3 or 5x5
+ * kernel, stride 1, dilation 1, the same pad 0 <= pad < k on every side.  The layer is NITI_Conv_Int8 over
+ * the block-diagonal dense weight W[o][i] = (o == i) ? w[o] : 0: forward acc[n][c][oy][ox] = sum over (ky, kx)
+ * of x[n][c][oy + ky - pad][ox + kx - pad] w[c][ky][kx] (zero outside the image), its range over the whole
+ * tensor, NITI_Conv_Int8's shift rule; the input gradient acc[n][c][y][x] = sum of dy[n][c][y - ky + pad]
+ * [x - kx + pad] w[c][ky][kx] under NITI_DeConv_Int8's rule; the weight gradient acc[c][ky][kx] = sum over
+ * (n, oy, ox) of dy[n][c][oy][ox] x[n][c][oy + ky - pad][ox + kx - pad], whose range is taken over these
+ * C k k values only.  x / dy / out: NHWC16.  w, the int32 gradient and its slabs: [k * k][round16(C)],
+ * tap-major -- the OHWI16 form of a c_out = 1, c_in = C layer, whose OIHW host order [1][C][k][k] is the flat
+ * order of [C][1][k][k]; niti_sgd_update* and niti_sgd_combine take it as co = 1, ci = C, kk = k * k.
+ * niti_dwconv_ok: 1 where the launches take g (host only).
+ * niti_dwconv_fwd / _dgrad: pass 0 publishes max|acc| into amax (NITI_MAX_WORDS words, zeroed by the
+ *   caller), pass 1 recomputes and requantises with the range found there (a MAX all-reduce may sit between
+ *   them); no int32 tensor is written.  relu: forward only; relu_mask (out's shape, out = mask > 0 ? q : 0):
+ *   input gradient only.  exp_out = exp_in + wscale + inc (any of the three may be NULL).
+ * niti_dwconv_wgrad: leaves *slabs partial sums [k * k][round16(C)] int32 in slab, that many elements
+ *   apart; niti_dwconv_wgrad_slabs is the count (a function of g alone; 0 where !niti_dwconv_ok).
+ *   niti_dwconv_wgrad_reduce sums them into acc with max|acc| into amax (may be NULL), as the training step
+ *   does where the update launch's combine does not.
+ * NITI_INVALID_VALUE, nothing launched: a NULL operand, !niti_dwconv_ok(g) (c_in != c_out, k not 3 or 5,
+ * stride != 1, an operand of 2^31 bytes or more), pass not 0 / 1, relu with _dgrad or relu_mask with _fwd,
+ * slab_bytes too small, slabs != niti_dwconv_wgrad_slabs(g). */
+typedef struct niti_dwconv_out {
+    int8_t* out;
+    const int8_t* relu_mask;
+    const int8_t* exp_in;
+    const int8_t* wscale;
+    int8_t* exp_out;
+    int relu;
+} niti_dwconv_out;
+int niti_dwconv_ok(const niti_geom* g);
+int niti_dwconv_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                    int pass, void* stream);
+int niti_dwconv_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                      int pass, void* stream);
+int niti_dwconv_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
+                      int* slabs, void* stream);
+int niti_dwconv_wgrad_slabs(const niti_geom* g);
+int niti_dwconv_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
+                             void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -726,6 +766,25 @@ int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int 
  * its code with nothing allocated and *out untouched.  Every other niti_model_* call takes the
  * handle; niti_model_copy_weights needs the same list and input on both sides. */
 int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with depthwise layers (niti_dwconv_* above; this library's extension, stated like the residual
+ * rule: the reference's NITI module takes a `depthwise` option, NN.cpp:1118-1125, and its CPU op ignores the
+ * group).  niti_chain_layer's seven fields, then depthwise: 1 makes the layer a depthwise conv of its
+ * derived c_in channels, weight [C][1][k][k] (niti_model_set_weight / _get_weight / the int8 gradient tap in
+ * that order), stride 1.  The two entry points above are these with depthwise = 0 everywhere.  Beside
+ * niti_model_chain_check's rule:
+ * NITI_INVALID_VALUE (malformed): depthwise other than 0 / 1; a depthwise layer whose c_out is neither 0
+ *   ("as the input") nor the derived c_in.
+ * NITI_NOT_SUPPORT: a depthwise layer that is layer 0 (the first layer's im2col form), the last layer (the
+ *   logits), or that follows a flatten; a depthwise layer with kernel other than 3 or 5.
+ * shapes[][8] is niti_model_chain_check's (c_out reported as derived).  A depthwise layer's MACs count
+ * n oh ow C k k; niti_model_plan_info / _plan_set on it return NITI_NOT_SUPPORT (it has no GEMM plan) and
+ * niti_model_autotune skips it. */
+typedef struct niti_chain_layer2 {
+    int c_out, kernel, stride, pad, relu, pool, flatten; /* as niti_chain_layer */
+    int depthwise;                                        /* 0: dense; 1: depthwise (c_out 0 or c_in) */
+} niti_chain_layer2;
+int niti_model_chain_check2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and
@@ -804,6 +863,9 @@ void niti_model_destroy(niti_model_t m);
 int niti_model_num_layers(niti_model_t m);
 /* per layer: {c_in, c_out, kh, kw, h_in, w_in, oh, ow, pad, stride, relu, pool} */
 int niti_model_layer_info(niti_model_t m, int layer, int info[12]);
+/* 1 where the layer is a depthwise conv (niti_chain_layer2), 0 where it is dense, -1 for a NULL handle or
+ * a layer out of range */
+int niti_model_layer_depthwise(niti_model_t m, int layer);
 int niti_model_set_weight(niti_model_t m, int layer, const int8_t* w_oihw_host, int wscale);
 int niti_model_get_weight(niti_model_t m, int layer, int8_t* w_oihw_host);
 /* One NITI_SGD step: forward, NITI_LOSS_Grad, backward, w <- clip(w - g).

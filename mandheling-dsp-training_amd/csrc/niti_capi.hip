@@ -779,6 +779,52 @@ void niti_diag_conv0_wgrad_blocks(int n) { niti::diag_conv0_wgrad_blocks(n); }
 void niti_diag_conv0_wgrad_codes(int mode) { niti::model_conv0_wgrad_codes(mode); }
 unsigned long long niti_diag_conv0_wgrad_codes_launches(void) { return niti::model_conv0_wgrad_codes_launches(); }
 
+// depthwise conv layers (niti_depthwise.hip): every refusal is INVALID_VALUE with nothing launched
+static bool dw_geom(const niti_geom* g, niti::ConvGeom* r) { return g != nullptr && to_geom(g, r) && niti::dwconv_ok(*r); }
+static niti::ActOut dw_out(const niti_dwconv_out* o) {
+    niti::ActOut a;
+    a.out = o->out;
+    a.relu = o->relu;
+    a.relu_mask = o->relu_mask;
+    a.exp_in = o->exp_in;
+    a.wscale = o->wscale;
+    a.exp_out = o->exp_out;
+    return a;
+}
+int niti_dwconv_ok(const niti_geom* g) {
+    niti::ConvGeom r;
+    return dw_geom(g, &r) ? 1 : 0;
+}
+int niti_dwconv_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                    int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!dw_geom(g, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_fwd(r, x, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_dwconv_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                      int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!dw_geom(g, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_dgrad(r, dy, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_dwconv_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
+                      int* slabs, void* stream) {
+    niti::ConvGeom r;
+    if (!dw_geom(g, &r)) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_wgrad(r, x, dy, slab, slab_bytes, slabs, S(stream)));
+}
+int niti_dwconv_wgrad_slabs(const niti_geom* g) {
+    niti::ConvGeom r;
+    return dw_geom(g, &r) ? niti::dwconv_wgrad_slabs(r) : 0;
+}
+int niti_dwconv_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
+                             void* stream) {
+    niti::ConvGeom r;
+    if (!dw_geom(g, &r) || !slab || !acc || slabs != niti::dwconv_wgrad_slabs(r)) return NITI_INVALID_VALUE;
+    const int64_t n = (int64_t)r.kh * r.kw * r.cip;
+    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
+}
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

@@ -175,6 +175,9 @@ struct ExpandPoolCodes {
 struct Layer {
     ConvGeom g{};
     int relu = 0, pool = 0, flatten = 0;
+    // a depthwise conv (niti_depthwise.hip): g.c_out == g.c_in == C; w, dwacc, g8 and the slabs are
+    // [k * k][cip], the OHWI16 form of a c_out = 1, c_in = C layer (w_co), and there is no wT
+    int dw = 0;
     int ph = 0, pw = 0;      // pooled size
     int8_t wscale = 0;
     // persistent
@@ -229,8 +232,9 @@ struct Layer {
     int fh() const { return pool ? ph : g.oh; }
     int fw() const { return pool ? pw : g.ow; }
     const int8_t* fsrc() const { return pool ? p : r; }
-    int64_t w_elems() const { return (int64_t)g.c_out * g.kh * g.kw * g.cip; }
-    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * og.c_in * og.kh * og.kw; }
+    int w_co() const { return dw ? 1 : g.c_out; }  // output channels as the weight layouts count them
+    int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * g.cip; }
+    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in) * og.kh * og.kw; }
 };
 
 struct Model final : StepDriver {
@@ -258,7 +262,7 @@ struct Model final : StepDriver {
     bool fc_sgd_layer(int i) const {
         static const bool off = getenv("NITI_FC_SGD") && atoi(getenv("NITI_FC_SGD")) == 0;
         const ConvGeom& g = L[i].g;
-        return in_step && !off && !dp() && !tuning && conv_wgrad_fc_sgd_ok(g) &&
+        return in_step && !off && !dp() && !tuning && !L[i].dw && conv_wgrad_fc_sgd_ok(g) &&
                !(head_layer(i) && g.c_out <= 32 && g.cip % 32 == 0) && wgrad_p16_splits(i) == 0;
     }
     // the GEMM speculative pairs' alternates (one bit width below / above A's guess), shared by every
@@ -389,7 +393,7 @@ struct Model final : StepDriver {
     // kernels (a plan override of another tile, or a geometry the P16 kernel does not take)
     int wgrad_p16_splits(int i) const {
         const ConvGeom& g = L[i].g;
-        if (!conv_wgrad_p16_ok(g)) return 0;
+        if (L[i].dw || !conv_wgrad_p16_ok(g)) return 0;
         PlanChoice c;
         if (plan_override_lookup(conv_plan_key(PLAN_WGRAD, g), &c)) return c.bm == PLAN_P16_TILE ? c.splits : 0;
         return conv_wgrad_p16_splits(g);
@@ -502,7 +506,8 @@ struct Model final : StepDriver {
     int build(int arch_, int batch_, int in_hw = 0);
     // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
     // built-in networks are build()'s own lists
-    int build_chain(int arch_, int batch_, const niti_chain_layer* layers, int n, int in_c_, int in_hw);
+    int build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int n, int in_c_, int in_hw);
+    int layer_depthwise(int layer) const override { return layer_ok(layer) ? L[layer].dw : -1; }
     int fwd_layer(int i, hipStream_t st);
     int wgrad_layer(int i, hipStream_t st);
     int dgrad_layer(int i, hipStream_t st);
@@ -678,8 +683,9 @@ struct Model final : StepDriver {
     }
 };
 
-static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0) {
+static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0, int dw = 0) {
     Layer l;
+    l.dw = dw;
     l.g.n = m.batch;
     l.g.c_in = ci;
     l.g.h = l.g.w = h;
@@ -713,42 +719,50 @@ static int64_t chain_mul(int64_t a, int64_t b) {
 // The shapes a layer list derives (the one rule niti_model_chain_check, niti_model_create_chain and
 // build_chain share): per layer {c_in, c_out, k, pad, h_in, oh, out_h, flat_c}.  Refuses malformed
 // lists and counts that do not fit an int; what else the library does not run is chain_check's.
-static int chain_shapes(const niti_chain_layer* layers, int n, int in_c, int in_hw, std::vector<std::array<int, 8>>* out) {
+static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in_hw, std::vector<std::array<int, 8>>* out) {
     if (layers == nullptr || n < 1 || in_c < 1 || in_hw < 1) return NITI_INVALID_VALUE;
     int64_t c = in_c, h = in_hw;
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer& l = layers[i];
-        if (l.c_out < 1 || l.kernel < 1 || l.pad < 0 || l.pad >= l.kernel) return NITI_INVALID_VALUE;
+        const niti_chain_layer2& l = layers[i];
+        if (l.depthwise != 0 && l.depthwise != 1) return NITI_INVALID_VALUE;
+        // a depthwise layer has its input's channels: c_out 0 ("as the input") or that count
+        if (l.depthwise && l.c_out != 0 && l.c_out != c) return NITI_INVALID_VALUE;
+        const int64_t co = l.depthwise ? c : l.c_out;
+        if (co < 1 || l.kernel < 1 || l.pad < 0 || l.pad >= l.kernel) return NITI_INVALID_VALUE;
         if (h + 2 * (int64_t)l.pad < l.kernel) return NITI_INVALID_VALUE;
         const int64_t oh = h + 2 * (int64_t)l.pad - l.kernel + 1;
         if (l.pool && oh < 2) return NITI_INVALID_VALUE;
         const int64_t ph = l.pool ? (oh - 2) / 2 + 1 : oh;
-        const int64_t fc = l.flatten ? chain_mul(chain_mul(l.c_out, ph), ph) : l.c_out;
+        const int64_t fc = l.flatten ? chain_mul(chain_mul(co, ph), ph) : co;
         // (a count past int never reaches a buffer: refused here as a size no tensor of it fits)
         if (c > CHAIN_MAX_ELEMS || fc > CHAIN_MAX_ELEMS || oh > CHAIN_MAX_ELEMS) return NITI_NOT_SUPPORT;
-        if (out) out->push_back({(int)c, l.c_out, l.kernel, l.pad, (int)h, (int)oh, (int)(l.flatten ? 1 : ph), (int)fc});
+        if (out) out->push_back({(int)c, (int)co, l.kernel, l.pad, (int)h, (int)oh, (int)(l.flatten ? 1 : ph), (int)fc});
         c = fc;
         h = l.flatten ? 1 : ph;
     }
     return NITI_NO_ERROR;
 }
 
-int chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]) {
+int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]) {
     std::vector<std::array<int, 8>> sh;
     if (batch < 1) return NITI_INVALID_VALUE;
     if (const int rc = chain_shapes(layers, n, in_c, in_hw, &sh)) return rc;
     if (n > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;  // (sgd_update_many's job table)
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer& l = layers[i];
+        const niti_chain_layer2& l = layers[i];
         const std::array<int, 8>& s = sh[i];
         if (l.stride != 1) return NITI_NOT_SUPPORT;
         if (l.kernel > CHAIN_MAX_KERNEL) return NITI_NOT_SUPPORT;
+        // a depthwise layer: not the first layer (its im2col form), not the logits, not on a flattened
+        // map; the kernels take 3x3 and 5x5
+        if (l.depthwise && (i == 0 || i == n - 1 || layers[i - 1].flatten || (l.kernel != 3 && l.kernel != 5)))
+            return NITI_NOT_SUPPORT;
         if (i > 0 && layers[i - 1].flatten && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
         // a first layer the fused input pass takes (input_im2col) stages kernel + band - 1 image rows
         // of 4 bytes a pixel in LDS: one output row must fit in half of a workgroup's 64 KiB
         if (i == 0 && Model::input_fused_ok(s[0], l.kernel, l.pad) && (int64_t)l.kernel * (s[4] + l.kernel - 1) * 4 > 32768)
             return NITI_NOT_SUPPORT;
-        if (i == n - 1 && (l.c_out > 2048 || l.pool || l.flatten || s[5] != 1)) return NITI_NOT_SUPPORT;
+        if (i == n - 1 && (s[1] > 2048 || l.pool || l.flatten || s[5] != 1)) return NITI_NOT_SUPPORT;
         // every tensor of the layer, in the padded layouts build_chain allocates
         const int64_t b = batch, k2 = (int64_t)l.kernel * l.kernel;
         const int64_t cip32 = round_up(s[0], 32), cop32 = round_up(s[1], 32);
@@ -765,32 +779,32 @@ int chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int 
 
 int Model::build(int arch_, int batch_, int in_hw) {
     // {c_out, kernel, stride, pad, relu, pool, flatten}
-    std::vector<niti_chain_layer> t;
+    std::vector<niti_chain_layer2> t;
     int ic = 3, hw = 32;
     if (arch_ == NITI_ARCH_LENET) {  // mnistTrain.cpp:131-181
         ic = 1;
         hw = 28;
-        t = {{20, 5, 1, 0, 1, 1, 0}, {52, 5, 1, 0, 1, 1, 1}, {500, 1, 1, 0, 1, 0, 0}, {12, 1, 1, 0, 0, 0, 0}};
+        t = {{20, 5, 1, 0, 1, 1, 0, 0}, {52, 5, 1, 0, 1, 1, 1, 0}, {500, 1, 1, 0, 1, 0, 0, 0}, {12, 1, 1, 0, 0, 0, 0, 0}};
     } else if (arch_ == NITI_ARCH_VGG11) {  // VGG-11 for 32x32 inputs, NITI layers (BASELINE cfg 3)
         static const int cfg[8][2] = {{64, 1}, {128, 1}, {256, 0}, {256, 1}, {512, 0}, {512, 1}, {512, 0}, {512, 1}};
-        for (int i = 0; i < 8; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], 0});
-        t.push_back({12, 1, 1, 0, 0, 0, 0});
+        for (int i = 0; i < 8; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], 0, 0});
+        t.push_back({12, 1, 1, 0, 0, 0, 0, 0});
     } else if (arch_ == NITI_ARCH_VGG16) {  // VGG-16 (configuration D), NITI layers (BASELINE cfg 4)
         hw = in_hw > 0 ? in_hw : 224;
         if (hw % 32 != 0) return NITI_INVALID_VALUE;
         static const int cfg[13][2] = {{64, 0},  {64, 1},  {128, 0}, {128, 1}, {256, 0}, {256, 0}, {256, 1},
                                        {512, 0}, {512, 0}, {512, 1}, {512, 0}, {512, 0}, {512, 1}};
-        for (int i = 0; i < 13; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], /*flatten=*/i == 12});
-        t.push_back({4096, 1, 1, 0, 1, 0, 0});
-        t.push_back({4096, 1, 1, 0, 1, 0, 0});
-        t.push_back({1000, 1, 1, 0, 0, 0, 0});
+        for (int i = 0; i < 13; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], /*flatten=*/i == 12, 0});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0});
+        t.push_back({1000, 1, 1, 0, 0, 0, 0, 0});
     } else {
         return NITI_NOT_SUPPORT;
     }
     return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw);
 }
 
-int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, int nlayers, int in_c_, int in_hw) {
+int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int nlayers, int in_c_, int in_hw) {
     arch = arch_;
     batch = batch_;
     std::vector<std::array<int, 8>> sh;
@@ -799,7 +813,9 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
     in_h = in_w = in_hw;
     for (int i = 0; i < nlayers; ++i)
         add_conv(*this, sh[i][0], sh[i][1], sh[i][2], sh[i][3], sh[i][4], layers[i].relu != 0, layers[i].pool != 0,
-                 layers[i].flatten != 0);
+                 layers[i].flatten != 0, layers[i].depthwise);
+    for (const Layer& l : L)
+        if (l.dw && !dwconv_ok(l.g)) return NITI_NOT_SUPPORT;
     const int n = batch;
     {
         Layer& f = L[0];
@@ -888,7 +904,12 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
         // the head's, or the GEMM path's fused-rescale launches (STRAT_FUSED)
         l.bar = (uint32_t*)ws.alloc(ROWCONV_BAR_WORDS * 4);
         if (!l.bar || hipMemset(l.bar, 0, ROWCONV_BAR_WORDS * 4) != hipSuccess) return NITI_OUT_OF_MEMORY;
-        if (!l.col && rowconv_ok(g)) {
+        if (l.dw) {  // its weight gradient's slabs: the layer's own until the update (the deferred combine)
+            l.slab16_bytes = (size_t)dwconv_wgrad_slabs(g) * l.w_elems() * sizeof(int32_t);
+            l.slab16 = (int32_t*)ws.alloc(l.slab16_bytes);
+            if (!l.slab16) return NITI_OUT_OF_MEMORY;
+        }
+        if (!l.col && !l.dw && rowconv_ok(g)) {
             l.rc = 1;
             l.wf = (int8_t*)ws.alloc(rowconv_wf_bytes(g.c_out, g.c_in));
             l.xc32 = (int8_t*)ws.alloc((size_t)n * round_up(g.c_in, 32) * g.h * g.w);
@@ -911,7 +932,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer* layers, in
                 if (hipMemset(l.wft, 0, rowconv_wf_bytes(g.c_in, g.c_out)) != hipSuccess) return NITI_NO_EXECUTION;
             }
         }
-        if (conv_wgrad_p16_ok(g)) {
+        if (!l.dw && conv_wgrad_p16_ok(g)) {
             slab_w_bytes = std::max(slab_w_bytes, conv_wgrad_p16_workspace(g, 8));
             xp16[i] = (int8_t*)ws.alloc((size_t)n * g.h * g.w * g.cip);
             l.slab16_bytes = conv_wgrad_p16_workspace(g, 8);
@@ -1107,6 +1128,18 @@ int Model::fwd_layer(int i, hipStream_t st) {
     o.exp_in = i == 0 ? exp0 : L[i - 1].exp;
     o.wscale = l.ws_dev;
     o.exp_out = l.exp;
+    if (l.dw) {
+        // depthwise: range launch, [all-reduce MAX], recompute-and-requantise launch; the unfused pool / flatten
+        const auto none = [](const ActOut&, auto) { return hipErrorNotSupported; };
+        const int rc = gemm_ranged(false, false, o, rng(i, 0), l.bar, l.epoch, st, none, none, [&](const ActOut& ao, int ph) {
+            return dwconv_fwd(g, l.in, l.w, rng(i, 0), ao, ph - 1, st);
+        });
+        if (rc != NITI_NO_ERROR) return rc;
+        probe(i, 0, false, st);
+        if (l.pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
+        if (l.flatten) DTRY(flatten_fwd());
+        return NITI_NO_ERROR;
+    }
     const bool spec = conv_fwd_spec_ok(g);
     // the 2x2 pool rides along the separate requant pass when there is one
     const bool fuse_pool = !spec && l.pool && g.oh % 2 == 0 && g.ow % 2 == 0 && conv_fwd_phase2_separate(g, slab_bytes);
@@ -1149,6 +1182,21 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     }
     l.fc_sgd = fc_sgd_layer(i);
     SgdJob& defer_job = grads[i].defer;
+    if (l.dw) {
+        // depthwise: one launch leaves C-shaped slabs; single device they go to the update launch's
+        // combine, else (data parallel, a capture, the combine off) they are reduced here with the range
+        probe(i, 2, true, st);
+        int slabs = 0;
+        defer_job = SgdJob{};
+        SgdJob d{};
+        DTRY(dwconv_wgrad(g, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
+        if (defer_combine())
+            defer_job = d;
+        else
+            DTRY(splitk_reduce_linear(l.slab16, slabs, l.w_elems(), d.slab_stride, l.dwacc, dp ? nullptr : rng(i, 2), st));
+        probe(i, 2, false, st);
+        return NITI_NO_ERROR;
+    }
     if (i == 0 && conv0_codes_route()) {
         // from g0 (the first quarter of dy, left by layer 1's input gradient), the codes and xcol; the
         // slabs go to the update launch's combine, as the GEMM path's do (wgrad_gemm)
@@ -1316,17 +1364,18 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     }
     dy16_valid[i - 1] = 1;
     const ConvGeom& pg = pv.g;
-    const bool spec = conv_dgrad_spec_ok(g);
+    // (a depthwise layer: its own two launches below, the fall-back's plain outputs around them)
+    const bool spec = !l.dw && conv_dgrad_spec_ok(g);
     // dy of layer i - 1 is rewritten here; its P16 copy comes along where the requant pass can
     // write it (the plain and the fused pool-gradient passes), else wgrad_layer converts it
-    int8_t* p16_out = !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
+    int8_t* p16_out = !l.dw && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
     dp16_valid[i - 1] = 0;
     ActOut o;
     bool fuse = false;
     if (pv.flatten) {
         o.out = pv.dflat;
     } else if (pv.pool) {
-        fuse = !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
+        fuse = !l.dw && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
         if (fuse) {  // pool gradient + relu gradient ride along the requant pass
             o.out = nullptr;
             o.pool.x = pv.r;
@@ -1346,17 +1395,18 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     } else {
         o.relu_mask = pv.relu ? pv.r : nullptr;
         o.out = pv.dy;
-        if (conv_dgrad_phase2_separate(g, slab_bytes)) o.out_p16 = p16_out;
+        if (!l.dw && conv_dgrad_phase2_separate(g, slab_bytes)) o.out_p16 = p16_out;
     }
     // (the pair: no int32 tensor while the bit width holds)
     const int rc = gemm_ranged(
-        !dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr, spec, o, rng(i, 1), l.bar, l.epoch, st,
+        !l.dw && !dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr, spec, o, rng(i, 1), l.bar, l.epoch, st,
         [&](const ActOut& ao, const FusedBar& fb) { return conv_dgrad_fused(g, l.dy, l.wT, ao, fb, st); },
         [&](const ActOut& ao, int ph) {
             int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
             return conv_dgrad_spec(g, l.dy, l.wT, rng(i, 1), ao, l.gspec + GEMM_SPEC_SLOT_WORDS, ph, st, alt);
         },
         [&](const ActOut& ao, int ph) {
+            if (l.dw) return dwconv_dgrad(g, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
             return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st)
                            : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st);
         });
@@ -1406,6 +1456,7 @@ int Model::autotune(hipStream_t st, int reps) {
     for (int i = 0; i < nl && rc == NITI_NO_ERROR; ++i) {
         for (int op : {PLAN_FWD, PLAN_WGRAD, PLAN_DGRAD}) {
             if (op == PLAN_DGRAD && i == 0) continue;
+            if (L[i].dw) continue;  // no GEMM plan: the depthwise launches
             if (op == PLAN_FWD && rowconv_layer(i)) continue;  // no GEMM plan: the register-fed forward
             if (op == PLAN_DGRAD && rowconv_dgrad_layer(i)) continue;
             if ((op == PLAN_FWD && head_layer(i)) || (op == PLAN_DGRAD && head_dgrad_ok(i))) continue;
@@ -1782,8 +1833,9 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         // transpose feeds only the GEMM input gradient, the int8 gradient only the
         // niti_model_get tap (keep_grads)
         // (rule: the layer's update-bits word, read by the launch that applies the update)
-        jobs[i] = SgdJob{l.dwacc, rng(i, 2), -(1 + i), g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.w,
-                         i > 0 && !rowconv_dgrad_layer(i) ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
+        // (a depthwise layer: the c_out = 1 form of its weight, no transposed copy)
+        jobs[i] = SgdJob{l.dwacc, rng(i, 2), -(1 + i), l.w_co(), g.c_in, g.kh * g.kw, g.cip, l.dw ? 16 : g.cop, l.w,
+                         i > 0 && !rowconv_dgrad_layer(i) && !l.dw ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
         jobs[i].wf = l.rc ? l.wf : nullptr;
         jobs[i].wft = l.rcd ? l.wft : nullptr;
         // the combine of this layer's split-K slabs, in the update launch
@@ -1856,7 +1908,7 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
             L[i].col != src.L[i].col || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
-            L[i].flatten != src.L[i].flatten)
+            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw)
             return NITI_INVALID_VALUE;
     }
     if (&src == this) return NITI_NO_ERROR;
@@ -1867,7 +1919,7 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         DTRY(copy_kernel(l.w, s.w, (size_t)l.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
         DTRY(copy_kernel(l.ws_dev, s.ws_dev, 1, st));
         l.wscale = s.wscale;
-        if (!l.rcd)  // (refresh_wt below rebuilds the row-kernel layers')
+        if (!l.rcd && !l.dw)  // (refresh_wt below rebuilds the row-kernel layers')
             DTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
     }
     int rc = refresh_wt(st);
@@ -1890,6 +1942,7 @@ int Model::run_phase(int layer, int phase, hipStream_t st) {
 
 int Model::plan_info(int layer, int phase, int info[4]) {
     if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    if (L[layer].dw) return NITI_NOT_SUPPORT;  // no GEMM plan
     const int op = plan_op(phase);
     PlanChoice c = conv_plan_query(op, L[layer].g, phase != 2, ws_bytes_for(op));
     if (phase == 2 && wgrad_p16_splits(layer) > 0) {
@@ -1904,6 +1957,7 @@ int Model::plan_info(int layer, int phase, int info[4]) {
 // over the weight-gradient slab it grows here
 int Model::plan_set(int layer, int phase, const int plan[4]) {
     if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
+    if (L[layer].dw) return NITI_NOT_SUPPORT;  // no GEMM plan
     const int op = plan_op(phase);
     const ConvGeom& g = L[layer].g;
     const PlanKey k = conv_plan_key(op, g);
@@ -1994,13 +2048,14 @@ int Model::set_weight(int layer, const int8_t* w_host, int wscale) {
         cols_from_oihw(l.og, w_host, colw.data(), 32);
         w_host = colw.data();
     }
-    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
+    // (a depthwise layer's [C][1][k][k] is the flat order of the c_out = 1 layer's OIHW; it has no wT)
+    const size_t n = (size_t)l.w_co() * l.g.c_in * l.g.kh * l.g.kw;
     int8_t* tmp = nullptr;
     if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
     int rc = NITI_NO_ERROR;
     if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
-        oihw_to_ohwi16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
-        oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess ||
+        oihw_to_ohwi16(tmp, l.w_co(), l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
+        (!l.dw && oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess) ||
         hipMemset(l.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess ||
         (l.rc && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, nullptr) != hipSuccess) ||
         (l.rcd && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, nullptr) != hipSuccess) ||
@@ -2014,12 +2069,12 @@ int Model::set_weight(int layer, const int8_t* w_host, int wscale) {
 int Model::get_weight(int layer, int8_t* w_host) {
     if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
     Layer& l = L[layer];
-    const size_t n = (size_t)l.g.c_out * l.g.c_in * l.g.kh * l.g.kw;
+    const size_t n = (size_t)l.w_co() * l.g.c_in * l.g.kh * l.g.kw;
     int8_t* tmp = nullptr;
     if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
     int rc = NITI_NO_ERROR;
     std::vector<int8_t> colw(l.col ? n : 0);
-    if (ohwi16_to_oihw(l.w, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, tmp, nullptr) != hipSuccess ||
+    if (ohwi16_to_oihw(l.w, l.w_co(), l.g.c_in, l.g.kh * l.g.kw, l.g.cip, tmp, nullptr) != hipSuccess ||
         hipMemcpy(l.col ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
         rc = NITI_NO_EXECUTION;
     if (rc == NITI_NO_ERROR && l.col) oihw_from_cols(l.og, colw.data(), w_host, 32);
@@ -2068,7 +2123,7 @@ int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t
     if (which == 0 || which == 2)
         need = (size_t)n * g.c_out * g.oh * g.ow;
     else if (which == 1 && g8_written)
-        need = (size_t)g.c_out * g.c_in * g.kh * g.kw;
+        need = (size_t)l.w_co() * g.c_in * g.kh * g.kw;
     else
         return NITI_INVALID_VALUE;
     const size_t out_need = which == 1 && l.col ? (size_t)l.og.c_out * l.og.c_in * l.og.kh * l.og.kw : need;
@@ -2099,7 +2154,7 @@ int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t
     } else if (which == 2)
         e = nhwc16_to_nchw(l.dy, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
     else
-        e = ohwi16_to_oihw(l.g8, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
+        e = ohwi16_to_oihw(l.g8, l.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
     if (which == 1 && l.col) {
         std::vector<int8_t> colw(need);
         if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
@@ -2144,7 +2199,7 @@ int Model::spec_stats(uint32_t* out, int max_layers) {
     return NITI_NO_ERROR;
 }
 
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch,
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc) {
     *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr);  // (nothing allocated on a refusal)
     if (*rc != NITI_NO_ERROR) return nullptr;

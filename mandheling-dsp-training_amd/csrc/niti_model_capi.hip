@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <vector>
 
 #include "../../include/niti_hip.h"
 #include "niti_step_driver.hpp"
@@ -42,17 +43,38 @@ int niti_model_create3(int arch, int batch, int in_hw, int classes, niti_model_t
     return NITI_NO_ERROR;
 }
 
-int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+int niti_model_chain_check2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
     return niti::chain_check(layers, n, in_c, in_hw, 1, shapes);
 }
 
-int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
     if (!out || batch <= 0) return NITI_INVALID_VALUE;
     int rc = NITI_NO_ERROR;
     std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc);
     if (rc != NITI_NO_ERROR) return rc;
     *out = new niti_model{std::move(d)};
     return NITI_NO_ERROR;
+}
+
+// the seven-field list as the same list with depthwise = 0 (empty where the arguments are malformed:
+// the check then refuses them as it always did)
+static std::vector<niti_chain_layer2> chain_layers2(const niti_chain_layer* layers, int n) {
+    std::vector<niti_chain_layer2> t;
+    for (int i = 0; layers != nullptr && i < n; ++i) {
+        const niti_chain_layer& l = layers[i];
+        t.push_back({l.c_out, l.kernel, l.stride, l.pad, l.relu, l.pool, l.flatten, 0});
+    }
+    return t;
+}
+
+int niti_model_chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    const std::vector<niti_chain_layer2> t = chain_layers2(layers, n);
+    return niti_model_chain_check2(t.empty() ? nullptr : t.data(), n, in_c, in_hw, shapes);
+}
+
+int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    const std::vector<niti_chain_layer2> t = chain_layers2(layers, n);
+    return niti_model_create_chain2(t.empty() ? nullptr : t.data(), n, in_c, in_hw, batch, out);
 }
 
 int niti_model_resnet_check(const niti_resnet_spec* spec, int in_hw, int* n_layers, int shapes[][8]) {
@@ -75,6 +97,8 @@ int niti_model_num_layers(niti_model_t m) { return m ? m->d->num_layers() : 0; }
 int niti_model_layer_info(niti_model_t m, int layer, int info[12]) {
     return m && info ? m->d->layer_info(layer, info) : NITI_INVALID_VALUE;
 }
+
+int niti_model_layer_depthwise(niti_model_t m, int layer) { return m ? m->d->layer_depthwise(layer) : -1; }
 
 int niti_model_set_weight(niti_model_t m, int layer, const int8_t* w_host, int wscale) {
     return m ? m->d->set_weight(layer, w_host, wscale) : NITI_INVALID_VALUE;

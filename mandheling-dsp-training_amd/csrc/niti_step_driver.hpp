@@ -240,6 +240,8 @@ struct StepDriver {
     // ---- what the C ABI asks of a driver (each validates its layer / phase itself)
     virtual int num_layers() const = 0;
     virtual int layer_info(int layer, int info[12]) const = 0;
+    // 1 a depthwise layer, 0 a dense one, -1 out of range (only the chain driver has such layers)
+    virtual int layer_depthwise(int layer) const { return layer >= 0 && layer < num_layers() ? 0 : -1; }
     virtual int set_weight(int layer, const int8_t* w_oihw_host, int wscale) = 0;
     virtual int get_weight(int layer, int8_t* w_oihw_host) = 0;
     virtual int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) = 0;
@@ -278,10 +280,10 @@ std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int
 // niti_model_resnet_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
 int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_layers, int shapes[][8]);
 // a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch,
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
-int chain_check(const niti_chain_layer* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]);
+int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]);
 
 // a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
 // zero padded to the column pitch kp <-> OIHW

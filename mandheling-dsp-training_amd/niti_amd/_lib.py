@@ -116,6 +116,16 @@ class ChainLayer(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten")]
 
 
+class ChainLayer2(C.Structure):
+    """niti_chain_layer2: niti_chain_layer's fields and `depthwise`."""
+    _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten", "depthwise")]
+
+
+class DwconvOut(C.Structure):
+    """niti_dwconv_out: the outputs and options of niti_dwconv_fwd / niti_dwconv_dgrad."""
+    _fields_ = [(n, C.c_void_p) for n in ("out", "relu_mask", "exp_in", "wscale", "exp_out")] + [("relu", C.c_int)]
+
+
 class ResnetSpec(C.Structure):
     """niti_resnet_spec: the stage list of a user-defined residual network."""
     _fields_ = ([(n, C.c_int) for n in ("in_c", "stem_kernel", "stem_stride", "stem_pad", "stem_pool", "width",
@@ -227,6 +237,12 @@ def lib():
         "niti_diag_conv0_wgrad_blocks": (None, [C.c_int]),
         "niti_diag_conv0_wgrad_codes": (None, [C.c_int]),
         "niti_diag_conv0_wgrad_codes_launches": (C.c_ulonglong, []),
+        "niti_dwconv_ok": (ci, [C.POINTER(Geom)]),
+        "niti_dwconv_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_dwconv_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_dwconv_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
+        "niti_dwconv_wgrad_slabs": (ci, [C.POINTER(Geom)]),
+        "niti_dwconv_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
@@ -266,6 +282,10 @@ def lib():
         # (layers: a ChainLayer array, passed untyped)
         "niti_model_chain_check": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        # (layers: a ChainLayer2 array, passed untyped)
+        "niti_model_chain_check2": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain2": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_layer_depthwise": (ci, [vp, ci]),
         # (spec: a ResnetSpec, passed untyped)
         "niti_model_resnet_check": (ci, [vp, ci, C.POINTER(ci), vp]),
         "niti_model_create_resnet": (ci, [vp, ci, ci, C.POINTER(vp)]),

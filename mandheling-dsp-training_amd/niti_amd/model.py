@@ -35,12 +35,14 @@ class NitiModel:
             check(self._lib.niti_model_layer_info(h, i, info), "layer_info")
             keys = ("c_in", "c_out", "kh", "kw", "h", "w", "oh", "ow", "pad", "stride", "relu", "pool")
             self.layers.append(dict(zip(keys, list(info))))
+            self.layers[-1]["depthwise"] = 1 if self._lib.niti_model_layer_depthwise(h, i) == 1 else 0
 
     @classmethod
     def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
-        """A model of the caller's own chain network (niti_model_create_chain): spec is a list of
-        dicts (c_out, kernel[, pad, relu, pool, flatten]) or tuples in that order, over
-        in_c x in_hw x in_hw inputs; the last layer's c_out is the class count.  ValueError for a
+        """A model of the caller's own chain network (niti_model_create_chain2): spec is a list of
+        dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise]) or tuples in that order, over
+        in_c x in_hw x in_hw inputs; the last layer's c_out is the class count.  A depthwise layer
+        (3x3 or 5x5, c_out 0 or its input's channels) has weights [C, 1, k, k].  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
         from .chain import normalize_spec, to_c
@@ -49,11 +51,13 @@ class NitiModel:
         m = cls.__new__(cls)
         m._lib = L.lib()
         h = C.c_void_p()
-        code = m._lib.niti_model_create_chain(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
+        code = m._lib.niti_model_create_chain2(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
         if code == L.INVALID_VALUE:
             raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input at batch {batch}: {spec}")
         check(code, "model_create_chain")
         m._adopt(h, L.ARCH_CHAIN, batch)
+        for d, l in zip(spec, m.layers):  # (a depthwise layer's c_out as derived, whatever normalize_spec could tell)
+            d["c_out"] = l["c_out"]
         m.chain, m.in_c, m.in_hw = spec, int(in_c), int(in_hw)
         return m
 
@@ -98,6 +102,8 @@ class NitiModel:
 
     def weight_shape(self, i):
         l = self.layers[i]
+        if l["depthwise"]:  # (NN.cpp:1118-1125: {C, 1, kh, kw} with group = C)
+            return (l["c_out"], 1, l["kh"], l["kw"])
         return (l["c_out"], l["c_in"], l["kh"], l["kw"])
 
     def set_weight(self, i, w: np.ndarray, wscale: int):
@@ -407,7 +413,7 @@ class NitiModel:
     def tap(self, i, which, stream=None):
         l = self.layers[i]
         if which == 1:
-            shape = (l["c_out"], l["c_in"], l["kh"], l["kw"])
+            shape = self.weight_shape(i)
         else:
             shape = (self.batch, l["c_out"], l["oh"], l["ow"])
         out = np.empty(shape, np.int8)
@@ -430,11 +436,12 @@ class NitiModel:
     def plans(self):
         """{(layer, phase): (bm, bn, splits, strategy)}; phase 0 fwd / 1 input grad / 2 weight grad,
         strategy 0 store / 1 recompute / 2 split-K / 3 the speculative pair / 4 fused: one launch with the
-        rescale behind an in-kernel grid barrier (forward / input gradient)."""
+        rescale behind an in-kernel grid barrier (forward / input gradient).  A depthwise layer has
+        no GEMM plan and no entry."""
         out = {}
         for i in range(len(self.layers)):
             for ph in (0, 1, 2):
-                if ph == 1 and i == 0:
+                if (ph == 1 and i == 0) or self.layers[i]["depthwise"]:
                     continue
                 out[(i, ph)] = self.plan(i, ph)
         return out

@@ -644,6 +644,76 @@ def conv0_wgrad_codes(g, g0, code, xcol, blocks=0, k=32, cop=None, amax=None, st
     return acc, range_max(amax)
 
 
+def dwconv_ok(g) -> bool:
+    """Whether the depthwise launches take g (niti_dwconv_ok; host only): c_out == c_in, a square 3x3 or
+    5x5 kernel, stride 1, one pad below the kernel size on every side, operands below 2^31 bytes."""
+    return bool(L.lib().niti_dwconv_ok(C.byref(g)))
+
+
+def dwconv_weight(w, stream=None):
+    """A depthwise layer's weights [C, 1, k, k] int8 (device) in its device layout [1][k][k][round16(C)]:
+    the OHWI16 form of the c_out = 1, c_in = C layer with the same flat OIHW order."""
+    c, one, kh, kw = w.shape
+    assert one == 1
+    return oihw_to_ohwi16(w.reshape(1, c, kh, kw).contiguous(), stream=stream)
+
+
+def _dwconv_act(fn, what, g, x16, w16, amax, pass_, shape, out, relu, relu_mask, exp_in, wscale, exp_out, stream):
+    o = L.DwconvOut()
+    if pass_ == 1 and out is None:
+        out = torch.empty(shape, dtype=torch.int8, device=x16.device)
+    for name, t in (("out", out), ("relu_mask", relu_mask), ("exp_in", exp_in), ("wscale", wscale),
+                    ("exp_out", exp_out)):
+        setattr(o, name, None if t is None else t.data_ptr())
+    o.relu = 1 if relu else 0
+    check(fn(C.byref(g), _ptr(x16), _ptr(w16), _ptr(amax), C.byref(o), int(pass_), _stream(stream)), what)
+    return out
+
+
+def dwconv_fwd(g, x16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
+               exp_out=None, stream=None):
+    """One pass of a depthwise layer's forward (niti_dwconv_fwd) on x NHWC16 [n][h][w][cp] and w16
+    (dwconv_weight): pass 0 publishes max|acc| into amax (new_range()), pass 1 requantises with the
+    range found there into out [n][oh][ow][cp] (created when None) and returns it."""
+    return _dwconv_act(L.lib().niti_dwconv_fwd, "dwconv_fwd", g, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cip), out,
+                       relu, relu_mask, exp_in, wscale, exp_out, stream)
+
+
+def dwconv_dgrad(g, dy16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
+                 exp_out=None, stream=None):
+    """The same for its input gradient (niti_dwconv_dgrad): dy NHWC16 [n][oh][ow][cp] -> [n][h][w][cp];
+    relu_mask (the output's shape): out = mask > 0 ? q : 0."""
+    return _dwconv_act(L.lib().niti_dwconv_dgrad, "dwconv_dgrad", g, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip),
+                       out, relu, relu_mask, exp_in, wscale, exp_out, stream)
+
+
+def dwconv_wgrad_slabs(g) -> int:
+    """The partial slabs niti_dwconv_wgrad leaves for g (0 where the launches do not take g)."""
+    return int(L.lib().niti_dwconv_wgrad_slabs(C.byref(g)))
+
+
+def dwconv_wgrad(g, x16, dy16, slab=None, stream=None):
+    """A depthwise layer's weight gradient as partial sums (niti_dwconv_wgrad): int32 [slabs][k * k * cp],
+    for sgd_combine, sgd_update_many_bits' slab or dwconv_wgrad_reduce."""
+    if slab is None:
+        slab = torch.full((max(dwconv_wgrad_slabs(g), 1), g.kh * g.kw * g.cip), 0x5A5A5A5A, dtype=torch.int32,
+                          device=x16.device)
+    wrote = C.c_int(-1)
+    check(L.lib().niti_dwconv_wgrad(C.byref(g), _ptr(x16), _ptr(dy16), _ptr(slab), slab.numel() * 4, C.byref(wrote),
+                                    _stream(stream)), "dwconv_wgrad")
+    assert wrote.value == slab.shape[0]
+    return slab
+
+
+def dwconv_wgrad_reduce(g, slab, amax=None, stream=None):
+    """The slabs summed into acc int32 [1][k][k][cp] with max|acc| into amax (zeroed by the caller; may be
+    None), by the reduce launch the training step uses where the update launch does not combine."""
+    acc = torch.full((1, g.kh, g.kw, g.cip), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
+    check(L.lib().niti_dwconv_wgrad_reduce(C.byref(g), _ptr(slab), slab.shape[0], _ptr(acc), _ptr(amax),
+                                           _stream(stream)), "dwconv_wgrad_reduce")
+    return acc
+
+
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
     """Exponent-aligned int32 sum of two int8 tensors (niti_resnet.hip) -> (z int32, ez int8 [1])."""
     assert a.shape == b.shape and a.dtype == b.dtype == torch.int8
