@@ -604,6 +604,31 @@ int niti_dwconv_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int
 int niti_dwconv_wgrad_slabs(const niti_geom* g);
 int niti_dwconv_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
                              void* stream);
+/* The same at stride_h == stride_w == 1 or 2 (the arguments are those of the calls above).  At stride 1 these
+ * are the launches above with the same results; at stride 2, with oh = floor((h + 2 pad - k) / 2) + 1 (ow so),
+ * the layer is NITI_Conv_Int8 over the same block-diagonal weight with stride 2:
+ *   forward          acc[n][c][oy][ox] = sum over (ky, kx) of x[n][c][2 oy + ky - pad][2 ox + kx - pad] w[c][ky][kx]
+ *                    (zero outside the image);
+ *   input gradient   acc[n][c][y][x] = sum over the (ky, kx) with y + pad - ky and x + pad - kx even and
+ *                    oy = (y + pad - ky) / 2, ox = (x + pad - kx) / 2 inside the output of
+ *                    dy[n][c][oy][ox] w[c][ky][kx]: each of the four pixel parities has its own tap subset
+ *                    (4 / 2 / 2 / 1 taps at 3x3 pad 1, 9 / 6 / 6 / 4 at 5x5 pad 2), and the kernel runs those
+ *                    alone, a wave per parity class, reading dy where it lies (no zero-stuffed copy).  Input
+ *                    rows and columns no output reads (h + 2 pad - k odd) get 0, written like any other;
+ *   weight gradient  acc[c][ky][kx] = sum over (n, oy, ox) of dy[n][c][oy][ox] x[n][c][2 oy + ky - pad][2 ox + kx - pad].
+ * Ranges, shift rules, layouts, the two passes and the slabs are as above.  NITI_INVALID_VALUE, nothing
+ * launched: everything that is so above, but for stride 2; a stride other than 1 or 2, unequal strides.  The
+ * six calls above keep refusing every stride but 1. */
+int niti_dwconv2_ok(const niti_geom* g);
+int niti_dwconv2_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                     int pass, void* stream);
+int niti_dwconv2_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                       int pass, void* stream);
+int niti_dwconv2_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
+                       int* slabs, void* stream);
+int niti_dwconv2_wgrad_slabs(const niti_geom* g);
+int niti_dwconv2_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
+                              void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -727,7 +752,7 @@ enum { NITI_ARCH_CHAIN = 5 };
 typedef struct niti_chain_layer {
     int c_out;    /* output channels; the last layer's is the class count */
     int kernel;   /* square kernel size */
-    int stride;   /* must be 1 (reserved) */
+    int stride;   /* must be 1 here; 1 or 2 through niti_chain_layer2 and niti_model_chain_check3 / _create_chain3 */
     int pad;      /* symmetric zero padding */
     int relu;     /* NITI_Relu_Int8 after the conv */
     int pool;     /* 2x2 / stride-2 max pool after it (floor, as NITI_Maxpool_Int8) */
@@ -742,7 +767,7 @@ typedef struct niti_chain_layer {
  *   (h + 2 pad < kernel), a pool on a map smaller than 2x2.
  * NITI_NOT_SUPPORT (well formed, not run by this library):
  *   - n > 24: the update launch takes at most that many layers;
- *   - stride != 1;
+ *   - stride != 1 (niti_model_chain_check3 / _create_chain3 below take stride 2);
  *   - kernel > 7: the implicit GEMM's tap loop is generic in the kernel size (above 32 taps the
  *     per-lane loaders serve it); 7 is the largest this library's tests run;
  *   - last layer: c_out > 2048 (the loss and metrics kernels keep a row of logits per thread), a
@@ -780,11 +805,22 @@ int niti_model_create_chain(const niti_chain_layer* layers, int n, int in_c, int
  * n oh ow C k k; niti_model_plan_info / _plan_set on it return NITI_NOT_SUPPORT (it has no GEMM plan) and
  * niti_model_autotune skips it. */
 typedef struct niti_chain_layer2 {
-    int c_out, kernel, stride, pad, relu, pool, flatten; /* as niti_chain_layer */
+    int c_out, kernel, stride, pad, relu, pool, flatten; /* as niti_chain_layer (stride: see niti_model_chain_check3) */
     int depthwise;                                        /* 0: dense; 1: depthwise (c_out 0 or c_in) */
 } niti_chain_layer2;
 int niti_model_chain_check2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with strided layers: niti_chain_layer2's `stride` is honoured, dense or depthwise (niti_dwconv2_*
+ * above), so oh = floor((h + 2 pad - kernel) / stride) + 1.  The four entry points above are these with their
+ * refusal of stride != 1 kept.  Beside niti_model_chain_check2's rule:
+ * NITI_INVALID_VALUE (malformed): stride < 1.
+ * NITI_NOT_SUPPORT: stride > 2; a strided layer after a flatten (its input is a 1x1 map).
+ * A strided layer may also pool, may be the first layer and may have kernel 1.  shapes[][8] keeps its meaning
+ * (oh under the stride); niti_model_layer_info reports the stride and the MACs count the strided oh ow.  A
+ * dense strided layer runs on the implicit GEMM (its input gradient as the sub-pixel class GEMMs on even
+ * maps), never in the row or P16 kernels. */
+int niti_model_chain_check3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and

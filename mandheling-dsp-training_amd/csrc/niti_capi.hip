@@ -825,6 +825,42 @@ int niti_dwconv_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs,
     return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
 }
 
+// the same at stride 1 or 2 (dwconv2_ok): at stride 1 the launches above
+static bool dw2_geom(const niti_geom* g, niti::ConvGeom* r) { return g != nullptr && to_geom(g, r) && niti::dwconv2_ok(*r); }
+int niti_dwconv2_ok(const niti_geom* g) {
+    niti::ConvGeom r;
+    return dw2_geom(g, &r) ? 1 : 0;
+}
+int niti_dwconv2_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                     int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!dw2_geom(g, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_fwd(r, x, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_dwconv2_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
+                       int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!dw2_geom(g, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_dgrad(r, dy, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_dwconv2_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
+                       int* slabs, void* stream) {
+    niti::ConvGeom r;
+    if (!dw2_geom(g, &r)) return NITI_INVALID_VALUE;
+    return code(niti::dwconv_wgrad(r, x, dy, slab, slab_bytes, slabs, S(stream)));
+}
+int niti_dwconv2_wgrad_slabs(const niti_geom* g) {
+    niti::ConvGeom r;
+    return dw2_geom(g, &r) ? niti::dwconv_wgrad_slabs(r) : 0;
+}
+int niti_dwconv2_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
+                              void* stream) {
+    niti::ConvGeom r;
+    if (!dw2_geom(g, &r) || !slab || !acc || slabs != niti::dwconv_wgrad_slabs(r)) return NITI_INVALID_VALUE;
+    const int64_t n = (int64_t)r.kh * r.kw * r.cip;
+    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
+}
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

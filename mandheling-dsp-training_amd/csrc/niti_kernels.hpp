@@ -305,22 +305,25 @@ int conv0_wgrad_codes_model_blocks();
 void model_conv0_wgrad_codes(int mode);  // niti_model.hip: niti_diag_conv0_wgrad_codes
 unsigned long long model_conv0_wgrad_codes_launches();
 // ---- depthwise conv layers (niti_depthwise.hip) ------------------------------------------------
-// c_out == c_in == C, a square 3x3 / 5x5 kernel, stride 1, one pad 0 <= pad < k on every side: NITI_Conv_Int8
+// c_out == c_in == C, a square 3x3 / 5x5 kernel, stride 1 or 2, one pad 0 <= pad < k on every side: NITI_Conv_Int8
 // over the block-diagonal dense weight.  x / dy NHWC16; w, the int32 gradient and its slabs [k * k][cp],
 // tap-major (the dense OHWI16 form of a c_out = 1, c_in = C layer: SgdJob co = 1, ci = C, kk = k * k).
-// dwconv_ok: the shape predicate (every operand below 2^31 bytes).
+// dwconv_ok: the stride-1 shape predicate (every operand below 2^31 bytes), what niti_dwconv_* admit.
 bool dwconv_ok(const ConvGeom& g);
+// the same with stride 2 (both ways) admitted beside stride 1, oh = (h + 2 pad - k) / stride + 1: what the
+// launches below take.  At stride 2 the input gradient sums, per pixel, the taps its parity admits.
+bool dwconv2_ok(const ConvGeom& g);
 // pass 0: max|acc| into amax (zeroed by the caller); pass 1: recompute and requantise with the range in amax
 // (a MAX all-reduce may sit between them).  ActOut: out, relu (forward) / relu_mask (input gradient), exp_in,
 // wscale, exp_out; any other field set is hipErrorInvalidValue, as is a null operand (nothing launched).
 hipError_t dwconv_fwd(const ConvGeom& g, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o, int pass,
                       hipStream_t st);
-// the input gradient reads the same w with the tap index reversed: no transposed copy
+// the input gradient reads the same w (stride 1: with the tap index reversed): no transposed copy
 hipError_t dwconv_dgrad(const ConvGeom& g, const int8_t* dy, const int8_t* w, uint32_t* amax, const ActOut& o, int pass,
                         hipStream_t st);
 // The weight gradient as *slabs partial sums [k * k][cp] int32 in slab, k * k * cp elements apart, for
 // splitk_reduce_linear or the update launch's combine (defer, may be null: its slab fields are filled in).
-// The slab count is a function of the shape alone.  hipErrorInvalidValue, nothing launched: !dwconv_ok, a null
+// The slab count is a function of the shape alone.  hipErrorInvalidValue, nothing launched: !dwconv2_ok, a null
 // operand, slab_bytes too small.
 int dwconv_wgrad_slabs(const ConvGeom& g);
 hipError_t dwconv_wgrad(const ConvGeom& g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,

@@ -185,6 +185,9 @@ struct Layer {
     int8_t* ws_dev = nullptr;  // wscale scalar
     // per step
     int8_t* wT = nullptr;    // IHWO16, kept in step with w by sgd_update
+    // a dense stride-2 layer on an even map: the sub-pixel classes' weights of its input gradient
+    // (conv_dgrad_subpix_bytes), written with wT and kept in step by the update (SgdJob::subw)
+    int8_t* subw = nullptr;
     int8_t* r = nullptr;     // conv (+relu) output NHWC16 [n][oh][ow][cop]
     int8_t* p = nullptr;     // pooled NHWC16
     // the 2x2 pool's gradient route recorded by the forward (pool_code4, [n][ph][pw][cop] bytes; the
@@ -328,6 +331,7 @@ struct Model final : StepDriver {
         if (L.size() < 2 || c0w_slab == nullptr) return false;
         const Layer& l = L[0];
         if (!l.col || !pool_code_layer(0) || keep_grads || coll != nullptr || coll_grad != nullptr) return false;
+        if (l.og.sh != 1 || l.og.sw != 1) return false;  // (measured and tested on stride-1 first layers only)
         if (use_graph || capturing || overlap) return false;  // (one stream, direct launches: the bench's step)
         if (!rowconv_dgrad_layer(1) || rowconv_seg(L[1].dg) || head_dgrad_ok(1)) return false;
         if (probe_layer == 0 && probe_phase == 2) return false;
@@ -506,7 +510,7 @@ struct Model final : StepDriver {
     int build(int arch_, int batch_, int in_hw = 0);
     // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
     // built-in networks are build()'s own lists
-    int build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int n, int in_c_, int in_hw);
+    int build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int n, int in_c_, int in_hw, bool strided = false);
     int layer_depthwise(int layer) const override { return layer_ok(layer) ? L[layer].dw : -1; }
     int fwd_layer(int i, hipStream_t st);
     int wgrad_layer(int i, hipStream_t st);
@@ -683,7 +687,8 @@ struct Model final : StepDriver {
     }
 };
 
-static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0, int dw = 0) {
+static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0, int dw = 0,
+                     int stride = 1) {
     Layer l;
     l.dw = dw;
     l.g.n = m.batch;
@@ -691,11 +696,16 @@ static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, 
     l.g.h = l.g.w = h;
     l.g.c_out = co;
     l.g.kh = l.g.kw = k;
-    l.g.sh = l.g.sw = 1;
+    l.g.sh = l.g.sw = stride;
     l.g.pt = l.g.pl = l.g.pb = l.g.pr = pad;
     l.g.dh = l.g.dw = 1;
     l.g.finalize();
     l.og = l.g;
+    // a strided 1x1 conv over a 1x1 map is the stride-1 layer: run as that (og keeps what the list says)
+    if (stride != 1 && h == 1 && k == 1 && pad == 0) {
+        l.g.sh = l.g.sw = 1;
+        l.g.finalize();
+    }
     l.relu = relu;
     l.pool = pool;
     l.flatten = flatten;
@@ -719,7 +729,10 @@ static int64_t chain_mul(int64_t a, int64_t b) {
 // The shapes a layer list derives (the one rule niti_model_chain_check, niti_model_create_chain and
 // build_chain share): per layer {c_in, c_out, k, pad, h_in, oh, out_h, flat_c}.  Refuses malformed
 // lists and counts that do not fit an int; what else the library does not run is chain_check's.
-static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in_hw, std::vector<std::array<int, 8>>* out) {
+// strided: the `3` entry points' rule, every layer at its own stride >= 1; else every layer is taken at
+// stride 1, as the entry points that refuse any other stride always derived the shapes.
+static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in_hw, bool strided,
+                        std::vector<std::array<int, 8>>* out) {
     if (layers == nullptr || n < 1 || in_c < 1 || in_hw < 1) return NITI_INVALID_VALUE;
     int64_t c = in_c, h = in_hw;
     for (int i = 0; i < n; ++i) {
@@ -729,8 +742,9 @@ static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in
         if (l.depthwise && l.c_out != 0 && l.c_out != c) return NITI_INVALID_VALUE;
         const int64_t co = l.depthwise ? c : l.c_out;
         if (co < 1 || l.kernel < 1 || l.pad < 0 || l.pad >= l.kernel) return NITI_INVALID_VALUE;
+        if (strided && l.stride < 1) return NITI_INVALID_VALUE;
         if (h + 2 * (int64_t)l.pad < l.kernel) return NITI_INVALID_VALUE;
-        const int64_t oh = h + 2 * (int64_t)l.pad - l.kernel + 1;
+        const int64_t oh = (h + 2 * (int64_t)l.pad - l.kernel) / (strided ? l.stride : 1) + 1;
         if (l.pool && oh < 2) return NITI_INVALID_VALUE;
         const int64_t ph = l.pool ? (oh - 2) / 2 + 1 : oh;
         const int64_t fc = l.flatten ? chain_mul(chain_mul(co, ph), ph) : co;
@@ -743,15 +757,17 @@ static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in
     return NITI_NO_ERROR;
 }
 
-int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]) {
+int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], bool strided) {
     std::vector<std::array<int, 8>> sh;
     if (batch < 1) return NITI_INVALID_VALUE;
-    if (const int rc = chain_shapes(layers, n, in_c, in_hw, &sh)) return rc;
+    if (const int rc = chain_shapes(layers, n, in_c, in_hw, strided, &sh)) return rc;
     if (n > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;  // (sgd_update_many's job table)
     for (int i = 0; i < n; ++i) {
         const niti_chain_layer2& l = layers[i];
         const std::array<int, 8>& s = sh[i];
-        if (l.stride != 1) return NITI_NOT_SUPPORT;
+        if (strided ? l.stride > 2 : l.stride != 1) return NITI_NOT_SUPPORT;
+        // a strided layer after a flatten: its input is a 1x1 map
+        if (l.stride != 1 && i > 0 && layers[i - 1].flatten) return NITI_NOT_SUPPORT;
         if (l.kernel > CHAIN_MAX_KERNEL) return NITI_NOT_SUPPORT;
         // a depthwise layer: not the first layer (its im2col form), not the logits, not on a flattened
         // map; the kernels take 3x3 and 5x5
@@ -760,7 +776,9 @@ int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int
         if (i > 0 && layers[i - 1].flatten && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
         // a first layer the fused input pass takes (input_im2col) stages kernel + band - 1 image rows
         // of 4 bytes a pixel in LDS: one output row must fit in half of a workgroup's 64 KiB
-        if (i == 0 && Model::input_fused_ok(s[0], l.kernel, l.pad) && (int64_t)l.kernel * (s[4] + l.kernel - 1) * 4 > 32768)
+        // (a strided first layer does not run there)
+        if (i == 0 && l.stride == 1 && Model::input_fused_ok(s[0], l.kernel, l.pad) &&
+            (int64_t)l.kernel * (s[4] + l.kernel - 1) * 4 > 32768)
             return NITI_NOT_SUPPORT;
         if (i == n - 1 && (s[1] > 2048 || l.pool || l.flatten || s[5] != 1)) return NITI_NOT_SUPPORT;
         // every tensor of the layer, in the padded layouts build_chain allocates
@@ -804,18 +822,19 @@ int Model::build(int arch_, int batch_, int in_hw) {
     return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw);
 }
 
-int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int nlayers, int in_c_, int in_hw) {
+int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int nlayers, int in_c_, int in_hw,
+                       bool strided) {
     arch = arch_;
     batch = batch_;
     std::vector<std::array<int, 8>> sh;
-    if (const int rc = chain_shapes(layers, nlayers, in_c_, in_hw, &sh)) return rc;
+    if (const int rc = chain_shapes(layers, nlayers, in_c_, in_hw, strided, &sh)) return rc;
     in_c = in_c_;
     in_h = in_w = in_hw;
     for (int i = 0; i < nlayers; ++i)
         add_conv(*this, sh[i][0], sh[i][1], sh[i][2], sh[i][3], sh[i][4], layers[i].relu != 0, layers[i].pool != 0,
-                 layers[i].flatten != 0, layers[i].depthwise);
+                 layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1);
     for (const Layer& l : L)
-        if (l.dw && !dwconv_ok(l.g)) return NITI_NOT_SUPPORT;
+        if (l.dw && !dwconv2_ok(l.g)) return NITI_NOT_SUPPORT;
     const int n = batch;
     {
         Layer& f = L[0];
@@ -908,6 +927,10 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
             l.slab16_bytes = (size_t)dwconv_wgrad_slabs(g) * l.w_elems() * sizeof(int32_t);
             l.slab16 = (int32_t*)ws.alloc(l.slab16_bytes);
             if (!l.slab16) return NITI_OUT_OF_MEMORY;
+        }
+        if (i > 0 && !l.dw && conv_dgrad_subpix_ok(g)) {
+            l.subw = (int8_t*)ws.alloc(conv_dgrad_subpix_bytes(g));
+            if (!l.subw) return NITI_OUT_OF_MEMORY;
         }
         if (!l.col && !l.dw && rowconv_ok(g)) {
             l.rc = 1;
@@ -1365,17 +1388,19 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     dy16_valid[i - 1] = 1;
     const ConvGeom& pg = pv.g;
     // (a depthwise layer: its own two launches below, the fall-back's plain outputs around them)
+    // (a strided layer on its sub-pixel class GEMMs: plain outputs too -- their requantise takes no others)
+    const bool sub = l.subw != nullptr;
     const bool spec = !l.dw && conv_dgrad_spec_ok(g);
     // dy of layer i - 1 is rewritten here; its P16 copy comes along where the requant pass can
     // write it (the plain and the fused pool-gradient passes), else wgrad_layer converts it
-    int8_t* p16_out = !l.dw && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
+    int8_t* p16_out = !l.dw && !sub && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
     dp16_valid[i - 1] = 0;
     ActOut o;
     bool fuse = false;
     if (pv.flatten) {
         o.out = pv.dflat;
     } else if (pv.pool) {
-        fuse = !l.dw && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
+        fuse = !l.dw && !sub && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
         if (fuse) {  // pool gradient + relu gradient ride along the requant pass
             o.out = nullptr;
             o.pool.x = pv.r;
@@ -1407,8 +1432,8 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         },
         [&](const ActOut& ao, int ph) {
             if (l.dw) return dwconv_dgrad(g, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
-            return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st)
-                           : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st);
+            return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st, l.subw)
+                           : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st, l.subw);
         });
     if (rc != NITI_NO_ERROR) return rc;
     probe(i, 1, false, st);
@@ -1838,6 +1863,13 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
                          i > 0 && !rowconv_dgrad_layer(i) && !l.dw ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
         jobs[i].wf = l.rc ? l.wf : nullptr;
         jobs[i].wft = l.rcd ? l.wft : nullptr;
+        if (l.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights
+            jobs[i].subw = l.subw;
+            jobs[i].sub_kh = g.kh;
+            jobs[i].sub_kw = g.kw;
+            jobs[i].sub_pt = g.pt;
+            jobs[i].sub_pl = g.pl;
+        }
         // the combine of this layer's split-K slabs, in the update launch
         if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
     }
@@ -1908,7 +1940,7 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
             L[i].col != src.L[i].col || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
-            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw)
+            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].og.sh != src.L[i].og.sh)
             return NITI_INVALID_VALUE;
     }
     if (&src == this) return NITI_NO_ERROR;
@@ -1921,6 +1953,7 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         l.wscale = s.wscale;
         if (!l.rcd && !l.dw)  // (refresh_wt below rebuilds the row-kernel layers')
             DTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
+        if (l.subw) DTRY(conv_dgrad_subpix_weights(g, l.wT, l.subw, st));
     }
     int rc = refresh_wt(st);
     if (rc == NITI_NO_ERROR) rc = refresh_wf(st);
@@ -2056,6 +2089,7 @@ int Model::set_weight(int layer, const int8_t* w_host, int wscale) {
     if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
         oihw_to_ohwi16(tmp, l.w_co(), l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
         (!l.dw && oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess) ||
+        (l.subw && conv_dgrad_subpix_weights(l.g, l.wT, l.subw, nullptr) != hipSuccess) ||
         hipMemset(l.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess ||
         (l.rc && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, nullptr) != hipSuccess) ||
         (l.rcd && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, nullptr) != hipSuccess) ||
@@ -2200,11 +2234,11 @@ int Model::spec_stats(uint32_t* out, int max_layers) {
 }
 
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
-                                                   int* rc) {
-    *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr);  // (nothing allocated on a refusal)
+                                                   int* rc, bool strided) {
+    *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr, strided);  // (nothing allocated on a refusal)
     if (*rc != NITI_NO_ERROR) return nullptr;
     auto m = std::make_unique<Model>();
-    *rc = m->build_chain(NITI_ARCH_CHAIN, batch, layers, n, in_c, in_hw);
+    *rc = m->build_chain(NITI_ARCH_CHAIN, batch, layers, n, in_c, in_hw, strided);
     if (*rc != NITI_NO_ERROR) return nullptr;
     return m;
 }

@@ -56,6 +56,19 @@ int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, i
     return NITI_NO_ERROR;
 }
 
+int niti_model_chain_check3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes, true);
+}
+
+int niti_model_create_chain3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    if (!out || batch <= 0) return NITI_INVALID_VALUE;
+    int rc = NITI_NO_ERROR;
+    std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc, true);
+    if (!d) return rc;
+    *out = new niti_model{std::move(d)};
+    return NITI_NO_ERROR;
+}
+
 // the seven-field list as the same list with depthwise = 0 (empty where the arguments are malformed:
 // the check then refuses them as it always did)
 static std::vector<niti_chain_layer2> chain_layers2(const niti_chain_layer* layers, int n) {

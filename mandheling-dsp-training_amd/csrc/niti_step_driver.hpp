@@ -280,10 +280,12 @@ std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int
 // niti_model_resnet_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
 int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_layers, int shapes[][8]);
 // a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch
+// (strided: niti_model_create_chain3's rule, the layers' strides honoured; else stride != 1 is refused)
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
-                                                   int* rc);
+                                                   int* rc, bool strided = false);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
-int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8]);
+int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8],
+                bool strided = false);
 
 // a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
 // zero padded to the column pitch kp <-> OIHW

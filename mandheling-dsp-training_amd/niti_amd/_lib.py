@@ -243,6 +243,12 @@ def lib():
         "niti_dwconv_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
         "niti_dwconv_wgrad_slabs": (ci, [C.POINTER(Geom)]),
         "niti_dwconv_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
+        "niti_dwconv2_ok": (ci, [C.POINTER(Geom)]),
+        "niti_dwconv2_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_dwconv2_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_dwconv2_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
+        "niti_dwconv2_wgrad_slabs": (ci, [C.POINTER(Geom)]),
+        "niti_dwconv2_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
@@ -286,6 +292,8 @@ def lib():
         "niti_model_chain_check2": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain2": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         "niti_model_layer_depthwise": (ci, [vp, ci]),
+        "niti_model_chain_check3": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain3": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         # (spec: a ResnetSpec, passed untyped)
         "niti_model_resnet_check": (ci, [vp, ci, C.POINTER(ci), vp]),
         "niti_model_create_resnet": (ci, [vp, ci, ci, C.POINTER(vp)]),

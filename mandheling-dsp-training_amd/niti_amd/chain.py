@@ -1,8 +1,8 @@
 """User-defined chain networks: a model from a layer list (niti_chain_layer2, include/niti_hip.h).
 
 A spec is a list of layers, each a dict with the keys c_out, kernel and optionally pad, relu,
-pool, flatten, depthwise (default 0), or a tuple (c_out, kernel, pad, relu, pool, flatten,
-depthwise) whose tail may be left out.  The input channels and map size of every layer are derived;
+pool, flatten, depthwise (default 0), stride (default 1; 1 or 2), or a tuple (c_out, kernel, pad, relu,
+pool, flatten, depthwise, stride) whose tail may be left out.  The input channels and map size of every layer are derived;
 the last layer's c_out is the class count.  A depthwise layer has its input's channels: its c_out
 may be 0 or, in a dict, left out.
 """
@@ -13,13 +13,15 @@ import ctypes as C
 from . import _lib as L
 from ._lib import check
 
-_KEYS = ("c_out", "kernel", "pad", "relu", "pool", "flatten", "depthwise")
+_KEYS = ("c_out", "kernel", "pad", "relu", "pool", "flatten", "depthwise", "stride")
+_DEFAULT = {"stride": 1}
 
 
 def normalize_spec(spec) -> list:
     """The spec as a list of dicts of plain ints (what snapshots store and compare): the keys c_out,
-    kernel, pad, relu, pool, flatten and, only for a list that has a depthwise layer, depthwise -- so
-    the record of a list without one is what it always was.  A depthwise layer's c_out of 0 becomes
+    kernel, pad, relu, pool, flatten and, only for a list that has a depthwise layer, depthwise, only
+    for a list that has a layer of stride other than 1, stride -- so the record of a list without one is
+    what it always was.  A depthwise layer's c_out of 0 becomes
     the previous layer's c_out where that is the layer's input (not after a flatten, not layer 0:
     lists the check refuses anyway)."""
     out = []
@@ -29,14 +31,17 @@ def normalize_spec(spec) -> list:
             dw = bool(l.get("depthwise", 0))
             if extra or ("c_out" not in l and not dw) or "kernel" not in l:
                 raise ValueError(f"layer {i}: needs c_out and kernel, takes {_KEYS}, got {sorted(l)}")
-            d = {k: int(l.get(k, 0)) for k in _KEYS}
+            d = {k: int(l.get(k, _DEFAULT.get(k, 0))) for k in _KEYS}
         else:
             l = tuple(l)
             if not 2 <= len(l) <= len(_KEYS):
-                raise ValueError(f"layer {i}: a tuple (c_out, kernel[, pad, relu, pool, flatten, depthwise]), got {l!r}")
-            d = {k: int(l[j]) if j < len(l) else 0 for j, k in enumerate(_KEYS)}
+                raise ValueError(
+                    f"layer {i}: a tuple (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride]), got {l!r}")
+            d = {k: int(l[j]) if j < len(l) else _DEFAULT.get(k, 0) for j, k in enumerate(_KEYS)}
         for k in ("relu", "pool", "flatten"):
             d[k] = 1 if d[k] else 0
+        if d["stride"] < 1:
+            raise ValueError(f"layer {i}: stride {d['stride']}")
         if d["depthwise"] == 1 and d["c_out"] == 0 and out and not out[-1]["flatten"]:
             d["c_out"] = out[-1]["c_out"]
         out.append(d)
@@ -45,14 +50,23 @@ def normalize_spec(spec) -> list:
     if not any(d["depthwise"] for d in out):
         for d in out:
             del d["depthwise"]
+    if all(d["stride"] == 1 for d in out):
+        for d in out:
+            del d["stride"]
     return out
+
+
+def strided(spec) -> bool:
+    """A normalised spec that has a layer of stride other than 1: it goes through the `3` entry points
+    (niti_model_chain_check3 / _create_chain3), every other list through the ones it always went through."""
+    return any("stride" in d for d in spec)
 
 
 def to_c(spec):
     """(niti_chain_layer2 array, count) of a normalised spec."""
     arr = (L.ChainLayer2 * len(spec))()
     for a, d in zip(arr, spec):
-        a.c_out, a.kernel, a.stride, a.pad = d["c_out"], d["kernel"], 1, d["pad"]
+        a.c_out, a.kernel, a.stride, a.pad = d["c_out"], d["kernel"], d.get("stride", 1), d["pad"]
         a.relu, a.pool, a.flatten = d["relu"], d["pool"], d["flatten"]
         a.depthwise = d.get("depthwise", 0)
     return arr, len(spec)
@@ -60,13 +74,15 @@ def to_c(spec):
 
 def chain_layers(spec, in_c: int, in_hw: int) -> list:
     """The derived layer list of a spec over in_c x in_hw x in_hw inputs, as dicts with the keys
-    ci, co, k, pad, h, relu, pool, flatten and, for a list that has a depthwise layer, depthwise (host
-    only: niti_model_chain_check2).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
+    ci, co, k, pad, h, relu, pool, flatten and, for a list that has a depthwise layer, depthwise, for a
+    list that has a strided layer, stride (host only: niti_model_chain_check2, or _check3 for a list with
+    a strided layer).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
     the library does not run."""
     spec = normalize_spec(spec)
     arr, n = to_c(spec)
     shapes = ((C.c_int * 8) * n)()
-    code = L.lib().niti_model_chain_check2(arr, n, int(in_c), int(in_hw), shapes)
+    fn = L.lib().niti_model_chain_check3 if strided(spec) else L.lib().niti_model_chain_check2
+    code = fn(arr, n, int(in_c), int(in_hw), shapes)
     if code == L.INVALID_VALUE:
         raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input: {spec}")
     check(code, "chain_check")
@@ -75,4 +91,6 @@ def chain_layers(spec, in_c: int, in_hw: int) -> list:
     for o, d in zip(out, spec):  # (the list of a spec without such a layer is what it always was)
         if "depthwise" in d:
             o["depthwise"] = d["depthwise"]
+        if "stride" in d:
+            o["stride"] = d["stride"]
     return out

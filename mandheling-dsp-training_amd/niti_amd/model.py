@@ -39,19 +39,21 @@ class NitiModel:
 
     @classmethod
     def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
-        """A model of the caller's own chain network (niti_model_create_chain2): spec is a list of
-        dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise]) or tuples in that order, over
-        in_c x in_hw x in_hw inputs; the last layer's c_out is the class count.  A depthwise layer
-        (3x3 or 5x5, c_out 0 or its input's channels) has weights [C, 1, k, k].  ValueError for a
+        """A model of the caller's own chain network (niti_model_create_chain2; _create_chain3 for a list
+        with a strided layer): spec is a list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise,
+        stride]) or tuples in that order, over in_c x in_hw x in_hw inputs; the last layer's c_out is the
+        class count.  A depthwise layer (3x3 or 5x5, c_out 0 or its input's channels) has weights
+        [C, 1, k, k]; stride (1 or 2) is a dense or depthwise layer's own.  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
-        from .chain import normalize_spec, to_c
+        from .chain import normalize_spec, strided, to_c
         spec = normalize_spec(spec)
         arr, n = to_c(spec)
         m = cls.__new__(cls)
         m._lib = L.lib()
         h = C.c_void_p()
-        code = m._lib.niti_model_create_chain2(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
+        create = m._lib.niti_model_create_chain3 if strided(spec) else m._lib.niti_model_create_chain2
+        code = create(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
         if code == L.INVALID_VALUE:
             raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input at batch {batch}: {spec}")
         check(code, "model_create_chain")

@@ -692,26 +692,72 @@ def dwconv_wgrad_slabs(g) -> int:
     return int(L.lib().niti_dwconv_wgrad_slabs(C.byref(g)))
 
 
+def _dwconv_wgrad(pre, g, x16, dy16, slab, stream):
+    if slab is None:
+        count = int(getattr(L.lib(), f"niti_{pre}_wgrad_slabs")(C.byref(g)))
+        slab = torch.full((max(count, 1), g.kh * g.kw * g.cip), 0x5A5A5A5A, dtype=torch.int32, device=x16.device)
+    wrote = C.c_int(-1)
+    check(getattr(L.lib(), f"niti_{pre}_wgrad")(C.byref(g), _ptr(x16), _ptr(dy16), _ptr(slab), slab.numel() * 4,
+                                                C.byref(wrote), _stream(stream)), f"{pre}_wgrad")
+    assert wrote.value == slab.shape[0]
+    return slab
+
+
+def _dwconv_wgrad_reduce(pre, g, slab, amax, stream):
+    acc = torch.full((1, g.kh, g.kw, g.cip), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
+    check(getattr(L.lib(), f"niti_{pre}_wgrad_reduce")(C.byref(g), _ptr(slab), slab.shape[0], _ptr(acc), _ptr(amax),
+                                                       _stream(stream)), f"{pre}_wgrad_reduce")
+    return acc
+
+
 def dwconv_wgrad(g, x16, dy16, slab=None, stream=None):
     """A depthwise layer's weight gradient as partial sums (niti_dwconv_wgrad): int32 [slabs][k * k * cp],
     for sgd_combine, sgd_update_many_bits' slab or dwconv_wgrad_reduce."""
-    if slab is None:
-        slab = torch.full((max(dwconv_wgrad_slabs(g), 1), g.kh * g.kw * g.cip), 0x5A5A5A5A, dtype=torch.int32,
-                          device=x16.device)
-    wrote = C.c_int(-1)
-    check(L.lib().niti_dwconv_wgrad(C.byref(g), _ptr(x16), _ptr(dy16), _ptr(slab), slab.numel() * 4, C.byref(wrote),
-                                    _stream(stream)), "dwconv_wgrad")
-    assert wrote.value == slab.shape[0]
-    return slab
+    return _dwconv_wgrad("dwconv", g, x16, dy16, slab, stream)
 
 
 def dwconv_wgrad_reduce(g, slab, amax=None, stream=None):
     """The slabs summed into acc int32 [1][k][k][cp] with max|acc| into amax (zeroed by the caller; may be
     None), by the reduce launch the training step uses where the update launch does not combine."""
-    acc = torch.full((1, g.kh, g.kw, g.cip), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
-    check(L.lib().niti_dwconv_wgrad_reduce(C.byref(g), _ptr(slab), slab.shape[0], _ptr(acc), _ptr(amax),
-                                           _stream(stream)), "dwconv_wgrad_reduce")
-    return acc
+    return _dwconv_wgrad_reduce("dwconv", g, slab, amax, stream)
+
+
+# The same six at stride 1 or 2 (niti_dwconv2_*; g = geom(..., stride=2) with oh = (h + 2 pad - k) // 2 + 1).  At
+# stride 1 they are the launches above; the wrappers above keep refusing every stride but 1.
+def dwconv2_ok(g) -> bool:
+    """Whether the strided depthwise launches take g (niti_dwconv2_ok; host only): dwconv_ok's rule with
+    stride_h == stride_w in {1, 2}."""
+    return bool(L.lib().niti_dwconv2_ok(C.byref(g)))
+
+
+def dwconv2_fwd(g, x16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
+                exp_out=None, stream=None):
+    """dwconv_fwd at stride 1 or 2 (niti_dwconv2_fwd)."""
+    return _dwconv_act(L.lib().niti_dwconv2_fwd, "dwconv2_fwd", g, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cip),
+                       out, relu, relu_mask, exp_in, wscale, exp_out, stream)
+
+
+def dwconv2_dgrad(g, dy16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
+                  exp_out=None, stream=None):
+    """dwconv_dgrad at stride 1 or 2 (niti_dwconv2_dgrad): at stride 2 every input pixel sums the taps its
+    parity admits; rows and columns no output reads come out 0."""
+    return _dwconv_act(L.lib().niti_dwconv2_dgrad, "dwconv2_dgrad", g, dy16, w16, amax, pass_,
+                       (g.n, g.h, g.w, g.cip), out, relu, relu_mask, exp_in, wscale, exp_out, stream)
+
+
+def dwconv2_wgrad_slabs(g) -> int:
+    """The partial slabs niti_dwconv2_wgrad leaves for g (0 where the launches do not take g)."""
+    return int(L.lib().niti_dwconv2_wgrad_slabs(C.byref(g)))
+
+
+def dwconv2_wgrad(g, x16, dy16, slab=None, stream=None):
+    """dwconv_wgrad at stride 1 or 2 (niti_dwconv2_wgrad)."""
+    return _dwconv_wgrad("dwconv2", g, x16, dy16, slab, stream)
+
+
+def dwconv2_wgrad_reduce(g, slab, amax=None, stream=None):
+    """dwconv_wgrad_reduce at stride 1 or 2 (niti_dwconv2_wgrad_reduce)."""
+    return _dwconv_wgrad_reduce("dwconv2", g, slab, amax, stream)
 
 
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):

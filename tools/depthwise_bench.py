@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Depthwise conv launches against two yardsticks measured in the same run (GPU box; not a test, not
 part of bench.py):  python3 tools/depthwise_bench.py [--reps 50] [--out profiles/depthwise_bench.txt]
+                    python3 tools/depthwise_bench.py --stride 2 --out profiles/depthwise_stride2_bench.txt
 
-Per shape (C channels at h x h pixels, 3x3 pad 1 unless --k 5) and phase:
+Per shape (C channels at h x h pixels, 3x3 pad 1 unless --k 5; --stride 2: MobileNet's downsampling layers,
+64 @ 112 -> 56, 128 @ 56 -> 28, 256 @ 28 -> 14, 512 @ 14 -> 7, through niti_dwconv2_*) and phase:
   dw     the depthwise launches: forward / input gradient = pass 0 (range) + pass 1 (requantise);
          weight gradient = the slab launch + the combine (niti_sgd_combine)
   copy   a device-to-device copy that moves the phase's algorithmic bytes: forward / input gradient read
          the input twice and write the output once (3 bytes per element: a copy of 1.5 n bytes); the
-         weight gradient reads x and dy once (2 bytes per element: a copy of n bytes)
+         weight gradient reads x and dy once (2 bytes per element: a copy of n bytes).  At stride 2 the
+         output is a quarter of the input: forward 2 in + out, input gradient 2 out + in, weight gradient in + out
   dense  the same layer the only way the library ran it before: a block-diagonal dense layer on the
          op-level GEMM path (conv_*_acc with its range, then requant_act; weight gradient: conv_wgrad_acc
          + absmax over the dense tensor, whose range is not the layer's)
@@ -27,6 +30,7 @@ import niti_amd._lib as L  # noqa: E402
 from niti_amd import ops  # noqa: E402
 
 SHAPES = [(256, 64, 32), (256, 128, 16), (256, 256, 8), (256, 512, 4), (32, 64, 112)]  # (batch, C, h)
+SHAPES_STRIDE2 = [(32, 64, 112), (32, 128, 56), (32, 256, 28), (32, 512, 14)]
 
 
 def timed(fn, reps):
@@ -49,19 +53,23 @@ def ok(code):
     assert code == 0, code
 
 
-def bench_shape(n, c, h, k, reps):
+def bench_shape(n, c, h, k, reps, stride=1):
     lib = L.lib()
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     pad = k // 2
-    g = ops.geom(n, c, h, h, c, k, pad=pad)
+    g = ops.geom(n, c, h, h, c, k, stride=stride, pad=pad)
     dev = "cuda"
     P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    elems = n * h * h * g.cip
+    fwd_fn, dgrad_fn, wgrad_fn = ((lib.niti_dwconv_fwd, lib.niti_dwconv_dgrad, lib.niti_dwconv_wgrad) if stride == 1 else
+                                  (lib.niti_dwconv2_fwd, lib.niti_dwconv2_dgrad, lib.niti_dwconv2_wgrad))
+    elems, oelems = n * h * h * g.cip, n * g.oh * g.ow * g.cip
+    # the phases' algorithmic bytes (at stride 1: 3 / 3 / 2 per element)
+    nbytes = {"fwd": 2 * elems + oelems, "dgrad": 2 * oelems + elems, "wgrad": elems + oelems}
     x = torch.randint(-127, 128, (n, h, h, g.cip), dtype=torch.int8, device=dev)
-    dy = torch.randint(-127, 128, (n, h, h, g.cip), dtype=torch.int8, device=dev)
+    dy = torch.randint(-127, 128, (n, g.oh, g.ow, g.cip), dtype=torch.int8, device=dev)
     w = torch.randint(-127, 128, (c, 1, k, k), dtype=torch.int8, device=dev)
     w16 = ops.dwconv_weight(w)
-    out = torch.empty_like(x)
+    out = torch.empty_like(x)  # (the larger of the two outputs)
     amax = ops.new_range()
     o = L.DwconvOut()
     o.out = out.data_ptr()
@@ -76,7 +84,7 @@ def bench_shape(n, c, h, k, reps):
 
     o2 = L.DwconvOut()
     o2.out = out.data_ptr()
-    slabs = ops.dwconv_wgrad_slabs(g)
+    slabs = ops.dwconv2_wgrad_slabs(g)
     slab = torch.empty((slabs, k * k * g.cip), dtype=torch.int32, device=dev)
     dwacc = torch.empty(k * k * g.cip, dtype=torch.int32, device=dev)
     job = (L.SgdCombineJob * 1)()
@@ -85,20 +93,21 @@ def bench_shape(n, c, h, k, reps):
 
     def dw_wgrad():
         amax.zero_()
-        ok(lib.niti_dwconv_wgrad(C.byref(g), P(x), P(dy), P(slab), slab.numel() * 4, None, s))
+        ok(wgrad_fn(C.byref(g), P(x), P(dy), P(slab), slab.numel() * 4, None, s))
         ok(lib.niti_sgd_combine(job, 1, s))
 
     def dw_dgrad_run():
         amax.zero_()
-        ok(lib.niti_dwconv_dgrad(C.byref(g), P(dy), P(w16), P(amax), C.byref(o2), 0, s))
-        ok(lib.niti_dwconv_dgrad(C.byref(g), P(dy), P(w16), P(amax), C.byref(o2), 1, s))
+        ok(dgrad_fn(C.byref(g), P(dy), P(w16), P(amax), C.byref(o2), 0, s))
+        ok(dgrad_fn(C.byref(g), P(dy), P(w16), P(amax), C.byref(o2), 1, s))
 
-    src = torch.empty(elems * 3 // 2, dtype=torch.int8, device=dev)
+    src = torch.empty(max(nbytes.values()) // 2, dtype=torch.int8, device=dev)
     dst = torch.empty_like(src)
+    copy = lambda ph: timed(lambda: dst[:nbytes[ph] // 2].copy_(src[:nbytes[ph] // 2]), reps)  # noqa: E731
     rows = {}
-    rows["fwd"] = [timed(dw_act(lib.niti_dwconv_fwd), reps), timed(lambda: dst.copy_(src), reps)]
-    rows["dgrad"] = [timed(dw_dgrad_run, reps), rows["fwd"][1]]
-    rows["wgrad"] = [timed(dw_wgrad, reps), timed(lambda: dst[:elems].copy_(src[:elems]), reps)]
+    rows["fwd"] = [timed(dw_act(fwd_fn), reps), copy("fwd")]
+    rows["dgrad"] = [timed(dw_dgrad_run, reps), rows["fwd"][1] if stride == 1 else copy("dgrad")]
+    rows["wgrad"] = [timed(dw_wgrad, reps), copy("wgrad")]
 
     # the dense emulation: W[o][i] = (o == i) ? w[o] : 0 on the op-level GEMM path
     wd = torch.zeros((c, c, k, k), dtype=torch.int8, device=dev)
@@ -106,6 +115,7 @@ def bench_shape(n, c, h, k, reps):
     wd[idx, idx] = w[:, 0]
     wd16 = ops.oihw_to_ohwi16(wd)
     wdT = ops.ohwi16_to_ihwo16(wd16, c)
+    opx = n * g.oh * g.ow
     acc = torch.empty((n * h * h, g.cop), dtype=torch.int32, device=dev)
     wacc = torch.empty((c, k, k, g.cip), dtype=torch.int32, device=dev)
     wss = [ops.conv_workspace(g, op) for op in (0, 1, 2)]
@@ -113,7 +123,7 @@ def bench_shape(n, c, h, k, reps):
     def dense_fwd():
         amax.zero_()
         ok(lib.niti_conv_fwd_acc(C.byref(g), P(x), P(wd16), P(acc), P(amax), P(wss[0][0]), wss[0][1], s))
-        ok(lib.niti_requant_act(P(acc), n * h * h, g.cop, P(amax), None, None, None, 1, None, P(out), s))
+        ok(lib.niti_requant_act(P(acc), opx, g.cop, P(amax), None, None, None, 1, None, P(out), s))
 
     def dense_dgrad():
         amax.zero_()
@@ -127,24 +137,26 @@ def bench_shape(n, c, h, k, reps):
     rows["fwd"].append(timed(dense_fwd, reps))
     rows["dgrad"].append(timed(dense_dgrad, reps))
     rows["wgrad"].append(timed(dense_wgrad, reps))
-    return elems, slabs, rows
+    return nbytes, slabs, rows
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--k", type=int, default=3, choices=[3, 5])
+    ap.add_argument("--stride", type=int, default=1, choices=[1, 2])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depthwise_bench.txt"))
     args = ap.parse_args()
-    lines = [f"# tools/depthwise_bench.py --reps {args.reps} --k {args.k}: {torch.cuda.get_device_name(0)}",
+    lines = [f"# tools/depthwise_bench.py --reps {args.reps} --k {args.k}" + (" --stride 2" if args.stride == 2 else "") +
+             f": {torch.cuda.get_device_name(0)}",
              "# us per phase: dw = the depthwise launches, copy = a copy moving the phase's algorithmic bytes,",
              "# dense = the block-diagonal dense layer on the op-level GEMM path",
              f"{'shape':>18} {'phase':>6} {'MB':>8} {'dw':>9} {'copy':>9} {'dense':>9} {'dw/copy':>8} {'dense/dw':>9} {'GB/s':>8}"]
-    for n, c, h in SHAPES:
-        elems, slabs, rows = bench_shape(n, c, h, args.k, args.reps)
+    for n, c, h in (SHAPES if args.stride == 1 else SHAPES_STRIDE2):
+        nbytes, slabs, rows = bench_shape(n, c, h, args.k, args.reps, args.stride)
         for ph, (dw, cp, dn) in rows.items():
-            mb = elems * (2 if ph == "wgrad" else 3) / 1e6
-            lines.append(f"{f'{c}@{h}px b{n}':>18} {ph:>6} {mb:8.1f} {dw:9.2f} {cp:9.2f} {dn:9.2f} {dw / cp:8.2f} "
+            mb = nbytes[ph] / 1e6
+            lines.append(f"{f'{c}@{h}px' + ('/2' if args.stride == 2 else '') + f' b{n}':>18} {ph:>6} {mb:8.1f} {dw:9.2f} {cp:9.2f} {dn:9.2f} {dw / cp:8.2f} "
                          f"{dn / dw:9.2f} {mb / dw * 1e3:8.0f}" + (f"   ({slabs} slabs)" if ph == "wgrad" else ""))
         print("\n".join(lines[-3:]), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
