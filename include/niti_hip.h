@@ -274,6 +274,11 @@ int niti_conv_rows_ok(const niti_geom* g);
  * g is the LAYER's geometry; dgrad != 0 asks for its input gradient with a fused relu / pool
  * gradient (niti_conv_dgrad_rows).  Returns 1, or 0 where niti_conv_rows_ok refuses the geometry. */
 int niti_conv_rows_plan(const niti_geom* g, int dgrad, int* W, int* R, int* ks, int* workgroups);
+/* The same with pooled != 0: the input gradient (dgrad != 0) is routed through the previous layer's 2x2
+ * max pool (niti_conv_dgrad_rows with pool_x / pool_y).  A pooled 4x4 input gradient whose grid at two
+ * rows per band is 384 .. 512 waves runs one row per band (R = 1, twice the workgroups).  pooled = 0 is
+ * niti_conv_rows_plan. */
+int niti_conv_rows_plan2(const niti_geom* g, int dgrad, int pooled, int* W, int* R, int* ks, int* workgroups);
 int niti_nhwc16_to_c32(const int8_t* in_nhwc16, int n, int hw, int cp, int c, int8_t* out_c32, void* stream);
 int niti_weights_to_wf(const int8_t* w_ohwi16, int co, int ci, int cip, int transpose, int8_t* out_wf,
                        void* stream);
@@ -331,6 +336,10 @@ void niti_diag_rowconv_barrier(uint32_t spin_limit, uint32_t expect_extra);
  * measured slower), 2 always guess wrong (every launch redoes its epilogue).  Results are identical
  * in every mode. */
 void niti_diag_rowconv_speculate(int mode);
+/* one row per band for pooled 4x4 input gradients (niti_conv_rows_plan2) for later launches and plans:
+ * 1 on, 0 off (two rows per band, as before), -1 the default (on; the environment's NITI_RC_ROWS1=0
+ * turns it off).  Results are identical either way.  Set it before a model is created. */
+void niti_diag_rowconv_rows1(int mode);
 /* diagnostics: launch A of every GEMM speculative pair (plan strategy 3) guesses the layer's previous
  * bit width + bias: +-1 makes launch B settle from an alternate, 2 makes it redo the GEMM (tests);
  * 0 (default) off.  Results are the rule's whatever the bias. */

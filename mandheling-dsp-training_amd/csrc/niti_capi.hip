@@ -317,8 +317,17 @@ int niti_conv_rows_plan(const niti_geom* g, int dgrad, int* W, int* R, int* ks, 
     niti::ConvGeom r, d;
     if (!g || !W || !R || !ks || !workgroups || !to_geom(g, &r)) return 0;
     if (dgrad && !niti::rowconv_dgrad_geom(r, &d)) return 0;
-    return niti::rowconv_plan(dgrad ? d : r, dgrad != 0, W, R, ks, workgroups) ? 1 : 0;
+    return niti::rowconv_plan(dgrad ? d : r, dgrad != 0, false, W, R, ks, workgroups) ? 1 : 0;
 }
+
+int niti_conv_rows_plan2(const niti_geom* g, int dgrad, int pooled, int* W, int* R, int* ks, int* workgroups) {
+    niti::ConvGeom r, d;
+    if (!g || !W || !R || !ks || !workgroups || !to_geom(g, &r)) return 0;
+    if (dgrad && !niti::rowconv_dgrad_geom(r, &d)) return 0;
+    return niti::rowconv_plan(dgrad ? d : r, dgrad != 0, dgrad != 0 && pooled != 0, W, R, ks, workgroups) ? 1 : 0;
+}
+
+void niti_diag_rowconv_rows1(int mode) { niti::rowconv_rows1(mode); }
 
 int niti_nhwc16_to_c32(const int8_t* in, int n, int hw, int cp, int c, int8_t* out, void* stream) {
     if (!in || !out || n <= 0 || hw <= 0 || c <= 0 || cp < c || cp % 16) return NITI_INVALID_VALUE;
@@ -378,7 +387,7 @@ int niti_conv_dgrad_rows(const niti_geom* g, const int8_t* dy_c32, const int8_t*
     niti::ConvGeom r, d;
     if (!to_geom(g, &r)) return NITI_COMPUTE_SIZE_ERROR;
     if (!niti::rowconv_dgrad_geom(r, &d)) return NITI_NOT_SUPPORT;
-    if (mode == 0 && !niti::rowconv_fused_ok(d, true)) return NITI_NOT_SUPPORT;
+    if (mode == 0 && !niti::rowconv_fused_ok(d, true, pool_x != nullptr)) return NITI_NOT_SUPPORT;
     if (dx_p16 != nullptr && !niti::rowconv_p16_ok(d, pool_x != nullptr)) return NITI_NOT_SUPPORT;
     if (x_nhwc && !niti::rowconv_nhwc_ok(d)) return NITI_NOT_SUPPORT;
     niti::RowConvOut o;

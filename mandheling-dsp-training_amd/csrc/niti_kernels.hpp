@@ -437,7 +437,9 @@ struct RowConvOut {
     // == 0: read in place, no C32 copy)
     int x_nhwc = 0;
 };
-size_t rowconv_acc_bytes(const ConvGeom& g, bool dg);
+// pooled (here and below): an input gradient routed through the previous layer's 2x2 pool -- a 4x4
+// one that would half-fill the chip takes one row per band (rowconv_rows)
+size_t rowconv_acc_bytes(const ConvGeom& g, bool dg, bool pooled = false);
 bool rowconv_nhwc_ok(const ConvGeom& g);
 bool rowconv_nhwc_pref(const ConvGeom& g);
 constexpr int ROWCONV_BAR_WORDS = 2 * 19 * 32;  // grid-barrier state (both parities)
@@ -452,12 +454,15 @@ bool rowconv_dgrad_geom(const ConvGeom& layer, ConvGeom* d);
 bool rowconv_p16_ok(const ConvGeom& d, bool pool);
 // FUSED (one launch, in-kernel grid barrier) possible: one unit per wave, every workgroup resident
 // dg: for the input-gradient epilogues (at most 4 rows per unit)
-bool rowconv_fused_ok(const ConvGeom& g, bool dg = false);
-int rowconv_units(const ConvGeom& g, bool dg = false);
+bool rowconv_fused_ok(const ConvGeom& g, bool dg = false, bool pooled = false);
+int rowconv_units(const ConvGeom& g, bool dg = false, bool pooled = false);
 // the instantiation and grid a launch of g runs (host arithmetic only, no device call): the kernel's W
 // (0: the row-segment form), rows per band R, chunks per wave of the K-split form (0: not K-split)
 // and the launch's workgroup tiles; false if rowconv_ok(g) is
-bool rowconv_plan(const ConvGeom& g, bool dg, int* W, int* R, int* ks, int* wgs);
+bool rowconv_plan(const ConvGeom& g, bool dg, bool pooled, int* W, int* R, int* ks, int* wgs);
+// diagnostics (niti_diag_rowconv_rows1): one row per band for pooled 4x4 input gradients -- 1 on, 0 off,
+// -1 the default (on; NITI_RC_ROWS1=0 off).  Set before a model is created: it sizes its buffers by the plan
+void rowconv_rows1(int mode);
 size_t rowconv_wf_bytes(int co, int ci);
 hipError_t nhwc16_to_c32(const int8_t* in, int n, int hw, int cp, int c, int8_t* out, hipStream_t st);
 // C32 [n][cb][hw][32] -> NHWC16 [n][hw][cp] (channels >= c written as zero)

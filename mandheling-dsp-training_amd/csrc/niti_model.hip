@@ -948,7 +948,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
                                          : (pv->g.oh == g.h && pv->g.ow == g.w));
             if (pv_ok && rowconv_dgrad_geom(g, &l.dg)) {
                 l.rcd = 1;
-                rc_acc_size = std::max(rc_acc_size, rowconv_acc_bytes(l.dg, true));
+                rc_acc_size = std::max(rc_acc_size, rowconv_acc_bytes(l.dg, true, pv->pool != 0));
                 l.wft = (int8_t*)ws.alloc(rowconv_wf_bytes(g.c_in, g.c_out));
                 l.dyc32 = (int8_t*)ws.alloc(out_px * round_up(g.c_out, 32));
                 if (!l.wft || !l.dyc32) return NITI_OUT_OF_MEMORY;
@@ -1374,7 +1374,8 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         }
         dy16_valid[i - 1] = !skip16 && !g0_only;
         const bool dgk = !g0_only;  // (rowconv_fwd's own rule: an operand of the input-gradient epilogues)
-        const int rc = rowconv_ranged(rowconv_fused_ok(d, dgk), rowconv_acc_bytes(d, dgk) != 0, o, rng(i, 1), l.bar,
+        const bool pooled = o.pool_dx != nullptr;  // (rowconv_fwd's own rule: the gradient goes through a pool)
+        const int rc = rowconv_ranged(rowconv_fused_ok(d, dgk, pooled), rowconv_acc_bytes(d, dgk, pooled) != 0, o, rng(i, 1), l.bar,
                                       l.epoch, st,
                                       [&](const RowConvOut& ro, int mode, uint32_t* bar, uint32_t epoch, uint32_t* err) {
                                           return rowconv_fwd(d, dyin, l.wft, ro, mode, rng(i, 1), bar, epoch, err, st);

@@ -265,7 +265,15 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     constexpr bool DPPX = true;
     constexpr int KXL = DPPX ? 1 : 3;        // loads per row and chunk
     constexpr int S = 4;                     // ring stages: chunk c computes, c + 1 .. c + 3 in flight
-    constexpr int L = KXL * NR + 3;          // vector-memory instructions per wave per chunk
+    // Two bands per image (W == 2 R): the bottom band runs mirrored top to bottom -- its rows loaded
+    // bottom-up, its output rows accumulated bottom-up, the ky = 0 and ky = 2 weight fragments
+    // swapped -- so both kinds of band have their one padding row at index 0 and none at index
+    // R + 1.  Row 0 is then neither loaded nor shifted nor multiplied, statically and alike in
+    // every wave; the kind of band only changes addresses (the row offsets, two LDS bases of the
+    // fragment reads).  A mirrored wave swaps its accumulator tiles back after the loop.
+    constexpr bool MIRROR = W > 0 && W == 2 * R && !(RC_EXP & 64);
+    constexpr int J0 = MIRROR ? 1 : 0;       // the first row loaded
+    constexpr int L = KXL * (NR - J0) + 3;   // vector-memory instructions per wave per chunk
     const int h = lane >> 5, c = lane & 31, ox = W == 0 ? U.x : c % WS;
     const __amdgpu_buffer_rsrc_t rX = make_rsrc(a.x, a.xbytes);
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(a.wf, a.wbytes);
@@ -275,6 +283,7 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     const uint32_t CHUNK = W == 0 ? a.xcs : (uint32_t)H * WR * 32;
     const uint32_t XROW = W == 0 ? a.xrs : (uint32_t)WR * 32;
     const int y0 = U.b * R - 1;
+    const bool flip = MIRROR && __builtin_amdgcn_readfirstlane(U.b) == 1;
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -283,7 +292,7 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     uint32_t off[3][NR];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        const int iy = y0 + j;
+        const int iy = flip ? H - j : y0 + j;  // (mirrored: row j of the band is image row H - j)
         const bool row_ok = iy >= 0 && iy < H && xl != OOB;
         const uint32_t base = xl + (uint32_t)iy * XROW;
         off[0][j] = row_ok && ox > 0 ? base - 32u : OOB;  // (unused: DPPX)
@@ -311,12 +320,14 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
                   wbase + (uint32_t)cc * 9216u + (uint32_t)(piece < 9 ? piece : 0) * 1024u);
         }
 #pragma unroll
-        for (int j = 0; j < NR; ++j)
+        for (int j = J0; j < NR; ++j)
 #pragma unroll
             for (int kx = 0; kx < KXL; ++kx)
                 X[ST][kx][j] = buf_load16(rX, off[DPPX ? 1 : kx][j] + (uint32_t)cc * CHUNK);
     };
     const uint32_t lds_lane = lds_addr(smem) + (uint32_t)lane * 16u;
+    // the fragment rows ky = 0 and ky = 2 (a mirrored band reads each where the other lies)
+    const uint32_t lds_ky0 = lds_lane + (flip ? 6u * 1024u : 0u), lds_ky2 = lds_lane + (flip ? 0u : 6u * 1024u);
     unsigned long long t_wait = 0, t_read = 0, t_issue = 0;  // (the last two: W = 0 only)
     const bool stamp = a.stamps != nullptr;
     // Software pipeline, per step c: wait for chunk c + 1's own loads (c + 2 stays in flight) and
@@ -327,7 +338,13 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     auto read_w = [&](auto st_c, v4i (&w)[9]) {
         constexpr int ST = decltype(st_c)::value;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) w[t] = lds_b128(lds_lane + (uint32_t)(ST * RC_STAGE_BYTES + t * 1024));
+        for (int t = 0; t < 9; ++t) {
+            if constexpr (MIRROR)
+                w[t] = lds_b128((t < 3 ? lds_ky0 : (t < 6 ? lds_lane : lds_ky2)) +
+                                (uint32_t)(ST * RC_STAGE_BYTES + (t < 6 ? t : t - 6) * 1024));
+            else
+                w[t] = lds_b128(lds_lane + (uint32_t)(ST * RC_STAGE_BYTES + t * 1024));
+        }
     };
     auto fence_w = [&](v4i (&w)[9]) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -349,7 +366,8 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     // workgroup; a wave-uniform branch round those MFMAs made hipcc carry the accumulator tile
     // through VGPRs at every merge (48 v_accvgpr moves per step, what the 3 MFMAs save), and one
     // copy of the loop per kind of band cost up to 60 more registers and scratch at R = 8, so
-    // those units multiply the zeros.
+    // those units multiply the zeros -- except where the image has exactly two
+    // bands (MIRROR, above), which needs no branch.
     constexpr bool SKIP = W > 0 && R == W && !(RC_EXP & 32);
     auto step = [&](auto st_c, int cc) {
         constexpr int ST = decltype(st_c)::value, WB = ST & 1;
@@ -381,11 +399,11 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
                 acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[3 * ky + 2], XR[r + ky], acc[r], 0, 0, 0);
             };
 #pragma unroll
-            for (int j = SKIP ? 1 : 0; j < (SKIP ? NR - 1 : NR); ++j) taps(j);
+            for (int j = SKIP || MIRROR ? 1 : 0; j < (SKIP ? NR - 1 : NR); ++j) taps(j);
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
-                for (int ky = SKIP && r == 0 ? 1 : 0; ky < (SKIP && r == R - 1 ? 2 : 3); ++ky) mfma3(r, ky);
+                for (int ky = (SKIP || MIRROR) && r == 0 ? 1 : 0; ky < (SKIP && r == R - 1 ? 2 : 3); ++ky) mfma3(r, ky);
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r)
@@ -436,6 +454,17 @@ __device__ __forceinline__ void rowconv_compute(const RowConvArgs& a, const RowU
     }
     // the ring's LDS is reused by the next unit's prologue only after every wave's last reads
     __builtin_amdgcn_s_barrier();
+    if constexpr (MIRROR) {
+        // back to top-down: everything after the loop reads acc[r] as output row b R + r
+        if (flip) {
+#pragma unroll
+            for (int r = 0; r < R / 2; ++r) {
+                const v16i t = acc[r];
+                acc[r] = acc[R - 1 - r];
+                acc[R - 1 - r] = t;
+            }
+        }
+    }
     if (stamp && lane == 0) {
         unsigned long long* st = a.stamps + (blockIdx.x * 4 + wid) * 16;
         st[3] = __builtin_amdgcn_s_memtime();
@@ -1700,8 +1729,19 @@ bool rowconv_dgrad_geom(const ConvGeom& l, ConvGeom* d) {
 
 // rows per band: the largest R (a power of two dividing H, at most 8: register budget) whose unit
 // count fills the chip (>= 768 waves), else R = 2, the most units; FUSED needs one unit per wave
-// and every workgroup resident (units <= 1024)
-static int rowconv_rows(const ConvGeom& g, bool dg, int* units_out) {
+// and every workgroup resident (units <= 1024).
+// pooled: an input gradient routed through the previous layer's 2x2 pool.  At 4x4 such a launch
+// whose R = 2 grid is 384 .. 512 units (96 .. 128 workgroups: half the chip idle) takes one row
+// per band: 768 .. 1024 units, and a wave's pixels through the pool are still one whole 16-pixel
+// P16 block per image.  (Without the pool a wave at R = 1 would hold a quarter of a P16 block:
+// those keep R = 2 and p16_pair_store.)  niti_diag_rowconv_rows1 / NITI_RC_ROWS1=0 switch it off.
+static int g_rc_rows1 = -1;
+void rowconv_rows1(int mode) { g_rc_rows1 = mode < 0 ? -1 : (mode != 0 ? 1 : 0); }
+static bool rows1_on() {
+    static const bool env = getenv("NITI_RC_ROWS1") ? atoi(getenv("NITI_RC_ROWS1")) != 0 : true;
+    return g_rc_rows1 < 0 ? env : g_rc_rows1 != 0;
+}
+static int rowconv_rows(const ConvGeom& g, bool dg, bool pooled, int* units_out) {
     if (rowconv_seg(g)) {
         const SegPlan p = seg_plan(g);
         *units_out = p.wgs * 4;
@@ -1714,15 +1754,19 @@ static int rowconv_rows(const ConvGeom& g, bool dg, int* units_out) {
     int R = W == 16 && !dg ? 8 : (W < 4 ? W : 4);
     if (RC_EXP & 16) R = 2;
     while (R > 2 && groups * (W / R) * cob < 768) R /= 2;
+    if (dg && pooled && W == 4 && R == 2 && rows1_on()) {
+        const int64_t u2 = groups * 2 * cob;  // the units at R = 2 (R = 1: twice as many, 768 .. 1024)
+        if (u2 >= 384 && u2 <= 512) R = 1;
+    }
     const int64_t ngb4 = (groups * (W / R) + 3) / 4 * 4;
     *units_out = (int)(ngb4 * cob);  // waves, whole workgroups of 4
     return R;
 }
 
-static int rowconv_ks(const ConvGeom& g, bool dg);
+static int rowconv_ks(const ConvGeom& g, bool dg, bool pooled);
 
 // the accumulator store of modes RANGE + REQUANT: every wave slot of the launch, R x 1 KiB x 4
-size_t rowconv_acc_bytes(const ConvGeom& g, bool dg) {
+size_t rowconv_acc_bytes(const ConvGeom& g, bool dg, bool pooled) {
     if (!rowconv_ok(g)) return 0;
     if (rowconv_seg(g)) {
         const SegPlan p = seg_plan(g);
@@ -1733,16 +1777,16 @@ size_t rowconv_acc_bytes(const ConvGeom& g, bool dg) {
     // 0.575 ms per step); NITI_RC_ACC_MIN_CIN applies the row-segment rule here too (A/B)
     if (getenv("NITI_RC_ACC_MIN_CIN") != nullptr && g.c_in < acc_min_cin()) return 0;
     int u = 0;
-    const int R = rowconv_rows(g, dg, &u);
+    const int R = rowconv_rows(g, dg, pooled, &u);
     const int G = 32 / g.w, ngb = ((g.n + G - 1) / G) * (g.h / R), ngb4 = (ngb + 3) / 4 * 4, COB = g.cop / 32;
-    const int64_t wgs = rowconv_ks(g, dg) > 0 ? (int64_t)COB * ngb : (int64_t)COB * ngb4 / 4;
+    const int64_t wgs = rowconv_ks(g, dg, pooled) > 0 ? (int64_t)COB * ngb : (int64_t)COB * ngb4 / 4;
     return (size_t)wgs * 4 * R * 1024 * sizeof(int32_t);
 }
 
 bool rowconv_p16_ok(const ConvGeom& d, bool pool) {
     if (!rowconv_ok(d) || rowconv_seg(d)) return false;
     int u = 0;
-    const int R = rowconv_rows(d, true, &u), W = d.w;
+    const int R = rowconv_rows(d, true, pool, &u), W = d.w;
     const int64_t px = (int64_t)d.n * d.h * d.w * (pool ? 4 : 1);
     if (px % 16 != 0) return false;
     // whole 16-pixel blocks per wave, or per pair of waves (4x4 at R = 2: p16_pair_store)
@@ -1751,20 +1795,20 @@ bool rowconv_p16_ok(const ConvGeom& d, bool pool) {
 
 // the K-split form (rowconv_compute_ks): chunks per wave, or 0.  Whole-image 2-row units whose
 // one-unit-per-wave grid leaves the chip more than a quarter empty, and at most 4 chunks per wave
-static int rowconv_ks(const ConvGeom& g, bool dg) {
+static int rowconv_ks(const ConvGeom& g, bool dg, bool pooled) {
     int u = 0;
-    const int R = rowconv_rows(g, dg, &u);
+    const int R = rowconv_rows(g, dg, pooled, &u);
     const int CB = (g.c_in + 31) / 32;
     if (g.w != 2 || R != 2 || CB % 4 != 0 || CB / 4 > RC_KS_MAX_NS || u >= 768) return 0;
     return CB / 4;
 }
 
 // waves of the launch (K-split: four per unit)
-int rowconv_units(const ConvGeom& g, bool dg) {
+int rowconv_units(const ConvGeom& g, bool dg, bool pooled) {
     if (rowconv_seg(g)) return seg_plan(g).wgs * 4;
     int u = 0;
-    (void)rowconv_rows(g, dg, &u);
-    if (rowconv_ks(g, dg) > 0) {
+    (void)rowconv_rows(g, dg, pooled, &u);
+    if (rowconv_ks(g, dg, pooled) > 0) {
         const int64_t units = (int64_t)(g.n + 15) / 16 * (g.cop / 32);  // W = 2: 16 images per unit
         return (int)(units * 4);
     }
@@ -1796,6 +1840,9 @@ static const void* rc_kernel(int W, int R, bool unc, int ks) {
     RC_CASE(8, 2)
     RC_CASE(4, 4)
     RC_CASE(4, 2)
+    // one row per band: a pooled 4x4 input gradient (rowconv_rows) -- its range launch, and the
+    // input-gradient instantiations of the other modes
+    if constexpr (DG || MODE == RC_RANGE) RC_CASE(4, 1)
     RC_CASE(2, 2)
     RC_CASE(1, 1)
     RC_CASE(0, 4)  // the row-segment form
@@ -1838,7 +1885,7 @@ int resident_wgs(const void* f, int threads) {
 }
 
 // workgroups of a launch (K-split: one unit each; else four units)
-static int rowconv_wgs(const ConvGeom& g, bool dg, int* R_out, int* ks_out) {
+static int rowconv_wgs(const ConvGeom& g, bool dg, bool pooled, int* R_out, int* ks_out) {
     if (rowconv_seg(g)) {
         const SegPlan p = seg_plan(g);
         *R_out = p.R;
@@ -1846,26 +1893,26 @@ static int rowconv_wgs(const ConvGeom& g, bool dg, int* R_out, int* ks_out) {
         return p.wgs;
     }
     int u = 0;
-    const int R = rowconv_rows(g, dg, &u);
-    const int ks = rowconv_ks(g, dg);
+    const int R = rowconv_rows(g, dg, pooled, &u);
+    const int ks = rowconv_ks(g, dg, pooled);
     const int G = 32 / g.w, ngb = ((g.n + G - 1) / G) * (g.h / R), ngb4 = (ngb + 3) / 4 * 4, COB = g.cop / 32;
     *R_out = R;
     *ks_out = ks;
     return ks > 0 ? COB * ngb : COB * ngb4 / 4;
 }
 
-bool rowconv_plan(const ConvGeom& g, bool dg, int* W, int* R, int* ks, int* wgs) {
+bool rowconv_plan(const ConvGeom& g, bool dg, bool pooled, int* W, int* R, int* ks, int* wgs) {
     if (!rowconv_ok(g)) return false;
-    *wgs = rowconv_wgs(g, dg, R, ks);
+    *wgs = rowconv_wgs(g, dg, pooled, R, ks);
     *W = rowconv_seg(g) ? 0 : g.w;
     return true;
 }
 
 // FUSED needs every workgroup resident (one unit per wave, the grid barrier inside the kernel)
-bool rowconv_fused_ok(const ConvGeom& g, bool dg) {
+bool rowconv_fused_ok(const ConvGeom& g, bool dg, bool pooled) {
     if (!rowconv_ok(g)) return false;
     int R = 0, ks = 0;
-    const int wgs = rowconv_wgs(g, dg, &R, &ks);
+    const int wgs = rowconv_wgs(g, dg, pooled, &R, &ks);
     const bool unc = (g.c_in + 31) / 32 % 4 == 0;
     const int W = rowconv_seg(g) ? 0 : g.w;
     const void* f = dg ? rc_kernel<RC_FUSED, true>(W, R, unc, ks) : rc_kernel<RC_FUSED, false>(W, R, unc, ks);
@@ -1957,8 +2004,9 @@ hipError_t rowconv_fwd(const ConvGeom& g, const int8_t* x_c32, const int8_t* wf,
     a.CB = CB;
     a.COB = COB;
     const bool dg = o.relu_mask != nullptr || o.pool_dx != nullptr || o.p16 != nullptr;
+    const bool pooled = o.pool_dx != nullptr;
     int units = 0;
-    const int R = rowconv_rows(g, dg, &units);
+    const int R = rowconv_rows(g, dg, pooled, &units);
     const bool seg = rowconv_seg(g);
     const int Wk = seg ? 0 : g.w;  // the kernel's W (0: the row-segment form)
     int ks = 0;
@@ -1976,7 +2024,7 @@ hipError_t rowconv_fwd(const ConvGeom& g, const int8_t* x_c32, const int8_t* wf,
         a.nbands = g.h / R;
         a.ngb = ((g.n + G - 1) / G) * a.nbands;
         a.ngb4 = (a.ngb + 3) / 4 * 4;
-        ks = rowconv_ks(g, dg);
+        ks = rowconv_ks(g, dg, pooled);
         a.wgs = ks > 0 ? COB * a.ngb : COB * a.ngb4 / 4;
     }
     a.wmajor = rowconv_wmajor(xb, wb);
@@ -2017,7 +2065,7 @@ hipError_t rowconv_fwd(const ConvGeom& g, const int8_t* x_c32, const int8_t* wf,
     if (o.p16 != nullptr && (!dg || !rowconv_p16_ok(g, o.pool_dx != nullptr))) return hipErrorInvalidValue;
     if (o.pool_out != nullptr && (R % 2 != 0 || g.h % 2 != 0)) return hipErrorInvalidValue;
     if (mode == RC_FUSED) {
-        if (bar == nullptr || err == nullptr || epoch == 0 || !rowconv_fused_ok(g, dg)) return hipErrorInvalidValue;
+        if (bar == nullptr || err == nullptr || epoch == 0 || !rowconv_fused_ok(g, dg, pooled)) return hipErrorInvalidValue;
         return dg ? launch_rc<RC_FUSED, true>(Wk, R, a.wgs, a, st, ks) : launch_rc<RC_FUSED, false>(Wk, R, a.wgs, a, st, ks);
     }
     int grid = a.wgs;

@@ -181,6 +181,7 @@ def lib():
         "niti_execution_status": (ci, [vp, vp]),
         "niti_diag_rowconv_barrier": (None, [C.c_uint32, C.c_uint32]),
         "niti_diag_rowconv_speculate": (None, [C.c_int]),
+        "niti_diag_rowconv_rows1": (None, [C.c_int]),
         "niti_diag_gemm_speculate": (None, [C.c_int]),
         "niti_diag_gemm_fused_launches": (C.c_ulonglong, []),
         "niti_diag_head_chain_launches": (C.c_ulonglong, []),
@@ -202,6 +203,8 @@ def lib():
         "niti_conv_fwd_phase1": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, C.c_size_t, vp]),
         "niti_conv_rows_ok": (ci, [C.POINTER(Geom)]),
         "niti_conv_rows_plan": (ci, [C.POINTER(Geom), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+        "niti_conv_rows_plan2": (ci, [C.POINTER(Geom), ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
+                                      C.POINTER(ci)]),
         "niti_nhwc16_to_c32": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_weights_to_wf": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_conv_fwd_rows": (ci, [C.POINTER(Geom), vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, C.c_uint32, vp,

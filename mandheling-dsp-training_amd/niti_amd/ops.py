@@ -211,13 +211,19 @@ def conv_rows_ok(g: L.Geom) -> bool:
     return bool(L.lib().niti_conv_rows_ok(C.byref(g)))
 
 
-def conv_rows_plan(g: L.Geom, dgrad=False):
+def conv_rows_plan(g: L.Geom, dgrad=False, pooled=False):
     """(W, R, ks, workgroups) of the row-kernel launch the layer of geometry g runs (dgrad: its input
-    gradient with a fused relu / pool gradient): rowconv_fwd_kernel<W, R, ...>, W = 0 the row-segment
-    form, ks > 0 the K-split form.  Host arithmetic only.  None where conv_rows_ok refuses g."""
+    gradient with a fused relu / pool gradient; pooled: that gradient goes through the previous
+    layer's 2x2 max pool): rowconv_fwd_kernel<W, R, ...>, W = 0 the row-segment form, ks > 0 the
+    K-split form.  Host arithmetic only.  None where conv_rows_ok refuses g."""
     w, r, ks, wgs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    if not L.lib().niti_conv_rows_plan(C.byref(g), 1 if dgrad else 0, C.byref(w), C.byref(r), C.byref(ks),
-                                       C.byref(wgs)):
+    if pooled:
+        ok = L.lib().niti_conv_rows_plan2(C.byref(g), 1 if dgrad else 0, 1, C.byref(w), C.byref(r), C.byref(ks),
+                                          C.byref(wgs))
+    else:
+        ok = L.lib().niti_conv_rows_plan(C.byref(g), 1 if dgrad else 0, C.byref(w), C.byref(r), C.byref(ks),
+                                         C.byref(wgs))
+    if not ok:
         return None
     return w.value, r.value, ks.value, wgs.value
 
