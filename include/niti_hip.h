@@ -665,6 +665,14 @@ int niti_residual_requant_relu_grad(const int8_t* a, const int8_t* ea, const int
                                     int8_t* out, void* stream);
 /* global sum pool: acc[img][c] = sum over hw pixels of x NHWC16 [n][hw][cp] (+ max into amax) */
 int niti_sum_pool(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, void* stream);
+/* The same sums and range, for maps of many pixels (a chain network's gpool layer): niti_sum_pool gives
+ * each (image, channel) a thread that walks the pixels bytewise, which suits 7x7x512; this one spreads an
+ * image's pixels over the lanes of a workgroup, reads 16-byte chunks, keeps a chunk's 16 channels in
+ * registers and reduces over the pixel lanes in LDS.  Each sum is written once (no atomics on acc, no
+ * int32 tensor beyond acc [n][cp]); max|sum| is MAXed into amax (may be NULL), never stored over it.
+ * NITI_INVALID_VALUE, nothing launched: x or acc NULL, n, hw or cp < 1, cp % 16 != 0, hw * 254 >= 2^31,
+ * cp > 16 * 16 * 65535 (the channel groups of 16 chunks are a grid dimension). */
+int niti_sum_pool_wide(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, void* stream);
 /* its gradient: dx[img][p][c] = dy[img][c] */
 int niti_sum_pool_grad(const int8_t* dy, int n, int hw, int cp, int8_t* dx, void* stream);
 /* im2col of a shallow NHWC16 input (c_in <= 4; the ResNet-18 stem) for a conv run as a 1x1 conv over
@@ -830,6 +838,57 @@ int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, i
  * maps), never in the row or P16 kernels. */
 int niti_model_chain_check3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with skip connections, a global sum pool after a layer and up to NITI_CHAIN_MAX_LAYERS layers.
+ * niti_chain_layer2's eight fields, then skip and gpool.  The six entry points above are these with
+ * skip = gpool = 0 everywhere and their refusals kept: n > 24, and a stride other than 1 where they refuse
+ * it.  Both rules are this library's (the reference's NITI_Eltwise_Int8 is a stub), the residual driver's:
+ * csrc/niti_resnet.hip, oracle/niti_resnet_ref.py.
+ *
+ * skip = d >= 1 on layer i: the source is the final output u of layer i - d, after that layer's own add
+ * and relu, with its exponent e_u.  The layer's conv runs and is requantised as always, giving y with
+ * exponent e_y; then z, e_z = niti_residual_add(y, e_y, u, e_u), the conv output as operand a, and
+ * q = the forward rule's requantisation of z (niti_residual_requant; the range MAX-reduced over the ranks
+ * in exact data parallelism).  The layer's exponent is e_z + inc; its relu, pool, flatten and gpool follow
+ * and apply to q; its relu mask and forward tap are q (y is a temporary).
+ *   Backward: every output gradient from the loss back to the earliest source carries its exponent in
+ * device memory -- the loss gradient has 0, an input gradient e_dy + wscale + inc, relu, pool, flatten and
+ * gpool gradients keep theirs.  dz, the gradient at q after the layer's own relu mask, is the conv's output
+ * gradient (weight and input gradient) and, unchanged, the skip's.  At the source s, layer s + 1's input
+ * gradient is produced unmasked; niti_residual_add(that gradient, its exponent, dz, e_dz) with the main
+ * path as operand a and the requantisation follow, then the source's own relu mask
+ * (niti_residual_requant_relu_grad; niti_residual_requant where it has no relu).  The result is the
+ * source's output gradient, and its exponent carries on down the chain.
+ *   An adding layer and a source run on the implicit GEMM (or the depthwise launches), never in the row
+ * kernels or as the head: both operands of a sum are NHWC16.  An adding layer that pools does so after its
+ * sum, with the unfused pool kernel; the pool's gradient takes whichever form the next layer's input
+ * gradient has for any pooled layer (fused into its requantise pass, or the unfused kernel).
+ *
+ * gpool = 1: after the layer's relu its oh x ow map is summed per image and channel into
+ * int32, the exponent unchanged (niti_sum_pool_wide); the sums are requantised by the forward rule
+ * (shift = bitwidth(max|sum|) - 7, exponent e + inc; the range MAX-reduced over the ranks in exact data
+ * parallelism).  The output is a 1x1 map of c_out channels, so the next layer has kernel 1 and pad 0, as
+ * after a flatten, and shapes[][8] reports out_h = 1 and flat_c = c_out.  The gradient hands the pooled
+ * gradient to every pixel of the image, then the layer's relu mask applies (niti_sum_pool_grad).  The
+ * layer's forward tap (niti_model_get_tap) stays its (summed) conv + relu output, the map that is pooled.
+ *
+ * Beside niti_model_chain_check3's rule:
+ * NITI_INVALID_VALUE (malformed): gpool other than 0 / 1; skip < 0; i - skip < 0; a source whose output
+ *   shape (channels, h, h) is not the adding layer's conv output shape.
+ * NITI_NOT_SUPPORT: n > NITI_CHAIN_MAX_LAYERS; gpool together with pool or flatten; gpool on the last
+ *   layer; oh * ow * 254 >= 2^31 (the int32 sums); a layer after a gpool layer with kernel != 1 or pad != 0,
+ *   a stride other than 1, or depthwise (its input is a 1x1 map); the last layer adds; an adding layer or a
+ *   source on the 1x1 map behind a flatten or a gpool; a source that pools, flattens or gpools; a layer that
+ *   is the source of two skips; skips whose spans [i - d, i] nest or cross (they may share an endpoint, as
+ *   consecutive blocks do).
+ * Every list that passes runs.  With 24 layers or fewer the step's launches are those of the same list
+ * through the older entry points; past that the update runs in consecutive launches of at most 24 layers. */
+#define NITI_CHAIN_MAX_LAYERS 64
+typedef struct niti_chain_layer3 {
+    int c_out, kernel, stride, pad, relu, pool, flatten, depthwise; /* as niti_chain_layer2 */
+    int skip, gpool;                                                /* see above */
+} niti_chain_layer3;
+int niti_model_chain_check4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and
@@ -911,6 +970,9 @@ int niti_model_layer_info(niti_model_t m, int layer, int info[12]);
 /* 1 where the layer is a depthwise conv (niti_chain_layer2), 0 where it is dense, -1 for a NULL handle or
  * a layer out of range */
 int niti_model_layer_depthwise(niti_model_t m, int layer);
+/* the layer's skip and gpool (niti_chain_layer3; 0 and 0 for every model not made through
+ * niti_model_create_chain4); NITI_INVALID_VALUE for a NULL handle or pointer or a layer out of range */
+int niti_model_layer_skip(niti_model_t m, int layer, int* skip, int* gpool);
 int niti_model_set_weight(niti_model_t m, int layer, const int8_t* w_oihw_host, int wscale);
 int niti_model_get_weight(niti_model_t m, int layer, int8_t* w_oihw_host);
 /* One NITI_SGD step: forward, NITI_LOSS_Grad, backward, w <- clip(w - g).

@@ -908,6 +908,9 @@ int niti_residual_requant_relu_grad(const int8_t* a, const int8_t* ea, const int
 int niti_sum_pool(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, void* stream) {
     return code(niti::sum_pool(x, n, hw, cp, acc, amax, S(stream)));
 }
+int niti_sum_pool_wide(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, void* stream) {
+    return code(niti::sum_pool_wide(x, n, hw, cp, acc, amax, S(stream)));
+}
 int niti_sum_pool_grad(const int8_t* dy, int n, int hw, int cp, int8_t* dx, void* stream) {
     return code(niti::sum_pool_grad(dy, n, hw, cp, dx, S(stream)));
 }

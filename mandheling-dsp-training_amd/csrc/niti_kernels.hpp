@@ -148,6 +148,9 @@ hipError_t residual_requant(const int8_t* a, const int8_t* ea, const int8_t* b, 
                             const int8_t* relu_mask = nullptr, int spec = 0, uint32_t* slot = nullptr);
 // acc[n][cp] = sum over hw pixels of x NHWC16 (+ max into amax); its gradient: dy broadcast
 hipError_t sum_pool(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, hipStream_t st);
+// the same sums with an image's pixels spread over a workgroup's lanes (maps of many pixels: the chain
+// driver's gpool layers)
+hipError_t sum_pool_wide(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, hipStream_t st);
 // (relu_mask: the pooled map, NHWC16 -- its relu gradient applied too, dx = mask > 0 ? dy : 0)
 hipError_t sum_pool_grad(const int8_t* dy, int n, int hw, int cp, int8_t* dx, hipStream_t st,
                          const int8_t* relu_mask = nullptr);

@@ -178,6 +178,24 @@ struct Layer {
     // a depthwise conv (niti_depthwise.hip): g.c_out == g.c_in == C; w, dwacc, g8 and the slabs are
     // [k * k][cip], the OHWI16 form of a c_out = 1, c_in = C layer (w_co), and there is no wT
     int dw = 0;
+    // a global sum pool after the relu (niti_chain_layer3): r [n][oh][ow][cop] summed per image and channel
+    // into gsum (sum_pool_wide, its range in gp_amax), requantised into flat [n][cop] with exponent exp_gp;
+    // the next layer's input gradient lands in dflat and sum_pool_grad hands it to every pixel of dy
+    int gpool = 0;
+    int32_t* gsum = nullptr;
+    int8_t* exp_gp = nullptr;
+    uint32_t* gp_amax = nullptr;
+    // a residual sum after the conv (niti_chain_layer3): skip = d > 0 adds the final output of layer i - d
+    // (its r, exponent exp) to this layer's requantised conv output (the model's sum_tmp, exponent ey), and
+    // the requantised sum (+ relu) is r; src_of = j >= 0 on the source names that adding layer, whose
+    // output gradient joins layer i + 1's unmasked input gradient (sum_tmp, exponent the model's e_tmp) in
+    // this layer's dy.  sum_amax: the range of the forward sum (adding layer) / the gradient sum (source).
+    // Neither kind runs on the row kernels or as the head: every tensor the sums read is NHWC16.
+    int skip = 0, src_of = -1;
+    int8_t* ey = nullptr;
+    uint32_t* sum_amax = nullptr;   // (adding layer)
+    uint32_t* bsum_amax = nullptr;  // (source)
+    int8_t* edy = nullptr;  // the exponent of dy (kept where the model has a skip: has_skip)
     int ph = 0, pw = 0;      // pooled size
     int8_t wscale = 0;
     // persistent
@@ -207,6 +225,8 @@ struct Layer {
     bool fc_sgd = false;  // this step's weight gradient took the fused NITI_SGD form (pass 1 in run())
     int8_t* g8 = nullptr;    // int8 weight gradient OHWI16
     int8_t* exp = nullptr;   // exponent of this layer's output
+    const int8_t* oexp() const { return gpool ? exp_gp : exp; }  // ... of what the next layer reads
+    bool to_1x1() const { return flatten || gpool; }             // the next layer reads flat, a 1x1 map
     const int8_t* in = nullptr;  // NHWC16 input (previous output or x0)
     // First layer with C_in * KH * KW <= 32 (VGG: 3 x 3 x 3, LeNet: 1 x 5 x 5): the conv runs as a
     // 1x1 conv over an im2col copy of its input (xcol [pixels][32], k = (ky * KW + kx) * C_in + c,
@@ -251,6 +271,16 @@ struct Model final : StepDriver {
     // output-gradient copy per layer, written by the input-gradient requantisation that produces
     // dy (requant_act's out_p16) where that pass can, else converted before the weight gradient
     int32_t* grad_bucket = nullptr;  // every layer's dwacc, contiguous
+    // the step's update jobs, one per layer, and the ones the batched update takes (sized in build_chain:
+    // nothing is allocated inside a step); more than SGD_MAX_JOBS of them go in consecutive launches
+    std::vector<SgdJob> sgd_jobs, sgd_many;
+    // a list with a residual sum: every output gradient carries its exponent on the device (Layer::edy; the
+    // loss gradient's is 0), the conv output / input gradient ahead of a sum waits in sum_tmp
+    bool has_skip = false;
+    int8_t* sum_tmp = nullptr;
+    int8_t* e_tmp = nullptr;
+    int skip_sum_fwd(int i, hipStream_t st);
+    int skip_sum_bwd(int s, hipStream_t st);
     size_t grad_bucket_elems = 0;
     std::vector<int8_t*> xp16, dp16;
     std::vector<char> dp16_valid;  // dp16[i] holds L[i].dy as it is now
@@ -307,12 +337,12 @@ struct Model final : StepDriver {
         const Layer& l = L[i];
         const ConvGeom& g = l.g;
         return use_rowconv && !l.col && l.bar != nullptr && g.kh == 1 && g.kw == 1 && g.h == 1 && g.w == 1 &&
-               g.c_out <= 64 && !l.pool && !l.flatten;
+               g.c_out <= 64 && !l.pool && !l.flatten && !l.skip && l.src_of < 0;
     }
     bool head_dgrad_ok(int i) const {
         if (i == 0 || !head_layer(i)) return false;
         const Layer& pv = L[i - 1];
-        if (pv.flatten || pv.col || pv.g.cop != L[i].g.cip) return false;
+        if (pv.to_1x1() || pv.col || pv.src_of >= 0 || pv.g.cop != L[i].g.cip) return false;
         return pv.pool ? (pv.ph == 1 && pv.pw == 1 && pv.g.oh == 2 && pv.g.ow == 2) : (pv.g.oh == 1 && pv.g.ow == 1);
     }
     // The first layer's expanded output gradient has one reader, its own weight gradient (no input
@@ -510,8 +540,17 @@ struct Model final : StepDriver {
     int build(int arch_, int batch_, int in_hw = 0);
     // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
     // built-in networks are build()'s own lists
-    int build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int n, int in_c_, int in_hw, bool strided = false);
+    int build_chain(int arch_, int batch_, const niti_chain_layer3* layers, int n, int in_c_, int in_hw, int rule);
     int layer_depthwise(int layer) const override { return layer_ok(layer) ? L[layer].dw : -1; }
+    int layer_skip(int layer, int* skip, int* gpool) const override {
+        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+        *skip = L[layer].skip;
+        *gpool = L[layer].gpool;
+        return NITI_NO_ERROR;
+    }
+    // the conv (+ relu, pool, flatten) of layer i's forward; fwd_layer adds the global pool
+    int fwd_conv_layer(int i, hipStream_t st);
+    int gpool_fwd(int i, hipStream_t st);
     int fwd_layer(int i, hipStream_t st);
     int wgrad_layer(int i, hipStream_t st);
     int dgrad_layer(int i, hipStream_t st);
@@ -523,7 +562,7 @@ struct Model final : StepDriver {
     // row kernel's W = 1 path after a pooled layer whose routes travel as codes (VGG-11)
     bool head_chain_on() const {
         const int h = (int)L.size() - 1;
-        if (!head_chain_enabled() || h < 1 || dp() || tuning || probe_layer == h) return false;
+        if (!head_chain_enabled() || h < 1 || dp() || tuning || probe_layer == h || has_skip) return false;
         const Layer& l = L[h];
         return head_layer(h) && head_dgrad_ok(h) && L[h - 1].pool && pool_code_layer(h - 1) &&
                head_chain_ok(batch, l.g.cip, l.g.c_out, l.g.cop) && L[h - 1].g.cop == l.g.cip && l.g.kh * l.g.kw == 1;
@@ -688,9 +727,11 @@ struct Model final : StepDriver {
 };
 
 static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0, int dw = 0,
-                     int stride = 1) {
+                     int stride = 1, int gpool = 0, int skip = 0) {
     Layer l;
     l.dw = dw;
+    l.gpool = gpool;
+    l.skip = skip;
     l.g.n = m.batch;
     l.g.c_in = ci;
     l.g.h = l.g.w = h;
@@ -731,13 +772,18 @@ static int64_t chain_mul(int64_t a, int64_t b) {
 // lists and counts that do not fit an int; what else the library does not run is chain_check's.
 // strided: the `3` entry points' rule, every layer at its own stride >= 1; else every layer is taken at
 // stride 1, as the entry points that refuse any other stride always derived the shapes.
-static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in_hw, bool strided,
+// A gpool layer (the `4` entry points' rule) leaves a 1x1 map of its c_out channels; a skip is checked for
+// form against its source's output shape.
+static int chain_shapes(const niti_chain_layer3* layers, int n, int in_c, int in_hw, bool strided,
                         std::vector<std::array<int, 8>>* out) {
     if (layers == nullptr || n < 1 || in_c < 1 || in_hw < 1) return NITI_INVALID_VALUE;
     int64_t c = in_c, h = in_hw;
+    std::vector<std::array<int64_t, 2>> outs;  // per layer: the channels and map size the next layer sees
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer2& l = layers[i];
+        const niti_chain_layer3& l = layers[i];
         if (l.depthwise != 0 && l.depthwise != 1) return NITI_INVALID_VALUE;
+        if (l.gpool != 0 && l.gpool != 1) return NITI_INVALID_VALUE;
+        if (l.skip < 0 || l.skip > i) return NITI_INVALID_VALUE;
         // a depthwise layer has its input's channels: c_out 0 ("as the input") or that count
         if (l.depthwise && l.c_out != 0 && l.c_out != c) return NITI_INVALID_VALUE;
         const int64_t co = l.depthwise ? c : l.c_out;
@@ -746,34 +792,57 @@ static int chain_shapes(const niti_chain_layer2* layers, int n, int in_c, int in
         if (h + 2 * (int64_t)l.pad < l.kernel) return NITI_INVALID_VALUE;
         const int64_t oh = (h + 2 * (int64_t)l.pad - l.kernel) / (strided ? l.stride : 1) + 1;
         if (l.pool && oh < 2) return NITI_INVALID_VALUE;
+        // a skip's source has the adding layer's conv output shape
+        if (l.skip > 0 && (outs[i - l.skip][0] != co || outs[i - l.skip][1] != oh)) return NITI_INVALID_VALUE;
         const int64_t ph = l.pool ? (oh - 2) / 2 + 1 : oh;
         const int64_t fc = l.flatten ? chain_mul(chain_mul(co, ph), ph) : co;
         // (a count past int never reaches a buffer: refused here as a size no tensor of it fits)
         if (c > CHAIN_MAX_ELEMS || fc > CHAIN_MAX_ELEMS || oh > CHAIN_MAX_ELEMS) return NITI_NOT_SUPPORT;
-        if (out) out->push_back({(int)c, (int)co, l.kernel, l.pad, (int)h, (int)oh, (int)(l.flatten ? 1 : ph), (int)fc});
+        const bool one = l.flatten || l.gpool;
+        if (out) out->push_back({(int)c, (int)co, l.kernel, l.pad, (int)h, (int)oh, (int)(one ? 1 : ph), (int)fc});
         c = fc;
-        h = l.flatten ? 1 : ph;
+        h = one ? 1 : ph;
+        outs.push_back({c, h});
     }
     return NITI_NO_ERROR;
 }
 
-int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], bool strided) {
+int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule) {
     std::vector<std::array<int, 8>> sh;
+    const bool strided = rule >= CHAIN_RULE_STRIDED;
     if (batch < 1) return NITI_INVALID_VALUE;
     if (const int rc = chain_shapes(layers, n, in_c, in_hw, strided, &sh)) return rc;
-    if (n > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;  // (sgd_update_many's job table)
+    // (the update launch takes SGD_MAX_JOBS layers; the `4` entry points' lists update in groups of them)
+    if (n > (rule >= CHAIN_RULE_WIDE ? NITI_CHAIN_MAX_LAYERS : SGD_MAX_JOBS)) return NITI_NOT_SUPPORT;
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer2& l = layers[i];
+        const niti_chain_layer3& l = layers[i];
         const std::array<int, 8>& s = sh[i];
+        // the previous layer leaves a 1x1 map (a flatten or a global pool)
+        const bool on_1x1 = i > 0 && (layers[i - 1].flatten || layers[i - 1].gpool);
         if (strided ? l.stride > 2 : l.stride != 1) return NITI_NOT_SUPPORT;
         // a strided layer after a flatten: its input is a 1x1 map
-        if (l.stride != 1 && i > 0 && layers[i - 1].flatten) return NITI_NOT_SUPPORT;
+        if (l.stride != 1 && on_1x1) return NITI_NOT_SUPPORT;
         if (l.kernel > CHAIN_MAX_KERNEL) return NITI_NOT_SUPPORT;
         // a depthwise layer: not the first layer (its im2col form), not the logits, not on a flattened
         // map; the kernels take 3x3 and 5x5
-        if (l.depthwise && (i == 0 || i == n - 1 || layers[i - 1].flatten || (l.kernel != 3 && l.kernel != 5)))
+        if (l.depthwise && (i == 0 || i == n - 1 || on_1x1 || (l.kernel != 3 && l.kernel != 5)))
             return NITI_NOT_SUPPORT;
-        if (i > 0 && layers[i - 1].flatten && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
+        if (on_1x1 && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
+        if (l.skip != 0) {
+            // a residual sum: not the logits; neither end on the 1x1 map behind a flatten or a global pool;
+            // a source hands on its map as it is; the spans [i - skip, i] of two sums share at most an
+            // endpoint (so no layer is the source of two)
+            const int s = i - l.skip;
+            const niti_chain_layer3& sl = layers[s];
+            if (i == n - 1 || on_1x1 || (s > 0 && (layers[s - 1].flatten || layers[s - 1].gpool))) return NITI_NOT_SUPPORT;
+            if (sl.pool || sl.flatten || sl.gpool) return NITI_NOT_SUPPORT;
+            for (int j = s + 1; j < i; ++j)
+                if (layers[j].skip != 0) return NITI_NOT_SUPPORT;
+        }
+        // a global pool: alone among pool / flatten, not the logits, int32 sums of at most 127 a pixel
+        // (chain_mul saturates just past 2^29: the product below fits)
+        if (l.gpool && (l.pool || l.flatten || i == n - 1 || chain_mul(s[5], s[5]) * 254 >= (int64_t(1) << 31)))
+            return NITI_NOT_SUPPORT;
         // a first layer the fused input pass takes (input_im2col) stages kernel + band - 1 image rows
         // of 4 bytes a pixel in LDS: one output row must fit in half of a workgroup's 64 KiB
         // (a strided first layer does not run there)
@@ -796,45 +865,52 @@ int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int
 }
 
 int Model::build(int arch_, int batch_, int in_hw) {
-    // {c_out, kernel, stride, pad, relu, pool, flatten}
-    std::vector<niti_chain_layer2> t;
+    // {c_out, kernel, stride, pad, relu, pool, flatten, depthwise, skip, gpool}
+    std::vector<niti_chain_layer3> t;
     int ic = 3, hw = 32;
     if (arch_ == NITI_ARCH_LENET) {  // mnistTrain.cpp:131-181
         ic = 1;
         hw = 28;
-        t = {{20, 5, 1, 0, 1, 1, 0, 0}, {52, 5, 1, 0, 1, 1, 1, 0}, {500, 1, 1, 0, 1, 0, 0, 0}, {12, 1, 1, 0, 0, 0, 0, 0}};
+        t = {{20, 5, 1, 0, 1, 1, 0, 0, 0, 0}, {52, 5, 1, 0, 1, 1, 1, 0, 0, 0}, {500, 1, 1, 0, 1, 0, 0, 0, 0, 0},
+             {12, 1, 1, 0, 0, 0, 0, 0, 0, 0}};
     } else if (arch_ == NITI_ARCH_VGG11) {  // VGG-11 for 32x32 inputs, NITI layers (BASELINE cfg 3)
         static const int cfg[8][2] = {{64, 1}, {128, 1}, {256, 0}, {256, 1}, {512, 0}, {512, 1}, {512, 0}, {512, 1}};
-        for (int i = 0; i < 8; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], 0, 0});
-        t.push_back({12, 1, 1, 0, 0, 0, 0, 0});
+        for (int i = 0; i < 8; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], 0, 0, 0, 0});
+        t.push_back({12, 1, 1, 0, 0, 0, 0, 0, 0, 0});
     } else if (arch_ == NITI_ARCH_VGG16) {  // VGG-16 (configuration D), NITI layers (BASELINE cfg 4)
         hw = in_hw > 0 ? in_hw : 224;
         if (hw % 32 != 0) return NITI_INVALID_VALUE;
         static const int cfg[13][2] = {{64, 0},  {64, 1},  {128, 0}, {128, 1}, {256, 0}, {256, 0}, {256, 1},
                                        {512, 0}, {512, 0}, {512, 1}, {512, 0}, {512, 0}, {512, 1}};
-        for (int i = 0; i < 13; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], /*flatten=*/i == 12, 0});
-        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0});
-        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0});
-        t.push_back({1000, 1, 1, 0, 0, 0, 0, 0});
+        for (int i = 0; i < 13; ++i) t.push_back({cfg[i][0], 3, 1, 1, 1, cfg[i][1], /*flatten=*/i == 12, 0, 0, 0});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0, 0, 0});
+        t.push_back({4096, 1, 1, 0, 1, 0, 0, 0, 0, 0});
+        t.push_back({1000, 1, 1, 0, 0, 0, 0, 0, 0, 0});
     } else {
         return NITI_NOT_SUPPORT;
     }
-    return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw);
+    return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw, CHAIN_RULE_PLAIN);
 }
 
-int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, int nlayers, int in_c_, int in_hw,
-                       bool strided) {
+int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, int nlayers, int in_c_, int in_hw,
+                       int rule) {
     arch = arch_;
     batch = batch_;
+    const bool strided = rule >= CHAIN_RULE_STRIDED;
     std::vector<std::array<int, 8>> sh;
     if (const int rc = chain_shapes(layers, nlayers, in_c_, in_hw, strided, &sh)) return rc;
     in_c = in_c_;
     in_h = in_w = in_hw;
     for (int i = 0; i < nlayers; ++i)
         add_conv(*this, sh[i][0], sh[i][1], sh[i][2], sh[i][3], sh[i][4], layers[i].relu != 0, layers[i].pool != 0,
-                 layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1);
+                 layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1, layers[i].gpool, layers[i].skip);
     for (const Layer& l : L)
         if (l.dw && !dwconv2_ok(l.g)) return NITI_NOT_SUPPORT;
+    for (int i = 0; i < nlayers; ++i)
+        if (L[i].skip) {
+            L[i - L[i].skip].src_of = i;
+            has_skip = true;
+        }
     const int n = batch;
     {
         Layer& f = L[0];
@@ -858,7 +934,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
     }
     x0 = (int8_t*)ws.alloc((size_t)n * in_h * in_w * round_up(in_c, 16));
     exp0 = (int8_t*)ws.alloc(16);
-    size_t acc_elems = 0;
+    size_t acc_elems = 0, sum_tmp_bytes = 0;
     const int nl = (int)L.size();
     // every layer's int32 weight gradient in one contiguous bucket: data parallel, one SUM
     // all-reduce covers the whole step's gradients
@@ -868,6 +944,8 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
     if (!grad_bucket) return NITI_OUT_OF_MEMORY;
     grad_bucket_elems = grad_elems;
     size_t grad_off = 0;
+    sgd_jobs.assign(nl, SgdJob{});
+    sgd_many.assign(nl, SgdJob{});
     xp16.assign(nl, nullptr);
     xp16_valid.assign(nl, 0);
     dp16.assign(nl, nullptr);
@@ -903,6 +981,13 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
             if (!l.pool) l.dtmp = (int8_t*)ws.alloc(out_px * g.cop);
             if (!l.flat || !l.dflat || !l.dtmp) return NITI_OUT_OF_MEMORY;
         }
+        if (l.gpool) {  // the sums, the pooled map and its gradient [n][cop], the pooled exponent
+            l.gsum = (int32_t*)ws.alloc((size_t)n * g.cop * 4);
+            l.flat = (int8_t*)ws.alloc((size_t)n * g.cop);
+            l.dflat = (int8_t*)ws.alloc((size_t)n * g.cop);
+            l.exp_gp = (int8_t*)ws.alloc(16);
+            if (!l.gsum || !l.flat || !l.dflat || !l.exp_gp) return NITI_OUT_OF_MEMORY;
+        }
         l.dy = (int8_t*)ws.alloc(out_px * g.cop);
         l.dwacc = grad_bucket + grad_off;
         grad_off += (size_t)l.w_elems();
@@ -932,7 +1017,16 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
             l.subw = (int8_t*)ws.alloc(conv_dgrad_subpix_bytes(g));
             if (!l.subw) return NITI_OUT_OF_MEMORY;
         }
-        if (!l.col && !l.dw && rowconv_ok(g)) {
+        if (has_skip) {
+            l.edy = (int8_t*)ws.alloc(16);
+            if (!l.edy || hipMemset(l.edy, 0, 16) != hipSuccess) return NITI_OUT_OF_MEMORY;
+        }
+        if (l.skip) {
+            l.ey = (int8_t*)ws.alloc(16);
+            if (!l.ey) return NITI_OUT_OF_MEMORY;
+            sum_tmp_bytes = std::max(sum_tmp_bytes, out_px * g.cop);
+        }
+        if (!l.col && !l.dw && !l.skip && rowconv_ok(g)) {
             l.rc = 1;
             l.wf = (int8_t*)ws.alloc(rowconv_wf_bytes(g.c_out, g.c_in));
             l.xc32 = (int8_t*)ws.alloc((size_t)n * round_up(g.c_in, 32) * g.h * g.w);
@@ -943,7 +1037,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
             // the input gradient too, where the previous layer's output (pooled 2x2 or not) is
             // this layer's input as is
             const Layer* pv = i > 0 ? &L[i - 1] : nullptr;
-            const bool pv_ok = pv != nullptr && !pv->flatten && pv->g.cop == g.cip &&
+            const bool pv_ok = pv != nullptr && !pv->to_1x1() && pv->src_of < 0 && pv->g.cop == g.cip &&
                                (pv->pool ? (pv->ph == g.h && pv->pw == g.w && pv->g.oh == 2 * g.h && pv->g.ow == 2 * g.w)
                                          : (pv->g.oh == g.h && pv->g.ow == g.w));
             if (pv_ok && rowconv_dgrad_geom(g, &l.dg)) {
@@ -969,7 +1063,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
             l.in = l.col ? l.xcol : x0;
         } else {
             const Layer& pr = L[i - 1];
-            l.in = pr.flatten ? pr.flat : (pr.pool ? pr.p : pr.r);
+            l.in = pr.to_1x1() ? pr.flat : (pr.pool ? pr.p : pr.r);
         }
     }
     acc = (int32_t*)ws.alloc(acc_elems * 4);
@@ -1001,8 +1095,24 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer2* layers, i
         if (i > 0 && !l.rcd) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_dgrad_spec_alt_bytes(l.g));
     }
     if (gspec_alt_bytes && !(gspec_alt = (int8_t*)ws.alloc(gspec_alt_bytes))) return NITI_OUT_OF_MEMORY;
-    amax_bytes = (size_t)3 * nl * MAX_BYTES;
+    // (a global pool's range: one more word set per gpool layer, behind the layers' three each)
+    // (and a residual sum's: one per adding layer, one per source)
+    int n_gp = 0;
+    for (const Layer& l : L) n_gp += l.gpool + (l.skip ? 2 : 0);
+    amax_bytes = (size_t)(3 * nl + n_gp) * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
+    for (int i = 0, k = 0; i < nl && amax != nullptr; ++i) {
+        if (L[i].gpool) L[i].gp_amax = amax + (size_t)(3 * nl + k++) * MAX_WORDS;
+        if (L[i].skip) {
+            L[i].sum_amax = amax + (size_t)(3 * nl + k++) * MAX_WORDS;
+            L[i - L[i].skip].bsum_amax = amax + (size_t)(3 * nl + k++) * MAX_WORDS;
+        }
+    }
+    if (has_skip) {
+        sum_tmp = (int8_t*)ws.alloc(sum_tmp_bytes);
+        e_tmp = (int8_t*)ws.alloc(16);
+        if (!sum_tmp || !e_tmp) return NITI_OUT_OF_MEMORY;
+    }
     if (const int rc = alloc_eval()) return rc;
     if (const int rc = alloc_update_bits()) return rc;
     if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
@@ -1060,6 +1170,56 @@ int Model::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const i
 // One layer's forward: GEMM range pass -> [all-reduce MAX] -> requantise (+relu, fused pool
 // when the requant is a separate pass) -> pool / flatten.
 int Model::fwd_layer(int i, hipStream_t st) {
+    const int rc = fwd_conv_layer(i, st);
+    if (rc != NITI_NO_ERROR || !L[i].gpool) return rc;
+    return gpool_fwd(i, st);
+}
+
+// The global sum pool of layer i's output: the sums and their range, [all-reduce MAX], the forward rule's
+// requantisation into the 1x1 map the next layer reads (exponent e + inc).
+int Model::gpool_fwd(int i, hipStream_t st) {
+    Layer& l = L[i];
+    const ConvGeom& g = l.g;
+    DTRY(sum_pool_wide(l.r, batch, g.oh * g.ow, g.cop, l.gsum, l.gp_amax, st));
+    DTRY(range_max(l.gp_amax, st));
+    ActRequant r;
+    r.acc = l.gsum;
+    r.rows = batch;
+    r.ldc = g.cop;
+    r.amax = l.gp_amax;
+    r.exp_in = l.exp;
+    r.exp_out = l.exp_gp;
+    r.out_nhwc16 = l.flat;
+    DTRY(requant_act(r, st));
+    return NITI_NO_ERROR;
+}
+
+// The residual sum of adding layer i (niti_resnet.hip's two launches: the range of the aligned sum,
+// [all-reduce MAX], the sum recomputed and requantised): conv output (operand a) + the source's final
+// output -> r, with the layer's relu; the layer's exponent is e_z + inc.
+int Model::skip_sum_fwd(int i, hipStream_t st) {
+    Layer& l = L[i];
+    const Layer& s = L[i - l.skip];
+    const int64_t n = (int64_t)batch * l.g.oh * l.g.ow * l.g.cop;
+    DTRY(residual_add(sum_tmp, l.ey, s.r, s.exp, n, nullptr, nullptr, l.sum_amax, st));
+    DTRY(range_max(l.sum_amax, st));
+    DTRY(residual_requant(sum_tmp, l.ey, s.r, s.exp, n, l.sum_amax, nullptr, l.exp, l.relu, l.r, st));
+    return NITI_NO_ERROR;
+}
+
+// The gradient sum at source s: layer s + 1's unmasked input gradient (operand a: sum_tmp, exponent e_tmp)
+// + the adding layer's output gradient -> the source's dy through its own relu mask, exponent e_z + inc.
+int Model::skip_sum_bwd(int si, hipStream_t st) {
+    Layer& s = L[si];
+    const Layer& a = L[s.src_of];
+    const int64_t n = (int64_t)batch * s.g.oh * s.g.ow * s.g.cop;
+    DTRY(residual_add(sum_tmp, e_tmp, a.dy, a.edy, n, nullptr, nullptr, s.bsum_amax, st));
+    DTRY(range_max(s.bsum_amax, st));
+    DTRY(residual_requant(sum_tmp, e_tmp, a.dy, a.edy, n, s.bsum_amax, nullptr, s.edy, 0, s.dy, st, s.relu ? s.r : nullptr));
+    return NITI_NO_ERROR;
+}
+
+int Model::fwd_conv_layer(int i, hipStream_t st) {
     const int n = batch;
     const bool dp = this->dp();
     Layer& l = L[i];
@@ -1096,7 +1256,7 @@ int Model::fwd_layer(int i, hipStream_t st) {
         // the classifier head on the row kernel (W = 1): one fused launch, or range + requantise
         RowConvOut o;
         o.out = l.r;
-        o.exp_in = i == 0 ? exp0 : L[i - 1].exp;
+        o.exp_in = i == 0 ? exp0 : L[i - 1].oexp();
         o.wscale = l.ws_dev;
         o.exp_out = l.exp;
         o.relu = l.relu;
@@ -1128,10 +1288,10 @@ int Model::fwd_layer(int i, hipStream_t st) {
         o.out = l.r_written ? l.r : nullptr;
         o.pool_out = l.pool ? l.p : nullptr;
         o.pool_code_out = code ? l.pc : nullptr;
-        const bool feeds_next = i + 1 < (int)L.size() && rowconv_layer(i + 1) && !l.flatten &&
+        const bool feeds_next = i + 1 < (int)L.size() && rowconv_layer(i + 1) && !l.to_1x1() &&
                                 !rowconv_nhwc_pref(L[i + 1].g);
         o.next = feeds_next ? L[i + 1].xc32 : nullptr;
-        o.exp_in = i == 0 ? exp0 : L[i - 1].exp;
+        o.exp_in = i == 0 ? exp0 : L[i - 1].oexp();
         o.wscale = l.ws_dev;
         o.exp_out = l.exp;
         o.relu = l.relu;
@@ -1145,12 +1305,13 @@ int Model::fwd_layer(int i, hipStream_t st) {
         if (l.flatten) DTRY(flatten_fwd());
         return NITI_NO_ERROR;
     }
+    // (an adding layer: the requantised conv output waits in sum_tmp, linear, for its sum)
     ActOut o;
-    o.out = l.r;
-    o.relu = l.relu;
-    o.exp_in = i == 0 ? exp0 : L[i - 1].exp;
+    o.out = l.skip ? sum_tmp : l.r;
+    o.relu = l.skip ? 0 : l.relu;
+    o.exp_in = i == 0 ? exp0 : L[i - 1].oexp();
     o.wscale = l.ws_dev;
-    o.exp_out = l.exp;
+    o.exp_out = l.skip ? l.ey : l.exp;
     if (l.dw) {
         // depthwise: range launch, [all-reduce MAX], recompute-and-requantise launch; the unfused pool / flatten
         const auto none = [](const ActOut&, auto) { return hipErrorNotSupported; };
@@ -1159,13 +1320,15 @@ int Model::fwd_layer(int i, hipStream_t st) {
         });
         if (rc != NITI_NO_ERROR) return rc;
         probe(i, 0, false, st);
+        if (l.skip)
+            if (const int rs = skip_sum_fwd(i, st)) return rs;
         if (l.pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
         if (l.flatten) DTRY(flatten_fwd());
         return NITI_NO_ERROR;
     }
     const bool spec = conv_fwd_spec_ok(g);
     // the 2x2 pool rides along the separate requant pass when there is one
-    const bool fuse_pool = !spec && l.pool && g.oh % 2 == 0 && g.ow % 2 == 0 && conv_fwd_phase2_separate(g, slab_bytes);
+    const bool fuse_pool = !spec && l.pool && !l.skip && g.oh % 2 == 0 && g.ow % 2 == 0 && conv_fwd_phase2_separate(g, slab_bytes);
     if (fuse_pool) {
         o.pool.pool_out = l.p;
         o.pool.H = g.oh;
@@ -1185,6 +1348,8 @@ int Model::fwd_layer(int i, hipStream_t st) {
         });
     if (rc != NITI_NO_ERROR) return rc;
     probe(i, 0, false, st);
+    if (l.skip)
+        if (const int rs = skip_sum_fwd(i, st)) return rs;
     if (l.pool && !fuse_pool) DTRY(maxpool_nhwc16(l.r, n, g.oh, g.ow, g.cop, 2, 2, 0, l.p, l.ph, l.pw, st));
     if (l.flatten) DTRY(flatten_fwd());
     return NITI_NO_ERROR;
@@ -1315,6 +1480,11 @@ int Model::dgrad_layer(int i, hipStream_t st) {
             o.relu_mask = pv.relu ? pv.r : nullptr;
             next = nullptr;  // a 1x1 previous layer has no row-kernel input gradient
         }
+        if (has_skip) {  // the gradient's exponent travels with it: e_dy + wscale + inc
+            o.exp_in = l.edy;
+            o.wscale = l.ws_dev;
+            o.exp_out = pv.edy;
+        }
         dy16_valid[i - 1] = !(pv.pool && o.pool_dx_nhwc == 0);
         const int K = g.c_out, rows = g.c_in;
         const int rc = rowconv_ranged(rowconv_fc_ok(n, K, rows, true), false, o, rng(i, 1), l.bar, l.epoch, st,
@@ -1372,6 +1542,11 @@ int Model::dgrad_layer(int i, hipStream_t st) {
             o.next = next;
             o.relu_mask = pv.relu ? pv.r : nullptr;
         }
+        if (has_skip) {  // the gradient's exponent travels with it: e_dy + wscale + inc
+            o.exp_in = l.edy;
+            o.wscale = l.ws_dev;
+            o.exp_out = pv.edy;
+        }
         dy16_valid[i - 1] = !skip16 && !g0_only;
         const bool dgk = !g0_only;  // (rowconv_fwd's own rule: an operand of the input-gradient epilogues)
         const bool pooled = o.pool_dx != nullptr;  // (rowconv_fwd's own rule: the gradient goes through a pool)
@@ -1396,9 +1571,18 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     // write it (the plain and the fused pool-gradient passes), else wgrad_layer converts it
     int8_t* p16_out = !l.dw && !sub && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
     dp16_valid[i - 1] = 0;
+    // the previous layer is a skip's source: the input gradient unmasked into sum_tmp, the sum after it
+    const bool src = pv.src_of >= 0;
     ActOut o;
     bool fuse = false;
-    if (pv.flatten) {
+    if (has_skip) {  // the gradient's exponent travels with it: e_dy + wscale + inc
+        o.exp_in = l.edy;
+        o.wscale = l.ws_dev;
+        o.exp_out = src ? e_tmp : pv.edy;
+    }
+    if (src) {
+        o.out = sum_tmp;
+    } else if (pv.to_1x1()) {
         o.out = pv.dflat;
     } else if (pv.pool) {
         fuse = !l.dw && !sub && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
@@ -1438,7 +1622,11 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         });
     if (rc != NITI_NO_ERROR) return rc;
     probe(i, 1, false, st);
-    if (pv.flatten) {
+    if (src) {
+        if (const int rs = skip_sum_bwd(i - 1, st)) return rs;
+    } else if (pv.gpool) {  // the pooled gradient to every pixel, then the layer's relu mask
+        DTRY(sum_pool_grad(pv.dflat, n, pg.oh * pg.ow, pg.cop, pv.dy, st, pv.relu ? pv.r : nullptr));
+    } else if (pv.flatten) {
         const int fhw = pv.fh() * pv.fw(), ld = round_up(pg.c_out * fhw, 16);
         const int64_t elems = (int64_t)n * fhw * pg.cop;
         // (no pool, no relu: the flatten's gradient is the layer's output gradient as it stands)
@@ -1572,7 +1760,7 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
             dp16_valid[i] = 1;
         }
     auto combine = [&]() -> int {
-        SgdJob jobs[SGD_MAX_JOBS];
+        SgdJob* jobs = sgd_many.data();  // (set holds distinct layers: no more jobs than sgd_many's one per layer)
         int n = 0;
         for (int i : set) {
             SgdJob& d = grads[i].defer;
@@ -1673,8 +1861,8 @@ int Model::tune_conv0_codes(hipStream_t st, TuneTimer& timer, bool log) {
 int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
     const int nl = (int)L.size();
     const bool dp = this->dp();
-    SgdJob jobs[SGD_MAX_JOBS];
-    if (nl > SGD_MAX_JOBS) return NITI_NOT_SUPPORT;
+    SgdJob* jobs = sgd_jobs.data();
+    if (nl > (int)sgd_jobs.size()) return NITI_NOT_SUPPORT;
     InStep in_step_guard(in_step);  // weight gradients inside this step may defer their combine (defer_combine)
     for (GradSlot& s : grads) s.defer = SgdJob{};
     if (dp) {
@@ -1899,11 +2087,19 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         DTRY(hipStreamWaitEvent(st, ev_side, 0));
     }
     // the fully connected layers that took the fused form update in their own recompute pass
-    SgdJob many[SGD_MAX_JOBS];
+    SgdJob* many = sgd_many.data();
     int n_many = 0;
     for (int i = 0; i < nl; ++i)
         if (!L[i].fc_sgd) many[n_many++] = jobs[i];
-    DTRY(sgd_update_many(many, n_many, st, upd_bits));  // (+ the deferred combines) also rewrites the fragment-major weight copies
+    // (+ the deferred combines) also rewrites the fragment-major weight copies; one launch up to
+    // SGD_MAX_JOBS layers, consecutive launches past that
+    if (n_many <= SGD_MAX_JOBS) {
+        DTRY(sgd_update_many(many, n_many, st, upd_bits));
+    } else {
+        const int rc = in_job_groups(n_many, SGD_MAX_JOBS,
+                                     [&](int first, int count) { return sgd_update_many(many + first, count, st, upd_bits); });
+        if (rc != NITI_NO_ERROR) return rc;
+    }
     for (int i = 0; i < nl; ++i)
         if (L[i].fc_sgd) DTRY(conv_wgrad_fc_sgd(L[i].g, L[i].in, L[i].dy, rng(i, 2), jobs[i], 1, st, upd_bits));
     g8_written = keep_grads;
@@ -1941,7 +2137,8 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
             L[i].col != src.L[i].col || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
-            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].og.sh != src.L[i].og.sh)
+            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].og.sh != src.L[i].og.sh ||
+            L[i].gpool != src.L[i].gpool || L[i].skip != src.L[i].skip)
             return NITI_INVALID_VALUE;
     }
     if (&src == this) return NITI_NO_ERROR;
@@ -2234,12 +2431,12 @@ int Model::spec_stats(uint32_t* out, int max_layers) {
     return NITI_NO_ERROR;
 }
 
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
-                                                   int* rc, bool strided) {
-    *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr, strided);  // (nothing allocated on a refusal)
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch,
+                                                   int* rc, int rule) {
+    *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr, rule);  // (nothing allocated on a refusal)
     if (*rc != NITI_NO_ERROR) return nullptr;
     auto m = std::make_unique<Model>();
-    *rc = m->build_chain(NITI_ARCH_CHAIN, batch, layers, n, in_c, in_hw, strided);
+    *rc = m->build_chain(NITI_ARCH_CHAIN, batch, layers, n, in_c, in_hw, rule);
     if (*rc != NITI_NO_ERROR) return nullptr;
     return m;
 }

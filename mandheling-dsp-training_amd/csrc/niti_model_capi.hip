@@ -43,30 +43,52 @@ int niti_model_create3(int arch, int batch, int in_hw, int classes, niti_model_t
     return NITI_NO_ERROR;
 }
 
-int niti_model_chain_check2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
-    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes);
+int niti_model_chain_check4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes, niti::CHAIN_RULE_WIDE);
 }
 
-int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+static int create_chain(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, int rule, niti_model_t* out) {
     if (!out || batch <= 0) return NITI_INVALID_VALUE;
     int rc = NITI_NO_ERROR;
-    std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc);
-    if (rc != NITI_NO_ERROR) return rc;
-    *out = new niti_model{std::move(d)};
-    return NITI_NO_ERROR;
-}
-
-int niti_model_chain_check3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
-    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes, true);
-}
-
-int niti_model_create_chain3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
-    if (!out || batch <= 0) return NITI_INVALID_VALUE;
-    int rc = NITI_NO_ERROR;
-    std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc, true);
+    std::unique_ptr<niti::StepDriver> d = niti::make_chain_list_driver(layers, n, in_c, in_hw, batch, &rc, rule);
     if (!d) return rc;
     *out = new niti_model{std::move(d)};
     return NITI_NO_ERROR;
+}
+
+int niti_model_create_chain4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    return create_chain(layers, n, in_c, in_hw, batch, niti::CHAIN_RULE_WIDE, out);
+}
+
+// the eight-field list as the same list with skip = gpool = 0 (empty where the arguments are malformed:
+// the check then refuses them as it always did)
+static std::vector<niti_chain_layer3> chain_layers3(const niti_chain_layer2* layers, int n) {
+    std::vector<niti_chain_layer3> t;
+    for (int i = 0; layers != nullptr && i < n; ++i) {
+        const niti_chain_layer2& l = layers[i];
+        t.push_back({l.c_out, l.kernel, l.stride, l.pad, l.relu, l.pool, l.flatten, l.depthwise, 0, 0});
+    }
+    return t;
+}
+
+int niti_model_chain_check2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    const std::vector<niti_chain_layer3> t = chain_layers3(layers, n);
+    return niti::chain_check(t.empty() ? nullptr : t.data(), n, in_c, in_hw, 1, shapes, niti::CHAIN_RULE_PLAIN);
+}
+
+int niti_model_create_chain2(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    const std::vector<niti_chain_layer3> t = chain_layers3(layers, n);
+    return create_chain(t.empty() ? nullptr : t.data(), n, in_c, in_hw, batch, niti::CHAIN_RULE_PLAIN, out);
+}
+
+int niti_model_chain_check3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    const std::vector<niti_chain_layer3> t = chain_layers3(layers, n);
+    return niti::chain_check(t.empty() ? nullptr : t.data(), n, in_c, in_hw, 1, shapes, niti::CHAIN_RULE_STRIDED);
+}
+
+int niti_model_create_chain3(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    const std::vector<niti_chain_layer3> t = chain_layers3(layers, n);
+    return create_chain(t.empty() ? nullptr : t.data(), n, in_c, in_hw, batch, niti::CHAIN_RULE_STRIDED, out);
 }
 
 // the seven-field list as the same list with depthwise = 0 (empty where the arguments are malformed:
@@ -112,6 +134,10 @@ int niti_model_layer_info(niti_model_t m, int layer, int info[12]) {
 }
 
 int niti_model_layer_depthwise(niti_model_t m, int layer) { return m ? m->d->layer_depthwise(layer) : -1; }
+
+int niti_model_layer_skip(niti_model_t m, int layer, int* skip, int* gpool) {
+    return m && skip && gpool ? m->d->layer_skip(layer, skip, gpool) : NITI_INVALID_VALUE;
+}
 
 int niti_model_set_weight(niti_model_t m, int layer, const int8_t* w_host, int wscale) {
     return m ? m->d->set_weight(layer, w_host, wscale) : NITI_INVALID_VALUE;

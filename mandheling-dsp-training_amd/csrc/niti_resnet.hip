@@ -216,6 +216,77 @@ hipError_t sum_pool(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32
     return hipGetLastError();
 }
 
+// The same sums for maps with many pixels and few channels (the chain driver's gpool layers: 64
+// channels at 32x32 would give sum_pool_kernel 16 K threads of 1024 strided byte loads each).  One
+// workgroup per (image, group of G = min(cp / 16, 16) 16-channel chunks): thread t holds chunk
+// t % G of pixel lane t / G, so a wave's loads are 16-byte chunks in runs of G * 16 contiguous bytes
+// (the whole pixel row where cp <= 256), and walks the image's pixels in steps of P = 256 / G.  A
+// chunk's 16 channels accumulate in 16 registers, one v_dot4 each (the packed word against 1 << 8k
+// adds byte k sign-extended, as the depthwise kernels do).  The P pixel lanes then meet in LDS: the
+// P x (G * 16) partial sums reduce over 256 / (G * 16) row groups, then over those, so each
+// (image, channel) sum is written once, by one thread, with no atomic and no int32 tensor but acc.
+__global__ void __launch_bounds__(256) sum_pool_wide_kernel(const int8_t* __restrict__ x, int hw, int c16, int G,
+                                                            int32_t* __restrict__ acc, uint32_t* __restrict__ amax) {
+    __shared__ int32_t red[256 * 16];
+    __shared__ int32_t part[256];
+    __shared__ uint32_t mred[4];
+    const int t = threadIdx.x;
+    const int P = 256 / G, C = G * 16;  // pixel lanes; columns (channels of the group)
+    const int g = t % G, p0 = t / G;
+    const int chunk = blockIdx.y * G + g;  // this thread's 16-channel chunk of the pixel
+    const int64_t img = blockIdx.x;
+    int32_t s[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = 0;
+    if (p0 < P && chunk < c16) {
+        const v4i* src = (const v4i*)x + img * hw * c16 + chunk;
+#pragma unroll 4
+        for (int p = p0; p < hw; p += P) {
+            const v4i v = src[(int64_t)p * c16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[4 * q + k] = __builtin_amdgcn_sdot4(v[q], 1 << (8 * k), s[4 * q + k], false);
+        }
+    }
+    if (p0 < P) {  // red[p0][g * 16 + e]
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ((v4i*)red)[t * 4 + q] = v4i{s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]};
+    }
+    __syncthreads();
+    const int R = 256 / C;  // row groups
+    if (t < R * C) {
+        const int c = t % C, r = t / C;
+        int32_t a = 0;
+        for (int p = r; p < P; p += R) a += red[p * C + c];
+        part[t] = a;  // part[r][c]
+    }
+    __syncthreads();
+    uint32_t m = 0;
+    if (t < C && blockIdx.y * G + (t >> 4) < c16) {
+        int32_t a = 0;
+        for (int r = 0; r < R; ++r) a += part[r * C + t];
+        acc[img * c16 * 16 + (int64_t)blockIdx.y * C + t] = a;
+        m = uabs32(a);
+    }
+    if (amax != nullptr) {
+        m = wave_max(m);
+        if ((t & 63) == 0) mred[t >> 6] = m;
+        __syncthreads();
+        if (t == 0) publish_max(amax, max(max(mred[0], mred[1]), max(mred[2], mred[3])));
+    }
+}
+
+hipError_t sum_pool_wide(const int8_t* x, int n, int hw, int cp, int32_t* acc, uint32_t* amax, hipStream_t st) {
+    if (!x || !acc || n <= 0 || hw <= 0 || cp <= 0 || cp % 16 != 0 || (int64_t)hw * 127 * 2 > 0x7fffffff)
+        return hipErrorInvalidValue;
+    const int c16 = cp / 16, G = c16 < 16 ? c16 : 16;
+    const int groups = (c16 + G - 1) / G;
+    if (groups > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sum_pool_wide_kernel, dim3((unsigned)n, (unsigned)groups), dim3(256), 0, st, x, hw, c16, G, acc, amax);
+    return hipGetLastError();
+}
+
 // dx[img][p][c] = dy[img][c] for every pixel p (16-byte chunks); with relu_mask (NHWC16, the pooled
 // map -- the last block's output) the relu gradient too: dx = mask > 0 ? dy : 0
 __global__ void __launch_bounds__(256) sum_pool_grad_kernel(const int8_t* __restrict__ dy, int64_t total16, int hw,

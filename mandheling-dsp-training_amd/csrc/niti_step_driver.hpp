@@ -242,6 +242,12 @@ struct StepDriver {
     virtual int layer_info(int layer, int info[12]) const = 0;
     // 1 a depthwise layer, 0 a dense one, -1 out of range (only the chain driver has such layers)
     virtual int layer_depthwise(int layer) const { return layer >= 0 && layer < num_layers() ? 0 : -1; }
+    // the layer's skip and gpool (only the chain driver has such layers)
+    virtual int layer_skip(int layer, int* skip, int* gpool) const {
+        if (layer < 0 || layer >= num_layers()) return NITI_INVALID_VALUE;
+        *skip = *gpool = 0;
+        return NITI_NO_ERROR;
+    }
     virtual int set_weight(int layer, const int8_t* w_oihw_host, int wscale) = 0;
     virtual int get_weight(int layer, int8_t* w_oihw_host) = 0;
     virtual int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) = 0;
@@ -279,13 +285,15 @@ std::unique_ptr<StepDriver> make_chain_driver(int arch, int batch, int in_hw, in
 std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int in_hw, int batch, int* rc);
 // niti_model_resnet_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
 int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_layers, int shapes[][8]);
-// a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch
-// (strided: niti_model_create_chain3's rule, the layers' strides honoured; else stride != 1 is refused)
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch,
-                                                   int* rc, bool strided = false);
+// a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch.  rule: which
+// entry points' rule holds -- CHAIN_RULE_PLAIN refuses stride != 1, CHAIN_RULE_STRIDED honours the layers'
+// strides (niti_model_create_chain3), CHAIN_RULE_WIDE also takes gpool and up to NITI_CHAIN_MAX_LAYERS
+// layers (niti_model_create_chain4); below CHAIN_RULE_WIDE the lists carry skip = gpool = 0
+enum { CHAIN_RULE_PLAIN = 0, CHAIN_RULE_STRIDED = 1, CHAIN_RULE_WIDE = 2 };
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch,
+                                                   int* rc, int rule);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
-int chain_check(const niti_chain_layer2* layers, int n, int in_c, int in_hw, int batch, int shapes[][8],
-                bool strided = false);
+int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule);
 
 // a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
 // zero padded to the column pitch kp <-> OIHW

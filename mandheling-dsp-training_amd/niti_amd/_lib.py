@@ -54,6 +54,7 @@ ARCH_LENET, ARCH_VGG11, ARCH_VGG16, ARCH_RESNET18 = 1, 2, 3, 4
 ARCH_CHAIN = 5  # a model of the caller's own layer list (niti_model_create_chain)
 ARCH_RESNET = 6  # a residual network of the caller's own stage list (niti_model_create_resnet)
 RESNET_MAX_STAGES, RESNET_MAX_LAYERS = 8, 256  # NITI_RESNET_MAX_STAGES / _LAYERS
+CHAIN_MAX_LAYERS = 64  # NITI_CHAIN_MAX_LAYERS (the `4` entry points; 24 through the older ones)
 
 
 class NitiError(RuntimeError):
@@ -119,6 +120,12 @@ class ChainLayer(C.Structure):
 class ChainLayer2(C.Structure):
     """niti_chain_layer2: niti_chain_layer's fields and `depthwise`."""
     _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten", "depthwise")]
+
+
+class ChainLayer3(C.Structure):
+    """niti_chain_layer3: niti_chain_layer2's fields, `skip` and `gpool`."""
+    _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten", "depthwise",
+                                       "skip", "gpool")]
 
 
 class DwconvOut(C.Structure):
@@ -263,6 +270,7 @@ def lib():
         "niti_residual_requant": (ci, [vp, vp, vp, vp, i64, vp, vp, vp, ci, vp, vp]),
         "niti_residual_requant_relu_grad": (ci, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         "niti_sum_pool": (ci, [vp, ci, ci, ci, vp, vp, vp]),
+        "niti_sum_pool_wide": (ci, [vp, ci, ci, ci, vp, vp, vp]),
         "niti_sum_pool_grad": (ci, [vp, ci, ci, ci, vp, vp]),
         "niti_im2col": (ci, [C.POINTER(Geom), vp, ci, vp, vp]),
         "niti_im2col_nchw": (ci, [C.POINTER(Geom), vp, ci, vp, vp]),
@@ -297,6 +305,9 @@ def lib():
         "niti_model_layer_depthwise": (ci, [vp, ci]),
         "niti_model_chain_check3": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain3": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_chain_check4": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain4": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_layer_skip": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
         # (spec: a ResnetSpec, passed untyped)
         "niti_model_resnet_check": (ci, [vp, ci, C.POINTER(ci), vp]),
         "niti_model_create_resnet": (ci, [vp, ci, ci, C.POINTER(vp)]),

@@ -40,26 +40,35 @@ class NitiModel:
     @classmethod
     def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
         """A model of the caller's own chain network (niti_model_create_chain2; _create_chain3 for a list
-        with a strided layer): spec is a list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise,
-        stride]) or tuples in that order, over in_c x in_hw x in_hw inputs; the last layer's c_out is the
+        with a strided layer, _create_chain4 for one with a skip, a global pool or more than 24 layers): spec is a
+        list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, gpool]) or tuples in
+        that order, over in_c x in_hw x in_hw inputs; the last layer's c_out is the
         class count.  A depthwise layer (3x3 or 5x5, c_out 0 or its input's channels) has weights
-        [C, 1, k, k]; stride (1 or 2) is a dense or depthwise layer's own.  ValueError for a
+        [C, 1, k, k]; stride (1 or 2) is a dense or depthwise layer's own; skip = d adds the final output of
+        the layer d places back to the layer's conv output, ahead of its relu; gpool = 1 sums the layer's map
+        into a 1x1 map; such a list may have up to 64 layers.  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
-        from .chain import normalize_spec, strided, to_c
+        from .chain import entry_points, normalize_spec, to_c
         spec = normalize_spec(spec)
         arr, n = to_c(spec)
         m = cls.__new__(cls)
         m._lib = L.lib()
         h = C.c_void_p()
-        create = m._lib.niti_model_create_chain3 if strided(spec) else m._lib.niti_model_create_chain2
+        create = entry_points(spec)[1]
         code = create(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
         if code == L.INVALID_VALUE:
             raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input at batch {batch}: {spec}")
         check(code, "model_create_chain")
         m._adopt(h, L.ARCH_CHAIN, batch)
-        for d, l in zip(spec, m.layers):  # (a depthwise layer's c_out as derived, whatever normalize_spec could tell)
+        for i, (d, l) in enumerate(zip(spec, m.layers)):  # (a depthwise layer's c_out as derived, whatever normalize_spec could tell)
             d["c_out"] = l["c_out"]
+            if "skip" in d or "gpool" in d:  # (reported for the lists that use them: niti_model_layer_skip)
+                sk, gp = C.c_int(), C.c_int()
+                check(m._lib.niti_model_layer_skip(h, i, C.byref(sk), C.byref(gp)), "layer_skip")
+                for k, v in (("skip", sk.value), ("gpool", gp.value)):
+                    if k in d:
+                        l[k] = v
         m.chain, m.in_c, m.in_hw = spec, int(in_c), int(in_hw)
         return m
 

@@ -814,6 +814,15 @@ def sum_pool(x16, amax, stream=None):
     return acc
 
 
+def sum_pool_wide(x16, amax, stream=None):
+    """The same sums (and max|sum| MAXed into amax) by niti_sum_pool_wide: an image's pixels spread over
+    the lanes of a workgroup, for maps of many pixels."""
+    n, h, w, cp = x16.shape
+    acc = torch.empty((n, cp), dtype=torch.int32, device=x16.device)
+    check(L.lib().niti_sum_pool_wide(_ptr(x16), n, h * w, cp, _ptr(acc), _ptr(amax), _stream(stream)), "sum_pool_wide")
+    return acc
+
+
 def im2col(g: L.Geom, x16, kp, stream=None, nchw=False):
     """im2col of a shallow NHWC16 input (c_in <= 4; nchw: an int8 NCHW input) -> xcol int8
     [n * oh * ow][kp], column (ky * kw + kx) * c_in + c (niti_im2col / niti_im2col_nchw)."""
