@@ -15,7 +15,11 @@
 // The network is a layer list (niti_chain_layer): LeNet, VGG-11 and VGG-16 are build()'s own tables,
 // niti_model_create_chain brings the caller's, checked by chain_check before anything is allocated.
 // What this driver shares with the ResNet-18 one (niti_resnet_model.hip) is its base, StepDriver
-// (niti_step_driver.hpp); the C ABI over both is niti_model_capi.hip.
+// (niti_step_driver.hpp): a Layer is the base's ParamLayer plus this driver's buffers, and the host
+// access over the layers (weights and their derived copies, taps, logits, layer_info, spec_stats), the
+// update jobs (sgd_job) and the GEMM weight gradient live there, over StepDriver::P.  Here: build(), the
+// step with its capture, the per-layer phases, autotune, plans, get_input, and get_tap's choice of
+// source.  The C ABI over both is niti_model_capi.hip.
 #include <stdlib.h>
 #include <string.h>
 
@@ -172,12 +176,10 @@ struct ExpandPoolCodes {
 
 }  // namespace
 
-struct Layer {
-    ConvGeom g{};
-    int relu = 0, pool = 0, flatten = 0;
-    // a depthwise conv (niti_depthwise.hip): g.c_out == g.c_in == C; w, dwacc, g8 and the slabs are
-    // [k * k][cip], the OHWI16 form of a c_out = 1, c_in = C layer (w_co), and there is no wT
-    int dw = 0;
+// one layer of the chain: the parameter layer the base knows (ParamLayer: geometry, weights and their
+// derived copies, the weight gradient) and this driver's activation / gradient buffers and routes
+struct Layer : ParamLayer {
+    int flatten = 0;
     // a global sum pool after the relu (niti_chain_layer3): r [n][oh][ow][cop] summed per image and channel
     // into gsum (sum_pool_wide, its range in gp_amax), requantised into flat [n][cop] with exponent exp_gp;
     // the next layer's input gradient lands in dflat and sum_pool_grad hands it to every pixel of dy
@@ -197,15 +199,6 @@ struct Layer {
     uint32_t* bsum_amax = nullptr;  // (source)
     int8_t* edy = nullptr;  // the exponent of dy (kept where the model has a skip: has_skip)
     int ph = 0, pw = 0;      // pooled size
-    int8_t wscale = 0;
-    // persistent
-    int8_t* w = nullptr;     // OHWI16
-    int8_t* ws_dev = nullptr;  // wscale scalar
-    // per step
-    int8_t* wT = nullptr;    // IHWO16, kept in step with w by sgd_update
-    // a dense stride-2 layer on an even map: the sub-pixel classes' weights of its input gradient
-    // (conv_dgrad_subpix_bytes), written with wT and kept in step by the update (SgdJob::subw)
-    int8_t* subw = nullptr;
     int8_t* r = nullptr;     // conv (+relu) output NHWC16 [n][oh][ow][cop]
     int8_t* p = nullptr;     // pooled NHWC16
     // the 2x2 pool's gradient route recorded by the forward (pool_code4, [n][ph][pw][cop] bytes; the
@@ -217,13 +210,11 @@ struct Layer {
     int8_t* dy = nullptr;    // output gradient NHWC16 [n][oh][ow][cop]
     int8_t* dtmp = nullptr;  // gradient wrt the pooled / flattened output
     int8_t* dflat = nullptr;
-    int32_t* dwacc = nullptr;  // [co][kk][cip]
     // the P16 weight gradient's own split-K slabs when its combine is deferred to the NITI_SGD
-    // launch (sgd_update_many); the deferred combine itself is grads[i].defer, as the GEMM path's
+    // launch (sgd_update_many); the deferred combine itself is ParamLayer::defer, as the GEMM path's
     int32_t* slab16 = nullptr;
     size_t slab16_bytes = 0;
     bool fc_sgd = false;  // this step's weight gradient took the fused NITI_SGD form (pass 1 in run())
-    int8_t* g8 = nullptr;    // int8 weight gradient OHWI16
     int8_t* exp = nullptr;   // exponent of this layer's output
     const int8_t* oexp() const { return gpool ? exp_gp : exp; }  // ... of what the next layer reads
     bool to_1x1() const { return flatten || gpool; }             // the next layer reads flat, a 1x1 map
@@ -231,33 +222,21 @@ struct Layer {
     // First layer with C_in * KH * KW <= 32 (VGG: 3 x 3 x 3, LeNet: 1 x 5 x 5): the conv runs as a
     // 1x1 conv over an im2col copy of its input (xcol [pixels][32], k = (ky * KW + kx) * C_in + c,
     // zero padded), so its GEMMs take K = 32 instead of 16 channels x 9 taps and the padded taps
-    // cost nothing.  g is that 1x1 geometry; og the layer as the network defines it (reported,
-    // weights and taps converted to / from it on the host).
-    int col = 0;
-    ConvGeom og{};
+    // cost nothing.  g is that 1x1 geometry and kp = 32 marks the layer; og the layer as the network
+    // defines it (reported, weights and taps converted to / from it on the host).
     int8_t* xcol = nullptr;
-    // stride-1 pad-1 3x3 layers on the register-fed forward with the fused rescale
-    // (niti_rowconv.hip): its C32 input copy, fragment-major weights, grid-barrier state
-    int rc = 0;
+    // stride-1 pad-1 3x3 layers on the register-fed forward with the fused rescale (rc;
+    // niti_rowconv.hip): its C32 input copy, the grid-barrier epoch
     int8_t* xc32 = nullptr;
-    int8_t* wf = nullptr;
-    uint32_t* bar = nullptr;
     uint32_t epoch = 0;
-    // its input gradient on the same kernel (rotated transposed weights in WF, dy in C32, the
+    // its input gradient on the same kernel (rcd: rotated transposed weights in wft, dy in C32, the
     // previous layer's relu / pool gradient in the epilogue); dg = that conv's geometry
-    int rcd = 0;
     ConvGeom dg{};
-    // the GEMM path's speculative pair (plan strategy 3): hint slots, forward and input gradient
-    uint32_t* gspec = nullptr;  // 2 x GEMM_SPEC_SLOT_WORDS
-    int8_t* wft = nullptr;
     int8_t* dyc32 = nullptr;
     // what a flatten reads and its gradient writes: the pooled map, or the conv (+relu) output itself
     int fh() const { return pool ? ph : g.oh; }
     int fw() const { return pool ? pw : g.ow; }
     const int8_t* fsrc() const { return pool ? p : r; }
-    int w_co() const { return dw ? 1 : g.c_out; }  // output channels as the weight layouts count them
-    int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * g.cip; }
-    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in) * og.kh * og.kw; }
 };
 
 struct Model final : StepDriver {
@@ -310,7 +289,7 @@ struct Model final : StepDriver {
     static bool input_fused_ok(int c_in, int k, int pad) { return input_im2col_ok(c_in, k, k) && 2 * pad < k; }
     static bool input_fused(const Layer& f) {
         const ConvGeom& o = f.og;
-        return f.col && o.kh == o.kw && o.pt == o.pl && input_fused_ok(o.c_in, o.kh, o.pt) && o.sh == 1 && o.sw == 1;
+        return f.kp && o.kh == o.kw && o.pt == o.pl && input_fused_ok(o.c_in, o.kh, o.pt) && o.sh == 1 && o.sw == 1;
     }
     bool rowconv_layer(int i) const { return use_rowconv && L[i].rc; }
     // dyc32_valid[i]: L[i].dyc32 holds L[i].dy as it is now (written by the next layer's input
@@ -327,7 +306,7 @@ struct Model final : StepDriver {
     bool pool_code_layer(int i) const {
         const Layer& l = L[i];
         if (!l.pool || l.flatten || l.pc == nullptr || i + 1 >= (int)L.size()) return false;
-        const bool fwd = (l.col && conv0_ok(l.g)) || rowconv_layer(i);
+        const bool fwd = (l.kp && conv0_ok(l.g)) || rowconv_layer(i);
         const bool bwd = rowconv_dgrad_layer(i + 1) || head_dgrad_ok(i + 1);
         return fwd && bwd;
     }
@@ -336,13 +315,13 @@ struct Model final : StepDriver {
     bool head_layer(int i) const {
         const Layer& l = L[i];
         const ConvGeom& g = l.g;
-        return use_rowconv && !l.col && l.bar != nullptr && g.kh == 1 && g.kw == 1 && g.h == 1 && g.w == 1 &&
+        return use_rowconv && !l.kp && l.bar != nullptr && g.kh == 1 && g.kw == 1 && g.h == 1 && g.w == 1 &&
                g.c_out <= 64 && !l.pool && !l.flatten && !l.skip && l.src_of < 0;
     }
     bool head_dgrad_ok(int i) const {
         if (i == 0 || !head_layer(i)) return false;
         const Layer& pv = L[i - 1];
-        if (pv.to_1x1() || pv.col || pv.src_of >= 0 || pv.g.cop != L[i].g.cip) return false;
+        if (pv.to_1x1() || pv.kp || pv.src_of >= 0 || pv.g.cop != L[i].g.cip) return false;
         return pv.pool ? (pv.ph == 1 && pv.pw == 1 && pv.g.oh == 2 && pv.g.ow == 2) : (pv.g.oh == 1 && pv.g.ow == 1);
     }
     // The first layer's expanded output gradient has one reader, its own weight gradient (no input
@@ -360,7 +339,7 @@ struct Model final : StepDriver {
     bool conv0_codes_eligible() const {
         if (L.size() < 2 || c0w_slab == nullptr) return false;
         const Layer& l = L[0];
-        if (!l.col || !pool_code_layer(0) || keep_grads || coll != nullptr || coll_grad != nullptr) return false;
+        if (!l.kp || !pool_code_layer(0) || keep_grads || coll != nullptr || coll_grad != nullptr) return false;
         if (l.og.sh != 1 || l.og.sw != 1) return false;  // (measured and tested on stride-1 first layers only)
         if (use_graph || capturing || overlap) return false;  // (one stream, direct launches: the bench's step)
         if (!rowconv_dgrad_layer(1) || rowconv_seg(L[1].dg) || head_dgrad_ok(1)) return false;
@@ -373,26 +352,6 @@ struct Model final : StepDriver {
         return conv0_codes_eligible();
     }
     int tune_conv0_codes(hipStream_t st, TuneTimer& timer, bool log);
-    bool g8_written = false;  // the last step stored the int8 weight gradients (tap(layer, 1))
-    // IHWO16 weights of the layers whose input gradient ran on the row kernel (the SGD kernel
-    // skips them there) -- rebuilt when the GEMM input gradient takes over again
-    int refresh_wt(hipStream_t st) {
-        for (Layer& l : L)
-            if (l.rcd && ohwi16_to_ihwo16(l.w, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.g.cop, l.wT, st) !=
-                             hipSuccess)
-                return NITI_NO_EXECUTION;
-        return NITI_NO_ERROR;
-    }
-    // refresh every rowconv layer's fragment-major weights from w (after set_weight / NITI_SGD)
-    int refresh_wf(hipStream_t st) {
-        for (Layer& l : L) {
-            if (l.rc && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, st) != hipSuccess)
-                return NITI_NO_EXECUTION;
-            if (l.rcd && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, st) != hipSuccess)
-                return NITI_NO_EXECUTION;
-        }
-        return NITI_NO_ERROR;
-    }
     // jobs per P16 conversion launch: P16_MAX_JOBS, lowered only by niti_diag_p16_jobs_cap (tests
     // reach the more-than-one-launch branches with a small net)
     static int p16_jobs_cap() { return std::min(std::max(g_p16_jobs_cap, 1), P16_MAX_JOBS); }
@@ -541,7 +500,6 @@ struct Model final : StepDriver {
     // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
     // built-in networks are build()'s own lists
     int build_chain(int arch_, int batch_, const niti_chain_layer3* layers, int n, int in_c_, int in_hw, int rule);
-    int layer_depthwise(int layer) const override { return layer_ok(layer) ? L[layer].dw : -1; }
     int layer_skip(int layer, int* skip, int* gpool) const override {
         if (!layer_ok(layer)) return NITI_INVALID_VALUE;
         *skip = L[layer].skip;
@@ -645,13 +603,13 @@ struct Model final : StepDriver {
     bool wgrad_batched(int i) const {
         return std::find(wgb_layers.begin(), wgb_layers.end(), i) != wgb_layers.end();
     }
-    // the batch launch and every member's combine fields (grads[i].defer) or, where the combine is not
+    // the batch launch and every member's combine fields (Layer::defer) or, where the combine is not
     // deferred to the update launch, its reduce
     int wgrad_batch_run(bool defer, hipStream_t st) {
         DTRY(conv_wgrad_p16_many(wgb, wgb_dev, st));
         for (size_t k = 0; k < wgb_layers.size(); ++k) {
             Layer& l = L[wgb_layers[k]];
-            SgdJob& d = grads[wgb_layers[k]].defer;
+            SgdJob& d = l.defer;
             d = SgdJob{};
             l.fc_sgd = false;
             if (wgb.splits[k] < 2) continue;
@@ -691,16 +649,9 @@ struct Model final : StepDriver {
     int run_phase(int layer, int phase, hipStream_t st) override;
     int plan_info(int layer, int phase, int info[4]) override;
     int plan_set(int layer, int phase, const int plan[4]) override;
-    int set_rowconv(bool enable) override;
     void set_overlap(bool enable) override { overlap = enable; }
     // host access
-    bool layer_ok(int layer) const { return layer >= 0 && layer < (int)L.size(); }
-    int num_layers() const override { return (int)L.size(); }
-    int layer_info(int layer, int info[12]) const override;
-    int set_weight(int layer, const int8_t* w_oihw_host, int wscale) override;
-    int get_weight(int layer, int8_t* w_oihw_host) override;
     int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
-    int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
     void logits_view(const int8_t** logits, int* classes, int* ld, const int8_t** exp) const override {
         const Layer& t = L.back();
         *logits = t.r;
@@ -709,13 +660,6 @@ struct Model final : StepDriver {
         *exp = t.exp;
     }
     int get_input(int8_t* host, int* ascale, hipStream_t st) override;
-    int64_t step_macs() const override;
-    int spec_stats(uint32_t* out, int max_layers) override;
-    int spec_state(int layer, uint32_t** bar) override {
-        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
-        *bar = L[layer].bar;
-        return NITI_NO_ERROR;
-    }
     ~Model() override {  // (the rest, in order, in ~StepDriver)
         clear_probe();
         drop_graph();
@@ -916,7 +860,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         Layer& f = L[0];
         const ConvGeom o = f.og;
         if (o.c_in * o.kh * o.kw <= 32 && o.dh == 1 && o.dw == 1) {
-            f.col = 1;
+            f.kp = 32;
             ConvGeom c{};
             c.n = o.n;
             c.c_in = 32;
@@ -1026,7 +970,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
             if (!l.ey) return NITI_OUT_OF_MEMORY;
             sum_tmp_bytes = std::max(sum_tmp_bytes, out_px * g.cop);
         }
-        if (!l.col && !l.dw && !l.skip && rowconv_ok(g)) {
+        if (!l.kp && !l.dw && !l.skip && rowconv_ok(g)) {
             l.rc = 1;
             l.wf = (int8_t*)ws.alloc(rowconv_wf_bytes(g.c_out, g.c_in));
             l.xc32 = (int8_t*)ws.alloc((size_t)n * round_up(g.c_in, 32) * g.h * g.w);
@@ -1060,7 +1004,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         }
         // layer input / its C alignment with the previous output
         if (i == 0) {
-            l.in = l.col ? l.xcol : x0;
+            l.in = l.kp ? l.xcol : x0;
         } else {
             const Layer& pr = L[i - 1];
             l.in = pr.to_1x1() ? pr.flat : (pr.pool ? pr.p : pr.r);
@@ -1083,7 +1027,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         rc_acc = (int32_t*)ws.alloc(rc_acc_size);
         if (!rc_acc) return NITI_OUT_OF_MEMORY;
     }
-    if (nl >= 2 && L[0].col && L[0].pc != nullptr &&
+    if (nl >= 2 && L[0].kp && L[0].pc != nullptr &&
         conv0_wgrad_codes_ok(L[0].g.n, L[0].g.oh, L[0].g.ow, L[0].g.cop, L[0].g.cip)) {
         c0w_slab_bytes = (size_t)conv0_wgrad_codes_blocks(L[0].g.n, L[0].g.oh, L[0].g.ow, 1 << 30) * L[0].g.cop * 32 * 4;
         c0w_slab = (int32_t*)ws.alloc(c0w_slab_bytes);
@@ -1091,7 +1035,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
     }
     for (int i = 0; i < nl; ++i) {  // the GEMM-path phases that may run the speculative pair
         const Layer& l = L[i];
-        if (!(l.col && conv0_ok(l.g)) && !l.rc) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_fwd_spec_alt_bytes(l.g));
+        if (!(l.kp && conv0_ok(l.g)) && !l.rc) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_fwd_spec_alt_bytes(l.g));
         if (i > 0 && !l.rcd) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_dgrad_spec_alt_bytes(l.g));
     }
     if (gspec_alt_bytes && !(gspec_alt = (int8_t*)ws.alloc(gspec_alt_bytes))) return NITI_OUT_OF_MEMORY;
@@ -1113,11 +1057,14 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         e_tmp = (int8_t*)ws.alloc(16);
         if (!sum_tmp || !e_tmp) return NITI_OUT_OF_MEMORY;
     }
+    if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
+    // L has its final size: the base's view of the layers (ahead of alloc_update_bits, which counts them)
+    for (int i = 0; i < nl; ++i) {
+        L[i].wg_amax = rng(i, 2);
+        P.push_back(&L[i]);
+    }
     if (const int rc = alloc_eval()) return rc;
     if (const int rc = alloc_update_bits()) return rc;
-    if (!x0 || !exp0 || !acc || !amax) return NITI_OUT_OF_MEMORY;
-    // (the bucket SUMs, the GEMM weight gradients)
-    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{L[i].dwacc, L[i].w_elems(), rng(i, 2), L[i].g});
     if (hipMemset(x0, 0, (size_t)n * in_h * in_w * round_up(in_c, 16)) != hipSuccess) return NITI_NO_EXECUTION;
     return hipDeviceSynchronize() == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
@@ -1230,7 +1177,7 @@ int Model::fwd_conv_layer(int i, hipStream_t st) {
     };
     probe(i, 0, true, st);
     l.r_written = true;
-    if (l.col && conv0_ok(g) && !l.flatten) {
+    if (l.kp && conv0_ok(g) && !l.flatten) {
         // first layer on its im2col copy: range pass, [all-reduce MAX], requant + relu + pool pass
         ActOut o;
         const bool code = pool_code_layer(i);
@@ -1369,7 +1316,7 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         return NITI_NO_ERROR;
     }
     l.fc_sgd = fc_sgd_layer(i);
-    SgdJob& defer_job = grads[i].defer;
+    SgdJob& defer_job = L[i].defer;
     if (l.dw) {
         // depthwise: one launch leaves C-shaped slabs; single device they go to the update launch's
         // combine, else (data parallel, a capture, the combine off) they are reduced here with the range
@@ -1763,7 +1710,7 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
         SgdJob* jobs = sgd_many.data();  // (set holds distinct layers: no more jobs than sgd_many's one per layer)
         int n = 0;
         for (int i : set) {
-            SgdJob& d = grads[i].defer;
+            SgdJob& d = L[i].defer;
             if (d.slab == nullptr) continue;
             jobs[n] = d;
             jobs[n].acc = L[i].dwacc;
@@ -1779,10 +1726,10 @@ int Model::tune_wgrad_batch(hipStream_t st, TuneTimer& timer, bool log) {
             const ConvGeom& g = l.g;
             const int s = wgrad_p16_splits(i);
             const bool defer = s > 1 && l.slab16 != nullptr && conv_wgrad_p16_workspace(g, s) <= l.slab16_bytes;
-            grads[i].defer = SgdJob{};
+            L[i].defer = SgdJob{};
             DTRY(conv_wgrad_p16(g, xp16[i], dp16[i], l.dwacc, rng(i, 2), defer ? l.slab16 : slab_w,
                                 defer ? l.slab16_bytes : slab_w_bytes, s, st, nullptr, nullptr, nullptr,
-                                defer ? &grads[i].defer : nullptr));
+                                defer ? &L[i].defer : nullptr));
         }
         return combine();
     };
@@ -1864,7 +1811,7 @@ int Model::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, const in
     SgdJob* jobs = sgd_jobs.data();
     if (nl > (int)sgd_jobs.size()) return NITI_NOT_SUPPORT;
     InStep in_step_guard(in_step);  // weight gradients inside this step may defer their combine (defer_combine)
-    for (GradSlot& s : grads) s.defer = SgdJob{};
+    for (Layer& l : L) l.defer = SgdJob{};
     if (dp) {
         const int rc = ensure_comm_stream();
         if (rc != NITI_NO_ERROR) return rc;
@@ -1940,7 +1887,7 @@ int Model::forward(const int8_t* x_nchw, int exp_in, const uint8_t* images, bool
         else
             DTRY(image_quantize(images, n, in_c, in_h * in_w, round_up(in_c, 16), qstats, count, x0, exp0, true, st));
     }
-    if (L[0].col && !fused_in) DTRY(im2col32(L[0].og, x0, L[0].xcol, st));
+    if (L[0].kp && !fused_in) DTRY(im2col32(L[0].og, x0, L[0].xcol, st));
     for (int i = 0; i < nl - (skip_head ? 1 : 0); ++i) {
         const int rc = fwd_layer(i, st);
         if (rc != NITI_NO_ERROR) return rc;
@@ -2034,8 +1981,6 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
             const int rc = convert_p16_inputs(wst);
             if (rc != NITI_NO_ERROR) return rc;
         }
-        Layer& l = L[i];
-        const ConvGeom& g = l.g;
         const bool in_chain = hc && i == nl - 1;  // (the head chain launch did both)
         int rc = in_chain || (wbatch && wgrad_batched(i)) ? NITI_NO_ERROR : wgrad_layer(i, wst);
         // data parallel: a completed gradient bucket goes to the comm stream right away
@@ -2045,22 +1990,8 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         // NITI_SGD (NITI_SGD.hpp:20-54) for this layer is deferred: every layer's update runs in one
         // launch after the backward pass (the input gradients above read the old weights); the IHWO16
         // transpose feeds only the GEMM input gradient, the int8 gradient only the
-        // niti_model_get tap (keep_grads)
-        // (rule: the layer's update-bits word, read by the launch that applies the update)
-        // (a depthwise layer: the c_out = 1 form of its weight, no transposed copy)
-        jobs[i] = SgdJob{l.dwacc, rng(i, 2), -(1 + i), l.w_co(), g.c_in, g.kh * g.kw, g.cip, l.dw ? 16 : g.cop, l.w,
-                         i > 0 && !rowconv_dgrad_layer(i) && !l.dw ? l.wT : nullptr, keep_grads ? l.g8 : nullptr};
-        jobs[i].wf = l.rc ? l.wf : nullptr;
-        jobs[i].wft = l.rcd ? l.wft : nullptr;
-        if (l.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights
-            jobs[i].subw = l.subw;
-            jobs[i].sub_kh = g.kh;
-            jobs[i].sub_kw = g.kw;
-            jobs[i].sub_pt = g.pt;
-            jobs[i].sub_pl = g.pl;
-        }
-        // the combine of this layer's split-K slabs, in the update launch
-        if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
+        // niti_model_get tap (keep_grads); with it the combine of this layer's split-K slabs
+        jobs[i] = sgd_job(i, i > 0 && !rowconv_dgrad_layer(i));
     }
     if (wbatch) {
         // dy's P16 copy where no input-gradient epilogue wrote it, all in one launch; then the batch
@@ -2077,7 +2008,7 @@ int Model::backward(bool hc, const int32_t* labels, SgdJob* jobs, hipStream_t st
         const int rc = wgrad_batch_run(defer_combine(), st);
         if (rc != NITI_NO_ERROR) return rc;
         for (int i : wgb_layers)
-            if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
+            if (L[i].defer.slab != nullptr) jobs[i].take_combine(L[i].defer);
     }
     if (dp) {  // every bucket summed and ranged on the comm stream before the update
         DTRY(hipEventRecord(ev_grads, cst));
@@ -2136,26 +2067,13 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
     for (size_t i = 0; i < L.size(); ++i) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
-            L[i].col != src.L[i].col || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
+            L[i].kp != src.L[i].kp || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
             L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].og.sh != src.L[i].og.sh ||
             L[i].gpool != src.L[i].gpool || L[i].skip != src.L[i].skip)
             return NITI_INVALID_VALUE;
     }
     if (&src == this) return NITI_NO_ERROR;
-    for (size_t i = 0; i < L.size(); ++i) {
-        Layer& l = L[i];
-        const Layer& s = src.L[i];
-        const ConvGeom& g = l.g;
-        DTRY(copy_kernel(l.w, s.w, (size_t)l.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
-        DTRY(copy_kernel(l.ws_dev, s.ws_dev, 1, st));
-        l.wscale = s.wscale;
-        if (!l.rcd && !l.dw)  // (refresh_wt below rebuilds the row-kernel layers')
-            DTRY(ohwi16_to_ihwo16(l.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, l.wT, st));
-        if (l.subw) DTRY(conv_dgrad_subpix_weights(g, l.wT, l.subw, st));
-    }
-    int rc = refresh_wt(st);
-    if (rc == NITI_NO_ERROR) rc = refresh_wf(st);
-    return rc;
+    return copy_layer_weights(src, st);
 }
 
 // One layer phase of the last step again, alone (single device: collectives off for the call).
@@ -2207,16 +2125,6 @@ int Model::plan_set(int layer, int phase, const int plan[4]) {
     return NITI_NO_ERROR;
 }
 
-int Model::set_rowconv(bool enable) {
-    if (use_rowconv && !enable) {
-        const int rc = refresh_wt(nullptr);
-        if (rc != NITI_NO_ERROR || hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-    }
-    use_rowconv = enable;
-    drop_graph();
-    return NITI_NO_ERROR;
-}
-
 int Model::probe_alloc(int phase, int max_launches) {
     if (phase == 2 && max_launches > 0) {  // per launch, a {start, end} pair per block (zero: no block)
         const size_t bytes = (size_t)max_launches * 2 * SPAN_MAX_BLOCKS * 8;
@@ -2261,59 +2169,6 @@ int Model::probe_read_span(double* total_ms, int* count) {
 }
 
 // ------------------------------------------------------------------------------ host access
-int Model::layer_info(int layer, int info[12]) const {
-    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
-    const Layer& l = L[layer];
-    const ConvGeom& g = l.og;  // the layer as the network defines it
-    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, l.relu, l.pool};
-    memcpy(info, v, sizeof(v));
-    return NITI_NO_ERROR;
-}
-
-int Model::set_weight(int layer, const int8_t* w_host, int wscale) {
-    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
-    Layer& l = L[layer];
-    std::vector<int8_t> colw;
-    if (l.col) {  // upload the [co][32] im2col weights as the 1x1 geometry's OIHW
-        colw.resize((size_t)l.g.c_out * 32);
-        cols_from_oihw(l.og, w_host, colw.data(), 32);
-        w_host = colw.data();
-    }
-    // (a depthwise layer's [C][1][k][k] is the flat order of the c_out = 1 layer's OIHW; it has no wT)
-    const size_t n = (size_t)l.w_co() * l.g.c_in * l.g.kh * l.g.kw;
-    int8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int rc = NITI_NO_ERROR;
-    if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
-        oihw_to_ohwi16(tmp, l.w_co(), l.g.c_in, l.g.kh * l.g.kw, l.g.cip, l.w, nullptr) != hipSuccess ||
-        (!l.dw && oihw_to_ihwo16(tmp, l.g.c_out, l.g.c_in, l.g.kh * l.g.kw, l.g.cop, l.wT, nullptr) != hipSuccess) ||
-        (l.subw && conv_dgrad_subpix_weights(l.g, l.wT, l.subw, nullptr) != hipSuccess) ||
-        hipMemset(l.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess ||
-        (l.rc && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, false, l.wf, nullptr) != hipSuccess) ||
-        (l.rcd && weights_to_wf(l.w, l.g.c_out, l.g.c_in, l.g.cip, true, l.wft, nullptr) != hipSuccess) ||
-        hipDeviceSynchronize() != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    l.wscale = (int8_t)wscale;
-    (void)hipFree(tmp);
-    return rc;
-}
-
-int Model::get_weight(int layer, int8_t* w_host) {
-    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
-    Layer& l = L[layer];
-    const size_t n = (size_t)l.w_co() * l.g.c_in * l.g.kh * l.g.kw;
-    int8_t* tmp = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int rc = NITI_NO_ERROR;
-    std::vector<int8_t> colw(l.col ? n : 0);
-    if (ohwi16_to_oihw(l.w, l.w_co(), l.g.c_in, l.g.kh * l.g.kw, l.g.cip, tmp, nullptr) != hipSuccess ||
-        hipMemcpy(l.col ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR && l.col) oihw_from_cols(l.og, colw.data(), w_host, 32);
-    (void)hipFree(tmp);
-    return rc;
-}
-
 int Model::get_input(int8_t* x_nchw_host, int* ascale, hipStream_t st) {
     const int n = batch, hw = in_h * in_w;
     if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
@@ -2330,105 +2185,26 @@ int Model::get_input(int8_t* x_nchw_host, int* ascale, hipStream_t st) {
     return err == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
 }
 
-int Model::get_logits(int8_t* logits_host, int* exp_out, hipStream_t st) {
-    Layer& t = L.back();
-    const int n = batch;
-    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
-    std::vector<int8_t> buf((size_t)n * t.g.cop);
-    int8_t e = 0;
-    if (hipMemcpy(buf.data(), t.r, buf.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&e, t.exp, 1, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    for (int i = 0; i < n; ++i) memcpy(logits_host + (size_t)i * t.g.c_out, buf.data() + (size_t)i * t.g.cop, t.g.c_out);
-    if (exp_out) *exp_out = e;
-    return NITI_NO_ERROR;
-}
-
+// The debug taps: what the last step left of layer `layer` (0 its conv (+relu) output, 1 its int8
+// weight gradient, 2 its output gradient), rebuilt where the step's route never wrote it in NHWC16.
 int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) {
     if (!layer_ok(layer)) return NITI_INVALID_VALUE;
-    Layer& l = L[layer];
+    const Layer& l = L[layer];
     const ConvGeom& g = l.g;
-    const int n = batch;
     if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
-    int8_t* tmp = nullptr;
-    size_t need = 0;
-    if (which == 0 || which == 2)
-        need = (size_t)n * g.c_out * g.oh * g.ow;
-    else if (which == 1 && g8_written)
-        need = (size_t)l.w_co() * g.c_in * g.kh * g.kw;
-    else
-        return NITI_INVALID_VALUE;
-    const size_t out_need = which == 1 && l.col ? (size_t)l.og.c_out * l.og.c_in * l.og.kh * l.og.kw : need;
-    if (bytes < out_need) return NITI_INVALID_VALUE;
-    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    hipError_t e;
-    if (which == 0 && !l.r_written) {  // (a pooled layer whose route went as codes under keep_grads(0))
-        (void)hipFree(tmp);
-        return NITI_INVALID_VALUE;
-    }
-    if (which == 0)
-        e = nhwc16_to_nchw(l.r, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else if (which == 2 && layer == 0 && dy0_codes) {  // the codes route never wrote it: rebuilt from g0 and the codes
-        int8_t* d16 = nullptr;
-        const int64_t elems = (int64_t)n * g.oh * g.ow * g.cop;
-        e = hipMalloc(&d16, (size_t)elems);
-        if (e == hipSuccess) e = launch_map(elems, ExpandPoolCodes{l.dy, l.pc, g.oh, g.ow, g.cop, d16}, nullptr);
-        if (e == hipSuccess) e = nhwc16_to_nchw(d16, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (d16) (void)hipFree(d16);
-    } else if (which == 2 && !dy16_valid[layer]) {  // rebuilt from the C32 copy the step wrote
-        int8_t* d16 = nullptr;
-        e = hipMalloc(&d16, (size_t)n * g.oh * g.ow * g.cop);
-        if (e == hipSuccess) e = c32_to_nhwc16(l.dyc32, n, g.oh * g.ow, g.cop, g.c_out, d16, nullptr);
-        if (e == hipSuccess) e = nhwc16_to_nchw(d16, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (d16) (void)hipFree(d16);
-    } else if (which == 2)
-        e = nhwc16_to_nchw(l.dy, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else
-        e = ohwi16_to_oihw(l.g8, l.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
-    if (which == 1 && l.col) {
-        std::vector<int8_t> colw(need);
-        if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) oihw_from_cols(l.og, colw.data(), host, 32);
-    } else if (e == hipSuccess) {
-        e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(tmp);
-    return e == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
-}
-
-int64_t Model::step_macs() const {
-    int64_t s = 0;
-    for (size_t i = 0; i < L.size(); ++i) {
-        const int64_t f = L[i].macs();
-        s += f;            // forward
-        s += f;            // weight gradient
-        if (i > 0) s += f; // input gradient
-    }
-    return s;
-}
-
-int Model::spec_stats(uint32_t* out, int max_layers) {
-    const int nl = std::min(max_layers, (int)L.size());
-    std::fill(out, out + (size_t)nl * 6, 0u);
-    for (int i = 0; i < nl; ++i) {
-        const Layer& l = L[i];
-        for (int d = 0; d < 2; ++d) {  // forward / input-gradient slot: hint, redone launches, stored pairs
-            uint32_t w[5] = {0, 0, 0, 0, 0}, gw[4] = {0, 0, 0, 0};
-            if (l.bar != nullptr &&
-                hipMemcpy(w, rowconv_spec_slot(l.bar, d != 0), sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            // the GEMM path's pair (plan strategy 3): its own slot, no store mode
-            if (l.gspec != nullptr &&
-                hipMemcpy(gw, l.gspec + d * GEMM_SPEC_SLOT_WORDS, sizeof(gw), hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            out[i * 6 + d * 3] = std::max(w[0], gw[0]);
-            out[i * 6 + d * 3 + 1] = w[2] + gw[2];
-            out[i * 6 + d * 3 + 2] = w[4] + gw[3];  // the GEMM pair: misses settled from an alternate
-        }
-    }
-    return NITI_NO_ERROR;
+    // (a pooled layer whose route went as codes under keep_grads(0))
+    if (which == 0) return l.r_written ? tap_out(l, 0, l.r, host, bytes) : NITI_INVALID_VALUE;
+    const bool codes = layer == 0 && dy0_codes;  // the codes route never wrote dy: rebuilt from g0 and the codes
+    if (which != 2 || (!codes && dy16_valid[layer])) return tap_out(l, which, which == 2 ? l.dy : l.g8, host, bytes);
+    int8_t* d16 = nullptr;  // (else from the C32 copy the step wrote)
+    const int64_t elems = (int64_t)batch * g.oh * g.ow * g.cop;
+    hipError_t e = hipMalloc(&d16, (size_t)elems);
+    if (e == hipSuccess)
+        e = codes ? launch_map(elems, ExpandPoolCodes{l.dy, l.pc, g.oh, g.ow, g.cop, d16}, nullptr)
+                  : c32_to_nhwc16(l.dyc32, batch, g.oh * g.ow, g.cop, g.c_out, d16, nullptr);
+    const int rc = e == hipSuccess ? tap_out(l, 2, d16, host, bytes) : NITI_NO_EXECUTION;
+    if (d16) (void)hipFree(d16);
+    return rc;
 }
 
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch,

@@ -20,6 +20,10 @@
 // exact protocol of niti_model.hip (ranges MAX-reduced on the step stream between the two launches
 // of each requantisation, int32 weight-gradient buckets SUM-reduced on the comm stream while the
 // backward pass goes on), so N ranks equal one device running the global batch bit for bit.
+// An RConv is the base's ParamLayer (niti_step_driver.hpp) plus this driver's buffers; the host access
+// over the convs (weights and their derived copies, taps, logits, layer_info, spec_stats) and the update
+// jobs (sgd_job) are the base's, over StepDriver::P.  Here: set_weight's drop_graph() and get_tap's
+// refusal of the stem output a step did not write.
 #include <string.h>
 
 #include <algorithm>
@@ -151,6 +155,7 @@ int ResNetModel::build(int batch_, int in_hw_, const niti_resnet_spec& spec_) {
     add(sh[0]);
     stem = C[0].og;
     C[0].g = make_geom(n, stem_kp, stem.oh, spec.width, 1, 1, 0);
+    C[0].kp = stem_kp;
     const int ph = spec.stem_pool ? (stem.oh + 2 - 3) / 2 + 1 : stem.oh;  // block 0's input size
     for (int i = 1; i + 1 < n_sh;) {  // a block: conv a, conv b, [the 1x1 projection]
         RBlock b;
@@ -224,14 +229,14 @@ int ResNetModel::build(int batch_, int in_hw_, const niti_resnet_spec& spec_) {
         c.bar = (uint32_t*)ws.alloc(ROWCONV_BAR_WORDS * 4);
         if (!c.bar || hipMemset(c.bar, 0, ROWCONV_BAR_WORDS * 4) != hipSuccess) return NITI_OUT_OF_MEMORY;
         if (i > 0 && rowconv_ok(g)) {
-            c.rows = 1;
+            c.rc = 1;
             c.wf = A8(rowconv_wf_bytes(g.c_out, g.c_in));
             if (!c.wf) return NITI_OUT_OF_MEMORY;
             if (!rowconv_nhwc_pref(g) && !(c.xc32 = A8((size_t)n * round_up(g.c_in, 32) * g.h * g.w)))
                 return NITI_OUT_OF_MEMORY;
             rc_acc_size = std::max(rc_acc_size, rowconv_acc_bytes(g, false));
             if (rowconv_dgrad_geom(g, &c.dg)) {
-                c.rows_dg = 1;
+                c.rcd = 1;
                 c.wft = A8(rowconv_wf_bytes(g.c_in, g.c_out));
                 if (!c.wft) return NITI_OUT_OF_MEMORY;
                 if (!rowconv_nhwc_pref(c.dg) && !(c.dyc32 = A8((size_t)n * g.oh * g.ow * round_up(g.c_out, 32))))
@@ -327,15 +332,18 @@ int ResNetModel::build(int batch_, int in_hw_, const niti_resnet_spec& spec_) {
     if (slab_w_bytes && !(slab_w = ws.alloc(slab_w_bytes))) return NITI_OUT_OF_MEMORY;
     if (rc_acc_size && !(rc_acc = (int32_t*)ws.alloc(rc_acc_size))) return NITI_OUT_OF_MEMORY;
     for (int i = 0; i < nl; ++i) {  // the GEMM-path phases that may run the speculative pair
-        if (!C[i].rows) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_fwd_spec_alt_bytes(C[i].g));
-        if (C[i].dx != nullptr && !C[i].rows_dg) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_dgrad_spec_alt_bytes(C[i].g));
+        if (!C[i].rc) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_fwd_spec_alt_bytes(C[i].g));
+        if (C[i].dx != nullptr && !C[i].rcd) gspec_alt_bytes = std::max(gspec_alt_bytes, conv_dgrad_spec_alt_bytes(C[i].g));
     }
     if (gspec_alt_bytes && !(gspec_alt = (int8_t*)ws.alloc(gspec_alt_bytes))) return NITI_OUT_OF_MEMORY;
     amax_bytes = (3 * C.size() + 2 * B.size() + 1) * MAX_BYTES;
     amax = (uint32_t*)ws.alloc(amax_bytes);
     if (!amax) return NITI_OUT_OF_MEMORY;
-    // (the bucket SUMs, the GEMM weight gradients)
-    for (int i = 0; i < nl; ++i) grads.push_back(GradSlot{C[i].dwacc, C[i].w_elems(), rng(i, 2), C[i].g});
+    // C has its final size: the base's view of the layers (ahead of alloc_update_bits, which counts them)
+    for (int i = 0; i < nl; ++i) {
+        C[i].wg_amax = rng(i, 2);
+        P.push_back(&C[i]);
+    }
     sgd_jobs.resize(nl);
     if (const int rc = alloc_eval()) return rc;
     if (const int rc = alloc_update_bits()) return rc;
@@ -535,7 +543,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
         if (rc != NITI_NO_ERROR) return rc;
     }
     InStep in_step_guard(in_step);  // weight gradients inside this step may defer their combine
-    for (GradSlot& s : grads) s.defer = SgdJob{};
+    for (RConv& c : C) c.defer = SgdJob{};
     if (!dp && !capturing && !tuning) {
         const int rc = size_wslabs();  // (plan changes: no allocation or sync inside the step)
         if (rc != NITI_NO_ERROR) return rc;
@@ -584,24 +592,7 @@ int ResNetModel::run(const int8_t* x_nchw, int exp_in, const uint8_t* images, co
     // gradient read the old weights; it also rewrites the row kernels' fragment-major copies and the
     // GEMM input gradient's transposed copy
     SgdJob* jobs = sgd_jobs.data();
-    for (int i = 0; i < nl; ++i) {
-        RConv& c = C[i];
-        const ConvGeom& g = c.g;
-        // (rule: the conv's update-bits word, whichever group's launch takes the job)
-        jobs[i] = SgdJob{c.dwacc, rng(i, 2), -(1 + i), g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, c.w,
-                         i > 0 && !rows_dg_on(i) ? c.wT : nullptr, keep_grads ? c.g8 : nullptr};
-        jobs[i].wf = c.rows ? c.wf : nullptr;
-        jobs[i].wft = c.rows_dg ? c.wft : nullptr;
-        if (c.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights
-            jobs[i].subw = c.subw;
-            jobs[i].sub_kh = g.kh;
-            jobs[i].sub_kw = g.kw;
-            jobs[i].sub_pt = g.pt;
-            jobs[i].sub_pl = g.pl;
-        }
-        // this conv's split-K slabs, combined in the update launch
-        if (grads[i].defer.slab != nullptr) jobs[i].take_combine(grads[i].defer);
-    }
+    for (int i = 0; i < nl; ++i) jobs[i] = sgd_job(i, i > 0 && !rows_dg_on(i));
     rc = in_job_groups(nl, SGD_MAX_JOBS, [&](int first, int count) { return sgd_update_many(jobs + first, count, st, upd_bits); });
     if (rc != NITI_NO_ERROR) return rc;
     g8_written = keep_grads;
@@ -707,15 +698,7 @@ int ResNetModel::copy_weights_from(StepDriver& other, hipStream_t st) {
     for (size_t i = 0; i < C.size(); ++i)
         if (C[i].w_elems() != src.C[i].w_elems()) return NITI_INVALID_VALUE;
     if (&src == this) return NITI_NO_ERROR;
-    for (size_t i = 0; i < C.size(); ++i) {
-        RConv& c = C[i];
-        DTRY(copy_kernel(c.w, src.C[i].w, (size_t)c.w_elems(), st));
-        DTRY(copy_kernel(c.ws_dev, src.C[i].ws_dev, 1, st));
-        c.wscale = src.C[i].wscale;
-        const int rc = refresh_copies((int)i, st);
-        if (rc != NITI_NO_ERROR) return rc;
-    }
-    return NITI_NO_ERROR;
+    return copy_layer_weights(src, st);
 }
 
 int ResNetModel::step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) {
@@ -820,108 +803,18 @@ int ResNetModel::run_phase(int layer, int phase, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------ host access
-int ResNetModel::refresh_copies(int i, hipStream_t st) {
-    RConv& c = C[i];
-    const ConvGeom& g = c.g;
-    if (c.wT && ohwi16_to_ihwo16(c.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, c.wT, st) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    if (c.rows && weights_to_wf(c.w, g.c_out, g.c_in, g.cip, false, c.wf, st) != hipSuccess) return NITI_NO_EXECUTION;
-    if (c.rows_dg && weights_to_wf(c.w, g.c_out, g.c_in, g.cip, true, c.wft, st) != hipSuccess) return NITI_NO_EXECUTION;
-    if (c.subw && conv_dgrad_subpix_weights(g, c.wT, c.subw, st) != hipSuccess) return NITI_NO_EXECUTION;
-    return NITI_NO_ERROR;
-}
-
 int ResNetModel::set_weight(int i, const int8_t* w_host, int wscale) {
-    if (i < 0 || i >= (int)C.size() || !w_host) return NITI_INVALID_VALUE;
-    RConv& c = C[i];
-    const ConvGeom& g = c.g;
-    std::vector<int8_t> colw;
-    if (i == 0) {
-        colw.resize((size_t)g.c_out * stem_kp);
-        cols_from_oihw(c.og, w_host, colw.data(), stem_kp);
-        w_host = colw.data();
-    }
-    const size_t nb = (size_t)g.c_out * g.c_in * g.kh * g.kw;
-    int8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, nb) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    int rc = NITI_NO_ERROR;
-    if (hipMemcpy(tmp, w_host, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        oihw_to_ohwi16(tmp, g.c_out, g.c_in, g.kh * g.kw, g.cip, c.w, nullptr) != hipSuccess ||
-        hipMemset(c.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR) rc = refresh_copies(i, nullptr);
-    if (rc == NITI_NO_ERROR && hipDeviceSynchronize() != hipSuccess) rc = NITI_NO_EXECUTION;
-    c.wscale = (int8_t)wscale;
-    (void)hipFree(tmp);
-    drop_graph();
-    return rc;
-}
-
-int ResNetModel::get_weight(int i, int8_t* w_host) {
-    if (i < 0 || i >= (int)C.size() || !w_host) return NITI_INVALID_VALUE;
-    const RConv& c = C[i];
-    const ConvGeom& g = c.g;
-    const size_t nb = (size_t)g.c_out * g.c_in * g.kh * g.kw;
-    int8_t* tmp = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, nb) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    std::vector<int8_t> colw(i == 0 ? nb : 0);
-    int rc = NITI_NO_ERROR;
-    if (ohwi16_to_oihw(c.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr) != hipSuccess ||
-        hipMemcpy(i == 0 ? colw.data() : w_host, tmp, nb, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = NITI_NO_EXECUTION;
-    if (rc == NITI_NO_ERROR && i == 0) oihw_from_cols(c.og, colw.data(), w_host, stem_kp);
-    (void)hipFree(tmp);
+    const int rc = StepDriver::set_weight(i, w_host, wscale);
+    drop_graph();  // (this driver captures again after a weight change; the chain driver does not)
     return rc;
 }
 
 int ResNetModel::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) {
-    if (layer < 0 || layer >= (int)C.size()) return NITI_INVALID_VALUE;
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
     const RConv& c = C[layer];
-    const ConvGeom& g = c.g;
-    const int n = batch;
     if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
-    size_t need = 0;
     if (which == 0 && layer == 0 && !stem_y_written) return NITI_INVALID_VALUE;  // (not written by the last step)
-    if (which == 0 || which == 2)
-        need = (size_t)n * g.c_out * g.oh * g.ow;
-    else if (which == 1 && g8_written)
-        need = (size_t)g.c_out * g.c_in * g.kh * g.kw;
-    else
-        return NITI_INVALID_VALUE;
-    const size_t out_need = which == 1 ? (size_t)c.og.c_out * c.og.c_in * c.og.kh * c.og.kw : need;
-    if (bytes < out_need) return NITI_INVALID_VALUE;
-    int8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    hipError_t e;
-    if (which == 0)
-        e = nhwc16_to_nchw(c.y, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else if (which == 2)
-        e = nhwc16_to_nchw(c.dy, n, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
-    else
-        e = ohwi16_to_oihw(c.g8, g.c_out, g.c_in, g.kh * g.kw, g.cip, tmp, nullptr);
-    if (which == 1 && layer == 0) {
-        std::vector<int8_t> colw(need);
-        if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) oihw_from_cols(c.og, colw.data(), host, stem_kp);
-    } else if (e == hipSuccess) {
-        e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(tmp);
-    return e == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
-}
-
-int ResNetModel::get_logits(int8_t* host, int* exp_out, hipStream_t st) {
-    const RConv& f = C.back();
-    const int n = batch;
-    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
-    std::vector<int8_t> buf((size_t)n * f.g.cop);
-    int8_t e = 0;
-    if (hipMemcpy(buf.data(), f.y, buf.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&e, f.y_exp, 1, hipMemcpyDeviceToHost) != hipSuccess)
-        return NITI_NO_EXECUTION;
-    for (int i = 0; i < n; ++i) memcpy(host + (size_t)i * f.g.c_out, buf.data() + (size_t)i * f.g.cop, f.g.c_out);
-    if (exp_out) *exp_out = e;
-    return NITI_NO_ERROR;
+    return tap_out(c, which, which == 0 ? c.y : which == 2 ? c.dy : c.g8, host, bytes);
 }
 
 int ResNetModel::get_input(int8_t* host, int* ascale, hipStream_t st) {
@@ -931,41 +824,6 @@ int ResNetModel::get_input(int8_t* host, int* ascale, hipStream_t st) {
         hipMemcpy(&e, exp0, 1, hipMemcpyDeviceToHost) != hipSuccess)
         return NITI_NO_EXECUTION;
     if (ascale) *ascale = e;
-    return NITI_NO_ERROR;
-}
-
-int64_t ResNetModel::step_macs() const {
-    // every layer's forward and weight gradient, every input gradient but the stem's (never run)
-    int64_t s = 0;
-    for (size_t i = 0; i < C.size(); ++i) s += C[i].macs() * (i > 0 ? 3 : 2);
-    return s;
-}
-
-int ResNetModel::spec_stats(uint32_t* out, int max_layers) {
-    const int nl = std::min(max_layers, (int)C.size());
-    std::fill(out, out + (size_t)nl * 6, 0u);
-    for (int i = 0; i < nl; ++i) {
-        for (int d = 0; d < 2; ++d) {  // the row kernels' pair and the GEMM's (its own slot, no store mode)
-            uint32_t w[5] = {0, 0, 0, 0, 0}, gw[4] = {0, 0, 0, 0};
-            if (C[i].bar != nullptr &&
-                hipMemcpy(w, rowconv_spec_slot(C[i].bar, d != 0), sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            if (hipMemcpy(gw, C[i].gspec + d * GEMM_SPEC_SLOT_WORDS, sizeof(gw), hipMemcpyDeviceToHost) != hipSuccess)
-                return NITI_INVALID_VALUE;
-            out[i * 6 + d * 3] = std::max(w[0], gw[0]);
-            out[i * 6 + d * 3 + 1] = w[2] + gw[2];
-            out[i * 6 + d * 3 + 2] = w[4] + gw[3];  // the GEMM pair: misses settled from an alternate
-        }
-    }
-    return NITI_NO_ERROR;
-}
-
-int ResNetModel::layer_info(int layer, int info[12]) const {
-    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
-    const RConv& c = C[layer];
-    const ConvGeom& g = c.og;
-    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, c.relu, 0};
-    memcpy(info, v, sizeof(v));
     return NITI_NO_ERROR;
 }
 
@@ -987,17 +845,6 @@ int ResNetModel::plan_set(int layer, int phase, const int plan[4]) {
     }
     if (!plan_valid(op, g, plan, false) || plan[2] > 4096) return NITI_INVALID_VALUE;
     return plan_commit(k, op, plan, true);
-}
-
-int ResNetModel::set_rowconv(bool enable) {
-    if (use_rowconv && !enable) {  // the GEMM input gradients read IHWO16 copies the update skipped
-        for (int i = 0; i < (int)C.size(); ++i)
-            if (refresh_copies(i, nullptr) != NITI_NO_ERROR) return NITI_NO_EXECUTION;
-        if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
-    }
-    use_rowconv = enable;
-    drop_graph();
-    return NITI_NO_ERROR;
 }
 
 std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int in_hw, int batch, int* rc) {

@@ -17,24 +17,11 @@
 
 namespace niti {
 
-// one parameter layer (conv1, per basic block conv a / conv b / the 1x1 projection, the fc head)
-struct RConv {
-    ConvGeom g{};   // as it runs (the stem: a 1x1 conv over its im2col, c_in = the im2col columns)
-    ConvGeom og{};  // as the network defines it (the stem: 7x7 / 2, pad 3)
-    int relu = 0;   // relu fused into the forward requantisation (conv1, conv a)
-    int rows = 0;   // forward and input gradient on the register-fed row kernels (niti_rowconv.hip)
-    int rows_dg = 0;
+// one parameter layer (conv1, per basic block conv a / conv b / the 1x1 projection, the fc head): the
+// base's ParamLayer (the stem: g a 1x1 conv over its im2col, c_in = kp = the im2col columns; og the
+// 7x7 / 2, pad 3 conv) and this driver's buffers
+struct RConv : ParamLayer {
     ConvGeom dg{};  // the input gradient's geometry on the row kernel (rowconv_dgrad_geom)
-    int8_t wscale = 0;
-    int8_t* w = nullptr;       // OHWI16
-    int8_t* wT = nullptr;      // IHWO16 (GEMM input gradient)
-    int8_t* subw = nullptr;    // stride 2: the sub-pixel classes' weights (conv_dgrad_subpix_bytes)
-    int8_t* wf = nullptr;      // fragment-major copies (row kernels)
-    int8_t* wft = nullptr;
-    int8_t* ws_dev = nullptr;  // wscale, device
-    int8_t* g8 = nullptr;      // int8 weight gradient (keep_grads)
-    uint32_t* bar = nullptr;   // row-kernel state: grid barrier words + speculation slots
-    uint32_t* gspec = nullptr; // the GEMM path's speculative pair: forward / input-gradient hint slots
     uint32_t epoch = 0;
     int8_t* xc32 = nullptr;    // C32 copies where the row kernel reads C32 (not NHWC16 in place)
     int8_t* dyc32 = nullptr;
@@ -47,9 +34,6 @@ struct RConv {
     int8_t* dx = nullptr;            // input gradient (null: none -- the stem)
     int8_t* dx_exp = nullptr;
     const int8_t* dx_mask = nullptr; // the previous op's relu gradient fused into the input gradient
-    int32_t* dwacc = nullptr;        // int32 weight gradient (in the contiguous gradient bucket)
-    int64_t w_elems() const { return (int64_t)g.c_out * g.kh * g.kw * g.cip; }
-    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * og.c_in * og.kh * og.kw; }
 };
 
 struct RBlock {
@@ -89,10 +73,9 @@ struct ResNetModel final : StepDriver {
     // the stem's requantise pass also max-pooled (Pool3) this step; with keep_grads off its pre-pool
     // output is then never written (its forward tap is unavailable)
     bool stem_pooled = false;
-    // what the last step wrote for the debug taps (get_tap reads these, not the current
-    // keep_grads): the stem's pre-pool output, the int8 weight gradients
+    // what the last step wrote for the debug taps (get_tap reads this, not the current
+    // keep_grads): the stem's pre-pool output
     bool stem_y_written = false;
-    bool g8_written = false;
     int8_t* d0 = nullptr;         // the stem's output gradient
     int32_t* gsum = nullptr;      // global sum pool [n][the last stage's width, padded]
     int8_t* g8pool = nullptr;     // its requantisation (the fc input)
@@ -141,8 +124,8 @@ struct ResNetModel final : StepDriver {
     std::vector<SgdJob> sgd_jobs;  // the update's job table (sized in build(): no allocation in a step)
 
     int build(int batch_, int in_hw_, const niti_resnet_spec& spec_);
-    bool rows_on(int i) const { return use_rowconv && C[i].rows; }
-    bool rows_dg_on(int i) const { return use_rowconv && C[i].rows_dg; }
+    bool rows_on(int i) const { return use_rowconv && C[i].rc; }
+    bool rows_dg_on(int i) const { return use_rowconv && C[i].rcd; }
     int fwd_conv(int i, hipStream_t st);
     int dgrad_conv(int i, hipStream_t st);
     int wgrad_conv(int i, hipStream_t st);
@@ -158,20 +141,13 @@ struct ResNetModel final : StepDriver {
     int run_phase(int layer, int phase, hipStream_t st) override;
     int plan_info(int layer, int phase, int info[4]) override;
     int plan_set(int layer, int phase, const int plan[4]) override;
-    int set_rowconv(bool enable) override;
     void set_overlap(bool) override {}  // one stream (the weight gradients interleave with the input gradients)
     // kernel probe: the events on the step stream around one conv phase (both launches of a
     // two-launch form)
     void probe(int layer, int phase, bool begin, hipStream_t st);
     void drop_graph() override;
-    int refresh_copies(int i, hipStream_t st);  // wT / wf / wft from w
-    bool layer_ok(int layer) const { return layer >= 0 && layer < (int)C.size(); }
-    int num_layers() const override { return (int)C.size(); }
-    int layer_info(int layer, int info[12]) const override;
     int set_weight(int i, const int8_t* w_oihw_host, int wscale) override;
-    int get_weight(int i, int8_t* w_oihw_host) override;
     int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) override;
-    int get_logits(int8_t* host, int* exp_out, hipStream_t st) override;
     void logits_view(const int8_t** logits, int* classes_out, int* ld, const int8_t** exp) const override {
         const RConv& f = C.back();
         *logits = f.y;
@@ -180,13 +156,6 @@ struct ResNetModel final : StepDriver {
         *exp = f.y_exp;
     }
     int get_input(int8_t* host, int* ascale, hipStream_t st) override;
-    int64_t step_macs() const override;
-    int spec_stats(uint32_t* out, int max_layers) override;
-    int spec_state(int layer, uint32_t** bar) override {
-        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
-        *bar = C[layer].bar;
-        return NITI_NO_ERROR;
-    }
     ~ResNetModel() override { drop_graph(); }  // (the rest in ~StepDriver)
 };
 

@@ -41,14 +41,15 @@ static bool wslab_plan(const ConvGeom& g, size_t slab_w_bytes, PlanChoice* c) {
 
 bool StepDriver::ensure_wslab(int i) const {
     PlanChoice c;
-    if (!wslab_plan(grads[i].g, slab_w_bytes, &c)) return false;
-    return grads[i].wslab_bytes >= conv_wgrad_slab_bytes(grads[i].g, c);  // (GEMM or tap-sharing slabs)
+    if (!wslab_plan(P[i]->g, slab_w_bytes, &c)) return false;
+    return P[i]->wslab_bytes >= conv_wgrad_slab_bytes(P[i]->g, c);  // (GEMM or tap-sharing slabs)
 }
 
 int StepDriver::size_wslabs() {
     if (wslab_epoch == plan_override_epoch()) return NITI_NO_ERROR;
     bool synced = false;
-    for (GradSlot& s : grads) {
+    for (ParamLayer* l : P) {
+        ParamLayer& s = *l;
         PlanChoice c;
         if (!wslab_plan(s.g, slab_w_bytes, &c)) continue;
         const size_t need = conv_wgrad_slab_bytes(s.g, c);
@@ -65,7 +66,7 @@ int StepDriver::size_wslabs() {
 }
 
 int StepDriver::wgrad_gemm(int i, const int8_t* x, const int8_t* dy, hipEvent_t after_gemm, hipStream_t st) {
-    GradSlot& s = grads[i];
+    ParamLayer& s = *P[i];
     const bool defer = defer_combine() && ensure_wslab(i);
     // the autotuner times a split plan of the generic GEMM with the combine it will run with in
     // the step (over the tuning workspace, right behind the GEMM), not with the reduce launch the
@@ -74,12 +75,12 @@ int StepDriver::wgrad_gemm(int i, const int8_t* x, const int8_t* dy, hipEvent_t 
     const bool tune_defer = tuning && in_step_combine() &&
                             conv_plan_query(PLAN_WGRAD, s.g, false, slab_w_bytes).bm != PLAN_TAPS_TILE;
     s.defer = SgdJob{};
-    DTRY(conv_wgrad_acc(s.g, x, dy, s.dwacc, dp() ? nullptr : s.amax, defer ? s.wslab : slab_w,
+    DTRY(conv_wgrad_acc(s.g, x, dy, s.dwacc, dp() ? nullptr : s.wg_amax, defer ? s.wslab : slab_w,
                         defer ? s.wslab_bytes : slab_w_bytes, st, after_gemm, defer || tune_defer ? &s.defer : nullptr));
     if (tune_defer && s.defer.slab != nullptr) {
         SgdJob j = s.defer;
         j.acc = s.dwacc;
-        j.amax = s.amax;
+        j.amax = s.wg_amax;
         s.defer = SgdJob{};
         DTRY(sgd_combine_many(&j, 1, st));
     }
@@ -88,13 +89,13 @@ int StepDriver::wgrad_gemm(int i, const int8_t* x, const int8_t* dy, hipEvent_t 
 
 // ------------------------------------------------------------------------------ data parallel
 void StepDriver::plan_buckets() {
-    const int nl = (int)grads.size();
+    const int nl = (int)P.size();
     bucket_lo.assign(nl, 0);
     closes_bucket.assign(nl, 0);
     size_t acc = 0;
     int hi = nl - 1;
     for (int i = nl - 1; i >= 0; --i) {
-        acc += (size_t)grads[i].elems * 4;
+        acc += (size_t)P[i]->w_elems() * 4;
         if (acc >= bucket_min_bytes || i == 0) {
             closes_bucket[i] = 1;
             for (int j = i; j <= hi; ++j) bucket_lo[j] = i;
@@ -109,7 +110,7 @@ int StepDriver::ensure_comm_stream() {
     if (hipStreamCreateWithFlags(&cst, hipStreamNonBlocking) != hipSuccess) return NITI_NO_EXECUTION;
     // cross-stream hand-offs on one device need a device-scope release only
     constexpr unsigned kFlags = hipEventDisableTiming | hipEventReleaseToDevice;
-    ev_bucket.assign(grads.size(), nullptr);
+    ev_bucket.assign(P.size(), nullptr);
     for (auto& e : ev_bucket)
         if (hipEventCreateWithFlags(&e, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
     if (hipEventCreateWithFlags(&ev_grads, kFlags) != hipSuccess) return NITI_NO_EXECUTION;
@@ -124,18 +125,18 @@ int StepDriver::ensure_comm_stream() {
 // NITI_GradientConv_Int8.cpp:274-296), while the step stream goes on with the input-gradient chain.
 int StepDriver::sum_bucket(int lo, hipStream_t wst) {
     int hi = lo;
-    while (hi + 1 < (int)grads.size() && bucket_lo[hi + 1] == lo) ++hi;
+    while (hi + 1 < (int)P.size() && bucket_lo[hi + 1] == lo) ++hi;
     size_t elems = 0;
-    for (int j = lo; j <= hi; ++j) elems += (size_t)grads[j].elems;
+    for (int j = lo; j <= hi; ++j) elems += (size_t)P[j]->w_elems();
     bucket_jobs.resize(hi - lo + 1);
-    for (int j = lo; j <= hi; ++j) bucket_jobs[j - lo] = AbsmaxJob{grads[j].dwacc, grads[j].elems, grads[j].amax, 0};
+    for (int j = lo; j <= hi; ++j) bucket_jobs[j - lo] = AbsmaxJob{P[j]->dwacc, P[j]->w_elems(), P[j]->wg_amax, 0};
     hipStream_t s = wst;  // one communicator: the SUMs stay in the step's program order
     if (!shared_comm) {   // own communicator: its own stream, overlapping the rest of the backward pass
         DTRY(hipEventRecord(ev_bucket[lo], wst));
         DTRY(hipStreamWaitEvent(cst, ev_bucket[lo], 0));
         s = cst;
     }
-    DTRY(coll_grad->allreduce(grads[lo].dwacc, elems, COLL_SUM_I32, s));
+    DTRY(coll_grad->allreduce(P[lo]->dwacc, elems, COLL_SUM_I32, s));
     // (a narrow deep network's bucket can hold more layers than one range launch takes)
     return in_job_groups(hi - lo + 1, ABSMAX_MAX_JOBS,
                          [&](int first, int count) { return absmax_many(bucket_jobs.data() + first, count, s); });
@@ -346,6 +347,190 @@ int StepDriver::plan_out(const PlanChoice& c, int info[4]) {
     info[1] = c.bn;
     info[2] = c.splits;
     info[3] = c.strat;
+    return NITI_NO_ERROR;
+}
+
+// ------------------------------------------------------------------------------ the update job
+SgdJob StepDriver::sgd_job(int i, bool wT_by_update) const {
+    const ParamLayer& p = *P[i];
+    const ConvGeom& g = p.g;
+    // (a depthwise layer: the c_out = 1 form of its weight, no transposed copy)
+    SgdJob j{p.dwacc, p.wg_amax, -(1 + i), p.w_co(), g.c_in, g.kh * g.kw, g.cip, p.dw ? 16 : g.cop, p.w,
+             wT_by_update && !p.dw ? p.wT : nullptr, keep_grads ? p.g8 : nullptr};
+    j.wf = p.rc ? p.wf : nullptr;
+    j.wft = p.rcd ? p.wft : nullptr;
+    if (p.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights
+        j.subw = p.subw;
+        j.sub_kh = g.kh;
+        j.sub_kw = g.kw;
+        j.sub_pt = g.pt;
+        j.sub_pl = g.pl;
+    }
+    // the combine of this layer's split-K slabs, in the update launch
+    if (p.defer.slab != nullptr) j.take_combine(p.defer);
+    return j;
+}
+
+// ------------------------------------------------------------------------------ host access
+int StepDriver::layer_info(int layer, int info[12]) const {
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+    const ParamLayer& p = *P[layer];
+    const ConvGeom& g = p.og;  // the layer as the network defines it
+    const int v[12] = {g.c_in, g.c_out, g.kh, g.kw, g.h, g.w, g.oh, g.ow, g.pt, g.sh, p.relu, p.pool};
+    memcpy(info, v, sizeof(v));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::refresh_copies(ParamLayer& p, hipStream_t st) {
+    const ConvGeom& g = p.g;
+    if (p.wT && !p.dw) DTRY(ohwi16_to_ihwo16(p.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, p.wT, st));
+    if (p.subw) DTRY(conv_dgrad_subpix_weights(g, p.wT, p.subw, st));
+    if (p.rc) DTRY(weights_to_wf(p.w, g.c_out, g.c_in, g.cip, false, p.wf, st));
+    if (p.rcd) DTRY(weights_to_wf(p.w, g.c_out, g.c_in, g.cip, true, p.wft, st));
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::set_weight(int layer, const int8_t* w_host, int wscale) {
+    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
+    ParamLayer& p = *P[layer];
+    const ConvGeom& g = p.g;
+    std::vector<int8_t> colw;
+    if (p.kp) {  // upload the [co][kp] im2col weights as the 1x1 geometry's OIHW
+        colw.resize((size_t)g.c_out * p.kp);
+        cols_from_oihw(p.og, w_host, colw.data(), p.kp);
+        w_host = colw.data();
+    }
+    // (a depthwise layer's [C][1][k][k] is the flat order of the c_out = 1 layer's OIHW)
+    const size_t n = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+    int8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    int rc = NITI_NO_ERROR;
+    if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
+        oihw_to_ohwi16(tmp, p.w_co(), g.c_in, g.kh * g.kw, g.cip, p.w, nullptr) != hipSuccess ||
+        hipMemset(p.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess)
+        rc = NITI_NO_EXECUTION;
+    if (rc == NITI_NO_ERROR) rc = refresh_copies(p, nullptr);
+    if (rc == NITI_NO_ERROR && hipDeviceSynchronize() != hipSuccess) rc = NITI_NO_EXECUTION;
+    p.wscale = (int8_t)wscale;
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int StepDriver::get_weight(int layer, int8_t* w_host) {
+    if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
+    const ParamLayer& p = *P[layer];
+    const ConvGeom& g = p.g;
+    const size_t n = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+    int8_t* tmp = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    int rc = NITI_NO_ERROR;
+    std::vector<int8_t> colw(p.kp ? n : 0);
+    if (ohwi16_to_oihw(p.w, p.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr) != hipSuccess ||
+        hipMemcpy(p.kp ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = NITI_NO_EXECUTION;
+    if (rc == NITI_NO_ERROR && p.kp) oihw_from_cols(p.og, colw.data(), w_host, p.kp);
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int StepDriver::copy_layer_weights(const StepDriver& src, hipStream_t st) {
+    for (size_t i = 0; i < P.size(); ++i) {
+        ParamLayer& p = *P[i];
+        const ParamLayer& s = *src.P[i];
+        DTRY(copy_kernel(p.w, s.w, (size_t)p.w_elems(), st));  // (by kernel: see fill_kernel in niti_map.hpp)
+        DTRY(copy_kernel(p.ws_dev, s.ws_dev, 1, st));
+        p.wscale = s.wscale;
+        const int rc = refresh_copies(p, st);
+        if (rc != NITI_NO_ERROR) return rc;
+    }
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::set_rowconv(bool enable) {
+    if (use_rowconv && !enable) {  // the GEMM input gradients read IHWO16 copies the update skipped
+        for (ParamLayer* p : P)
+            if (p->rcd && refresh_copies(*p, nullptr) != NITI_NO_ERROR) return NITI_NO_EXECUTION;
+        if (hipDeviceSynchronize() != hipSuccess) return NITI_NO_EXECUTION;
+    }
+    use_rowconv = enable;
+    drop_graph();
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::tap_out(const ParamLayer& p, int which, const int8_t* src, int8_t* host, size_t bytes) {
+    const ConvGeom& g = p.g;
+    size_t need = 0;
+    if (which == 0 || which == 2)
+        need = (size_t)batch * g.c_out * g.oh * g.ow;
+    else if (which == 1 && g8_written)
+        need = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+    else
+        return NITI_INVALID_VALUE;
+    // (an im2col layer's gradient goes out in the network's own shape)
+    const size_t out_need = which == 1 && p.kp ? (size_t)p.og.c_out * p.og.c_in * p.og.kh * p.og.kw : need;
+    if (bytes < out_need) return NITI_INVALID_VALUE;
+    int8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
+    hipError_t e = which == 1 ? ohwi16_to_oihw(src, p.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr)
+                              : nhwc16_to_nchw(src, batch, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
+    if (which == 1 && p.kp) {
+        std::vector<int8_t> colw(need);
+        if (e == hipSuccess) e = hipMemcpy(colw.data(), tmp, need, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) oihw_from_cols(p.og, colw.data(), host, p.kp);
+    } else if (e == hipSuccess) {
+        e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(tmp);
+    return e == hipSuccess ? NITI_NO_ERROR : NITI_NO_EXECUTION;
+}
+
+int StepDriver::get_logits(int8_t* host, int* exp_out, hipStream_t st) {
+    const int8_t* logits = nullptr;
+    const int8_t* lexp = nullptr;
+    int classes = 0, ld = 0;
+    logits_view(&logits, &classes, &ld, &lexp);
+    if (hipStreamSynchronize(st) != hipSuccess) return NITI_NO_EXECUTION;
+    std::vector<int8_t> buf((size_t)batch * ld);
+    int8_t e = 0;
+    if (hipMemcpy(buf.data(), logits, buf.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&e, lexp, 1, hipMemcpyDeviceToHost) != hipSuccess)
+        return NITI_NO_EXECUTION;
+    for (int i = 0; i < batch; ++i) memcpy(host + (size_t)i * classes, buf.data() + (size_t)i * ld, classes);
+    if (exp_out) *exp_out = e;
+    return NITI_NO_ERROR;
+}
+
+int64_t StepDriver::step_macs() const {
+    int64_t s = 0;
+    for (size_t i = 0; i < P.size(); ++i) s += P[i]->macs() * (i > 0 ? 3 : 2);
+    return s;
+}
+
+int StepDriver::spec_stats(uint32_t* out, int max_layers) {
+    const int nl = std::min(max_layers, (int)P.size());
+    std::fill(out, out + (size_t)nl * 6, 0u);
+    for (int i = 0; i < nl; ++i) {
+        const ParamLayer& p = *P[i];
+        for (int d = 0; d < 2; ++d) {  // forward / input-gradient slot: hint, redone launches, stored pairs
+            uint32_t w[5] = {0, 0, 0, 0, 0}, gw[4] = {0, 0, 0, 0};
+            if (p.bar != nullptr &&
+                hipMemcpy(w, rowconv_spec_slot(p.bar, d != 0), sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
+                return NITI_INVALID_VALUE;
+            // the GEMM path's pair (plan strategy 3): its own slot, no store mode
+            if (p.gspec != nullptr &&
+                hipMemcpy(gw, p.gspec + d * GEMM_SPEC_SLOT_WORDS, sizeof(gw), hipMemcpyDeviceToHost) != hipSuccess)
+                return NITI_INVALID_VALUE;
+            out[i * 6 + d * 3] = std::max(w[0], gw[0]);
+            out[i * 6 + d * 3 + 1] = w[2] + gw[2];
+            out[i * 6 + d * 3 + 2] = w[4] + gw[3];  // the GEMM pair: misses settled from an alternate
+        }
+    }
+    return NITI_NO_ERROR;
+}
+
+int StepDriver::spec_state(int layer, uint32_t** bar) {
+    if (!layer_ok(layer)) return NITI_INVALID_VALUE;
+    *bar = P[layer]->bar;
     return NITI_NO_ERROR;
 }
 

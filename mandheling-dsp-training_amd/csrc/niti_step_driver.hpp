@@ -2,14 +2,22 @@
 // share: the chain driver (LeNet / VGG, niti_model.hip) and the residual driver (ResNet-18 and the
 // stage lists, niti_resnet_model.hip).
 //
+// ParamLayer is one parameter layer as the base reads it: its geometry, its weight and the copies
+// derived from it, its weight gradient with the range word, the split-K slabs and the deferred
+// combine.  The drivers' own layer records (Layer, RConv) derive from it and add their activation and
+// gradient buffers; each build() lists them once in StepDriver::P.
+//
 // StepDriver holds the state and the logic both have in the same form -- split-K slabs, the
 // data-parallel gradient buckets, the range / rescale launch protocol (range_max, rowconv_ranged,
-// gemm_ranged), the GEMM weight gradient with its deferred combine, the event probe, the evaluation
-// totals, the device-resident dataset steps, the graph stream and its fences, the teardown -- and
-// declares, as virtuals, what the C ABI (niti_model_capi.hip) asks of a
-// driver.  A virtual is called at most once per ABI call; nothing inside a step (run(), forward(),
-// backward(), the per-layer functions) goes through one.  The base does not know which driver it
-// serves: where the two differ, the difference is the derived class's.
+// gemm_ranged), the GEMM weight gradient with its deferred combine, a layer's NITI_SGD job (sgd_job),
+// the event probe, the evaluation totals, the device-resident dataset steps, the graph stream and its
+// fences, the teardown, and the host-access half of the C ABI over P: layer_info, set_weight /
+// get_weight with the derived copies (refresh_copies), the copy loop of copy_weights_from,
+// set_rowconv, the tap conversions (tap_out), get_logits, step_macs, spec_stats -- and declares, as
+// virtuals, what else the C ABI (niti_model_capi.hip) asks of a driver.  A virtual is called at most
+// once per ABI call; nothing inside a step (run(), forward(), backward(), the per-layer functions) goes
+// through one: P is a plain vector.  The base does not know which driver it serves: where the two
+// differ, the difference is the derived class's.
 #pragma once
 
 #include <stdlib.h>
@@ -29,13 +37,33 @@
 
 namespace niti {
 
-// one parameter layer's weight gradient as the base sees it (filled by the driver's build()): what the
-// bucket SUMs and the GEMM weight gradient (wgrad_gemm) need of it
-struct GradSlot {
-    int32_t* dwacc = nullptr;  // int32 gradient, in the contiguous gradient bucket
-    int64_t elems = 0;         // w_elems()
-    uint32_t* amax = nullptr;  // its range word (rng(layer, 2))
-    ConvGeom g{};              // the layer's conv as it runs
+// one parameter layer as the base sees it (Layer and RConv derive from it; filled by the driver's
+// build()): exactly what the shared code reads
+struct ParamLayer {
+    ConvGeom g{};   // the layer's conv as it runs (an im2col layer: the 1x1 conv over its columns)
+    ConvGeom og{};  // as the network defines it (reported; weights and taps converted to / from it)
+    int relu = 0;   // relu fused into the forward requantisation
+    int pool = 0;   // a 2x2 max pool behind it (chain driver)
+    // a depthwise conv (chain driver; niti_depthwise.hip): g.c_out == g.c_in == C; w, dwacc, g8 and the
+    // slabs are [k * k][cip], the OHWI16 form of a c_out = 1, c_in = C layer (w_co), [C][1][k][k] on
+    // the host, and there is no wT
+    int dw = 0;
+    int kp = 0;  // the im2col column pitch of a first layer that runs over its im2col (0: not one)
+    int8_t wscale = 0;
+    int8_t* w = nullptr;       // OHWI16
+    int8_t* ws_dev = nullptr;  // wscale, device
+    // the copies derived from w (null: none), kept in step by the update launch and by refresh_copies
+    int8_t* wT = nullptr;    // IHWO16 (GEMM input gradient)
+    int8_t* subw = nullptr;  // stride 2: the sub-pixel classes' weights (conv_dgrad_subpix_bytes)
+    int8_t* wf = nullptr;    // fragment-major (row kernels, niti_rowconv.hip): forward, input gradient
+    int8_t* wft = nullptr;
+    int rc = 0;   // forward on the register-fed row kernels with the fused rescale
+    int rcd = 0;  // its input gradient on the same kernel
+    int8_t* g8 = nullptr;       // int8 weight gradient OHWI16 (keep_grads)
+    uint32_t* bar = nullptr;    // row-kernel state: grid barrier words + speculation slots
+    uint32_t* gspec = nullptr;  // the GEMM path's speculative pair: forward / input-gradient hint slots
+    int32_t* dwacc = nullptr;   // int32 weight gradient [w_co][kk][cip], in the contiguous gradient bucket
+    uint32_t* wg_amax = nullptr;  // its range word (the driver's rng(layer, 2))
     // single device: a split-K GEMM weight gradient's own slabs (sized for the current plans at the
     // head of run(), size_wslabs), and this step's combine deferred to the NITI_SGD launch
     // (sgd_update_many; slab == null: none -- the chain driver's P16 weight gradients leave theirs
@@ -43,6 +71,9 @@ struct GradSlot {
     int32_t* wslab = nullptr;
     size_t wslab_bytes = 0;
     SgdJob defer{};
+    int w_co() const { return dw ? 1 : g.c_out; }  // output channels as the weight layouts count them
+    int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * g.cip; }
+    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in) * og.kh * og.kw; }
 };
 
 struct StepDriver {
@@ -56,6 +87,7 @@ struct StepDriver {
     bool ensure_slab(size_t bytes, bool wgrad);
     uint32_t* rc_err = nullptr;  // set by an in-kernel grid barrier that timed out
     bool keep_grads = true;      // the int8 weight gradient of the last step kept for get_tap (which = 1)
+    bool g8_written = false;     // the last step stored the int8 weight gradients (get_tap reads this, not keep_grads)
     bool use_rowconv = true;     // the register-fed kernels (niti_rowconv.hip) for the layers they take
     bool tuning = false;         // autotune in progress: no collectives, no probe
     bool capturing = false;
@@ -75,7 +107,7 @@ struct StepDriver {
     // the gradient SUMs share the range communicator (ncclCommSplit unavailable): they then run on
     // the weight-gradient stream itself, keeping that one communicator in program order
     bool shared_comm = false;
-    std::vector<GradSlot> grads;
+    std::vector<ParamLayer*> P;  // the parameter layers in layer order (build(), once its layer list is final)
     std::vector<hipEvent_t> ev_bucket;  // per layer: the bucket closed after this layer's weight gradient
     hipEvent_t ev_grads = nullptr;      // every bucket summed and ranged (the NITI_SGD join)
     size_t bucket_min_bytes = grad_bucket_bytes();
@@ -154,7 +186,7 @@ struct StepDriver {
     }
 
     // ---- the GEMM-path weight gradient.  Single device, inside run(): a split-K plan leaves its
-    // slabs (the layer's own, GradSlot::wslab) to the NITI_SGD launch's combine, which sums them and
+    // slabs (the layer's own, ParamLayer::wslab) to the NITI_SGD launch's combine, which sums them and
     // takes the range -- no reduce launch, no int32 round trip (NITI_DIAG_SGD_COMBINE=0: off)
     static bool sgd_combine_on() {
         static const bool off = getenv("NITI_DIAG_SGD_COMBINE") && atoi(getenv("NITI_DIAG_SGD_COMBINE")) == 0;
@@ -237,28 +269,51 @@ struct StepDriver {
     int plan_commit(const PlanKey& k, int op, const int plan[4], bool gemm_slab);
     static int plan_out(const PlanChoice& c, int info[4]);
 
-    // ---- what the C ABI asks of a driver (each validates its layer / phase itself)
-    virtual int num_layers() const = 0;
-    virtual int layer_info(int layer, int info[12]) const = 0;
-    // 1 a depthwise layer, 0 a dense one, -1 out of range (only the chain driver has such layers)
-    virtual int layer_depthwise(int layer) const { return layer >= 0 && layer < num_layers() ? 0 : -1; }
+    // layer i's NITI_SGD job as both run()s build it: the update of w (a depthwise layer's in its
+    // c_out = 1 form) with the int8 gradient where keep_grads, the derived copies it keeps in step
+    // (wT where the caller says the GEMM input gradient reads it: wT_by_update; wf / wft, subw) and the
+    // combine this step's weight gradient deferred (rule: the layer's update-bits word)
+    SgdJob sgd_job(int i, bool wT_by_update) const;
+
+    // ---- host access over P (each validates its layer itself)
+    bool layer_ok(int layer) const { return layer >= 0 && layer < (int)P.size(); }
+    int num_layers() const { return (int)P.size(); }
+    int layer_info(int layer, int info[12]) const;
+    // 1 a depthwise layer, 0 a dense one, -1 out of range
+    int layer_depthwise(int layer) const { return layer_ok(layer) ? P[layer]->dw : -1; }
+    // every derived copy p has, from w, on st: wT, subw, and the row kernels' wf / wft
+    int refresh_copies(ParamLayer& p, hipStream_t st);
+    // w from the host's OIHW (an im2col layer: through its columns), the scale, the derived copies
+    virtual int set_weight(int layer, const int8_t* w_oihw_host, int wscale);
+    int get_weight(int layer, int8_t* w_oihw_host);
+    // copy_weights_from's loop, after the driver's own compatibility check: every layer's w and scale
+    // device to device on st, then the derived copies
+    int copy_layer_weights(const StepDriver& src, hipStream_t st);
+    // off: the GEMM input gradients read IHWO16 copies the update skipped -- rebuilt here
+    int set_rowconv(bool enable);
+    // one tap to the host: src an NHWC16 activation / gradient of p's output (which 0 / 2) as NCHW, or
+    // p.g8 (which 1) as OIHW; INVALID_VALUE for another `which`, for which 1 without g8_written and for
+    // a short buffer, before anything is allocated or written
+    int tap_out(const ParamLayer& p, int which, const int8_t* src, int8_t* host, size_t bytes);
+    int get_logits(int8_t* host, int* exp_out, hipStream_t st);
+    // every layer's forward and weight gradient, every input gradient but the first layer's (never run)
+    int64_t step_macs() const;
+    int spec_stats(uint32_t* out, int max_layers);
+    // a layer's row-kernel state (grid barrier words + speculation slots; may be null)
+    int spec_state(int layer, uint32_t** bar);
+
+    // ---- what else the C ABI asks of a driver (each validates its layer / phase itself)
     // the layer's skip and gpool (only the chain driver has such layers)
     virtual int layer_skip(int layer, int* skip, int* gpool) const {
-        if (layer < 0 || layer >= num_layers()) return NITI_INVALID_VALUE;
+        if (!layer_ok(layer)) return NITI_INVALID_VALUE;
         *skip = *gpool = 0;
         return NITI_NO_ERROR;
     }
-    virtual int set_weight(int layer, const int8_t* w_oihw_host, int wscale) = 0;
-    virtual int get_weight(int layer, int8_t* w_oihw_host) = 0;
+    // syncs st, refuses what the last step did not write, picks or rebuilds the source: then tap_out
     virtual int get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t st) = 0;
-    virtual int get_logits(int8_t* host, int* exp_out, hipStream_t st) = 0;
     virtual int get_input(int8_t* host, int* ascale, hipStream_t st) = 0;
     // the logits as the last step left them on the device: int8 [batch][*ld], their exponent
     virtual void logits_view(const int8_t** logits, int* classes, int* ld, const int8_t** exp) const = 0;
-    virtual int64_t step_macs() const = 0;
-    virtual int spec_stats(uint32_t* out, int max_layers) = 0;
-    // a layer's row-kernel state (grid barrier words + speculation slots; may be null)
-    virtual int spec_state(int layer, uint32_t** bar) = 0;
     // x_nchw int8 with exponent exp_in, or (x_nchw == null) uint8 images through the on-device
     // input quantiser (MnistUtils.cpp:83-93)
     virtual int step(const int8_t* x_nchw, int exp_in, const uint8_t* images, const int32_t* labels, hipStream_t st) = 0;
@@ -268,7 +323,6 @@ struct StepDriver {
     virtual int run_phase(int layer, int phase, hipStream_t st) = 0;
     virtual int plan_info(int layer, int phase, int info[4]) = 0;
     virtual int plan_set(int layer, int phase, const int plan[4]) = 0;
-    virtual int set_rowconv(bool enable) = 0;
     virtual void set_overlap(bool enable) = 0;
     virtual void drop_graph() = 0;
     virtual int probe_alloc(int phase, int max_launches) { return NITI_NO_ERROR; }  // set_probe's extra
