@@ -638,6 +638,35 @@ int niti_dwconv2_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, in
 int niti_dwconv2_wgrad_slabs(const niti_geom* g);
 int niti_dwconv2_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
                               void* stream);
+/* Grouped 3x3 conv layers (csrc/niti_grouped.hip; this library's extension, stated like the depthwise block
+ * above).  groups = G >= 2, c_in = c_out = G cg with cg = 16, 32 or 64 channels a group, a 3x3 kernel, stride 1,
+ * one pad 0..2 on every side.  Output channel o reads input channels cg (o / cg) .. cg (o / cg) + cg - 1: the
+ * layer is NITI_Conv_Int8 over the block-diagonal dense weight, exact int32 sums, its range over the whole
+ * tensor and NITI_Conv_Int8's shift rule forward, NITI_DeConv_Int8's for the input gradient; the weight
+ * gradient's range is taken over the layer's c_out cg 9 values only.  x / dy / out: NHWC16.  w, the int32
+ * gradient and its slabs: [c_out][9][cg] -- the OHWI16 form of a dense layer with c_in = cg, host order
+ * [c_out][cg][3][3]; niti_oihw_to_ohwi16, niti_sgd_update* and niti_sgd_combine take it as co = c_out, ci = cg,
+ * kk = 9.  The multiply-adds run on v_mfma_i32_16x16x64_i8; there is one launch for all groups, no dense GEMM
+ * over the zero blocks and no int32 activation tensor.
+ * niti_gconv_ok: 1 where the launches take (g, groups) (host only).
+ * niti_gconv_fwd / _dgrad: the two passes of niti_dwconv_fwd / _dgrad, and niti_dwconv_out's fields as there.
+ * niti_gconv_wgrad: leaves *slabs partial sums [c_out][9][cg] int32 in slab, that many elements apart;
+ *   niti_gconv_wgrad_slabs is the count (a function of g and groups alone; 0 where !niti_gconv_ok);
+ *   niti_gconv_wgrad_reduce sums them into acc with max|acc| into amax (may be NULL).
+ * NITI_INVALID_VALUE, nothing launched: a NULL operand, !niti_gconv_ok (groups < 2, c_in != c_out, channels not
+ * divisible by groups, cg not 16 / 32 / 64, k != 3, stride != 1, unequal pads or a pad above 2, an operand of
+ * 2^31 bytes or more, the niti_gconv_wgrad_slabs slabs of the weight gradient among them), pass not 0 / 1, relu with _dgrad or relu_mask with _fwd, slab_bytes too small,
+ * slabs != niti_gconv_wgrad_slabs(g, groups). */
+int niti_gconv_ok(const niti_geom* g, int groups);
+int niti_gconv_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                   const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                     const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                     size_t slab_bytes, int* slabs, void* stream);
+int niti_gconv_wgrad_slabs(const niti_geom* g, int groups);
+int niti_gconv_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                            uint32_t* amax, void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -889,6 +918,23 @@ typedef struct niti_chain_layer3 {
 } niti_chain_layer3;
 int niti_model_chain_check4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain4(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with grouped 3x3 conv layers (niti_gconv_* above).  niti_chain_layer3's ten fields, then groups:
+ * 0 or 1 is a dense layer, G >= 2 makes the layer a grouped conv of G groups, c_in = c_out = G cg.  The eight
+ * entry points above are these with groups = 1 everywhere and behave as they always did.  A grouped layer runs
+ * through the range protocol like a depthwise layer (the unfused pool, skip sum and flatten behind it; as an
+ * adding layer or a skip's source it is treated as a depthwise layer is), its weight is [c_out][cg][3][3] for
+ * niti_model_set_weight / _get_weight, and its MACs in shapes[][8]'s sense count cg, not c_in.
+ * Beside niti_model_chain_check4's rule:
+ * NITI_INVALID_VALUE (malformed): groups < 0; groups > 1 together with depthwise; c_in or c_out not divisible
+ *   by groups.
+ * NITI_NOT_SUPPORT: c_in / groups != c_out / groups, or not 16, 32 or 64; a kernel other than 3; a stride other
+ *   than 1; a grouped layer that is layer 0 or the last layer, or on the 1x1 map behind a flatten or a gpool. */
+typedef struct niti_chain_layer4 {
+    int c_out, kernel, stride, pad, relu, pool, flatten, depthwise, skip, gpool; /* as niti_chain_layer3 */
+    int groups;                                                                   /* see above */
+} niti_chain_layer4;
+int niti_model_chain_check5(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain5(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and
@@ -970,6 +1016,9 @@ int niti_model_layer_info(niti_model_t m, int layer, int info[12]);
 /* 1 where the layer is a depthwise conv (niti_chain_layer2), 0 where it is dense, -1 for a NULL handle or
  * a layer out of range */
 int niti_model_layer_depthwise(niti_model_t m, int layer);
+/* the layer's groups (niti_chain_layer4; 1 for a dense or depthwise layer), -1 for a NULL handle or a layer
+ * out of range */
+int niti_model_layer_groups(niti_model_t m, int layer);
 /* the layer's skip and gpool (niti_chain_layer3; 0 and 0 for every model not made through
  * niti_model_create_chain4); NITI_INVALID_VALUE for a NULL handle or pointer or a layer out of range */
 int niti_model_layer_skip(niti_model_t m, int layer, int* skip, int* gpool);

@@ -1,0 +1,484 @@
+// niti_grouped.hip -- grouped 3x3 conv layers (gconv_*, niti_kernels.hpp): groups = G >= 2, c_in = c_out =
+// G * cg with cg 16, 32 or 64 channels a group, stride 1, one pad 0..2 on every side.
+//
+// The layer is NITI_Conv_Int8 over the block-diagonal dense weight.  A group contracts over 9 cg terms:
+// that fits v_mfma_i32_16x16x64_i8, 16 rows x 16 columns over 64 bytes of K, four 16-byte K slots of
+// which lane l supplies slot l / 16 of row (A) or column (B) l % 16.  The accumulator, by the ISA's
+// table for the 16x16 forms: lane l holds column l % 16, rows 4 (l / 16) + r in register r = 0..3.
+//
+// Layouts.  Activations NHWC16 [n][h][w][C].  The weight, its int32 gradient and the gradient's slabs
+// are [c_out][9][cg]: the OHWI16 form of a dense layer with c_in = cg.  Nothing else exists: no
+// transposed weight, no fragment copy.
+//
+// gconv_act (forward; the input gradient is the same conv on dy with the taps reversed and pad 2 - pad).
+// A = the weights (rows: 16 output channels of the group), B = the pixels (columns: 16 consecutive
+// output pixels of a row), so a lane's accumulator registers are 4 consecutive channels of one pixel:
+// one dword of the int8 output.  Slot map, the same for A and B: slot s = tap * (cg / 16) + c16 is the
+// tap's channels 16 c16 .. 16 c16 + 15 (of the input for the forward, of dy for the input gradient);
+// MFMA number s / 4 takes it in K slot s % 4, and the slots past 9 cg / 16 are zeros in A.
+// A workgroup takes (image, group, 4 output rows, up to 4 strips of 16 columns).  LDS:
+//   xs  [c16][6 rows][16 strips + 2 columns][16 bytes]  the input rows with halo, the group's channels;
+//       a slot's 16 lanes read 256 contiguous bytes (conflict-free); outside the image: zeros, decided
+//       from row and column;
+//   wsm [slot][cg rows][16 bytes]                        the group's weights, fragment-major; for the
+//       input gradient transposed within the group on the way in (4x4 byte blocks, tr4) and the tap
+//       reversed.
+// The weight fragments stay in registers at cg 16 (3 MFMAs a tile) and 32 (2 x 5) and are read per
+// tile from LDS at cg 64 (4 x 9).  Pass 0 publishes max|acc|, pass 1 reads the range and recomputes,
+// requantising by NITI_Conv_Int8.cpp:260-307's rule chosen once per wave: no int32 tensor.
+//
+// gconv_wgrad.  Per group and tap a cg x cg product over the pixels: A = dy (rows: output channels),
+// B = x (columns: input channels), a slot = 16 consecutive pixels of one channel.  A workgroup takes
+// one group and a share of the (image, 4 output rows, 4 strips) bands; per band it writes the 4 dy
+// rows and 6 x rows into LDS pixel-major (tr4 again: [channel][row][pixel], channel pitches padded so
+// that a slot's 16 lanes read conflict-free), zeros outside the image.  K slot q of MFMA k is output
+// row q, strip k; the kx shifts of x are v_alignbyte_b32 over an aligned 16-byte read and the dword
+// behind it, the ky shifts other rows.  The waves split the 9 (cg / 16)^2 accumulator tiles:
+// cg 16: a tap row each (3 tiles, the fourth wave only loads); cg 32: one (o16, i16) pair each, 9 taps;
+// cg 64: one o16 each, 4 x 9 = 36 tiles, 144 accumulator registers.  The workgroup writes its group's
+// part of one slab; the slab count is a function of the shape alone.
+#include <algorithm>
+
+#include "niti_device.hpp"
+#include "niti_kernels.hpp"
+#include "niti_sgd.hpp"
+
+namespace niti {
+
+namespace {
+
+constexpr int GC_ROWS = 4;    // output rows of a band
+constexpr int GC_STRIPS = 4;  // 16-pixel strips of a band, at most
+constexpr int GC_MAX_SLABS = 1024;
+constexpr size_t GC_SLAB_BYTES = size_t(4) << 20;  // of all slabs, past 64 of them: the combine reads every one
+
+// 4 x 4 byte transpose: R[e] = bytes e of (A, B, C, D), A's lowest
+__device__ __forceinline__ void tr4(int A, int B, int C, int D, int (&R)[4]) {
+    const uint32_t ab_lo = __builtin_amdgcn_perm((uint32_t)B, (uint32_t)A, 0x05010400u);
+    const uint32_t ab_hi = __builtin_amdgcn_perm((uint32_t)B, (uint32_t)A, 0x07030602u);
+    const uint32_t cd_lo = __builtin_amdgcn_perm((uint32_t)D, (uint32_t)C, 0x05010400u);
+    const uint32_t cd_hi = __builtin_amdgcn_perm((uint32_t)D, (uint32_t)C, 0x07030602u);
+    R[0] = (int)__builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u);
+    R[1] = (int)__builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u);
+    R[2] = (int)__builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u);
+    R[3] = (int)__builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
+}
+
+struct GcActArgs {
+    const int8_t* x;  // [n][ih][iw][C]
+    const int8_t* w;  // [C][9][cg]
+    int8_t* out;      // [n][oh][ow][C]
+    const int8_t* relu_mask;
+    uint32_t xbytes, wbytes;
+    int ih, iw, oh, ow, C, pad, relu;
+    int bands, segs;  // row bands and column segments of an image
+    uint32_t* amax;
+    const int8_t* exp_in;
+    const int8_t* wscale;
+    int8_t* exp_out;
+};
+
+template <int CG, bool DGRAD, int PASS>
+__global__ void __launch_bounds__(256) gconv_act_kernel(GcActArgs a) {
+    constexpr int NCH = CG / 16;             // 16-channel chunks of a group
+    constexpr int NS = 9 * NCH;              // K slots
+    constexpr int NK = (NS + 3) / 4;         // MFMAs of a tile
+    constexpr int NT = NCH;                  // 16-channel output tiles
+    constexpr bool WREG = CG <= 32;          // the weight fragments in registers
+    constexpr int TR = GC_ROWS + 2, TWMAX = 16 * GC_STRIPS + 2;
+    __shared__ __attribute__((aligned(16))) int8_t xs[NCH * TR * TWMAX * 16];
+    __shared__ __attribute__((aligned(16))) int8_t wsm[NS * CG * 16];
+    __shared__ uint32_t red[4];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, q = lane >> 4;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.xbytes), rw = make_rsrc(a.w, a.wbytes);
+    uint32_t gm = 0;
+    if (PASS == 1) gm = a.amax[lane * MAX_SLOT_STRIDE];
+
+    const int grp = (int)blockIdx.y;
+    const int tiles = a.bands * a.segs;
+    const int img = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - img * tiles;
+    const int band = tile / a.segs, seg = tile - band * a.segs;
+    const int oy0 = band * GC_ROWS, s0 = seg * GC_STRIPS;
+    const int strips_all = (a.ow + 15) >> 4;
+    const int S = min(GC_STRIPS, strips_all - s0);  // this tile's strips
+    const int TW = 16 * S + 2;
+
+    // the input tile: rows oy0 - pad .. + 5, columns 16 s0 - pad .. + TW - 1, the group's channels
+    for (int e = threadIdx.x; e < TR * TW * NCH; e += 256) {
+        const int ch = e % NCH, px = e / NCH;
+        const int r = px / TW, c = px - r * TW;
+        const int iy = oy0 - a.pad + r, ix = 16 * s0 - a.pad + c;
+        const bool ok = iy >= 0 && iy < a.ih && ix >= 0 && ix < a.iw;
+        const v4i v = buf_load16(
+            rx, ok ? (uint32_t)(((img * a.ih + iy) * a.iw + ix) * a.C + grp * CG + ch * 16) : OOB);
+        *(v4i*)(xs + ((ch * TR + r) * TW + c) * 16) = v;
+    }
+    // the group's weights, fragment-major [slot][row][16]
+    if (!DGRAD) {
+        // row = output channel o, slot = (tap, 16 input channels): a 16-byte unit of w as it lies
+        for (int e = threadIdx.x; e < CG * NS; e += 256) {
+            const int o = e / NS, s = e - o * NS;
+            const v4i v = buf_load16(rw, (uint32_t)(((grp * CG + o) * NS + s) * 16));
+            *(v4i*)(wsm + (s * CG + o) * 16) = v;
+        }
+    } else {
+        // row = input channel i, slot = (reversed tap, 16 output channels): four output channels' 16-byte
+        // units of one (tap, i16) transpose into 16 dwords, one per input channel
+        for (int e = threadIdx.x; e < 9 * (CG / 4) * NCH; e += 256) {
+            const int ic = e % NCH, rest = e / NCH;
+            const int oq = rest % (CG / 4), tap = rest / (CG / 4);
+            v4i v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                v[r] = buf_load16(rw, (uint32_t)((((grp * CG + 4 * oq + r) * 9 + tap) * NCH + ic) * 16));
+            const int s = (8 - tap) * NCH + (oq >> 2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int R[4];
+                tr4(v[0][j], v[1][j], v[2][j], v[3][j], R);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) *(int*)(wsm + (s * CG + ic * 16 + 4 * j + b) * 16 + 4 * (oq & 3)) = R[b];
+            }
+        }
+    }
+    __syncthreads();
+
+    // this lane's K slots: slot 4 k + q = (tap, c16) reads the tile at (row + ky, column + kx) of plane c16
+    int xoff[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int s = 4 * k + q;
+        const int tap = s / NCH, ch = s - tap * NCH;
+        xoff[k] = s < NS ? ((ch * TR + tap / 3) * TW + tap % 3) * 16 : 0;
+    }
+    auto wfrag = [&](int t, int k) {
+        const int s = 4 * k + q;
+        return s < NS ? *(const v4i*)(wsm + (s * CG + 16 * t + col) * 16) : v4i{0, 0, 0, 0};
+    };
+    v4i wr[WREG ? NT : 1][WREG ? NK : 1];
+    if (WREG) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int k = 0; k < NK; ++k) wr[t][k] = wfrag(t, k);
+    }
+
+    int s = 2;
+    bool raw = true;
+    if (PASS == 1) {
+        const int shift = __builtin_amdgcn_readfirstlane(bitwidth_of(wave_max(gm))) - 7;
+        s = shift > 1 ? shift : 2;
+        raw = shift <= 0;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && a.exp_out != nullptr) {
+            const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
+            *a.exp_out = (int8_t)((a.exp_in ? (int)*a.exp_in : 0) + (a.wscale ? (int)*a.wscale : 0) + inc);
+        }
+    }
+
+    uint32_t m = 0;
+    // a wave's units: (row, strip) pairs of the tile
+    for (int u = wave; u < GC_ROWS * S; u += 4) {
+        const int r = u / S, sx = u - r * S;
+        const int oy = oy0 + r, ox = 16 * (s0 + sx) + col;
+        if (oy >= a.oh) break;  // (uniform: rows ascend with u)
+        const bool valid = ox < a.ow;  // a partial last strip computes masked pixels and stores nothing
+        const int8_t* xb = xs + (r * TW + 16 * sx + col) * 16;
+        v4i xf[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) xf[k] = *(const v4i*)(xb + xoff[k]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            v4i acc{0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(WREG ? wr[WREG ? t : 0][WREG ? k : 0] : wfrag(t, k), xf[k],
+                                                            acc, 0, 0, 0);
+            // acc[e]: pixel `col` of the strip, channel 16 t + 4 q + e of the group
+            if (PASS == 0) {
+                if (valid)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m = max(m, uabs32(acc[e]));
+            } else if (valid) {
+                const size_t off = (((size_t)img * a.oh + oy) * a.ow + ox) * a.C + grp * CG + 16 * t + 4 * q;
+                uint32_t mk = 0;
+                if (a.relu_mask != nullptr) mk = *(const uint32_t*)(a.relu_mask + off);
+                uint32_t o = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    int32_t v = raw ? (int32_t)(int8_t)acc[e] : psto_fast(acc[e], s);
+                    if (a.relu && v < 0) v = 0;
+                    if (a.relu_mask != nullptr && (int8_t)(mk >> (8 * e)) <= 0) v = 0;
+                    o |= ((uint32_t)v & 0xffu) << (8 * e);
+                }
+                *(uint32_t*)(a.out + off) = o;
+            }
+        }
+    }
+
+    if (PASS == 0) {
+        m = wave_max(m);
+        if (lane == 0) red[wave] = m;
+        __syncthreads();
+        if (threadIdx.x == 0) publish_max(a.amax, max(max(red[0], red[1]), max(red[2], red[3])));
+    }
+}
+
+struct GcWgArgs {
+    const int8_t* x;   // [n][h][w][C]
+    const int8_t* dy;  // [n][oh][ow][C]
+    int32_t* slab;     // [gridDim.x][C][9][cg]
+    uint32_t xbytes, dbytes;
+    int h, w, oh, ow, C, pad;
+    int bands, segs;  // row bands and column segments of an image
+    int units;        // n * bands * segs
+};
+
+template <int CG>
+__global__ void __launch_bounds__(256) gconv_wgrad_kernel(GcWgArgs a) {
+    constexpr int NCH = CG / 16;
+    constexpr int NTI = CG == 64 ? 4 : 1;  // input-channel tiles of a wave
+    constexpr int NKY = CG == 16 ? 1 : 3;  // tap rows of a wave
+    // pitches in bytes, for 4 strips: a dy row, an x row (16 more: the kx shifts read past the last strip),
+    // a channel of each (16 more: a slot's 16 lanes, one channel each, then read conflict-free)
+    constexpr int DPMAX = 16 * GC_STRIPS, XPMAX = DPMAX + 16;
+    constexpr int XROWS = GC_ROWS + 2;
+    __shared__ __attribute__((aligned(16))) int8_t dT[CG * (GC_ROWS * DPMAX + 16)];
+    __shared__ __attribute__((aligned(16))) int8_t xT[CG * (XROWS * XPMAX + 16)];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, q = lane >> 4;
+    const int grp = (int)blockIdx.y;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.xbytes), rd = make_rsrc(a.dy, a.dbytes);
+    // this wave's tiles: output channels 16 to .., input channels 16 (ti0 + i) .., tap rows ky0 + j
+    const int to = CG == 64 ? wave : CG == 32 ? wave >> 1 : 0;
+    const int ti0 = CG == 32 ? wave & 1 : 0;
+    const int ky0 = CG == 16 ? wave : 0;
+    const bool works = CG != 16 || wave < 3;
+
+    v4i acc[NTI][NKY][3];
+#pragma unroll
+    for (int i = 0; i < NTI; ++i)
+#pragma unroll
+        for (int j = 0; j < NKY; ++j)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) acc[i][j][kx] = v4i{0, 0, 0, 0};
+
+    const int strips_all = (a.ow + 15) >> 4;
+    const int per_img = a.bands * a.segs;
+    for (int unit = (int)blockIdx.x; unit < a.units; unit += (int)gridDim.x) {
+        const int img = unit / per_img, tile = unit - img * per_img;
+        const int band = tile / a.segs, seg = tile - band * a.segs;
+        const int oy0 = band * GC_ROWS, s0 = seg * GC_STRIPS;
+        const int S = min(GC_STRIPS, strips_all - s0);
+        const int DP = 16 * S, XP = DP + 16;
+        const int DCH = GC_ROWS * DP + 16, XCH = XROWS * XP + 16;
+        __syncthreads();  // (the previous band's reads are over)
+        // dy rows oy0 .. + 3, columns 16 s0 .. + DP - 1: four pixels x 16 channels -> 16 dwords of four pixels
+        for (int e = threadIdx.x; e < GC_ROWS * (DP / 4) * NCH; e += 256) {
+            const int ch = e % NCH, rest = e / NCH;
+            const int pq = rest % (DP / 4), r = rest / (DP / 4);
+            const int oy = oy0 + r;
+            v4i v[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int ox = 16 * s0 + 4 * pq + p;
+                const bool ok = oy < a.oh && ox < a.ow;
+                v[p] = buf_load16(
+                    rd, ok ? (uint32_t)(((img * a.oh + oy) * a.ow + ox) * a.C + grp * CG + ch * 16) : OOB);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int R[4];
+                tr4(v[0][j], v[1][j], v[2][j], v[3][j], R);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) *(int*)(dT + (ch * 16 + 4 * j + b) * DCH + r * DP + 4 * pq) = R[b];
+            }
+        }
+        // x rows oy0 - pad .. + 5, columns 16 s0 - pad .. + XP - 1 (position p = column + pad - 16 s0)
+        for (int e = threadIdx.x; e < XROWS * (XP / 4) * NCH; e += 256) {
+            const int ch = e % NCH, rest = e / NCH;
+            const int pq = rest % (XP / 4), r = rest / (XP / 4);
+            const int iy = oy0 - a.pad + r;
+            v4i v[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int ix = 16 * s0 - a.pad + 4 * pq + p;
+                const bool ok = iy >= 0 && iy < a.h && ix >= 0 && ix < a.w;
+                v[p] = buf_load16(
+                    rx, ok ? (uint32_t)(((img * a.h + iy) * a.w + ix) * a.C + grp * CG + ch * 16) : OOB);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int R[4];
+                tr4(v[0][j], v[1][j], v[2][j], v[3][j], R);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) *(int*)(xT + (ch * 16 + 4 * j + b) * XCH + r * XP + 4 * pq) = R[b];
+            }
+        }
+        __syncthreads();
+        if (!works) continue;
+        // MFMA k: K slot q = output row oy0 + q, strip s0 + k
+        for (int k = 0; k < S; ++k) {
+            const v4i fa = *(const v4i*)(dT + (16 * to + col) * DCH + q * DP + 16 * k);
+#pragma unroll
+            for (int i = 0; i < NTI; ++i) {
+                const int8_t* xc = xT + (16 * (ti0 + i) + col) * XCH + 16 * k;
+#pragma unroll
+                for (int j = 0; j < NKY; ++j) {
+                    const int8_t* xr = xc + (q + ky0 + j) * XP;
+                    const v4i lo = *(const v4i*)xr;
+                    const int hi = *(const int*)(xr + 16);
+                    const int d[5] = {lo[0], lo[1], lo[2], lo[3], hi};
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        v4i fb = lo;
+                        if (kx > 0)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                fb[e] = (int)__builtin_amdgcn_alignbyte((uint32_t)d[e + 1], (uint32_t)d[e], (uint32_t)kx);
+                        acc[i][j][kx] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa, fb, acc[i][j][kx], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    // acc[i][j][kx][e]: output channel 16 to + 4 q + e, input channel 16 (ti0 + i) + col, tap (ky0 + j, kx)
+    if (!works) return;
+    int32_t* sl = a.slab + (size_t)blockIdx.x * a.C * 9 * CG;
+#pragma unroll
+    for (int i = 0; i < NTI; ++i)
+#pragma unroll
+        for (int j = 0; j < NKY; ++j)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int o = grp * CG + 16 * to + 4 * q + e, tap = 3 * (ky0 + j) + kx;
+                    sl[((size_t)o * 9 + tap) * CG + 16 * (ti0 + i) + col] = acc[i][j][kx][e];
+                }
+}
+
+int gc_wgrad_plan(const ConvGeom& g, int groups) {
+    const int cg = g.c_in / groups;
+    const int64_t units = (int64_t)g.n * ((g.oh + GC_ROWS - 1) / GC_ROWS) * (((g.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS);
+    const int64_t one = (int64_t)g.c_out * 9 * cg * sizeof(int32_t);
+    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(GC_MAX_SLABS, (int64_t)GC_SLAB_BYTES / one));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, units));
+}
+
+hipError_t gc_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, const int8_t* w, uint32_t* amax,
+                  const ActOut& o, int pass, hipStream_t st) {
+    if (!gconv_ok(g, groups) || in == nullptr || w == nullptr || amax == nullptr || pass < 0 || pass > 1)
+        return hipErrorInvalidValue;
+    // the fields this launch honours: out, relu (forward), relu_mask (input gradient), the exponents
+    if (o.pool.pool_out != nullptr || o.pool.x != nullptr || o.pool.y != nullptr || o.pool.dx != nullptr ||
+        o.pool.dx_c32 != nullptr || o.out_p16 != nullptr || o.zero_cls != 0 || o.pool3.out != nullptr ||
+        o.pool3.arg != nullptr)
+        return hipErrorInvalidValue;
+    if ((dgrad && o.relu != 0) || (!dgrad && o.relu_mask != nullptr)) return hipErrorInvalidValue;
+    if (pass == 1 && o.out == nullptr) return hipErrorInvalidValue;
+    const int cg = g.c_in / groups;
+    GcActArgs a{};
+    a.x = in;
+    a.w = w;
+    a.out = o.out;
+    a.relu_mask = o.relu_mask;
+    a.C = g.c_in;
+    a.ih = dgrad ? g.oh : g.h;
+    a.iw = dgrad ? g.ow : g.w;
+    a.oh = dgrad ? g.h : g.oh;
+    a.ow = dgrad ? g.w : g.ow;
+    a.pad = dgrad ? 2 - g.pt : g.pt;
+    a.relu = o.relu;
+    a.xbytes = (uint32_t)((int64_t)g.n * a.ih * a.iw * a.C);
+    a.wbytes = (uint32_t)((int64_t)g.c_out * 9 * cg);
+    a.bands = (a.oh + GC_ROWS - 1) / GC_ROWS;
+    a.segs = ((a.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS;
+    a.amax = amax;
+    a.exp_in = o.exp_in;
+    a.wscale = o.wscale;
+    a.exp_out = o.exp_out;
+    const int64_t gx = (int64_t)g.n * a.bands * a.segs;
+    if (gx > 0x7fffffff) return hipErrorInvalidValue;
+    using Kern = void (*)(GcActArgs);
+    static const Kern tab[3][2][2] = {
+        {{gconv_act_kernel<16, false, 0>, gconv_act_kernel<16, false, 1>},
+         {gconv_act_kernel<16, true, 0>, gconv_act_kernel<16, true, 1>}},
+        {{gconv_act_kernel<32, false, 0>, gconv_act_kernel<32, false, 1>},
+         {gconv_act_kernel<32, true, 0>, gconv_act_kernel<32, true, 1>}},
+        {{gconv_act_kernel<64, false, 0>, gconv_act_kernel<64, false, 1>},
+         {gconv_act_kernel<64, true, 0>, gconv_act_kernel<64, true, 1>}}};
+    const Kern f = tab[cg == 16 ? 0 : cg == 32 ? 1 : 2][dgrad ? 1 : 0][pass];
+    hipLaunchKernelGGL(f, dim3((unsigned)gx, (unsigned)groups), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool gconv_ok(const ConvGeom& g, int groups) {
+    if (groups < 2 || groups > 65535 || g.n < 1 || g.c_in < 1 || g.c_in != g.c_out || g.c_in % groups != 0) return false;
+    const int cg = g.c_in / groups;
+    if (cg != 16 && cg != 32 && cg != 64) return false;
+    if (g.kh != 3 || g.kw != 3 || g.sh != 1 || g.sw != 1 || g.dh != 1 || g.dw != 1) return false;
+    if (g.pt < 0 || g.pt > 2 || g.pl != g.pt || g.pb != g.pt || g.pr != g.pt) return false;
+    if (g.h < 1 || g.w < 1 || g.h + 2 * g.pt < 3 || g.w + 2 * g.pt < 3) return false;
+    if (g.oh != g.h + 2 * g.pt - 2 || g.ow != g.w + 2 * g.pt - 2) return false;
+    if (g.cip != g.c_in || g.cop != g.c_out) return false;
+    // every operand below 2^31 bytes: the two maps and the slab buffer the weight gradient writes
+    const int64_t lim = (int64_t)1 << 31;
+    return (int64_t)g.n * g.h * g.w * g.cip < lim && (int64_t)g.n * g.oh * g.ow * g.cop < lim &&
+           (int64_t)gc_wgrad_plan(g, groups) * g.c_out * 9 * cg * 4 < lim;
+}
+
+hipError_t gconv_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o,
+                     int pass, hipStream_t st) {
+    return gc_act(g, groups, false, x, w, amax, o, pass, st);
+}
+
+hipError_t gconv_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                       const ActOut& o, int pass, hipStream_t st) {
+    return gc_act(g, groups, true, dy, w, amax, o, pass, st);
+}
+
+int gconv_wgrad_slabs(const ConvGeom& g, int groups) { return gconv_ok(g, groups) ? gc_wgrad_plan(g, groups) : 0; }
+
+hipError_t gconv_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                       size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer) {
+    if (!gconv_ok(g, groups) || x == nullptr || dy == nullptr || slab == nullptr) return hipErrorInvalidValue;
+    const int cg = g.c_in / groups;
+    const int ns = gc_wgrad_plan(g, groups);
+    const size_t one = (size_t)g.c_out * 9 * cg;  // elements of a slab
+    if (ns * one * sizeof(int32_t) > slab_bytes) return hipErrorInvalidValue;
+    GcWgArgs a{};
+    a.x = x;
+    a.dy = dy;
+    a.slab = slab;
+    a.xbytes = (uint32_t)((int64_t)g.n * g.h * g.w * g.cip);
+    a.dbytes = (uint32_t)((int64_t)g.n * g.oh * g.ow * g.cop);
+    a.h = g.h;
+    a.w = g.w;
+    a.oh = g.oh;
+    a.ow = g.ow;
+    a.C = g.c_in;
+    a.pad = g.pt;
+    a.bands = (g.oh + GC_ROWS - 1) / GC_ROWS;
+    a.segs = ((g.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS;
+    a.units = g.n * a.bands * a.segs;
+    using Kern = void (*)(GcWgArgs);
+    const Kern f = cg == 16 ? gconv_wgrad_kernel<16> : cg == 32 ? gconv_wgrad_kernel<32> : gconv_wgrad_kernel<64>;
+    hipLaunchKernelGGL(f, dim3((unsigned)ns, (unsigned)groups), dim3(256), 0, st, a);
+    if (slabs != nullptr) *slabs = ns;
+    if (defer != nullptr) {  // C-shaped slabs for the update launch's combine
+        defer->slab = slab;
+        defer->splits = ns;
+        defer->slab_stride = (int64_t)one;
+        defer->slab_n = (int64_t)one;
+        defer->slab_map = 0;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace niti

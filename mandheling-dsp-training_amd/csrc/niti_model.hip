@@ -274,7 +274,7 @@ struct Model final : StepDriver {
     bool fc_sgd_layer(int i) const {
         static const bool off = getenv("NITI_FC_SGD") && atoi(getenv("NITI_FC_SGD")) == 0;
         const ConvGeom& g = L[i].g;
-        return in_step && !off && !dp() && !tuning && !L[i].dw && conv_wgrad_fc_sgd_ok(g) &&
+        return in_step && !off && !dp() && !tuning && !L[i].own() && conv_wgrad_fc_sgd_ok(g) &&
                !(head_layer(i) && g.c_out <= 32 && g.cip % 32 == 0) && wgrad_p16_splits(i) == 0;
     }
     // the GEMM speculative pairs' alternates (one bit width below / above A's guess), shared by every
@@ -386,7 +386,7 @@ struct Model final : StepDriver {
     // kernels (a plan override of another tile, or a geometry the P16 kernel does not take)
     int wgrad_p16_splits(int i) const {
         const ConvGeom& g = L[i].g;
-        if (L[i].dw || !conv_wgrad_p16_ok(g)) return 0;
+        if (L[i].own() || !conv_wgrad_p16_ok(g)) return 0;
         PlanChoice c;
         if (plan_override_lookup(conv_plan_key(PLAN_WGRAD, g), &c)) return c.bm == PLAN_P16_TILE ? c.splits : 0;
         return conv_wgrad_p16_splits(g);
@@ -499,7 +499,7 @@ struct Model final : StepDriver {
     int build(int arch_, int batch_, int in_hw = 0);
     // the model of a layer list (c_in and the map sizes derived as chain_check derives them); the
     // built-in networks are build()'s own lists
-    int build_chain(int arch_, int batch_, const niti_chain_layer3* layers, int n, int in_c_, int in_hw, int rule);
+    int build_chain(int arch_, int batch_, const niti_chain_layer4* layers, int n, int in_c_, int in_hw, int rule);
     int layer_skip(int layer, int* skip, int* gpool) const override {
         if (!layer_ok(layer)) return NITI_INVALID_VALUE;
         *skip = L[layer].skip;
@@ -671,9 +671,10 @@ struct Model final : StepDriver {
 };
 
 static void add_conv(Model& m, int ci, int co, int k, int pad, int h, int relu, int pool, int flatten = 0, int dw = 0,
-                     int stride = 1, int gpool = 0, int skip = 0) {
+                     int stride = 1, int gpool = 0, int skip = 0, int groups = 1) {
     Layer l;
     l.dw = dw;
+    l.groups = groups;
     l.gpool = gpool;
     l.skip = skip;
     l.g.n = m.batch;
@@ -718,13 +719,13 @@ static int64_t chain_mul(int64_t a, int64_t b) {
 // stride 1, as the entry points that refuse any other stride always derived the shapes.
 // A gpool layer (the `4` entry points' rule) leaves a 1x1 map of its c_out channels; a skip is checked for
 // form against its source's output shape.
-static int chain_shapes(const niti_chain_layer3* layers, int n, int in_c, int in_hw, bool strided,
+static int chain_shapes(const niti_chain_layer4* layers, int n, int in_c, int in_hw, bool strided,
                         std::vector<std::array<int, 8>>* out) {
     if (layers == nullptr || n < 1 || in_c < 1 || in_hw < 1) return NITI_INVALID_VALUE;
     int64_t c = in_c, h = in_hw;
     std::vector<std::array<int64_t, 2>> outs;  // per layer: the channels and map size the next layer sees
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer3& l = layers[i];
+        const niti_chain_layer4& l = layers[i];
         if (l.depthwise != 0 && l.depthwise != 1) return NITI_INVALID_VALUE;
         if (l.gpool != 0 && l.gpool != 1) return NITI_INVALID_VALUE;
         if (l.skip < 0 || l.skip > i) return NITI_INVALID_VALUE;
@@ -732,6 +733,9 @@ static int chain_shapes(const niti_chain_layer3* layers, int n, int in_c, int in
         if (l.depthwise && l.c_out != 0 && l.c_out != c) return NITI_INVALID_VALUE;
         const int64_t co = l.depthwise ? c : l.c_out;
         if (co < 1 || l.kernel < 1 || l.pad < 0 || l.pad >= l.kernel) return NITI_INVALID_VALUE;
+        // a grouped layer (niti_chain_layer4): both channel counts split into its groups
+        if (l.groups < 0 || (l.groups > 1 && (l.depthwise || c % l.groups != 0 || co % l.groups != 0)))
+            return NITI_INVALID_VALUE;
         if (strided && l.stride < 1) return NITI_INVALID_VALUE;
         if (h + 2 * (int64_t)l.pad < l.kernel) return NITI_INVALID_VALUE;
         const int64_t oh = (h + 2 * (int64_t)l.pad - l.kernel) / (strided ? l.stride : 1) + 1;
@@ -751,7 +755,7 @@ static int chain_shapes(const niti_chain_layer3* layers, int n, int in_c, int in
     return NITI_NO_ERROR;
 }
 
-int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule) {
+int chain_check(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule) {
     std::vector<std::array<int, 8>> sh;
     const bool strided = rule >= CHAIN_RULE_STRIDED;
     if (batch < 1) return NITI_INVALID_VALUE;
@@ -759,7 +763,7 @@ int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int
     // (the update launch takes SGD_MAX_JOBS layers; the `4` entry points' lists update in groups of them)
     if (n > (rule >= CHAIN_RULE_WIDE ? NITI_CHAIN_MAX_LAYERS : SGD_MAX_JOBS)) return NITI_NOT_SUPPORT;
     for (int i = 0; i < n; ++i) {
-        const niti_chain_layer3& l = layers[i];
+        const niti_chain_layer4& l = layers[i];
         const std::array<int, 8>& s = sh[i];
         // the previous layer leaves a 1x1 map (a flatten or a global pool)
         const bool on_1x1 = i > 0 && (layers[i - 1].flatten || layers[i - 1].gpool);
@@ -771,13 +775,21 @@ int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int
         // map; the kernels take 3x3 and 5x5
         if (l.depthwise && (i == 0 || i == n - 1 || on_1x1 || (l.kernel != 3 && l.kernel != 5)))
             return NITI_NOT_SUPPORT;
+        // a grouped layer: as a depthwise layer, and what the kernels take (gconv_ok): 3x3, stride 1, equal group
+        // widths of 16, 32 or 64 channels
+        if (l.groups > 1) {
+            const int cg = s[0] / l.groups;
+            if (i == 0 || i == n - 1 || on_1x1 || l.kernel != 3 || l.stride != 1 || s[1] / l.groups != cg ||
+                (cg != 16 && cg != 32 && cg != 64))
+                return NITI_NOT_SUPPORT;
+        }
         if (on_1x1 && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
         if (l.skip != 0) {
             // a residual sum: not the logits; neither end on the 1x1 map behind a flatten or a global pool;
             // a source hands on its map as it is; the spans [i - skip, i] of two sums share at most an
             // endpoint (so no layer is the source of two)
             const int s = i - l.skip;
-            const niti_chain_layer3& sl = layers[s];
+            const niti_chain_layer4& sl = layers[s];
             if (i == n - 1 || on_1x1 || (s > 0 && (layers[s - 1].flatten || layers[s - 1].gpool))) return NITI_NOT_SUPPORT;
             if (sl.pool || sl.flatten || sl.gpool) return NITI_NOT_SUPPORT;
             for (int j = s + 1; j < i; ++j)
@@ -810,7 +822,7 @@ int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int
 
 int Model::build(int arch_, int batch_, int in_hw) {
     // {c_out, kernel, stride, pad, relu, pool, flatten, depthwise, skip, gpool}
-    std::vector<niti_chain_layer3> t;
+    std::vector<niti_chain_layer4> t;
     int ic = 3, hw = 32;
     if (arch_ == NITI_ARCH_LENET) {  // mnistTrain.cpp:131-181
         ic = 1;
@@ -836,7 +848,7 @@ int Model::build(int arch_, int batch_, int in_hw) {
     return build_chain(arch_, batch_, t.data(), (int)t.size(), ic, hw, CHAIN_RULE_PLAIN);
 }
 
-int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, int nlayers, int in_c_, int in_hw,
+int Model::build_chain(int arch_, int batch_, const niti_chain_layer4* layers, int nlayers, int in_c_, int in_hw,
                        int rule) {
     arch = arch_;
     batch = batch_;
@@ -847,9 +859,10 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
     in_h = in_w = in_hw;
     for (int i = 0; i < nlayers; ++i)
         add_conv(*this, sh[i][0], sh[i][1], sh[i][2], sh[i][3], sh[i][4], layers[i].relu != 0, layers[i].pool != 0,
-                 layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1, layers[i].gpool, layers[i].skip);
+                 layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1, layers[i].gpool, layers[i].skip,
+                 layers[i].groups > 1 ? layers[i].groups : 1);
     for (const Layer& l : L)
-        if (l.dw && !dwconv2_ok(l.g)) return NITI_NOT_SUPPORT;
+        if ((l.dw && !dwconv2_ok(l.g)) || (l.groups > 1 && !gconv_ok(l.g, l.groups))) return NITI_NOT_SUPPORT;
     for (int i = 0; i < nlayers; ++i)
         if (L[i].skip) {
             L[i - L[i].skip].src_of = i;
@@ -905,7 +918,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         const size_t out_px = (size_t)n * g.oh * g.ow;
         l.w = (int8_t*)ws.alloc(l.w_elems());
         l.ws_dev = (int8_t*)ws.alloc(16);
-        l.wT = (int8_t*)ws.alloc((size_t)g.c_in * g.kh * g.kw * g.cop);
+        if (!l.own()) l.wT = (int8_t*)ws.alloc((size_t)g.c_in * g.kh * g.kw * g.cop);
         l.r = (int8_t*)ws.alloc(out_px * g.cop);
         if (l.pool) {
             l.p = (int8_t*)ws.alloc((size_t)n * l.ph * l.pw * g.cop);
@@ -938,7 +951,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         l.g8 = (int8_t*)ws.alloc(l.w_elems());
         l.exp = (int8_t*)ws.alloc(16);
         l.gspec = (uint32_t*)ws.alloc(2 * GEMM_SPEC_SLOT_WORDS * 4);
-        if (!l.w || !l.ws_dev || !l.wT || !l.r || !l.dy || !l.dwacc || !l.g8 || !l.exp || !l.gspec)
+        if (!l.w || !l.ws_dev || (!l.wT && !l.own()) || !l.r || !l.dy || !l.dwacc || !l.g8 || !l.exp || !l.gspec)
             return NITI_OUT_OF_MEMORY;
         if (hipMemset(l.gspec, 0, 2 * GEMM_SPEC_SLOT_WORDS * 4) != hipSuccess) return NITI_NO_EXECUTION;
         if (hipMemset(l.w, 0, l.w_elems()) != hipSuccess) return NITI_NO_EXECUTION;
@@ -952,12 +965,13 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
         // the head's, or the GEMM path's fused-rescale launches (STRAT_FUSED)
         l.bar = (uint32_t*)ws.alloc(ROWCONV_BAR_WORDS * 4);
         if (!l.bar || hipMemset(l.bar, 0, ROWCONV_BAR_WORDS * 4) != hipSuccess) return NITI_OUT_OF_MEMORY;
-        if (l.dw) {  // its weight gradient's slabs: the layer's own until the update (the deferred combine)
-            l.slab16_bytes = (size_t)dwconv_wgrad_slabs(g) * l.w_elems() * sizeof(int32_t);
+        if (l.own()) {  // its weight gradient's slabs: the layer's own until the update (the deferred combine)
+            const int ns = l.dw ? dwconv_wgrad_slabs(g) : gconv_wgrad_slabs(g, l.groups);
+            l.slab16_bytes = (size_t)ns * l.w_elems() * sizeof(int32_t);
             l.slab16 = (int32_t*)ws.alloc(l.slab16_bytes);
             if (!l.slab16) return NITI_OUT_OF_MEMORY;
         }
-        if (i > 0 && !l.dw && conv_dgrad_subpix_ok(g)) {
+        if (i > 0 && !l.own() && conv_dgrad_subpix_ok(g)) {
             l.subw = (int8_t*)ws.alloc(conv_dgrad_subpix_bytes(g));
             if (!l.subw) return NITI_OUT_OF_MEMORY;
         }
@@ -970,7 +984,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
             if (!l.ey) return NITI_OUT_OF_MEMORY;
             sum_tmp_bytes = std::max(sum_tmp_bytes, out_px * g.cop);
         }
-        if (!l.kp && !l.dw && !l.skip && rowconv_ok(g)) {
+        if (!l.kp && !l.own() && !l.skip && rowconv_ok(g)) {
             l.rc = 1;
             l.wf = (int8_t*)ws.alloc(rowconv_wf_bytes(g.c_out, g.c_in));
             l.xc32 = (int8_t*)ws.alloc((size_t)n * round_up(g.c_in, 32) * g.h * g.w);
@@ -993,7 +1007,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer3* layers, i
                 if (hipMemset(l.wft, 0, rowconv_wf_bytes(g.c_in, g.c_out)) != hipSuccess) return NITI_NO_EXECUTION;
             }
         }
-        if (!l.dw && conv_wgrad_p16_ok(g)) {
+        if (!l.own() && conv_wgrad_p16_ok(g)) {
             slab_w_bytes = std::max(slab_w_bytes, conv_wgrad_p16_workspace(g, 8));
             xp16[i] = (int8_t*)ws.alloc((size_t)n * g.h * g.w * g.cip);
             l.slab16_bytes = conv_wgrad_p16_workspace(g, 8);
@@ -1259,11 +1273,12 @@ int Model::fwd_conv_layer(int i, hipStream_t st) {
     o.exp_in = i == 0 ? exp0 : L[i - 1].oexp();
     o.wscale = l.ws_dev;
     o.exp_out = l.skip ? l.ey : l.exp;
-    if (l.dw) {
-        // depthwise: range launch, [all-reduce MAX], recompute-and-requantise launch; the unfused pool / flatten
+    if (l.own()) {
+        // depthwise / grouped: range launch, [all-reduce MAX], recompute-and-requantise launch; the unfused pool / flatten
         const auto none = [](const ActOut&, auto) { return hipErrorNotSupported; };
         const int rc = gemm_ranged(false, false, o, rng(i, 0), l.bar, l.epoch, st, none, none, [&](const ActOut& ao, int ph) {
-            return dwconv_fwd(g, l.in, l.w, rng(i, 0), ao, ph - 1, st);
+            return l.dw ? dwconv_fwd(g, l.in, l.w, rng(i, 0), ao, ph - 1, st)
+                        : gconv_fwd(g, l.groups, l.in, l.w, rng(i, 0), ao, ph - 1, st);
         });
         if (rc != NITI_NO_ERROR) return rc;
         probe(i, 0, false, st);
@@ -1317,14 +1332,17 @@ int Model::wgrad_layer(int i, hipStream_t st) {
     }
     l.fc_sgd = fc_sgd_layer(i);
     SgdJob& defer_job = L[i].defer;
-    if (l.dw) {
-        // depthwise: one launch leaves C-shaped slabs; single device they go to the update launch's
+    if (l.own()) {
+        // depthwise / grouped: one launch leaves C-shaped slabs; single device they go to the update launch's
         // combine, else (data parallel, a capture, the combine off) they are reduced here with the range
         probe(i, 2, true, st);
         int slabs = 0;
         defer_job = SgdJob{};
         SgdJob d{};
-        DTRY(dwconv_wgrad(g, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
+        if (l.dw)
+            DTRY(dwconv_wgrad(g, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
+        else
+            DTRY(gconv_wgrad(g, l.groups, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
         if (defer_combine())
             defer_job = d;
         else
@@ -1513,10 +1531,10 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     // (a depthwise layer: its own two launches below, the fall-back's plain outputs around them)
     // (a strided layer on its sub-pixel class GEMMs: plain outputs too -- their requantise takes no others)
     const bool sub = l.subw != nullptr;
-    const bool spec = !l.dw && conv_dgrad_spec_ok(g);
+    const bool spec = !l.own() && conv_dgrad_spec_ok(g);
     // dy of layer i - 1 is rewritten here; its P16 copy comes along where the requant pass can
     // write it (the plain and the fused pool-gradient passes), else wgrad_layer converts it
-    int8_t* p16_out = !l.dw && !sub && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
+    int8_t* p16_out = !l.own() && !sub && !spec && fuse_dp16 && wgrad_p16_splits(i - 1) > 0 ? dp16[i - 1] : nullptr;
     dp16_valid[i - 1] = 0;
     // the previous layer is a skip's source: the input gradient unmasked into sum_tmp, the sum after it
     const bool src = pv.src_of >= 0;
@@ -1532,7 +1550,7 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     } else if (pv.to_1x1()) {
         o.out = pv.dflat;
     } else if (pv.pool) {
-        fuse = !l.dw && !sub && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
+        fuse = !l.own() && !sub && !spec && pg.oh % 2 == 0 && pg.ow % 2 == 0 && conv_dgrad_phase2_separate(g, slab_bytes);
         if (fuse) {  // pool gradient + relu gradient ride along the requant pass
             o.out = nullptr;
             o.pool.x = pv.r;
@@ -1552,11 +1570,11 @@ int Model::dgrad_layer(int i, hipStream_t st) {
     } else {
         o.relu_mask = pv.relu ? pv.r : nullptr;
         o.out = pv.dy;
-        if (!l.dw && conv_dgrad_phase2_separate(g, slab_bytes)) o.out_p16 = p16_out;
+        if (!l.own() && conv_dgrad_phase2_separate(g, slab_bytes)) o.out_p16 = p16_out;
     }
     // (the pair: no int32 tensor while the bit width holds)
     const int rc = gemm_ranged(
-        !l.dw && !dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr, spec, o, rng(i, 1), l.bar, l.epoch, st,
+        !l.own() && !dp && !capturing && !fuse && o.out_p16 == nullptr && o.out != nullptr, spec, o, rng(i, 1), l.bar, l.epoch, st,
         [&](const ActOut& ao, const FusedBar& fb) { return conv_dgrad_fused(g, l.dy, l.wT, ao, fb, st); },
         [&](const ActOut& ao, int ph) {
             int8_t* alt = conv_dgrad_spec_alt_bytes(g) <= gspec_alt_bytes ? gspec_alt : nullptr;
@@ -1564,6 +1582,7 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         },
         [&](const ActOut& ao, int ph) {
             if (l.dw) return dwconv_dgrad(g, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
+            if (l.groups > 1) return gconv_dgrad(g, l.groups, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
             return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st, l.subw)
                            : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st, l.subw);
         });
@@ -1617,7 +1636,7 @@ int Model::autotune(hipStream_t st, int reps) {
     for (int i = 0; i < nl && rc == NITI_NO_ERROR; ++i) {
         for (int op : {PLAN_FWD, PLAN_WGRAD, PLAN_DGRAD}) {
             if (op == PLAN_DGRAD && i == 0) continue;
-            if (L[i].dw) continue;  // no GEMM plan: the depthwise launches
+            if (L[i].own()) continue;  // no GEMM plan: the depthwise / grouped launches
             if (op == PLAN_FWD && rowconv_layer(i)) continue;  // no GEMM plan: the register-fed forward
             if (op == PLAN_DGRAD && rowconv_dgrad_layer(i)) continue;
             if ((op == PLAN_FWD && head_layer(i)) || (op == PLAN_DGRAD && head_dgrad_ok(i))) continue;
@@ -2068,7 +2087,7 @@ int Model::copy_weights_from(StepDriver& other, hipStream_t st) {
         const ConvGeom &a = L[i].g, &b = src.L[i].g;
         if (a.c_in != b.c_in || a.c_out != b.c_out || a.kh != b.kh || a.kw != b.kw || a.cip != b.cip || a.cop != b.cop ||
             L[i].kp != src.L[i].kp || L[i].relu != src.L[i].relu || L[i].pool != src.L[i].pool ||
-            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].og.sh != src.L[i].og.sh ||
+            L[i].flatten != src.L[i].flatten || L[i].dw != src.L[i].dw || L[i].groups != src.L[i].groups || L[i].og.sh != src.L[i].og.sh ||
             L[i].gpool != src.L[i].gpool || L[i].skip != src.L[i].skip)
             return NITI_INVALID_VALUE;
     }
@@ -2091,7 +2110,7 @@ int Model::run_phase(int layer, int phase, hipStream_t st) {
 
 int Model::plan_info(int layer, int phase, int info[4]) {
     if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
-    if (L[layer].dw) return NITI_NOT_SUPPORT;  // no GEMM plan
+    if (L[layer].own()) return NITI_NOT_SUPPORT;  // no GEMM plan
     const int op = plan_op(phase);
     PlanChoice c = conv_plan_query(op, L[layer].g, phase != 2, ws_bytes_for(op));
     if (phase == 2 && wgrad_p16_splits(layer) > 0) {
@@ -2106,7 +2125,7 @@ int Model::plan_info(int layer, int phase, int info[4]) {
 // over the weight-gradient slab it grows here
 int Model::plan_set(int layer, int phase, const int plan[4]) {
     if (!layer_ok(layer) || phase < 0 || phase > 2) return NITI_INVALID_VALUE;
-    if (L[layer].dw) return NITI_NOT_SUPPORT;  // no GEMM plan
+    if (L[layer].own()) return NITI_NOT_SUPPORT;  // no GEMM plan
     const int op = plan_op(phase);
     const ConvGeom& g = L[layer].g;
     const PlanKey k = conv_plan_key(op, g);
@@ -2207,7 +2226,7 @@ int Model::get_tap(int layer, int which, int8_t* host, size_t bytes, hipStream_t
     return rc;
 }
 
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch,
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc, int rule) {
     *rc = chain_check(layers, n, in_c, in_hw, batch, nullptr, rule);  // (nothing allocated on a refusal)
     if (*rc != NITI_NO_ERROR) return nullptr;

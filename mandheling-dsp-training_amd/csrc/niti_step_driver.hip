@@ -354,9 +354,9 @@ int StepDriver::plan_out(const PlanChoice& c, int info[4]) {
 SgdJob StepDriver::sgd_job(int i, bool wT_by_update) const {
     const ParamLayer& p = *P[i];
     const ConvGeom& g = p.g;
-    // (a depthwise layer: the c_out = 1 form of its weight, no transposed copy)
-    SgdJob j{p.dwacc, p.wg_amax, -(1 + i), p.w_co(), g.c_in, g.kh * g.kw, g.cip, p.dw ? 16 : g.cop, p.w,
-             wT_by_update && !p.dw ? p.wT : nullptr, keep_grads ? p.g8 : nullptr};
+    // (a depthwise layer: the c_out = 1 form of its weight; a grouped layer: the c_in = cg form; no transposed copy)
+    SgdJob j{p.dwacc, p.wg_amax, -(1 + i), p.w_co(), p.w_ci(), g.kh * g.kw, p.w_cip(), p.dw ? 16 : g.cop, p.w,
+             wT_by_update && !p.own() ? p.wT : nullptr, keep_grads ? p.g8 : nullptr};
     j.wf = p.rc ? p.wf : nullptr;
     j.wft = p.rcd ? p.wft : nullptr;
     if (p.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights
@@ -383,7 +383,7 @@ int StepDriver::layer_info(int layer, int info[12]) const {
 
 int StepDriver::refresh_copies(ParamLayer& p, hipStream_t st) {
     const ConvGeom& g = p.g;
-    if (p.wT && !p.dw) DTRY(ohwi16_to_ihwo16(p.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, p.wT, st));
+    if (p.wT && !p.own()) DTRY(ohwi16_to_ihwo16(p.w, g.c_out, g.c_in, g.kh * g.kw, g.cip, g.cop, p.wT, st));
     if (p.subw) DTRY(conv_dgrad_subpix_weights(g, p.wT, p.subw, st));
     if (p.rc) DTRY(weights_to_wf(p.w, g.c_out, g.c_in, g.cip, false, p.wf, st));
     if (p.rcd) DTRY(weights_to_wf(p.w, g.c_out, g.c_in, g.cip, true, p.wft, st));
@@ -400,13 +400,14 @@ int StepDriver::set_weight(int layer, const int8_t* w_host, int wscale) {
         cols_from_oihw(p.og, w_host, colw.data(), p.kp);
         w_host = colw.data();
     }
-    // (a depthwise layer's [C][1][k][k] is the flat order of the c_out = 1 layer's OIHW)
-    const size_t n = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+    // (a depthwise layer's [C][1][k][k] is the flat order of the c_out = 1 layer's OIHW; a grouped layer's
+    // [c_out][cg][3][3] is the c_in = cg layer's)
+    const size_t n = (size_t)p.w_co() * p.w_ci() * g.kh * g.kw;
     int8_t* tmp = nullptr;
     if (hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
     int rc = NITI_NO_ERROR;
     if (hipMemcpy(tmp, w_host, n, hipMemcpyHostToDevice) != hipSuccess ||
-        oihw_to_ohwi16(tmp, p.w_co(), g.c_in, g.kh * g.kw, g.cip, p.w, nullptr) != hipSuccess ||
+        oihw_to_ohwi16(tmp, p.w_co(), p.w_ci(), g.kh * g.kw, p.w_cip(), p.w, nullptr) != hipSuccess ||
         hipMemset(p.ws_dev, (int)(int8_t)wscale, 1) != hipSuccess)
         rc = NITI_NO_EXECUTION;
     if (rc == NITI_NO_ERROR) rc = refresh_copies(p, nullptr);
@@ -420,12 +421,12 @@ int StepDriver::get_weight(int layer, int8_t* w_host) {
     if (!layer_ok(layer) || !w_host) return NITI_INVALID_VALUE;
     const ParamLayer& p = *P[layer];
     const ConvGeom& g = p.g;
-    const size_t n = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+    const size_t n = (size_t)p.w_co() * p.w_ci() * g.kh * g.kw;
     int8_t* tmp = nullptr;
     if (hipDeviceSynchronize() != hipSuccess || hipMalloc(&tmp, n) != hipSuccess) return NITI_OUT_OF_MEMORY;
     int rc = NITI_NO_ERROR;
     std::vector<int8_t> colw(p.kp ? n : 0);
-    if (ohwi16_to_oihw(p.w, p.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr) != hipSuccess ||
+    if (ohwi16_to_oihw(p.w, p.w_co(), p.w_ci(), g.kh * g.kw, p.w_cip(), tmp, nullptr) != hipSuccess ||
         hipMemcpy(p.kp ? colw.data() : w_host, tmp, n, hipMemcpyDeviceToHost) != hipSuccess)
         rc = NITI_NO_EXECUTION;
     if (rc == NITI_NO_ERROR && p.kp) oihw_from_cols(p.og, colw.data(), w_host, p.kp);
@@ -463,7 +464,7 @@ int StepDriver::tap_out(const ParamLayer& p, int which, const int8_t* src, int8_
     if (which == 0 || which == 2)
         need = (size_t)batch * g.c_out * g.oh * g.ow;
     else if (which == 1 && g8_written)
-        need = (size_t)p.w_co() * g.c_in * g.kh * g.kw;
+        need = (size_t)p.w_co() * p.w_ci() * g.kh * g.kw;
     else
         return NITI_INVALID_VALUE;
     // (an im2col layer's gradient goes out in the network's own shape)
@@ -471,7 +472,7 @@ int StepDriver::tap_out(const ParamLayer& p, int which, const int8_t* src, int8_
     if (bytes < out_need) return NITI_INVALID_VALUE;
     int8_t* tmp = nullptr;
     if (hipMalloc(&tmp, need) != hipSuccess) return NITI_OUT_OF_MEMORY;
-    hipError_t e = which == 1 ? ohwi16_to_oihw(src, p.w_co(), g.c_in, g.kh * g.kw, g.cip, tmp, nullptr)
+    hipError_t e = which == 1 ? ohwi16_to_oihw(src, p.w_co(), p.w_ci(), g.kh * g.kw, p.w_cip(), tmp, nullptr)
                               : nhwc16_to_nchw(src, batch, g.c_out, g.oh * g.ow, g.cop, tmp, nullptr);
     if (which == 1 && p.kp) {
         std::vector<int8_t> colw(need);

@@ -48,6 +48,10 @@ struct ParamLayer {
     // slabs are [k * k][cip], the OHWI16 form of a c_out = 1, c_in = C layer (w_co), [C][1][k][k] on
     // the host, and there is no wT
     int dw = 0;
+    // a grouped 3x3 conv of `groups` >= 2 groups (chain driver; niti_grouped.hip): g.c_in == g.c_out == groups * cg;
+    // w, dwacc, g8 and the slabs are [c_out][9][cg], the OHWI16 form of a dense layer with c_in = cg (w_ci, w_cip),
+    // [c_out][cg][3][3] on the host, and there is no wT
+    int groups = 1;
     int kp = 0;  // the im2col column pitch of a first layer that runs over its im2col (0: not one)
     int8_t wscale = 0;
     int8_t* w = nullptr;       // OHWI16
@@ -71,9 +75,15 @@ struct ParamLayer {
     int32_t* wslab = nullptr;
     size_t wslab_bytes = 0;
     SgdJob defer{};
+    // a layer with launches of its own (depthwise, grouped): no GEMM plan, row-kernel, P16, wT, subw or fc-sgd route
+    bool own() const { return dw != 0 || groups > 1; }
     int w_co() const { return dw ? 1 : g.c_out; }  // output channels as the weight layouts count them
-    int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * g.cip; }
-    int64_t macs() const { return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in) * og.kh * og.kw; }
+    int w_ci() const { return g.c_in / groups; }   // input channels so, and their padded count
+    int w_cip() const { return groups > 1 ? g.c_in / groups : g.cip; }
+    int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * w_cip(); }
+    int64_t macs() const {
+        return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in / groups) * og.kh * og.kw;
+    }
 };
 
 struct StepDriver {
@@ -281,6 +291,7 @@ struct StepDriver {
     int layer_info(int layer, int info[12]) const;
     // 1 a depthwise layer, 0 a dense one, -1 out of range
     int layer_depthwise(int layer) const { return layer_ok(layer) ? P[layer]->dw : -1; }
+    int layer_groups(int layer) const { return layer_ok(layer) ? P[layer]->groups : -1; }
     // every derived copy p has, from w, on st: wT, subw, and the row kernels' wf / wft
     int refresh_copies(ParamLayer& p, hipStream_t st);
     // w from the host's OIHW (an im2col layer: through its columns), the scale, the derived copies
@@ -342,12 +353,13 @@ int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_laye
 // a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch.  rule: which
 // entry points' rule holds -- CHAIN_RULE_PLAIN refuses stride != 1, CHAIN_RULE_STRIDED honours the layers'
 // strides (niti_model_create_chain3), CHAIN_RULE_WIDE also takes gpool and up to NITI_CHAIN_MAX_LAYERS
-// layers (niti_model_create_chain4); below CHAIN_RULE_WIDE the lists carry skip = gpool = 0
+// layers (niti_model_create_chain4 / 5; a list's grouped layers come with niti_chain_layer4's groups); below
+// CHAIN_RULE_WIDE the lists carry skip = gpool = 0
 enum { CHAIN_RULE_PLAIN = 0, CHAIN_RULE_STRIDED = 1, CHAIN_RULE_WIDE = 2 };
-std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch,
+std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc, int rule);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
-int chain_check(const niti_chain_layer3* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule);
+int chain_check(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, int shapes[][8], int rule);
 
 // a first layer's weights as its im2col GEMM holds them: [co][kp], column (ky * KW + kx) * C_in + c,
 // zero padded to the column pitch kp <-> OIHW

@@ -128,6 +128,12 @@ class ChainLayer3(C.Structure):
                                        "skip", "gpool")]
 
 
+class ChainLayer4(C.Structure):
+    """niti_chain_layer4: niti_chain_layer3's fields and `groups`."""
+    _fields_ = [(n, C.c_int) for n in ("c_out", "kernel", "stride", "pad", "relu", "pool", "flatten", "depthwise",
+                                       "skip", "gpool", "groups")]
+
+
 class DwconvOut(C.Structure):
     """niti_dwconv_out: the outputs and options of niti_dwconv_fwd / niti_dwconv_dgrad."""
     _fields_ = [(n, C.c_void_p) for n in ("out", "relu_mask", "exp_in", "wscale", "exp_out")] + [("relu", C.c_int)]
@@ -253,6 +259,12 @@ def lib():
         "niti_dwconv_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
         "niti_dwconv_wgrad_slabs": (ci, [C.POINTER(Geom)]),
         "niti_dwconv_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
+        "niti_gconv_ok": (ci, [C.POINTER(Geom), ci]),
+        "niti_gconv_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_gconv_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_gconv_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
+        "niti_gconv_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
+        "niti_gconv_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
         "niti_dwconv2_ok": (ci, [C.POINTER(Geom)]),
         "niti_dwconv2_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
         "niti_dwconv2_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
@@ -307,6 +319,9 @@ def lib():
         "niti_model_create_chain3": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         "niti_model_chain_check4": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain4": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_chain_check5": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain5": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_layer_groups": (ci, [vp, ci]),
         "niti_model_layer_skip": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
         # (spec: a ResnetSpec, passed untyped)
         "niti_model_resnet_check": (ci, [vp, ci, C.POINTER(ci), vp]),

@@ -1,9 +1,10 @@
-"""User-defined chain networks: a model from a layer list (niti_chain_layer3, include/niti_hip.h).
+"""User-defined chain networks: a model from a layer list (niti_chain_layer4, include/niti_hip.h).
 
 A spec is a list of layers, each a dict with the keys c_out, kernel and optionally pad, relu,
 pool, flatten, depthwise (default 0), stride (default 1; 1 or 2), skip (default 0), gpool (default 0: 1 sums
-the layer's map into a 1x1 map, the global sum pool), or a tuple (c_out, kernel, pad, relu,
-pool, flatten, depthwise, stride, skip, gpool) whose tail may be left out.  The input channels and map size of every layer are derived;
+the layer's map into a 1x1 map, the global sum pool), groups (default 1; G >= 2 makes a 3x3 layer a grouped conv
+of G groups, weights [c_out, c_in / G, 3, 3]), or a tuple (c_out, kernel, pad, relu, pool, flatten, depthwise,
+stride, skip, gpool, groups) whose tail may be left out.  The input channels and map size of every layer are derived;
 the last layer's c_out is the class count.  A depthwise layer has its input's channels: its c_out
 may be 0 or, in a dict, left out.
 """
@@ -14,16 +15,17 @@ import ctypes as C
 from . import _lib as L
 from ._lib import check
 
-_KEYS = ("c_out", "kernel", "pad", "relu", "pool", "flatten", "depthwise", "stride", "skip", "gpool")
+_KEYS = ("c_out", "kernel", "pad", "relu", "pool", "flatten", "depthwise", "stride", "skip", "gpool", "groups")
 _OLD_MAX_LAYERS = 24  # what the entry points before niti_model_chain_check4 / _create_chain4 take
-_DEFAULT = {"stride": 1}
+_DEFAULT = {"stride": 1, "groups": 1}
 
 
 def normalize_spec(spec) -> list:
     """The spec as a list of dicts of plain ints (what snapshots store and compare): the keys c_out,
     kernel, pad, relu, pool, flatten and, only for a list that has a depthwise layer, depthwise, only
     for a list that has a layer of stride other than 1, stride, only for a list that has a skip, skip, only
-    for a list that has a global pool, gpool -- so the record of a list without one is what it always was.  A depthwise layer's c_out of 0 becomes
+    for a list that has a global pool, gpool, only for a list that has a grouped layer, groups -- so the record of
+    a list without one is what it always was.  A depthwise layer's c_out of 0 becomes
     the previous layer's c_out where that is the layer's input (not after a flatten, not layer 0:
     lists the check refuses anyway)."""
     out = []
@@ -37,11 +39,13 @@ def normalize_spec(spec) -> list:
         else:
             l = tuple(l)
             if not 2 <= len(l) <= len(_KEYS):
-                raise ValueError(
-                    f"layer {i}: a tuple (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, gpool]), got {l!r}")
+                raise ValueError(f"layer {i}: a tuple (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, "
+                                 f"gpool, groups]), got {l!r}")
             d = {k: int(l[j]) if j < len(l) else _DEFAULT.get(k, 0) for j, k in enumerate(_KEYS)}
         for k in ("relu", "pool", "flatten"):
             d[k] = 1 if d[k] else 0
+        if d["groups"] == 0:  # (0 or 1: a dense layer)
+            d["groups"] = 1
         if d["stride"] < 1:
             raise ValueError(f"layer {i}: stride {d['stride']}")
         if d["depthwise"] == 1 and d["c_out"] == 0 and out and not out[-1]["flatten"]:
@@ -59,7 +63,16 @@ def normalize_spec(spec) -> list:
         if all(d[k] == 0 for d in out):
             for d in out:
                 del d[k]
+    if all(d["groups"] == 1 for d in out):
+        for d in out:
+            del d["groups"]
     return out
+
+
+def grouped(spec) -> bool:
+    """A normalised spec that has a grouped layer: it goes through the `5` entry points
+    (niti_model_chain_check5 / _create_chain5), every other list where it always went."""
+    return any("groups" in d for d in spec)
 
 
 def strided(spec) -> bool:
@@ -77,6 +90,8 @@ def wide(spec) -> bool:
 def entry_points(spec):
     """(check, create) -- the C entry points a normalised spec goes through."""
     lib = L.lib()
+    if grouped(spec):
+        return lib.niti_model_chain_check5, lib.niti_model_create_chain5
     if wide(spec):
         return lib.niti_model_chain_check4, lib.niti_model_create_chain4
     if strided(spec):
@@ -85,15 +100,19 @@ def entry_points(spec):
 
 
 def to_c(spec):
-    """(niti_chain_layer2 array -- niti_chain_layer3 for a wide() spec --, count) of a normalised spec."""
-    w = wide(spec)
-    arr = ((L.ChainLayer3 if w else L.ChainLayer2) * len(spec))()
+    """(niti_chain_layer2 array -- niti_chain_layer3 for a wide() spec, niti_chain_layer4 for a grouped() one --,
+    count) of a normalised spec."""
+    gr = grouped(spec)
+    w = wide(spec) or gr
+    arr = ((L.ChainLayer4 if gr else L.ChainLayer3 if w else L.ChainLayer2) * len(spec))()
     for a, d in zip(arr, spec):
         a.c_out, a.kernel, a.stride, a.pad = d["c_out"], d["kernel"], d.get("stride", 1), d["pad"]
         a.relu, a.pool, a.flatten = d["relu"], d["pool"], d["flatten"]
         a.depthwise = d.get("depthwise", 0)
         if w:
             a.skip, a.gpool = d.get("skip", 0), d.get("gpool", 0)
+        if gr:
+            a.groups = d["groups"]
     return arr, len(spec)
 
 
@@ -101,8 +120,8 @@ def chain_layers(spec, in_c: int, in_hw: int) -> list:
     """The derived layer list of a spec over in_c x in_hw x in_hw inputs, as dicts with the keys
     ci, co, k, pad, h, relu, pool, flatten and, for a list that has a depthwise layer, depthwise, for a
     list that has a strided layer, stride, for a list that has a skip, skip, for a list that has a global
-    pool, gpool (host only: niti_model_chain_check2, _check3 for a list with a strided layer, _check4 for a
-    wide() list).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
+    pool, gpool, for a list that has a grouped layer, groups (host only: niti_model_chain_check2, _check3 for a
+    list with a strided layer, _check4 for a wide() list, _check5 for a grouped() one).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
     the library does not run."""
     spec = normalize_spec(spec)
     arr, n = to_c(spec)
@@ -119,7 +138,7 @@ def chain_layers(spec, in_c: int, in_hw: int) -> list:
             o["depthwise"] = d["depthwise"]
         if "stride" in d:
             o["stride"] = d["stride"]
-        for k in ("skip", "gpool"):
+        for k in ("skip", "gpool", "groups"):
             if k in d:
                 o[k] = d[k]
     return out

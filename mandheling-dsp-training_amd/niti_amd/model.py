@@ -41,12 +41,13 @@ class NitiModel:
     def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
         """A model of the caller's own chain network (niti_model_create_chain2; _create_chain3 for a list
         with a strided layer, _create_chain4 for one with a skip, a global pool or more than 24 layers): spec is a
-        list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, gpool]) or tuples in
+        list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, gpool, groups]) or tuples in
         that order, over in_c x in_hw x in_hw inputs; the last layer's c_out is the
         class count.  A depthwise layer (3x3 or 5x5, c_out 0 or its input's channels) has weights
         [C, 1, k, k]; stride (1 or 2) is a dense or depthwise layer's own; skip = d adds the final output of
         the layer d places back to the layer's conv output, ahead of its relu; gpool = 1 sums the layer's map
-        into a 1x1 map; such a list may have up to 64 layers.  ValueError for a
+        into a 1x1 map; such a list may have up to 64 layers; groups = G >= 2 makes a 3x3 stride-1 layer a
+        grouped conv (weights [c_out, c_in / G, 3, 3], group width 16, 32 or 64; _create_chain5).  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
         from .chain import entry_points, normalize_spec, to_c
@@ -63,6 +64,8 @@ class NitiModel:
         m._adopt(h, L.ARCH_CHAIN, batch)
         for i, (d, l) in enumerate(zip(spec, m.layers)):  # (a depthwise layer's c_out as derived, whatever normalize_spec could tell)
             d["c_out"] = l["c_out"]
+            if "groups" in d:  # (reported for the lists that use it: niti_model_layer_groups)
+                l["groups"] = m._lib.niti_model_layer_groups(h, i)
             if "skip" in d or "gpool" in d:  # (reported for the lists that use them: niti_model_layer_skip)
                 sk, gp = C.c_int(), C.c_int()
                 check(m._lib.niti_model_layer_skip(h, i, C.byref(sk), C.byref(gp)), "layer_skip")
@@ -115,6 +118,8 @@ class NitiModel:
         l = self.layers[i]
         if l["depthwise"]:  # (NN.cpp:1118-1125: {C, 1, kh, kw} with group = C)
             return (l["c_out"], 1, l["kh"], l["kw"])
+        if l.get("groups", 1) > 1:  # (the framework convention: {c_out, c_in / groups, kh, kw})
+            return (l["c_out"], l["c_in"] // l["groups"], l["kh"], l["kw"])
         return (l["c_out"], l["c_in"], l["kh"], l["kw"])
 
     def set_weight(self, i, w: np.ndarray, wscale: int):
@@ -447,12 +452,12 @@ class NitiModel:
     def plans(self):
         """{(layer, phase): (bm, bn, splits, strategy)}; phase 0 fwd / 1 input grad / 2 weight grad,
         strategy 0 store / 1 recompute / 2 split-K / 3 the speculative pair / 4 fused: one launch with the
-        rescale behind an in-kernel grid barrier (forward / input gradient).  A depthwise layer has
-        no GEMM plan and no entry."""
+        rescale behind an in-kernel grid barrier (forward / input gradient).  A depthwise or grouped layer
+        has no GEMM plan and no entry."""
         out = {}
         for i in range(len(self.layers)):
             for ph in (0, 1, 2):
-                if (ph == 1 and i == 0) or self.layers[i]["depthwise"]:
+                if (ph == 1 and i == 0) or self.layers[i]["depthwise"] or self.layers[i].get("groups", 1) > 1:
                     continue
                 out[(i, ph)] = self.plan(i, ph)
         return out

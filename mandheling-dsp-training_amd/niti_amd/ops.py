@@ -766,6 +766,66 @@ def dwconv2_wgrad_reduce(g, slab, amax=None, stream=None):
     return _dwconv_wgrad_reduce("dwconv2", g, slab, amax, stream)
 
 
+# Grouped 3x3 conv layers (niti_gconv_*): the dwconv_* signatures with `groups` behind g.
+def gconv_ok(g, groups) -> bool:
+    """Whether the grouped launches take (g, groups) (niti_gconv_ok; host only): groups >= 2, c_in == c_out ==
+    groups * cg with cg 16, 32 or 64, a 3x3 kernel, stride 1, one pad 0..2 on every side, operands below 2^31
+    bytes."""
+    return bool(L.lib().niti_gconv_ok(C.byref(g), int(groups)))
+
+
+def gconv_weight(w, stream=None):
+    """A grouped layer's weights [c_out, cg, 3, 3] int8 (device) in their device layout [c_out][9][cg]: the OHWI16
+    form of a dense layer with c_in = cg."""
+    return oihw_to_ohwi16(w.contiguous(), stream=stream)
+
+
+def gconv_fwd(g, groups, x16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
+              exp_out=None, stream=None):
+    """One pass of a grouped layer's forward (niti_gconv_fwd) on x NHWC16 [n][h][w][C] and w16 (gconv_weight):
+    the two passes of dwconv_fwd."""
+    fn = lambda gp, *a: L.lib().niti_gconv_fwd(gp, int(groups), *a)  # noqa: E731
+    return _dwconv_act(fn, "gconv_fwd", g, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), out, relu, relu_mask,
+                       exp_in, wscale, exp_out, stream)
+
+
+def gconv_dgrad(g, groups, dy16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None,
+                wscale=None, exp_out=None, stream=None):
+    """The same for its input gradient (niti_gconv_dgrad): dy NHWC16 [n][oh][ow][C] -> [n][h][w][C], from the
+    same w16."""
+    fn = lambda gp, *a: L.lib().niti_gconv_dgrad(gp, int(groups), *a)  # noqa: E731
+    return _dwconv_act(fn, "gconv_dgrad", g, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), out, relu, relu_mask,
+                       exp_in, wscale, exp_out, stream)
+
+
+def gconv_wgrad_slabs(g, groups) -> int:
+    """The partial slabs niti_gconv_wgrad leaves for (g, groups) (0 where the launches do not take them)."""
+    return int(L.lib().niti_gconv_wgrad_slabs(C.byref(g), int(groups)))
+
+
+def gconv_wgrad(g, groups, x16, dy16, slab=None, stream=None):
+    """A grouped layer's weight gradient as partial sums (niti_gconv_wgrad): int32 [slabs][c_out * 9 * cg], for
+    sgd_combine, sgd_update_many_bits' slab or gconv_wgrad_reduce."""
+    if slab is None:
+        cg = g.c_in // max(int(groups), 1)
+        slab = torch.full((max(gconv_wgrad_slabs(g, groups), 1), g.c_out * 9 * cg), 0x5A5A5A5A, dtype=torch.int32,
+                          device=x16.device)
+    wrote = C.c_int(-1)
+    check(L.lib().niti_gconv_wgrad(C.byref(g), int(groups), _ptr(x16), _ptr(dy16), _ptr(slab), slab.numel() * 4,
+                                   C.byref(wrote), _stream(stream)), "gconv_wgrad")
+    assert wrote.value == slab.shape[0]
+    return slab
+
+
+def gconv_wgrad_reduce(g, groups, slab, amax=None, stream=None):
+    """The slabs summed into acc int32 [c_out][3][3][cg] with max|acc| into amax (zeroed by the caller; may be
+    None), by the reduce launch the training step uses where the update launch does not combine."""
+    acc = torch.full((g.c_out, 3, 3, g.c_in // max(int(groups), 1)), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
+    check(L.lib().niti_gconv_wgrad_reduce(C.byref(g), int(groups), _ptr(slab), slab.shape[0], _ptr(acc), _ptr(amax),
+                                          _stream(stream)), "gconv_wgrad_reduce")
+    return acc
+
+
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
     """Exponent-aligned int32 sum of two int8 tensors (niti_resnet.hip) -> (z int32, ez int8 [1])."""
     assert a.shape == b.shape and a.dtype == b.dtype == torch.int8
