@@ -667,6 +667,25 @@ int niti_gconv_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8
 int niti_gconv_wgrad_slabs(const niti_geom* g, int groups);
 int niti_gconv_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
                             uint32_t* amax, void* stream);
+/* The same six at stride 1 or 2 (stride_h == stride_w; this library's extension): kernel 3, one pad 0..2 on every
+ * side, c_in = c_out = G cg with cg 16, 32 or 64, oh = (h + 2 pad - 3) / stride + 1 (floor; odd and even maps),
+ * the same for ow.  Layouts, the two passes, shift rules, exponents, slabs and their combine are niti_gconv_*'s.
+ * At stride 1 these are the launches above.  At stride 2 the input gradient of pixel (y, x) sums
+ * dy((y + pad - ky) / 2, (x + pad - kx) / 2) w(ky, kx) over the taps with both numerators even -- four parity
+ * classes of 4, 2, 2 and 1 taps, each its own contraction, no zero-stuffed dy; a row or column of dx that no
+ * output reads (h + 2 pad - 3 odd) is written as zeros.
+ * NITI_INVALID_VALUE, nothing launched: niti_gconv_*'s list with "stride != 1" replaced by: unequal strides, a
+ * stride above 2, dilation, oh / ow that disagree with the rule.  niti_gconv_* keep refusing stride 2. */
+int niti_gconv2_ok(const niti_geom* g, int groups);
+int niti_gconv2_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                    const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv2_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                      const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv2_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                      size_t slab_bytes, int* slabs, void* stream);
+int niti_gconv2_wgrad_slabs(const niti_geom* g, int groups);
+int niti_gconv2_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                             uint32_t* amax, void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -935,6 +954,11 @@ typedef struct niti_chain_layer4 {
 } niti_chain_layer4;
 int niti_model_chain_check5(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain5(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with a grouped layer at stride 1 or 2 (niti_gconv2_* above; oh = (h + 2 pad - 3) / 2 + 1): every other
+ * refusal of niti_model_chain_check5 stands, and the ten entry points above keep refusing a grouped stride-2
+ * layer with NITI_NOT_SUPPORT. */
+int niti_model_chain_check6(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain6(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and

@@ -332,13 +332,17 @@ int dwconv_wgrad_slabs(const ConvGeom& g);
 hipError_t dwconv_wgrad(const ConvGeom& g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
                         int* slabs, hipStream_t st, SgdJob* defer = nullptr);
 // ---- grouped 3x3 conv layers (niti_grouped.hip) -------------------------------------------------
-// groups >= 2, c_in == c_out == groups * cg with cg 16, 32 or 64, a 3x3 kernel, stride 1, one pad 0..2 on every
-// side: NITI_Conv_Int8 over the block-diagonal dense weight, on v_mfma_i32_16x16x64_i8.  x / dy NHWC16; w, the
+// groups >= 2, c_in == c_out == groups * cg with cg 16, 32 or 64, a 3x3 kernel, stride 1 or 2, one pad 0..2 on
+// every side: NITI_Conv_Int8 over the block-diagonal dense weight, on v_mfma_i32_16x16x64_i8.  x / dy NHWC16; w, the
 // int32 gradient and its slabs [c_out][9][cg] (the OHWI16 form of a dense layer with c_in = cg: SgdJob
-// co = c_out, ci = cip = cg, kk = 9).  gconv_ok: the accepted set, every operand below 2^31 bytes.
+// co = c_out, ci = cip = cg, kk = 9).  gconv_ok: the stride-1 set, every operand below 2^31 bytes: what
+// niti_gconv_* admit.
 bool gconv_ok(const ConvGeom& g, int groups);
+// the same with stride 2 (both ways) admitted beside stride 1, oh = (h + 2 pad - 3) / stride + 1: what the
+// launches below take (niti_gconv2_*).  At stride 2 the input gradient runs one contraction per parity class.
+bool gconv2_ok(const ConvGeom& g, int groups);
 // the two-pass protocol and the ActOut fields of dwconv_fwd / dwconv_dgrad; hipErrorInvalidValue, nothing
-// launched: !gconv_ok, a null operand, a field this launch does not honour
+// launched: !gconv2_ok, a null operand, a field this launch does not honour
 hipError_t gconv_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o,
                      int pass, hipStream_t st);
 // the input gradient reads the same w, transposed within the group on its way into LDS

@@ -775,11 +775,12 @@ int chain_check(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int
         // map; the kernels take 3x3 and 5x5
         if (l.depthwise && (i == 0 || i == n - 1 || on_1x1 || (l.kernel != 3 && l.kernel != 5)))
             return NITI_NOT_SUPPORT;
-        // a grouped layer: as a depthwise layer, and what the kernels take (gconv_ok): 3x3, stride 1, equal group
-        // widths of 16, 32 or 64 channels
+        // a grouped layer: as a depthwise layer, and what the kernels take (gconv2_ok): 3x3, stride 1 (the `6`
+        // entry points' rule: or 2), equal group widths of 16, 32 or 64 channels
         if (l.groups > 1) {
             const int cg = s[0] / l.groups;
-            if (i == 0 || i == n - 1 || on_1x1 || l.kernel != 3 || l.stride != 1 || s[1] / l.groups != cg ||
+            if (i == 0 || i == n - 1 || on_1x1 || l.kernel != 3 ||
+                (l.stride != 1 && (rule < CHAIN_RULE_GROUPED2 || l.stride != 2)) || s[1] / l.groups != cg ||
                 (cg != 16 && cg != 32 && cg != 64))
                 return NITI_NOT_SUPPORT;
         }
@@ -862,7 +863,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer4* layers, i
                  layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1, layers[i].gpool, layers[i].skip,
                  layers[i].groups > 1 ? layers[i].groups : 1);
     for (const Layer& l : L)
-        if ((l.dw && !dwconv2_ok(l.g)) || (l.groups > 1 && !gconv_ok(l.g, l.groups))) return NITI_NOT_SUPPORT;
+        if ((l.dw && !dwconv2_ok(l.g)) || (l.groups > 1 && !gconv2_ok(l.g, l.groups))) return NITI_NOT_SUPPORT;
     for (int i = 0; i < nlayers; ++i)
         if (L[i].skip) {
             L[i - L[i].skip].src_of = i;

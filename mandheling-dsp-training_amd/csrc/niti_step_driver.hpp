@@ -355,7 +355,8 @@ int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_laye
 // strides (niti_model_create_chain3), CHAIN_RULE_WIDE also takes gpool and up to NITI_CHAIN_MAX_LAYERS
 // layers (niti_model_create_chain4 / 5; a list's grouped layers come with niti_chain_layer4's groups); below
 // CHAIN_RULE_WIDE the lists carry skip = gpool = 0
-enum { CHAIN_RULE_PLAIN = 0, CHAIN_RULE_STRIDED = 1, CHAIN_RULE_WIDE = 2 };
+// CHAIN_RULE_GROUPED2 (niti_model_create_chain6): WIDE, and a grouped layer may have stride 2
+enum { CHAIN_RULE_PLAIN = 0, CHAIN_RULE_STRIDED = 1, CHAIN_RULE_WIDE = 2, CHAIN_RULE_GROUPED2 = 3 };
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc, int rule);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`

@@ -87,9 +87,20 @@ def wide(spec) -> bool:
     return any("skip" in d or "gpool" in d for d in spec) or len(spec) > _OLD_MAX_LAYERS
 
 
-def entry_points(spec):
-    """(check, create) -- the C entry points a normalised spec goes through."""
+def level_of(spec, level):
+    """The entry-point level a normalised spec is routed by: None (the routing above, which refuses a grouped layer
+    of stride 2) or, for level=6 and a grouped() spec, 6 (niti_model_chain_check6 / _create_chain6, which take
+    one).  ValueError for any other level."""
+    if level is not None and int(level) != 6:
+        raise ValueError(f"level {level!r}: None or 6")
+    return 6 if level is not None and grouped(spec) else None
+
+
+def entry_points(spec, level=None):
+    """(check, create) -- the C entry points a normalised spec goes through (level: level_of)."""
     lib = L.lib()
+    if level_of(spec, level) == 6:
+        return lib.niti_model_chain_check6, lib.niti_model_create_chain6
     if grouped(spec):
         return lib.niti_model_chain_check5, lib.niti_model_create_chain5
     if wide(spec):
@@ -116,17 +127,18 @@ def to_c(spec):
     return arr, len(spec)
 
 
-def chain_layers(spec, in_c: int, in_hw: int) -> list:
+def chain_layers(spec, in_c: int, in_hw: int, level=None) -> list:
     """The derived layer list of a spec over in_c x in_hw x in_hw inputs, as dicts with the keys
     ci, co, k, pad, h, relu, pool, flatten and, for a list that has a depthwise layer, depthwise, for a
     list that has a strided layer, stride, for a list that has a skip, skip, for a list that has a global
     pool, gpool, for a list that has a grouped layer, groups (host only: niti_model_chain_check2, _check3 for a
-    list with a strided layer, _check4 for a wide() list, _check5 for a grouped() one).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
+    list with a strided layer, _check4 for a wide() list, _check5 for a grouped() one, _check6 for that one with
+    level=6: a grouped layer may then have stride 2).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
     the library does not run."""
     spec = normalize_spec(spec)
     arr, n = to_c(spec)
     shapes = ((C.c_int * 8) * n)()
-    fn = entry_points(spec)[0]
+    fn = entry_points(spec, level)[0]
     code = fn(arr, n, int(in_c), int(in_hw), shapes)
     if code == L.INVALID_VALUE:
         raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input: {spec}")

@@ -26,10 +26,14 @@ from safetensors.numpy import load_file, save_file
 FORMAT = "niti-int8-params-v1"
 
 
-def chain_record(spec, in_c: int, in_hw: int) -> dict:
-    """What a chain model's snapshot stores about its network (compared as a whole on load)."""
+def chain_record(spec, in_c: int, in_hw: int, level=None) -> dict:
+    """What a chain model's snapshot stores about its network (compared as a whole on load).  level: the
+    entry-point level of a model made with from_chain(level=6), recorded only then."""
     from .chain import normalize_spec
-    return {"spec": normalize_spec(spec), "in_c": int(in_c), "in_hw": int(in_hw)}
+    rec = {"spec": normalize_spec(spec), "in_c": int(in_c), "in_hw": int(in_hw)}
+    if level is not None:
+        rec["level"] = int(level)
+    return rec
 
 
 def resnet_record(spec, in_hw: int) -> dict:
@@ -84,7 +88,7 @@ def load_chain(path: str):
         return None
     try:
         rec = json.loads(meta["chain"])
-        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"])
+        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"], rec.get("level"))
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f"{path}: malformed chain record ({e!r})") from None
 

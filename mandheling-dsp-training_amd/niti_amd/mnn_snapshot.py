@@ -264,7 +264,7 @@ def chain_of(meta: dict):
         return None
     from .checkpoint import chain_record
     try:
-        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"])
+        return chain_record(rec["spec"], rec["in_c"], rec["in_hw"], rec.get("level"))
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f"malformed chain record in the side-car ({e!r})") from None
 

@@ -27,6 +27,7 @@ class NitiModel:
         self._h = h
         self.arch, self.batch = arch, batch
         self.chain = None  # from_chain: the normalised layer list
+        self.chain_level = None  # from_chain(level=6) of a list with a grouped layer: 6
         self.resnet = None  # from_resnet: the normalised stage list
         self._wscale = {}
         self.layers = []
@@ -38,7 +39,7 @@ class NitiModel:
             self.layers[-1]["depthwise"] = 1 if self._lib.niti_model_layer_depthwise(h, i) == 1 else 0
 
     @classmethod
-    def from_chain(cls, spec, in_c: int, in_hw: int, batch: int) -> "NitiModel":
+    def from_chain(cls, spec, in_c: int, in_hw: int, batch: int, level=None) -> "NitiModel":
         """A model of the caller's own chain network (niti_model_create_chain2; _create_chain3 for a list
         with a strided layer, _create_chain4 for one with a skip, a global pool or more than 24 layers): spec is a
         list of dicts (c_out, kernel[, pad, relu, pool, flatten, depthwise, stride, skip, gpool, groups]) or tuples in
@@ -47,16 +48,18 @@ class NitiModel:
         [C, 1, k, k]; stride (1 or 2) is a dense or depthwise layer's own; skip = d adds the final output of
         the layer d places back to the layer's conv output, ahead of its relu; gpool = 1 sums the layer's map
         into a 1x1 map; such a list may have up to 64 layers; groups = G >= 2 makes a 3x3 stride-1 layer a
-        grouped conv (weights [c_out, c_in / G, 3, 3], group width 16, 32 or 64; _create_chain5).  ValueError for a
+        grouped conv (weights [c_out, c_in / G, 3, 3], group width 16, 32 or 64; _create_chain5); level=6 sends
+        a list with a grouped layer through _create_chain6, where that layer may have stride 2 (the default keeps
+        refusing it; snapshots of such a model record the level).  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
-        from .chain import entry_points, normalize_spec, to_c
+        from .chain import entry_points, level_of, normalize_spec, to_c
         spec = normalize_spec(spec)
         arr, n = to_c(spec)
         m = cls.__new__(cls)
         m._lib = L.lib()
         h = C.c_void_p()
-        create = entry_points(spec)[1]
+        create = entry_points(spec, level)[1]
         code = create(arr, n, int(in_c), int(in_hw), int(batch), C.byref(h))
         if code == L.INVALID_VALUE:
             raise ValueError(f"malformed layer list for a {in_c} x {in_hw} x {in_hw} input at batch {batch}: {spec}")
@@ -73,6 +76,7 @@ class NitiModel:
                     if k in d:
                         l[k] = v
         m.chain, m.in_c, m.in_hw = spec, int(in_c), int(in_hw)
+        m.chain_level = level_of(spec, level)
         return m
 
     @classmethod
@@ -103,7 +107,7 @@ class NitiModel:
 
     def _chain_record(self):
         from .checkpoint import chain_record
-        return None if self.chain is None else chain_record(self.chain, self.in_c, self.in_hw)
+        return None if self.chain is None else chain_record(self.chain, self.in_c, self.in_hw, self.chain_level)
 
     def init_weights(self, seed: int):
         """Every layer's weights and scale from the reference's initialiser (niti_amd.init.xavier_int8),

@@ -780,22 +780,43 @@ def gconv_weight(w, stream=None):
     return oihw_to_ohwi16(w.contiguous(), stream=stream)
 
 
-def gconv_fwd(g, groups, x16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None, wscale=None,
-              exp_out=None, stream=None):
+def _gconv_act(pre, kind, g, groups, a16, w16, amax, pass_, shape, kw):
+    fn = lambda gp, *a: getattr(L.lib(), f"niti_{pre}_{kind}")(gp, int(groups), *a)  # noqa: E731
+    return _dwconv_act(fn, f"{pre}_{kind}", g, a16, w16, amax, pass_, shape, kw.pop("out", None), kw.pop("relu", False),
+                       kw.pop("relu_mask", None), kw.pop("exp_in", None), kw.pop("wscale", None),
+                       kw.pop("exp_out", None), kw.pop("stream", None), **kw)
+
+
+def _gconv_wgrad(pre, g, groups, x16, dy16, slab, stream):
+    lib = L.lib()
+    if slab is None:
+        cg = g.c_in // max(int(groups), 1)
+        count = int(getattr(lib, f"niti_{pre}_wgrad_slabs")(C.byref(g), int(groups)))
+        slab = torch.full((max(count, 1), g.c_out * 9 * cg), 0x5A5A5A5A, dtype=torch.int32, device=x16.device)
+    wrote = C.c_int(-1)
+    check(getattr(lib, f"niti_{pre}_wgrad")(C.byref(g), int(groups), _ptr(x16), _ptr(dy16), _ptr(slab),
+                                            slab.numel() * 4, C.byref(wrote), _stream(stream)), f"{pre}_wgrad")
+    assert wrote.value == slab.shape[0]
+    return slab
+
+
+def _gconv_wgrad_reduce(pre, g, groups, slab, amax, stream):
+    acc = torch.full((g.c_out, 3, 3, g.c_in // max(int(groups), 1)), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
+    check(getattr(L.lib(), f"niti_{pre}_wgrad_reduce")(C.byref(g), int(groups), _ptr(slab), slab.shape[0], _ptr(acc),
+                                                       _ptr(amax), _stream(stream)), f"{pre}_wgrad_reduce")
+    return acc
+
+
+def gconv_fwd(g, groups, x16, w16, amax, pass_, **kw):
     """One pass of a grouped layer's forward (niti_gconv_fwd) on x NHWC16 [n][h][w][C] and w16 (gconv_weight):
-    the two passes of dwconv_fwd."""
-    fn = lambda gp, *a: L.lib().niti_gconv_fwd(gp, int(groups), *a)  # noqa: E731
-    return _dwconv_act(fn, "gconv_fwd", g, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), out, relu, relu_mask,
-                       exp_in, wscale, exp_out, stream)
+    the two passes of dwconv_fwd, and its keywords (out, relu, relu_mask, exp_in, wscale, exp_out, stream)."""
+    return _gconv_act("gconv", "fwd", g, groups, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), kw)
 
 
-def gconv_dgrad(g, groups, dy16, w16, amax, pass_, *, out=None, relu=False, relu_mask=None, exp_in=None,
-                wscale=None, exp_out=None, stream=None):
+def gconv_dgrad(g, groups, dy16, w16, amax, pass_, **kw):
     """The same for its input gradient (niti_gconv_dgrad): dy NHWC16 [n][oh][ow][C] -> [n][h][w][C], from the
     same w16."""
-    fn = lambda gp, *a: L.lib().niti_gconv_dgrad(gp, int(groups), *a)  # noqa: E731
-    return _dwconv_act(fn, "gconv_dgrad", g, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), out, relu, relu_mask,
-                       exp_in, wscale, exp_out, stream)
+    return _gconv_act("gconv", "dgrad", g, groups, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), kw)
 
 
 def gconv_wgrad_slabs(g, groups) -> int:
@@ -806,24 +827,47 @@ def gconv_wgrad_slabs(g, groups) -> int:
 def gconv_wgrad(g, groups, x16, dy16, slab=None, stream=None):
     """A grouped layer's weight gradient as partial sums (niti_gconv_wgrad): int32 [slabs][c_out * 9 * cg], for
     sgd_combine, sgd_update_many_bits' slab or gconv_wgrad_reduce."""
-    if slab is None:
-        cg = g.c_in // max(int(groups), 1)
-        slab = torch.full((max(gconv_wgrad_slabs(g, groups), 1), g.c_out * 9 * cg), 0x5A5A5A5A, dtype=torch.int32,
-                          device=x16.device)
-    wrote = C.c_int(-1)
-    check(L.lib().niti_gconv_wgrad(C.byref(g), int(groups), _ptr(x16), _ptr(dy16), _ptr(slab), slab.numel() * 4,
-                                   C.byref(wrote), _stream(stream)), "gconv_wgrad")
-    assert wrote.value == slab.shape[0]
-    return slab
+    return _gconv_wgrad("gconv", g, groups, x16, dy16, slab, stream)
 
 
 def gconv_wgrad_reduce(g, groups, slab, amax=None, stream=None):
     """The slabs summed into acc int32 [c_out][3][3][cg] with max|acc| into amax (zeroed by the caller; may be
     None), by the reduce launch the training step uses where the update launch does not combine."""
-    acc = torch.full((g.c_out, 3, 3, g.c_in // max(int(groups), 1)), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
-    check(L.lib().niti_gconv_wgrad_reduce(C.byref(g), int(groups), _ptr(slab), slab.shape[0], _ptr(acc), _ptr(amax),
-                                          _stream(stream)), "gconv_wgrad_reduce")
-    return acc
+    return _gconv_wgrad_reduce("gconv", g, groups, slab, amax, stream)
+
+
+# The same six at stride 1 or 2 (niti_gconv2_*; g = geom(..., stride=2) with oh = (h + 2 pad - 3) // 2 + 1).  At
+# stride 1 they are the launches above.
+def gconv2_ok(g, groups) -> bool:
+    """Whether the strided grouped launches take (g, groups) (niti_gconv2_ok; host only): gconv_ok's rule with
+    stride 2 (both ways) admitted beside stride 1."""
+    return bool(L.lib().niti_gconv2_ok(C.byref(g), int(groups)))
+
+
+def gconv2_fwd(g, groups, x16, w16, amax, pass_, **kw):
+    """gconv_fwd at stride 1 or 2 (niti_gconv2_fwd)."""
+    return _gconv_act("gconv2", "fwd", g, groups, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), kw)
+
+
+def gconv2_dgrad(g, groups, dy16, w16, amax, pass_, **kw):
+    """gconv_dgrad at stride 1 or 2 (niti_gconv2_dgrad): at stride 2 every input pixel sums the taps its parity
+    admits, one contraction per parity class."""
+    return _gconv_act("gconv2", "dgrad", g, groups, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), kw)
+
+
+def gconv2_wgrad_slabs(g, groups) -> int:
+    """The partial slabs niti_gconv2_wgrad leaves for (g, groups) (0 where the launches do not take them)."""
+    return int(L.lib().niti_gconv2_wgrad_slabs(C.byref(g), int(groups)))
+
+
+def gconv2_wgrad(g, groups, x16, dy16, slab=None, stream=None):
+    """gconv_wgrad at stride 1 or 2 (niti_gconv2_wgrad)."""
+    return _gconv_wgrad("gconv2", g, groups, x16, dy16, slab, stream)
+
+
+def gconv2_wgrad_reduce(g, groups, slab, amax=None, stream=None):
+    """gconv_wgrad_reduce at stride 1 or 2 (niti_gconv2_wgrad_reduce)."""
+    return _gconv_wgrad_reduce("gconv2", g, groups, slab, amax, stream)
 
 
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
