@@ -686,6 +686,24 @@ int niti_gconv2_wgrad(const niti_geom* g, int groups, const int8_t* x, const int
 int niti_gconv2_wgrad_slabs(const niti_geom* g, int groups);
 int niti_gconv2_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
                              uint32_t* amax, void* stream);
+/* The same six at group widths 4 and 8 (this library's extension; ResNeXt 32x4d's first stages, the small RegNets):
+ * c_in = c_out = G cg with cg 4 or 8 and c_in a multiple of 16, stride 1 or 2 as niti_gconv2_*.  The kernels are
+ * their own, on v_mfma_i32_4x4x4_16b_i8 (sixteen 4x4x4 blocks an issue: a block is a group at cg 4, half of one at
+ * cg 8).  w (niti_oihw_to_ohwi16 of [c_out][cg][3][3] with ci = cg, cip = 16), the int32 gradient and the slabs are
+ * [c_out][9][16] with entries cg..15 zero -- the weight-gradient launch writes those zeros -- so the update and
+ * combine launches take them as a dense layer's with ci = cg, cip = 16.  Everything else is niti_gconv2_*'s.
+ * NITI_INVALID_VALUE, nothing launched: niti_gconv2_*'s list with "cg other than 16, 32 or 64" replaced by: cg other
+ * than 4 or 8, c_in not a multiple of 16.  niti_gconv_* / niti_gconv2_* keep refusing these widths. */
+int niti_gconv_narrow_ok(const niti_geom* g, int groups);
+int niti_gconv_narrow_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                          const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_narrow_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                            const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_narrow_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                            size_t slab_bytes, int* slabs, void* stream);
+int niti_gconv_narrow_wgrad_slabs(const niti_geom* g, int groups);
+int niti_gconv_narrow_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                                   uint32_t* amax, void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -959,6 +977,11 @@ int niti_model_create_chain5(const niti_chain_layer4* layers, int n, int in_c, i
  * layer with NITI_NOT_SUPPORT. */
 int niti_model_chain_check6(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain6(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with group widths 4 and 8 admitted (niti_gconv_narrow_* above; the layer's weight is [c_out][cg][3][3] on
+ * the host as for any grouped layer): every other refusal of niti_model_chain_check6 stands, and the twelve entry
+ * points above keep refusing such a layer with NITI_NOT_SUPPORT. */
+int niti_model_chain_check7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and

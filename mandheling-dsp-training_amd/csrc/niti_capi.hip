@@ -946,6 +946,45 @@ int niti_gconv2_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab
     return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
 }
 
+// group widths 4 and 8 (gconv_narrow_ok; niti_grouped_narrow.hip): weights, gradient and slabs [c_out][9][16]
+static bool gcn_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
+    return g != nullptr && to_geom(g, r) && niti::gconv_narrow_ok(*r, groups);
+}
+int niti_gconv_narrow_ok(const niti_geom* g, int groups) {
+    niti::ConvGeom r;
+    return gcn_geom(g, groups, &r) ? 1 : 0;
+}
+int niti_gconv_narrow_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                          const niti_dwconv_out* o, int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!gcn_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::gconv_narrow_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_gconv_narrow_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                            const niti_dwconv_out* o, int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!gcn_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::gconv_narrow_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_gconv_narrow_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                            size_t slab_bytes, int* slabs, void* stream) {
+    niti::ConvGeom r;
+    if (!gcn_geom(g, groups, &r)) return NITI_INVALID_VALUE;
+    return code(niti::gconv_narrow_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
+}
+int niti_gconv_narrow_wgrad_slabs(const niti_geom* g, int groups) {
+    niti::ConvGeom r;
+    return gcn_geom(g, groups, &r) ? niti::gconv_narrow_wgrad_slabs(r, groups) : 0;
+}
+int niti_gconv_narrow_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                                   uint32_t* amax, void* stream) {
+    niti::ConvGeom r;
+    if (!gcn_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_narrow_wgrad_slabs(r, groups))
+        return NITI_INVALID_VALUE;
+    const int64_t n = (int64_t)r.c_out * 9 * 16;
+    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
+}
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

@@ -41,6 +41,7 @@
 #include <algorithm>
 
 #include "niti_device.hpp"
+#include "niti_grouped.hpp"
 #include "niti_kernels.hpp"
 #include "niti_sgd.hpp"
 
@@ -50,35 +51,6 @@ namespace {
 
 constexpr int GC_ROWS = 4;    // output rows of a band
 constexpr int GC_STRIPS = 4;  // 16-pixel strips of a band, at most
-constexpr int GC_MAX_SLABS = 1024;
-constexpr size_t GC_SLAB_BYTES = size_t(4) << 20;  // of all slabs, past 64 of them: the combine reads every one
-
-// 4 x 4 byte transpose: R[e] = bytes e of (A, B, C, D), A's lowest
-__device__ __forceinline__ void tr4(int A, int B, int C, int D, int (&R)[4]) {
-    const uint32_t ab_lo = __builtin_amdgcn_perm((uint32_t)B, (uint32_t)A, 0x05010400u);
-    const uint32_t ab_hi = __builtin_amdgcn_perm((uint32_t)B, (uint32_t)A, 0x07030602u);
-    const uint32_t cd_lo = __builtin_amdgcn_perm((uint32_t)D, (uint32_t)C, 0x05010400u);
-    const uint32_t cd_hi = __builtin_amdgcn_perm((uint32_t)D, (uint32_t)C, 0x07030602u);
-    R[0] = (int)__builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u);
-    R[1] = (int)__builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u);
-    R[2] = (int)__builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u);
-    R[3] = (int)__builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
-}
-
-struct GcActArgs {
-    const int8_t* x;  // [n][ih][iw][C]
-    const int8_t* w;  // [C][9][cg]
-    int8_t* out;      // [n][oh][ow][C]
-    const int8_t* relu_mask;
-    uint32_t xbytes, wbytes;
-    int ih, iw, oh, ow, C, pad, relu;
-    int bands, segs;  // row bands and column segments of an image
-    uint32_t* amax;
-    const int8_t* exp_in;
-    const int8_t* wscale;
-    int8_t* exp_out;
-};
-
 template <int CG, bool DGRAD, int PASS>
 __global__ void __launch_bounds__(256) gconv_act_kernel(GcActArgs a) {
     constexpr int NCH = CG / 16;             // 16-channel chunks of a group
@@ -225,16 +197,6 @@ __global__ void __launch_bounds__(256) gconv_act_kernel(GcActArgs a) {
         if (threadIdx.x == 0) publish_max(a.amax, max(max(red[0], red[1]), max(red[2], red[3])));
     }
 }
-
-struct GcWgArgs {
-    const int8_t* x;   // [n][h][w][C]
-    const int8_t* dy;  // [n][oh][ow][C]
-    int32_t* slab;     // [gridDim.x][C][9][cg]
-    uint32_t xbytes, dbytes;
-    int h, w, oh, ow, C, pad;
-    int bands, segs;  // row bands and column segments of an image
-    int units;        // n * bands * segs
-};
 
 template <int CG>
 __global__ void __launch_bounds__(256) gconv_wgrad_kernel(GcWgArgs a) {
@@ -417,57 +379,6 @@ __device__ __forceinline__ void gc2_load_w(const __amdgpu_buffer_rsrc_t rw, int 
                 for (int b = 0; b < 4; ++b) *(int*)(wsm + (s * CG + ic * 16 + 4 * j + b) * 16 + 4 * (oq & 3)) = R[b];
             }
         }
-    }
-}
-
-// pass 1's shift from the published range (NITI_Conv_Int8.cpp:260-307), the exponent written by one thread
-struct Gc2Quant {
-    int s;
-    bool raw;
-};
-template <int PASS>
-__device__ __forceinline__ Gc2Quant gc2_quant(const GcActArgs& a, uint32_t gm) {
-    Gc2Quant z{2, true};
-    if (PASS == 1) {
-        const int shift = __builtin_amdgcn_readfirstlane(bitwidth_of(wave_max(gm))) - 7;
-        z.s = shift > 1 ? shift : 2;
-        z.raw = shift <= 0;
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && a.exp_out != nullptr) {
-            const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-            *a.exp_out = (int8_t)((a.exp_in ? (int)*a.exp_in : 0) + (a.wscale ? (int)*a.wscale : 0) + inc);
-        }
-    }
-    return z;
-}
-
-// a lane's four accumulators, 4 consecutive channels of one pixel: pass 0 the range, pass 1 one dword of out
-template <int PASS>
-__device__ __forceinline__ void gc2_emit(const GcActArgs& a, const v4i& acc, size_t off, Gc2Quant z, uint32_t& m) {
-    if (PASS == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m = max(m, uabs32(acc[e]));
-    } else {
-        uint32_t mk = 0;
-        if (a.relu_mask != nullptr) mk = *(const uint32_t*)(a.relu_mask + off);
-        uint32_t o = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            int32_t v = z.raw ? (int32_t)(int8_t)acc[e] : psto_fast(acc[e], z.s);
-            if (a.relu && v < 0) v = 0;
-            if (a.relu_mask != nullptr && (int8_t)(mk >> (8 * e)) <= 0) v = 0;
-            o |= ((uint32_t)v & 0xffu) << (8 * e);
-        }
-        *(uint32_t*)(a.out + off) = o;
-    }
-}
-
-template <int PASS>
-__device__ __forceinline__ void gc2_publish(const GcActArgs& a, uint32_t m, uint32_t* red) {
-    if (PASS == 0) {
-        m = wave_max(m);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) publish_max(a.amax, max(max(red[0], red[1]), max(red[2], red[3])));
     }
 }
 
@@ -869,19 +780,23 @@ hipError_t gc_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, c
 
 bool gconv_ok(const ConvGeom& g, int groups) { return g.sh == 1 && g.sw == 1 && gconv2_ok(g, groups); }
 
-bool gconv2_ok(const ConvGeom& g, int groups) {
+bool gconv_shape_ok(const ConvGeom& g, int groups) {
     if (groups < 2 || groups > 65535 || g.n < 1 || g.c_in < 1 || g.c_in != g.c_out || g.c_in % groups != 0) return false;
-    const int cg = g.c_in / groups;
-    if (cg != 16 && cg != 32 && cg != 64) return false;
     if (g.kh != 3 || g.kw != 3 || g.sh < 1 || g.sh > 2 || g.sw != g.sh || g.dh != 1 || g.dw != 1) return false;
     if (g.pt < 0 || g.pt > 2 || g.pl != g.pt || g.pb != g.pt || g.pr != g.pt) return false;
     if (g.h < 1 || g.w < 1 || g.h + 2 * g.pt < 3 || g.w + 2 * g.pt < 3) return false;
     if (g.oh != (g.h + 2 * g.pt - 3) / g.sh + 1 || g.ow != (g.w + 2 * g.pt - 3) / g.sh + 1) return false;
     if (g.cip != g.c_in || g.cop != g.c_out) return false;
-    // every operand below 2^31 bytes: the two maps and the slab buffer the weight gradient writes
     const int64_t lim = (int64_t)1 << 31;
-    return (int64_t)g.n * g.h * g.w * g.cip < lim && (int64_t)g.n * g.oh * g.ow * g.cop < lim &&
-           (int64_t)gc_plan(g, groups) * g.c_out * 9 * cg * 4 < lim;
+    return (int64_t)g.n * g.h * g.w * g.cip < lim && (int64_t)g.n * g.oh * g.ow * g.cop < lim;
+}
+
+bool gconv2_ok(const ConvGeom& g, int groups) {
+    if (!gconv_shape_ok(g, groups)) return false;
+    const int cg = g.c_in / groups;
+    if (cg != 16 && cg != 32 && cg != 64) return false;
+    // every operand below 2^31 bytes: the two maps (gconv_shape_ok) and the slab buffer the weight gradient writes
+    return (int64_t)gc_plan(g, groups) * g.c_out * 9 * cg * 4 < ((int64_t)1 << 31);
 }
 
 hipError_t gconv_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o,

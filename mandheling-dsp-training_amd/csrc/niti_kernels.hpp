@@ -352,6 +352,21 @@ hipError_t gconv_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const in
 int gconv_wgrad_slabs(const ConvGeom& g, int groups);
 hipError_t gconv_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
                        size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
+// ---- grouped 3x3 conv layers at group widths 4 and 8 (niti_grouped_narrow.hip) ------------------
+// gconv2_ok's set with cg 4 or 8 in place of 16, 32 or 64 (c_in a multiple of 16 still), on v_mfma_i32_4x4x4_16b_i8:
+// sixteen 4x4x4 blocks an issue, a block a group (cg 4) or half of one (cg 8).  w, the int32 gradient and its
+// slabs [c_out][9][16], entries cg..15 zero (SgdJob ci = cg, cip = 16); the protocols, ActOut fields and errors of
+// the five launches above.  gconv_shape_ok: what both families ask of (g, groups) but the group width and the
+// slab bound.
+bool gconv_shape_ok(const ConvGeom& g, int groups);
+bool gconv_narrow_ok(const ConvGeom& g, int groups);
+hipError_t gconv_narrow_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                            const ActOut& o, int pass, hipStream_t st);
+hipError_t gconv_narrow_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                              const ActOut& o, int pass, hipStream_t st);
+int gconv_narrow_wgrad_slabs(const ConvGeom& g, int groups);
+hipError_t gconv_narrow_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
 bool conv_dgrad_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // The speculative pair on the implicit GEMM (plan strategy 3 = STRAT_SPEC, forward / input
 // gradient, no K split; NITI_Conv_Int8.cpp:260-307, NITI_DeConv_Int8.cpp:294-329): pass 0 (launch A)

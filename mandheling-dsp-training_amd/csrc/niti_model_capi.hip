@@ -68,6 +68,14 @@ int niti_model_create_chain6(const niti_chain_layer4* layers, int n, int in_c, i
     return create_chain(layers, n, in_c, in_hw, batch, niti::CHAIN_RULE_GROUPED2, out);
 }
 
+int niti_model_chain_check7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes, niti::CHAIN_RULE_NARROW);
+}
+
+int niti_model_create_chain7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    return create_chain(layers, n, in_c, in_hw, batch, niti::CHAIN_RULE_NARROW, out);
+}
+
 // the ten-field list as the same list with groups = 1 (empty where the arguments are malformed: the check
 // then refuses them as it always did)
 static std::vector<niti_chain_layer4> chain_layers4(const niti_chain_layer3* layers, int n) {

@@ -776,7 +776,7 @@ def gconv_ok(g, groups) -> bool:
 
 def gconv_weight(w, stream=None):
     """A grouped layer's weights [c_out, cg, 3, 3] int8 (device) in their device layout [c_out][9][cg]: the OHWI16
-    form of a dense layer with c_in = cg."""
+    form of a dense layer with c_in = cg (a width of 4 or 8 so pads to 16 with zeros)."""
     return oihw_to_ohwi16(w.contiguous(), stream=stream)
 
 
@@ -787,10 +787,15 @@ def _gconv_act(pre, kind, g, groups, a16, w16, amax, pass_, shape, kw):
                        kw.pop("exp_out", None), kw.pop("stream", None), **kw)
 
 
+def _gconv_cgp(g, groups) -> int:
+    """The group width as the device layouts pad it: to 16 (a width of 4 or 8: gconv_narrow_*)."""
+    return -(-(g.c_in // max(int(groups), 1)) // 16) * 16
+
+
 def _gconv_wgrad(pre, g, groups, x16, dy16, slab, stream):
     lib = L.lib()
     if slab is None:
-        cg = g.c_in // max(int(groups), 1)
+        cg = _gconv_cgp(g, groups)
         count = int(getattr(lib, f"niti_{pre}_wgrad_slabs")(C.byref(g), int(groups)))
         slab = torch.full((max(count, 1), g.c_out * 9 * cg), 0x5A5A5A5A, dtype=torch.int32, device=x16.device)
     wrote = C.c_int(-1)
@@ -801,7 +806,7 @@ def _gconv_wgrad(pre, g, groups, x16, dy16, slab, stream):
 
 
 def _gconv_wgrad_reduce(pre, g, groups, slab, amax, stream):
-    acc = torch.full((g.c_out, 3, 3, g.c_in // max(int(groups), 1)), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
+    acc = torch.full((g.c_out, 3, 3, _gconv_cgp(g, groups)), 0x5A5A5A5A, dtype=torch.int32, device=slab.device)
     check(getattr(L.lib(), f"niti_{pre}_wgrad_reduce")(C.byref(g), int(groups), _ptr(slab), slab.shape[0], _ptr(acc),
                                                        _ptr(amax), _stream(stream)), f"{pre}_wgrad_reduce")
     return acc
@@ -868,6 +873,40 @@ def gconv2_wgrad(g, groups, x16, dy16, slab=None, stream=None):
 def gconv2_wgrad_reduce(g, groups, slab, amax=None, stream=None):
     """gconv_wgrad_reduce at stride 1 or 2 (niti_gconv2_wgrad_reduce)."""
     return _gconv_wgrad_reduce("gconv2", g, groups, slab, amax, stream)
+
+
+# The same six at group widths 4 and 8 (niti_gconv_narrow_*: kernels of their own on the 4x4x4 block MFMA; c_in a
+# multiple of 16, stride 1 or 2).  gconv_weight gives w16 [c_out][3][3][16], entries cg..15 zero; the slabs and the
+# reduced gradient have that shape too, their padding written as zeros.
+def gconv_narrow_ok(g, groups) -> bool:
+    """Whether the narrow grouped launches take (g, groups) (niti_gconv_narrow_ok; host only): gconv2_ok's rule with
+    group widths 4 and 8 in place of 16, 32 and 64."""
+    return bool(L.lib().niti_gconv_narrow_ok(C.byref(g), int(groups)))
+
+
+def gconv_narrow_fwd(g, groups, x16, w16, amax, pass_, **kw):
+    """gconv2_fwd at group width 4 or 8 (niti_gconv_narrow_fwd)."""
+    return _gconv_act("gconv_narrow", "fwd", g, groups, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), kw)
+
+
+def gconv_narrow_dgrad(g, groups, dy16, w16, amax, pass_, **kw):
+    """gconv2_dgrad at group width 4 or 8 (niti_gconv_narrow_dgrad)."""
+    return _gconv_act("gconv_narrow", "dgrad", g, groups, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), kw)
+
+
+def gconv_narrow_wgrad_slabs(g, groups) -> int:
+    """The partial slabs niti_gconv_narrow_wgrad leaves for (g, groups) (0 where the launches do not take them)."""
+    return int(L.lib().niti_gconv_narrow_wgrad_slabs(C.byref(g), int(groups)))
+
+
+def gconv_narrow_wgrad(g, groups, x16, dy16, slab=None, stream=None):
+    """gconv2_wgrad at group width 4 or 8 (niti_gconv_narrow_wgrad): int32 [slabs][c_out * 9 * 16]."""
+    return _gconv_wgrad("gconv_narrow", g, groups, x16, dy16, slab, stream)
+
+
+def gconv_narrow_wgrad_reduce(g, groups, slab, amax=None, stream=None):
+    """gconv2_wgrad_reduce at group width 4 or 8 (niti_gconv_narrow_wgrad_reduce): acc int32 [c_out][3][3][16]."""
+    return _gconv_wgrad_reduce("gconv_narrow", g, groups, slab, amax, stream)
 
 
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):

@@ -3,6 +3,8 @@
 bench.py):  python3 tools/grouped_bench.py [--reps 1000] [--stride 2] [--out profiles/grouped_bench.txt]
 --stride 2 measures the same layers at stride 2 (h -> h / 2 pixels; niti_gconv2_*, the dense emulation on the
 strided op-level GEMM launches) into profiles/grouped_stride2_bench.txt.
+--narrow measures group widths 4 and 8 (niti_gconv_narrow_*) at ResNeXt-50 32x4d's shapes, each at its own stride,
+into profiles/grouped_narrow_bench.txt.
 
 Per shape (C channels in G groups at h x h pixels, 3x3 pad 1, batch 64) and phase:
   grouped  the niti_gconv_* launches: forward / input gradient = pass 0 (range) + pass 1 (requantise);
@@ -32,6 +34,7 @@ import niti_amd._lib as L  # noqa: E402
 from niti_amd import ops  # noqa: E402
 
 SHAPES = [(64, 256, 16, 32), (64, 512, 8, 16), (64, 128, 2, 32)]  # (batch, C, G, h)
+NARROW_SHAPES = [(64, 128, 32, 56, 1), (64, 256, 32, 56, 2)]  # (batch, C, G, h, stride): stage 1 (cg 4), stage 2's first block (cg 8)
 PEAK_INT8_TOPS = 256 * 4 * 2048 * 2.4e9 / 1e12
 
 
@@ -60,8 +63,9 @@ def bench_shape(n, c, groups, h, reps, stride=1):
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     g = ops.geom(n, c, h, h, c, 3, stride=stride, pad=1)
     oh = g.oh
-    fns = [getattr(lib, f"niti_gconv{2 if stride == 2 else ''}_{k}") for k in ("fwd", "dgrad", "wgrad", "wgrad_slabs")]
     cg = c // groups
+    pre = "gconv_narrow" if cg < 16 else "gconv2" if stride == 2 else "gconv"
+    fns = [getattr(lib, f"niti_{pre}_{k}") for k in ("fwd", "dgrad", "wgrad", "wgrad_slabs")]
     dev = "cuda"
     P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     x = torch.randint(-127, 128, (n, h, h, c), dtype=torch.int8, device=dev)
@@ -84,7 +88,7 @@ def bench_shape(n, c, groups, h, reps, stride=1):
         return run
 
     slabs = int(fns[3](C.byref(g), groups))
-    one = c * 9 * cg
+    one = c * 9 * max(cg, 16)  # (a width of 4 or 8 pads to 16)
     slab = torch.empty((slabs, one), dtype=torch.int32, device=dev)
     gacc = torch.empty(one, dtype=torch.int32, device=dev)
     job = (L.SgdCombineJob * 1)()
@@ -135,20 +139,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--stride", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--narrow", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "grouped_stride2_bench.txt" if args.stride == 2 else "grouped_bench.txt")
-    lines = [f"# tools/grouped_bench.py --reps {args.reps} --stride {args.stride}: {torch.cuda.get_device_name(0)}",
+    args.out = args.out or os.path.join(ROOT, "profiles", "grouped_narrow_bench.txt" if args.narrow else
+                                        "grouped_stride2_bench.txt" if args.stride == 2 else "grouped_bench.txt")
+    shapes = NARROW_SHAPES if args.narrow else [sh + (args.stride,) for sh in SHAPES]
+    lines = [f"# tools/grouped_bench.py --reps {args.reps} " + ("--narrow" if args.narrow else f"--stride {args.stride}") +
+             f": {torch.cuda.get_device_name(0)}",
              f"# us per phase, medians of 5 rounds of {args.reps} runs: grouped / dense measured grouped-first (1) and",
              "# dense-first (2); dense = the block-diagonal weight on the op-level GEMM path (int32 stored, then requantised);",
              "# dense/grp = the ratio of the two orders' means (above 1: the grouped launches are faster); TOPS = the layer's own",
              f"# int8 operations, counted once (no recompute), over the faster grouped time, peak {PEAK_INT8_TOPS:.0f}",
              f"{'shape':>20} {'phase':>6} {'grp1':>9} {'dense1':>9} {'grp2':>9} {'dense2':>9} {'dense/grp':>10} {'TOPS':>8} {'of peak':>8}"]
-    for n, c, groups, h in SHAPES:
-        slabs, rows = bench_shape(n, c, groups, h, args.reps, args.stride)
+    for n, c, groups, h, stride in shapes:
+        slabs, rows = bench_shape(n, c, groups, h, args.reps, stride)
         for ph, (g1, d1, g2, d2, tops) in rows.items():
             ratio = (d1 + d2) / (g1 + g2)
-            lines.append(f"{f'{c}/G{groups}@{h}px' + ('/2' if args.stride == 2 else '') + f' b{n}':>20} {ph:>6} {g1:9.2f} {d1:9.2f} {g2:9.2f} {d2:9.2f} {ratio:10.2f} {tops:8.1f} "
+            lines.append(f"{f'{c}/G{groups}@{h}px' + ('/2' if stride == 2 else '') + f' b{n}':>20} {ph:>6} {g1:9.2f} {d1:9.2f} {g2:9.2f} {d2:9.2f} {ratio:10.2f} {tops:8.1f} "
                          f"{tops / PEAK_INT8_TOPS:8.4f}" + (f"   ({slabs} slabs)" if ph == "wgrad" else "") +
                          ("   SLOWER than the dense emulation" if ratio < 1 else ""))
         print("\n".join(lines[-3:]), flush=True)
