@@ -112,8 +112,8 @@ struct RowPath {
         return NITI_NO_ERROR;
     }
     // x16 / w16: the Execution's NHWC16 input and OHWI16 weights (already converted); amax zeroed.
-    // Under stream capture the fused launch's barrier parity (epoch, a kernel argument) would be
-    // replayed unchanged with counts nobody resets, so a captured call takes the two-launch form
+    // Under stream capture the fused launch's barrier epoch (a kernel argument) would be replayed
+    // unchanged over slots that already carry it, so a captured call takes the two-launch form
     // (range launch, then recompute + requantise with the published max): same results.
     hipError_t run(const ConvGeom& g, const int8_t* x16, const int8_t* w16, uint32_t* amax, const int8_t* exp_in,
                    const int8_t* wscale, int8_t* exp_out, int8_t* out_c4, hipStream_t st) {

@@ -2143,7 +2143,8 @@ static hipError_t act_fused(int op, const LA& la, const LB& lb, int M, int N, in
         o.out == nullptr || fb.bar == nullptr || fb.err == nullptr)
         return hipErrorInvalidValue;
     const auto f = gemm_fn<LA, LB, EPI_REQUANT, false>(p);
-    if (p.tiles > resident_wgs(f.first, f.second)) return hipErrorNotSupported;
+    if (fb.epoch == 0) return hipErrorInvalidValue;  // zeroed barrier state reads as epoch 0
+    if (!grid_bar_fits(p.tiles) || p.tiles > resident_wgs(f.first, f.second)) return hipErrorNotSupported;
     Epi e;
     e.out = o.out;
     e.ldo = N;

@@ -481,7 +481,7 @@ struct RowConvOut {
 size_t rowconv_acc_bytes(const ConvGeom& g, bool dg, bool pooled = false);
 bool rowconv_nhwc_ok(const ConvGeom& g);
 bool rowconv_nhwc_pref(const ConvGeom& g);
-constexpr int ROWCONV_BAR_WORDS = 2 * 19 * 32;  // grid-barrier state (both parities)
+constexpr int ROWCONV_BAR_WORDS = 2 * 19 * 32;  // grid-barrier state (512 slots + the two hint lines: niti_gridbar.hpp)
 static_assert(ROWCONV_BAR_WORDS == NITI_ROWCONV_STATE_WORDS, "header constant");
 bool rowconv_ok(const ConvGeom& g);
 bool rowconv_seg(const ConvGeom& g);  // the row-segment form (W = 0) takes g

@@ -171,7 +171,7 @@ hipError_t residual_fused(const int8_t* a, const int8_t* ea, const int8_t* b, co
         constexpr bool MK = decltype(mc)::value;
         const void* f = (const void*)residual_fused_kernel<V, MK>;
         const int64_t blocks = std::max<int64_t>(1, (n16 + 256 * V - 1) / (256 * V));
-        if (blocks > resident_wgs(f)) return hipErrorNotSupported;
+        if (!grid_bar_fits(blocks) || blocks > resident_wgs(f)) return hipErrorNotSupported;
         hipLaunchKernelGGL((residual_fused_kernel<V, MK>), dim3((unsigned)blocks), dim3(256), 0, st, p);
         return hipGetLastError();
     };

@@ -1916,7 +1916,7 @@ bool rowconv_fused_ok(const ConvGeom& g, bool dg, bool pooled) {
     const bool unc = (g.c_in + 31) / 32 % 4 == 0;
     const int W = rowconv_seg(g) ? 0 : g.w;
     const void* f = dg ? rc_kernel<RC_FUSED, true>(W, R, unc, ks) : rc_kernel<RC_FUSED, false>(W, R, unc, ks);
-    return wgs <= resident_wgs(f);
+    return grid_bar_fits(wgs) && wgs <= resident_wgs(f);
 }
 
 static uint32_t g_rc_spin_limit = BAR_SPIN_LIMIT, g_rc_expect_extra = 0;
@@ -2158,7 +2158,7 @@ bool rowconv_fc_ok(int n, int K, int rows, bool fused) {
     // either epilogue form: the resident limit of the smaller-occupancy instantiation
     const int cap = std::min(resident_wgs(rc_kernel<RC_FUSED, false>(1, 1, false, 0)),
                              resident_wgs(rc_kernel<RC_FUSED, true>(1, 1, false, 0)));
-    return wgs <= cap;
+    return grid_bar_fits(wgs) && wgs <= cap;
 }
 
 hipError_t rowconv_fc(int n, int K, int rows, const int8_t* x, int xld, const int8_t* w, int wld,

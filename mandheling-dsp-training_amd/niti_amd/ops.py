@@ -296,8 +296,8 @@ def conv_fwd_rows(g: L.Geom, xc32, wf, amax, mode=0, state: RowConvState | None 
     st_ptr = err_ptr = None
     epoch = 0
     if mode == 0:
-        # the launch's epoch; state.epoch advances only when the launch happened (a NOT_SUPPORT
-        # return launches nothing, and a skipped epoch would reuse the previous launch's barrier words)
+        # the launch's epoch, the tag of this launch's barrier slots: each launch on a state takes a
+        # new one; state.epoch advances only when the launch happened (a NOT_SUPPORT return launches nothing)
         epoch, st_ptr, err_ptr = state.epoch + 1, _ptr(state.state), _ptr(state.err)
     elif mode >= 3:
         st_ptr = _ptr(state.state)
@@ -328,8 +328,8 @@ def conv_dgrad_rows(g: L.Geom, dyc32, wft, amax, mode=0, state: RowConvState | N
     st_ptr = err_ptr = None
     epoch = 0
     if mode == 0:
-        # the launch's epoch; state.epoch advances only when the launch happened (a NOT_SUPPORT
-        # return launches nothing, and a skipped epoch would reuse the previous launch's barrier words)
+        # the launch's epoch, the tag of this launch's barrier slots: each launch on a state takes a
+        # new one; state.epoch advances only when the launch happened (a NOT_SUPPORT return launches nothing)
         epoch, st_ptr, err_ptr = state.epoch + 1, _ptr(state.state), _ptr(state.err)
     elif mode >= 3:
         st_ptr = _ptr(state.state)

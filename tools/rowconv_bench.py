@@ -90,6 +90,10 @@ for li, (ci, co, h, pool) in enumerate(layers, start=1):
                 print(f"      grid barrier (us): arrivals spread {(arr.max() - arr.min()) / 100:.2f}, median wait "
                       f"{np.median(rel_ - arr) / 100:.2f}, last arrival -> last release {(rel_.max() - arr.max()) / 100:.2f}",
                       flush=True)
+                # each workgroup's release after the last arrival: all late together, or a few stragglers
+                lag = (rel_ - arr.max()) / 100
+                print(f"      release after the last arrival (us), {len(lag)} workgroups: min {lag.min():.2f}  median "
+                      f"{np.median(lag):.2f}  max {lag.max():.2f}", flush=True)
     ops_ = 2 * n * h * h * co * ci * 9
     print(f"{ci:4d}->{co:4d} @{h:2d} pool={pool}: " + "  ".join(f"mode {m} {t:6.2f} us ({ops_ / t / 1e6 / PEAK:.3f})"
                                                                  for m, t in res.items()), flush=True)
