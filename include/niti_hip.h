@@ -704,6 +704,25 @@ int niti_gconv_narrow_wgrad(const niti_geom* g, int groups, const int8_t* x, con
 int niti_gconv_narrow_wgrad_slabs(const niti_geom* g, int groups);
 int niti_gconv_narrow_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
                                    uint32_t* amax, void* stream);
+/* The same six at every other group width that is a multiple of 8 up to 128 (this library's extension; what most of
+ * the RegNets run): cg in {24, 40, 48, 56, 72, 80, 88, 96, 104, 112, 120, 128}, stride 1 or 2 as niti_gconv2_*.  The
+ * kernels are their own, on v_mfma_i32_16x16x64_i8 with K packed across the taps: ceil(9 cg / 64) issues a tile.
+ * c_in = c_out = G cg need be no multiple of 16: x, dy, out and relu_mask are [n][h][w][cip] with niti_geom's cip
+ * (c_in rounded up to 16); the padding channels are never read and pass 1 writes them as zeros.  w
+ * (niti_oihw_to_ohwi16 of [c_out][cg][3][3] with ci = cip = cg), the int32 gradient and the slabs are
+ * [c_out][9][cg], unpadded.  Everything else is niti_gconv2_*'s.
+ * NITI_INVALID_VALUE, nothing launched: niti_gconv2_*'s list with "cg other than 16, 32 or 64" replaced by: cg not
+ * in the set above.  The other two families keep refusing these widths. */
+int niti_gconv_packed_ok(const niti_geom* g, int groups);
+int niti_gconv_packed_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                          const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_packed_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                            const niti_dwconv_out* o, int pass, void* stream);
+int niti_gconv_packed_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                            size_t slab_bytes, int* slabs, void* stream);
+int niti_gconv_packed_wgrad_slabs(const niti_geom* g, int groups);
+int niti_gconv_packed_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                                   uint32_t* amax, void* stream);
 /* layout helpers */
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream);
 int niti_ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, void* stream);
@@ -982,6 +1001,11 @@ int niti_model_create_chain6(const niti_chain_layer4* layers, int n, int in_c, i
  * points above keep refusing such a layer with NITI_NOT_SUPPORT. */
 int niti_model_chain_check7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
 int niti_model_create_chain7(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
+/* The same with the group widths of niti_gconv_packed_* admitted (24, 40, 48, 56, 72, ..., 128; c_in need be no
+ * multiple of 16): every other refusal of niti_model_chain_check7 stands, the fourteen entry points above keep
+ * refusing such a layer with NITI_NOT_SUPPORT, and a layer of width 4, 8, 16, 32 or 64 runs the kernels it runs there. */
+int niti_model_chain_check8(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]);
+int niti_model_create_chain8(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out);
 
 /* A residual network of the caller's own (niti_model_create_resnet): a stem conv with relu and an
  * optional 3x3 / 2 pad-1 max pool, then n_stages stages of basic blocks, the global sum pool and

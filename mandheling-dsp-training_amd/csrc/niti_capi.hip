@@ -985,6 +985,46 @@ int niti_gconv_narrow_wgrad_reduce(const niti_geom* g, int groups, const int32_t
     return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
 }
 
+// the other multiples of 8 up to 128 (gconv_packed_ok; niti_grouped_packed.hip): weights, gradient and slabs
+// [c_out][9][cg], unpadded
+static bool gcp_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
+    return g != nullptr && to_geom(g, r) && niti::gconv_packed_ok(*r, groups);
+}
+int niti_gconv_packed_ok(const niti_geom* g, int groups) {
+    niti::ConvGeom r;
+    return gcp_geom(g, groups, &r) ? 1 : 0;
+}
+int niti_gconv_packed_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                          const niti_dwconv_out* o, int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!gcp_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::gconv_packed_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_gconv_packed_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                            const niti_dwconv_out* o, int pass, void* stream) {
+    niti::ConvGeom r;
+    if (!gcp_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
+    return code(niti::gconv_packed_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
+}
+int niti_gconv_packed_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                            size_t slab_bytes, int* slabs, void* stream) {
+    niti::ConvGeom r;
+    if (!gcp_geom(g, groups, &r)) return NITI_INVALID_VALUE;
+    return code(niti::gconv_packed_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
+}
+int niti_gconv_packed_wgrad_slabs(const niti_geom* g, int groups) {
+    niti::ConvGeom r;
+    return gcp_geom(g, groups, &r) ? niti::gconv_packed_wgrad_slabs(r, groups) : 0;
+}
+int niti_gconv_packed_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
+                                   uint32_t* amax, void* stream) {
+    niti::ConvGeom r;
+    if (!gcp_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_packed_wgrad_slabs(r, groups))
+        return NITI_INVALID_VALUE;
+    const int64_t n = (int64_t)r.c_out * 9 * (r.c_in / groups);
+    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
+}
+
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));
 }

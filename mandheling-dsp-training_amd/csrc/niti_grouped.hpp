@@ -1,6 +1,7 @@
 // niti_grouped.hpp -- what the grouped conv kernel families share (niti_grouped.hip: group widths 16, 32, 64 on the
-// 16x16x64 MFMA; niti_grouped_narrow.hip: 4 and 8 on the 4x4x4 block MFMA): the launch arguments, the 4 x 4 byte
-// transpose, pass 1's requantisation of a lane's four accumulators and pass 0's range.
+// 16x16x64 MFMA; niti_grouped_narrow.hip: 4 and 8 on the 4x4x4 block MFMA; niti_grouped_packed.hip: the other
+// multiples of 8 up to 128, K packed across taps): the launch arguments, the 4 x 4 byte transpose, pass 1's
+// requantisation of a lane's four accumulators and pass 0's range.
 #pragma once
 #include "niti_device.hpp"
 #include "niti_sgd.hpp"
@@ -34,6 +35,7 @@ struct GcActArgs {
     const int8_t* exp_in;
     const int8_t* wscale;
     int8_t* exp_out;
+    int cp;  // niti_grouped_packed.hip: the channel pitch of x, out and relu_mask (C rounded up to 16)
 };
 
 struct GcWgArgs {
@@ -44,6 +46,7 @@ struct GcWgArgs {
     int h, w, oh, ow, C, pad;
     int bands, segs;  // row bands and column segments of an image
     int units;        // n * bands * segs
+    int cp;           // niti_grouped_packed.hip: the channel pitch of x and dy (C rounded up to 16)
 };
 
 // pass 1's shift from the published range (NITI_Conv_Int8.cpp:260-307), the exponent written by one thread

@@ -367,6 +367,19 @@ hipError_t gconv_narrow_dgrad(const ConvGeom& g, int groups, const int8_t* dy, c
 int gconv_narrow_wgrad_slabs(const ConvGeom& g, int groups);
 hipError_t gconv_narrow_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
                               size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
+// ---- grouped 3x3 conv layers at the other group widths (niti_grouped_packed.hip) ----------------
+// gconv2_ok's set with cg a multiple of 8 from 24 to 128 but 32 and 64, and the channel pitch of x / dy / out that
+// of ConvGeom (cip == cop == c_in rounded up to 16: C need be no multiple of 16; the padding is written as zeros), on
+// v_mfma_i32_16x16x64_i8 with K packed across the taps.  w, the int32 gradient and its slabs [c_out][9][cg],
+// unpadded; the protocols, ActOut fields and errors of the launches above.
+bool gconv_packed_ok(const ConvGeom& g, int groups);
+hipError_t gconv_packed_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
+                            const ActOut& o, int pass, hipStream_t st);
+hipError_t gconv_packed_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
+                              const ActOut& o, int pass, hipStream_t st);
+int gconv_packed_wgrad_slabs(const ConvGeom& g, int groups);
+hipError_t gconv_packed_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
+                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
 bool conv_dgrad_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // The speculative pair on the implicit GEMM (plan strategy 3 = STRAT_SPEC, forward / input
 // gradient, no K split; NITI_Conv_Int8.cpp:260-307, NITI_DeConv_Int8.cpp:294-329): pass 0 (launch A)

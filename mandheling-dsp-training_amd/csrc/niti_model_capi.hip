@@ -76,6 +76,14 @@ int niti_model_create_chain7(const niti_chain_layer4* layers, int n, int in_c, i
     return create_chain(layers, n, in_c, in_hw, batch, niti::CHAIN_RULE_NARROW, out);
 }
 
+int niti_model_chain_check8(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int shapes[][8]) {
+    return niti::chain_check(layers, n, in_c, in_hw, 1, shapes, niti::CHAIN_RULE_PACKED);
+}
+
+int niti_model_create_chain8(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch, niti_model_t* out) {
+    return create_chain(layers, n, in_c, in_hw, batch, niti::CHAIN_RULE_PACKED, out);
+}
+
 // the ten-field list as the same list with groups = 1 (empty where the arguments are malformed: the check
 // then refuses them as it always did)
 static std::vector<niti_chain_layer4> chain_layers4(const niti_chain_layer3* layers, int n) {

@@ -357,6 +357,15 @@ SgdJob StepDriver::sgd_job(int i, bool wT_by_update) const {
     // (a depthwise layer: the c_out = 1 form of its weight; a grouped layer: the c_in = cg form; no transposed copy)
     SgdJob j{p.dwacc, p.wg_amax, -(1 + i), p.w_co(), p.w_ci(), g.kh * g.kw, p.w_cip(), p.dw ? 16 : g.cop, p.w,
              wT_by_update && !p.own() ? p.wT : nullptr, keep_grads ? p.g8 : nullptr};
+    // The update's tiles step 16 input channels at a time.  A packed grouped layer's [c_out][9][cg] with cg no
+    // multiple of 16 goes in as the same bytes seen as [elems / 64][1][64] (G 9 cg^2 elements, cg^2 a multiple of
+    // 64): the rule is elementwise, the range the whole tensor's, and the layer has no copy that follows a shape
+    if (p.packed() && p.w_cip() % 16 != 0) {
+        j.co = (int)(p.w_elems() / 64);
+        j.kk = 1;
+        j.ci = j.cip = 64;
+        j.cop = (j.co + 15) / 16 * 16;  // (the launch counts a job's row tiles from cop)
+    }
     j.wf = p.rc ? p.wf : nullptr;
     j.wft = p.rcd ? p.wft : nullptr;
     if (p.subw != nullptr) {  // the stride-2 input gradient's sub-pixel class weights

@@ -277,6 +277,12 @@ def lib():
         "niti_gconv_narrow_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
         "niti_gconv_narrow_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
         "niti_gconv_narrow_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
+        "niti_gconv_packed_ok": (ci, [C.POINTER(Geom), ci]),
+        "niti_gconv_packed_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_gconv_packed_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
+        "niti_gconv_packed_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
+        "niti_gconv_packed_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
+        "niti_gconv_packed_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
         "niti_dwconv2_ok": (ci, [C.POINTER(Geom)]),
         "niti_dwconv2_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
         "niti_dwconv2_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
@@ -337,6 +343,8 @@ def lib():
         "niti_model_create_chain6": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         "niti_model_chain_check7": (ci, [vp, ci, ci, ci, vp]),
         "niti_model_create_chain7": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
+        "niti_model_chain_check8": (ci, [vp, ci, ci, ci, vp]),
+        "niti_model_create_chain8": (ci, [vp, ci, ci, ci, ci, C.POINTER(vp)]),
         "niti_model_layer_groups": (ci, [vp, ci]),
         "niti_model_layer_skip": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
         # (spec: a ResnetSpec, passed untyped)

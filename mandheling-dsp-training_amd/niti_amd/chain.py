@@ -90,15 +90,18 @@ def wide(spec) -> bool:
 def level_of(spec, level):
     """The entry-point level a normalised spec is routed by: None (the routing above, which refuses a grouped layer
     of stride 2) or, for level=6 or 7 and a grouped() spec, that level (niti_model_chain_check6 / _create_chain6,
-    which take one; _check7 / _create_chain7, which also take group widths 4 and 8).  ValueError for any other level."""
-    if level is not None and int(level) not in (6, 7):
-        raise ValueError(f"level {level!r}: None, 6 or 7")
+    which take one; _check7 / _create_chain7, which also take group widths 4 and 8; _check8 / _create_chain8, which
+    also take every other multiple of 8 up to 128).  ValueError for any other level."""
+    if level is not None and int(level) not in (6, 7, 8):
+        raise ValueError(f"level {level!r}: None, 6, 7 or 8")
     return int(level) if level is not None and grouped(spec) else None
 
 
 def entry_points(spec, level=None):
     """(check, create) -- the C entry points a normalised spec goes through (level: level_of)."""
     lib = L.lib()
+    if level_of(spec, level) == 8:
+        return lib.niti_model_chain_check8, lib.niti_model_create_chain8
     if level_of(spec, level) == 7:
         return lib.niti_model_chain_check7, lib.niti_model_create_chain7
     if level_of(spec, level) == 6:
@@ -135,7 +138,8 @@ def chain_layers(spec, in_c: int, in_hw: int, level=None) -> list:
     list that has a strided layer, stride, for a list that has a skip, skip, for a list that has a global
     pool, gpool, for a list that has a grouped layer, groups (host only: niti_model_chain_check2, _check3 for a
     list with a strided layer, _check4 for a wide() list, _check5 for a grouped() one, _check6 for that one with
-    level=6: a grouped layer may then have stride 2, _check7 with level=7: and a group width of 4 or 8).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
+    level=6: a grouped layer may then have stride 2, _check7 with level=7: and a group width of 4 or 8, _check8
+    with level=8: or any other multiple of 8 up to 128).  ValueError for a malformed spec, NitiError (NOT_SUPPORT) for one
     the library does not run."""
     spec = normalize_spec(spec)
     arr, n = to_c(spec)

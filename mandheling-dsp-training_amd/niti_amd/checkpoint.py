@@ -28,7 +28,7 @@ FORMAT = "niti-int8-params-v1"
 
 def chain_record(spec, in_c: int, in_hw: int, level=None) -> dict:
     """What a chain model's snapshot stores about its network (compared as a whole on load).  level: the
-    entry-point level of a model made with from_chain(level=6 or 7), recorded only then."""
+    entry-point level of a model made with from_chain(level=6, 7 or 8), recorded only then."""
     from .chain import normalize_spec
     rec = {"spec": normalize_spec(spec), "in_c": int(in_c), "in_hw": int(in_hw)}
     if level is not None:

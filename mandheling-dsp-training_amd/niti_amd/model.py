@@ -27,7 +27,7 @@ class NitiModel:
         self._h = h
         self.arch, self.batch = arch, batch
         self.chain = None  # from_chain: the normalised layer list
-        self.chain_level = None  # from_chain(level=6 or 7) of a list with a grouped layer: that level
+        self.chain_level = None  # from_chain(level=6, 7 or 8) of a list with a grouped layer: that level
         self.resnet = None  # from_resnet: the normalised stage list
         self._wscale = {}
         self.layers = []
@@ -51,7 +51,8 @@ class NitiModel:
         grouped conv (weights [c_out, c_in / G, 3, 3], group width 16, 32 or 64; _create_chain5); level=6 sends
         a list with a grouped layer through _create_chain6, where that layer may have stride 2 (the default keeps
         refusing it; snapshots of such a model record the level); level=7 through _create_chain7, where its group width
-        may also be 4 or 8 (ResNeXt 32x4d's first stages, the small RegNets).  ValueError for a
+        may also be 4 or 8 (ResNeXt 32x4d's first stages, the small RegNets); level=8 through _create_chain8, where it
+        may be any other multiple of 8 up to 128 and the channel count no multiple of 16 (the RegNets).  ValueError for a
         malformed list, NitiError (NOT_SUPPORT) for one the library does not run -- nothing is
         allocated then.  The model reports arch ARCH_CHAIN; .chain holds the normalised spec."""
         from .chain import entry_points, level_of, normalize_spec, to_c

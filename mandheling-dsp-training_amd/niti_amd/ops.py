@@ -776,8 +776,14 @@ def gconv_ok(g, groups) -> bool:
 
 def gconv_weight(w, stream=None):
     """A grouped layer's weights [c_out, cg, 3, 3] int8 (device) in their device layout [c_out][9][cg]: the OHWI16
-    form of a dense layer with c_in = cg (a width of 4 or 8 so pads to 16 with zeros)."""
-    return oihw_to_ohwi16(w.contiguous(), stream=stream)
+    form of a dense layer with c_in = cg (a width of 4 or 8 so pads to 16 with zeros; a width of gconv_packed_* --
+    24, 40, ... -- does not pad).  ohwi16_to_oihw(w16, cg) is the inverse at every width."""
+    co, cg, kh, kw = w.shape
+    if _gconv_cgp_of(cg) == r16(cg):
+        return oihw_to_ohwi16(w.contiguous(), stream=stream)
+    out = torch.empty((co, kh, kw, cg), dtype=torch.int8, device=w.device)
+    check(L.lib().niti_oihw_to_ohwi16(_ptr(w.contiguous()), co, cg, kh * kw, cg, _ptr(out), _stream(stream)), "oihw->ohwi16")
+    return out
 
 
 def _gconv_act(pre, kind, g, groups, a16, w16, amax, pass_, shape, kw):
@@ -787,9 +793,14 @@ def _gconv_act(pre, kind, g, groups, a16, w16, amax, pass_, shape, kw):
                        kw.pop("exp_out", None), kw.pop("stream", None), **kw)
 
 
+def _gconv_cgp_of(cg: int) -> int:
+    """A group width as the device layouts pad it: to 16 (a width of 4 or 8: gconv_narrow_*), but not a width of
+    gconv_packed_* (a multiple of 8 from 24 up)."""
+    return cg if cg >= 24 and cg % 8 == 0 else r16(cg)
+
+
 def _gconv_cgp(g, groups) -> int:
-    """The group width as the device layouts pad it: to 16 (a width of 4 or 8: gconv_narrow_*)."""
-    return -(-(g.c_in // max(int(groups), 1)) // 16) * 16
+    return _gconv_cgp_of(g.c_in // max(int(groups), 1))
 
 
 def _gconv_wgrad(pre, g, groups, x16, dy16, slab, stream):
@@ -907,6 +918,41 @@ def gconv_narrow_wgrad(g, groups, x16, dy16, slab=None, stream=None):
 def gconv_narrow_wgrad_reduce(g, groups, slab, amax=None, stream=None):
     """gconv2_wgrad_reduce at group width 4 or 8 (niti_gconv_narrow_wgrad_reduce): acc int32 [c_out][3][3][16]."""
     return _gconv_wgrad_reduce("gconv_narrow", g, groups, slab, amax, stream)
+
+
+# The same six at every other group width that is a multiple of 8 up to 128 (niti_gconv_packed_*: 24, 40, 48, 56, 72,
+# ..., 128; kernels of their own with K packed across the taps; stride 1 or 2).  c_in need be no multiple of 16: x, dy
+# and out are NHWC16 with g.cip channels, the padding written as zeros.  gconv_weight gives w16 [c_out][3][3][cg],
+# unpadded; the slabs and the reduced gradient have that shape too.
+def gconv_packed_ok(g, groups) -> bool:
+    """Whether the packed grouped launches take (g, groups) (niti_gconv_packed_ok; host only): gconv2_ok's rule with
+    these group widths in place of 16, 32 and 64."""
+    return bool(L.lib().niti_gconv_packed_ok(C.byref(g), int(groups)))
+
+
+def gconv_packed_fwd(g, groups, x16, w16, amax, pass_, **kw):
+    """gconv2_fwd at these group widths (niti_gconv_packed_fwd)."""
+    return _gconv_act("gconv_packed", "fwd", g, groups, x16, w16, amax, pass_, (g.n, g.oh, g.ow, g.cop), kw)
+
+
+def gconv_packed_dgrad(g, groups, dy16, w16, amax, pass_, **kw):
+    """gconv2_dgrad at these group widths (niti_gconv_packed_dgrad)."""
+    return _gconv_act("gconv_packed", "dgrad", g, groups, dy16, w16, amax, pass_, (g.n, g.h, g.w, g.cip), kw)
+
+
+def gconv_packed_wgrad_slabs(g, groups) -> int:
+    """The partial slabs niti_gconv_packed_wgrad leaves for (g, groups) (0 where the launches do not take them)."""
+    return int(L.lib().niti_gconv_packed_wgrad_slabs(C.byref(g), int(groups)))
+
+
+def gconv_packed_wgrad(g, groups, x16, dy16, slab=None, stream=None):
+    """gconv2_wgrad at these group widths (niti_gconv_packed_wgrad): int32 [slabs][c_out * 9 * cg]."""
+    return _gconv_wgrad("gconv_packed", g, groups, x16, dy16, slab, stream)
+
+
+def gconv_packed_wgrad_reduce(g, groups, slab, amax=None, stream=None):
+    """gconv2_wgrad_reduce at these group widths (niti_gconv_packed_wgrad_reduce): acc int32 [c_out][3][3][cg]."""
+    return _gconv_wgrad_reduce("gconv_packed", g, groups, slab, amax, stream)
 
 
 def residual_add(a, ea, b, eb, amax, stream=None, ez=None):
