@@ -3,6 +3,7 @@
 #include <memory>
 #include <vector>
 
+#include "niti_grouped.hpp"
 #include "niti_internal.hpp"
 #include "niti_kernels.hpp"
 
@@ -788,8 +789,6 @@ void niti_diag_conv0_wgrad_blocks(int n) { niti::diag_conv0_wgrad_blocks(n); }
 void niti_diag_conv0_wgrad_codes(int mode) { niti::model_conv0_wgrad_codes(mode); }
 unsigned long long niti_diag_conv0_wgrad_codes_launches(void) { return niti::model_conv0_wgrad_codes_launches(); }
 
-// depthwise conv layers (niti_depthwise.hip): every refusal is INVALID_VALUE with nothing launched
-static bool dw_geom(const niti_geom* g, niti::ConvGeom* r) { return g != nullptr && to_geom(g, r) && niti::dwconv_ok(*r); }
 static niti::ActOut dw_out(const niti_dwconv_out* o) {
     niti::ActOut a;
     a.out = o->out;
@@ -800,230 +799,91 @@ static niti::ActOut dw_out(const niti_dwconv_out* o) {
     a.exp_out = o->exp_out;
     return a;
 }
-int niti_dwconv_ok(const niti_geom* g) {
-    niti::ConvGeom r;
-    return dw_geom(g, &r) ? 1 : 0;
-}
-int niti_dwconv_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
-                    int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!dw_geom(g, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_fwd(r, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_dwconv_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
-                      int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!dw_geom(g, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_dgrad(r, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_dwconv_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
-                      int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!dw_geom(g, &r)) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_wgrad(r, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_dwconv_wgrad_slabs(const niti_geom* g) {
-    niti::ConvGeom r;
-    return dw_geom(g, &r) ? niti::dwconv_wgrad_slabs(r) : 0;
-}
-int niti_dwconv_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
-                             void* stream) {
-    niti::ConvGeom r;
-    if (!dw_geom(g, &r) || !slab || !acc || slabs != niti::dwconv_wgrad_slabs(r)) return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.kh * r.kw * r.cip;
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
 
-// the same at stride 1 or 2 (dwconv2_ok): at stride 1 the launches above
-static bool dw2_geom(const niti_geom* g, niti::ConvGeom* r) { return g != nullptr && to_geom(g, r) && niti::dwconv2_ok(*r); }
-int niti_dwconv2_ok(const niti_geom* g) {
-    niti::ConvGeom r;
-    return dw2_geom(g, &r) ? 1 : 0;
-}
-int niti_dwconv2_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
-                     int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!dw2_geom(g, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_fwd(r, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_dwconv2_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o,
-                       int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!dw2_geom(g, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_dgrad(r, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_dwconv2_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
-                       int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!dw2_geom(g, &r)) return NITI_INVALID_VALUE;
-    return code(niti::dwconv_wgrad(r, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_dwconv2_wgrad_slabs(const niti_geom* g) {
-    niti::ConvGeom r;
-    return dw2_geom(g, &r) ? niti::dwconv_wgrad_slabs(r) : 0;
-}
-int niti_dwconv2_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,
-                              void* stream) {
-    niti::ConvGeom r;
-    if (!dw2_geom(g, &r) || !slab || !acc || slabs != niti::dwconv_wgrad_slabs(r)) return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.kh * r.kw * r.cip;
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
+// Depthwise conv layers (niti_depthwise.hip): the six entries of one prefix, OK the predicate of what the prefix
+// admits.  Every refusal is INVALID_VALUE with nothing launched.
+#define NITI_DWCONV_ENTRIES(P, OK)                                                                                    \
+    static bool P##_geom(const niti_geom* g, niti::ConvGeom* r) { return g != nullptr && to_geom(g, r) && OK(*r); }    \
+    int niti_##P##_ok(const niti_geom* g) {                                                                           \
+        niti::ConvGeom r;                                                                                             \
+        return P##_geom(g, &r) ? 1 : 0;                                                                               \
+    }                                                                                                                 \
+    int niti_##P##_fwd(const niti_geom* g, const int8_t* x, const int8_t* w, uint32_t* amax, const niti_dwconv_out* o, \
+                       int pass, void* stream) {                                                                      \
+        niti::ConvGeom r;                                                                                             \
+        if (!P##_geom(g, &r) || !o) return NITI_INVALID_VALUE;                                                        \
+        return code(niti::dwconv_fwd(r, x, w, amax, dw_out(o), pass, S(stream)));                                     \
+    }                                                                                                                 \
+    int niti_##P##_dgrad(const niti_geom* g, const int8_t* dy, const int8_t* w, uint32_t* amax,                       \
+                         const niti_dwconv_out* o, int pass, void* stream) {                                          \
+        niti::ConvGeom r;                                                                                             \
+        if (!P##_geom(g, &r) || !o) return NITI_INVALID_VALUE;                                                        \
+        return code(niti::dwconv_dgrad(r, dy, w, amax, dw_out(o), pass, S(stream)));                                  \
+    }                                                                                                                 \
+    int niti_##P##_wgrad(const niti_geom* g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,     \
+                         int* slabs, void* stream) {                                                                  \
+        niti::ConvGeom r;                                                                                             \
+        if (!P##_geom(g, &r)) return NITI_INVALID_VALUE;                                                              \
+        return code(niti::dwconv_wgrad(r, x, dy, slab, slab_bytes, slabs, S(stream)));                                \
+    }                                                                                                                 \
+    int niti_##P##_wgrad_slabs(const niti_geom* g) {                                                                  \
+        niti::ConvGeom r;                                                                                             \
+        return P##_geom(g, &r) ? niti::dwconv_wgrad_slabs(r) : 0;                                                     \
+    }                                                                                                                 \
+    int niti_##P##_wgrad_reduce(const niti_geom* g, const int32_t* slab, int slabs, int32_t* acc, uint32_t* amax,     \
+                                void* stream) {                                                                       \
+        niti::ConvGeom r;                                                                                             \
+        if (!P##_geom(g, &r) || !slab || !acc || slabs != niti::dwconv_wgrad_slabs(r)) return NITI_INVALID_VALUE;     \
+        const int64_t n = (int64_t)r.kh * r.kw * r.cip;                                                               \
+        return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));                             \
+    }
+NITI_DWCONV_ENTRIES(dwconv, niti::dwconv_ok)    // stride 1
+NITI_DWCONV_ENTRIES(dwconv2, niti::dwconv2_ok)  // stride 1 or 2: at stride 1 the launches above
 
-// grouped 3x3 conv layers (niti_grouped.hip): every refusal is INVALID_VALUE with nothing launched
-static bool gc_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
-    return g != nullptr && to_geom(g, r) && niti::gconv_ok(*r, groups);
-}
-int niti_gconv_ok(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gc_geom(g, groups, &r) ? 1 : 0;
-}
-int niti_gconv_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                   const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gc_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                     const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gc_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                     size_t slab_bytes, int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!gc_geom(g, groups, &r)) return NITI_INVALID_VALUE;
-    return code(niti::gconv_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_gconv_wgrad_slabs(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gc_geom(g, groups, &r) ? niti::gconv_wgrad_slabs(r, groups) : 0;
-}
-int niti_gconv_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
-                            uint32_t* amax, void* stream) {
-    niti::ConvGeom r;
-    if (!gc_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_wgrad_slabs(r, groups)) return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.c_out * 9 * (r.c_in / groups);
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
-
-// the same at stride 1 or 2 (gconv2_ok): at stride 1 the launches above
-static bool gc2_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
-    return g != nullptr && to_geom(g, r) && niti::gconv2_ok(*r, groups);
-}
-int niti_gconv2_ok(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gc2_geom(g, groups, &r) ? 1 : 0;
-}
-int niti_gconv2_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                    const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gc2_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv2_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                      const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gc2_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv2_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                      size_t slab_bytes, int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!gc2_geom(g, groups, &r)) return NITI_INVALID_VALUE;
-    return code(niti::gconv_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_gconv2_wgrad_slabs(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gc2_geom(g, groups, &r) ? niti::gconv_wgrad_slabs(r, groups) : 0;
-}
-int niti_gconv2_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
-                             uint32_t* amax, void* stream) {
-    niti::ConvGeom r;
-    if (!gc2_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_wgrad_slabs(r, groups)) return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.c_out * 9 * (r.c_in / groups);
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
-
-// group widths 4 and 8 (gconv_narrow_ok; niti_grouped_narrow.hip): weights, gradient and slabs [c_out][9][16]
-static bool gcn_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
-    return g != nullptr && to_geom(g, r) && niti::gconv_narrow_ok(*r, groups);
-}
-int niti_gconv_narrow_ok(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gcn_geom(g, groups, &r) ? 1 : 0;
-}
-int niti_gconv_narrow_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                          const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gcn_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_narrow_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_narrow_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                            const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gcn_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_narrow_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_narrow_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                            size_t slab_bytes, int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!gcn_geom(g, groups, &r)) return NITI_INVALID_VALUE;
-    return code(niti::gconv_narrow_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_gconv_narrow_wgrad_slabs(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gcn_geom(g, groups, &r) ? niti::gconv_narrow_wgrad_slabs(r, groups) : 0;
-}
-int niti_gconv_narrow_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
-                                   uint32_t* amax, void* stream) {
-    niti::ConvGeom r;
-    if (!gcn_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_narrow_wgrad_slabs(r, groups))
-        return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.c_out * 9 * 16;
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
-
-// the other multiples of 8 up to 128 (gconv_packed_ok; niti_grouped_packed.hip): weights, gradient and slabs
-// [c_out][9][cg], unpadded
-static bool gcp_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {
-    return g != nullptr && to_geom(g, r) && niti::gconv_packed_ok(*r, groups);
-}
-int niti_gconv_packed_ok(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gcp_geom(g, groups, &r) ? 1 : 0;
-}
-int niti_gconv_packed_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                          const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gcp_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_packed_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_packed_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                            const niti_dwconv_out* o, int pass, void* stream) {
-    niti::ConvGeom r;
-    if (!gcp_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;
-    return code(niti::gconv_packed_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));
-}
-int niti_gconv_packed_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                            size_t slab_bytes, int* slabs, void* stream) {
-    niti::ConvGeom r;
-    if (!gcp_geom(g, groups, &r)) return NITI_INVALID_VALUE;
-    return code(niti::gconv_packed_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));
-}
-int niti_gconv_packed_wgrad_slabs(const niti_geom* g, int groups) {
-    niti::ConvGeom r;
-    return gcp_geom(g, groups, &r) ? niti::gconv_packed_wgrad_slabs(r, groups) : 0;
-}
-int niti_gconv_packed_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,
-                                   uint32_t* amax, void* stream) {
-    niti::ConvGeom r;
-    if (!gcp_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_packed_wgrad_slabs(r, groups))
-        return NITI_INVALID_VALUE;
-    const int64_t n = (int64_t)r.c_out * 9 * (r.c_in / groups);
-    return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));
-}
+// Grouped 3x3 conv layers (niti_grouped_host.hip): the same six, the group width picking the kernels; the slabs
+// are [c_out][9][cgp] (gc_width)
+#define NITI_GCONV_ENTRIES(P, OK)                                                                                   \
+    static bool P##_geom(const niti_geom* g, int groups, niti::ConvGeom* r) {                                       \
+        return g != nullptr && to_geom(g, r) && OK(*r, groups);                                                     \
+    }                                                                                                               \
+    int niti_##P##_ok(const niti_geom* g, int groups) {                                                             \
+        niti::ConvGeom r;                                                                                           \
+        return P##_geom(g, groups, &r) ? 1 : 0;                                                                     \
+    }                                                                                                               \
+    int niti_##P##_fwd(const niti_geom* g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,            \
+                       const niti_dwconv_out* o, int pass, void* stream) {                                          \
+        niti::ConvGeom r;                                                                                           \
+        if (!P##_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;                                              \
+        return code(niti::gconv_fwd(r, groups, x, w, amax, dw_out(o), pass, S(stream)));                            \
+    }                                                                                                               \
+    int niti_##P##_dgrad(const niti_geom* g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,         \
+                         const niti_dwconv_out* o, int pass, void* stream) {                                        \
+        niti::ConvGeom r;                                                                                           \
+        if (!P##_geom(g, groups, &r) || !o) return NITI_INVALID_VALUE;                                              \
+        return code(niti::gconv_dgrad(r, groups, dy, w, amax, dw_out(o), pass, S(stream)));                         \
+    }                                                                                                               \
+    int niti_##P##_wgrad(const niti_geom* g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,          \
+                         size_t slab_bytes, int* slabs, void* stream) {                                             \
+        niti::ConvGeom r;                                                                                           \
+        if (!P##_geom(g, groups, &r)) return NITI_INVALID_VALUE;                                                    \
+        return code(niti::gconv_wgrad(r, groups, x, dy, slab, slab_bytes, slabs, S(stream)));                       \
+    }                                                                                                               \
+    int niti_##P##_wgrad_slabs(const niti_geom* g, int groups) {                                                    \
+        niti::ConvGeom r;                                                                                           \
+        return P##_geom(g, groups, &r) ? niti::gconv_wgrad_slabs(r, groups) : 0;                                    \
+    }                                                                                                               \
+    int niti_##P##_wgrad_reduce(const niti_geom* g, int groups, const int32_t* slab, int slabs, int32_t* acc,       \
+                                uint32_t* amax, void* stream) {                                                     \
+        niti::ConvGeom r;                                                                                           \
+        if (!P##_geom(g, groups, &r) || !slab || !acc || slabs != niti::gconv_wgrad_slabs(r, groups))               \
+            return NITI_INVALID_VALUE;                                                                              \
+        const int64_t n = (int64_t)r.c_out * 9 * niti::gc_width(r.c_in / groups).cgp;                               \
+        return code(niti::splitk_reduce_linear(slab, slabs, n, n, acc, amax, S(stream)));                           \
+    }
+NITI_GCONV_ENTRIES(gconv, niti::gconv_ok)                // group widths 16, 32, 64 at stride 1
+NITI_GCONV_ENTRIES(gconv2, niti::gconv2_ok)              // the same at stride 1 or 2
+NITI_GCONV_ENTRIES(gconv_narrow, niti::gconv_narrow_ok)  // group widths 4 and 8
+NITI_GCONV_ENTRIES(gconv_packed, niti::gconv_packed_ok)  // the other multiples of 8 up to 128
 
 int niti_nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, void* stream) {
     return code(niti::nhwc16_to_chwn16(in, n, hw, cp, np, out, S(stream)));

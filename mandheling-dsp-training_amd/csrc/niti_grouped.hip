@@ -1,4 +1,5 @@
-// niti_grouped.hip -- grouped 3x3 conv layers (gconv_*, niti_kernels.hpp): groups = G >= 2, c_in = c_out =
+// niti_grouped.hip -- grouped 3x3 conv layers (the kernels and gc_wide(); launched by niti_grouped_host.hip, behind
+// gconv_* of niti_kernels.hpp): groups = G >= 2, c_in = c_out =
 // G * cg with cg 16, 32 or 64 channels a group, stride 1 or 2 (the stride-2 kernels: below, "stride 2"), one pad
 // 0..2 on every side.
 //
@@ -690,165 +691,44 @@ __global__ void __launch_bounds__(256) gconv2_wgrad_kernel(GcWgArgs a) {
                 }
 }
 
-// the row bands and column segments of `rows` x `cols` unit pixels for group width cg
-inline int gc2_bands(int rows) { return (rows + GC_ROWS - 1) / GC_ROWS; }
-inline int gc2_segs(int cols, int cg) { return ((cols + 15) / 16 + gc2_strips(cg) - 1) / gc2_strips(cg); }
-
-int gc_wgrad_plan(const ConvGeom& g, int groups) {
-    const int cg = g.c_in / groups;
-    const int64_t units = (int64_t)g.n * ((g.oh + GC_ROWS - 1) / GC_ROWS) * (((g.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS);
-    const int64_t one = (int64_t)g.c_out * 9 * cg * sizeof(int32_t);
-    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(GC_MAX_SLABS, (int64_t)GC_SLAB_BYTES / one));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, units));
+// the column segments of `cols` unit pixels: 4 strips a workgroup at stride 1, gc2_strips(cg) at stride 2
+int gc_segs(int cols, int cg, int stride) {
+    const int s = stride == 2 ? gc2_strips(cg) : GC_STRIPS;
+    return ((cols + 15) / 16 + s - 1) / s;
 }
 
-// the same rule over the stride-2 kernel's units
-int gc2_wgrad_plan(const ConvGeom& g, int groups) {
-    const int cg = g.c_in / groups;
-    const int64_t units = (int64_t)g.n * gc2_bands(g.oh) * gc2_segs(g.ow, cg);
-    const int64_t one = (int64_t)g.c_out * 9 * cg * sizeof(int32_t);
-    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(GC_MAX_SLABS, (int64_t)GC_SLAB_BYTES / one));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, units));
-}
-
-int gc_plan(const ConvGeom& g, int groups) { return g.sh == 2 ? gc2_wgrad_plan(g, groups) : gc_wgrad_plan(g, groups); }
-
-hipError_t gc_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, const int8_t* w, uint32_t* amax,
-                  const ActOut& o, int pass, hipStream_t st) {
-    if (!gconv2_ok(g, groups) || in == nullptr || w == nullptr || amax == nullptr || pass < 0 || pass > 1)
-        return hipErrorInvalidValue;
-    // the fields this launch honours: out, relu (forward), relu_mask (input gradient), the exponents
-    if (o.pool.pool_out != nullptr || o.pool.x != nullptr || o.pool.y != nullptr || o.pool.dx != nullptr ||
-        o.pool.dx_c32 != nullptr || o.out_p16 != nullptr || o.zero_cls != 0 || o.pool3.out != nullptr ||
-        o.pool3.arg != nullptr)
-        return hipErrorInvalidValue;
-    if ((dgrad && o.relu != 0) || (!dgrad && o.relu_mask != nullptr)) return hipErrorInvalidValue;
-    if (pass == 1 && o.out == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    GcActArgs a{};
-    a.x = in;
-    a.w = w;
-    a.out = o.out;
-    a.relu_mask = o.relu_mask;
-    a.C = g.c_in;
-    a.ih = dgrad ? g.oh : g.h;
-    a.iw = dgrad ? g.ow : g.w;
-    a.oh = dgrad ? g.h : g.oh;
-    a.ow = dgrad ? g.w : g.ow;
-    a.pad = dgrad ? 2 - g.pt : g.pt;
-    a.relu = o.relu;
-    a.xbytes = (uint32_t)((int64_t)g.n * a.ih * a.iw * a.C);
-    a.wbytes = (uint32_t)((int64_t)g.c_out * 9 * cg);
-    a.bands = (a.oh + GC_ROWS - 1) / GC_ROWS;
-    a.segs = ((a.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS;
-    a.amax = amax;
-    a.exp_in = o.exp_in;
-    a.wscale = o.wscale;
-    a.exp_out = o.exp_out;
-    using Kern = void (*)(GcActArgs);
-    if (g.sh == 2) {
-        // forward: bands / segments over the output; input gradient: over (a, b) = ((y + pad) / 2, (x + pad) / 2),
-        // the kernel's pad the layer's own
-        a.pad = g.pt;
-        a.bands = gc2_bands(dgrad ? (g.h - 1 + g.pt) / 2 + 1 : g.oh);
-        a.segs = gc2_segs(dgrad ? (g.w - 1 + g.pt) / 2 + 1 : g.ow, cg);
-        const int64_t gx2 = (int64_t)g.n * a.bands * a.segs;
-        if (gx2 > 0x7fffffff) return hipErrorInvalidValue;
-        static const Kern tab2[3][2][2] = {
+GcActKern gc_act_kernel(int cg, int stride, bool dgrad, int pass) {
+    if (stride == 2) {
+        static const GcActKern tab2[3][2][2] = {
             {{gconv2_fwd_kernel<16, 0>, gconv2_fwd_kernel<16, 1>}, {gconv2_dgrad_kernel<16, 0>, gconv2_dgrad_kernel<16, 1>}},
             {{gconv2_fwd_kernel<32, 0>, gconv2_fwd_kernel<32, 1>}, {gconv2_dgrad_kernel<32, 0>, gconv2_dgrad_kernel<32, 1>}},
             {{gconv2_fwd_kernel<64, 0>, gconv2_fwd_kernel<64, 1>}, {gconv2_dgrad_kernel<64, 0>, gconv2_dgrad_kernel<64, 1>}}};
-        const Kern f2 = tab2[cg == 16 ? 0 : cg == 32 ? 1 : 2][dgrad ? 1 : 0][pass];
-        hipLaunchKernelGGL(f2, dim3((unsigned)gx2, (unsigned)groups), dim3(256), 0, st, a);
-        return hipGetLastError();
+        return tab2[cg == 16 ? 0 : cg == 32 ? 1 : 2][dgrad ? 1 : 0][pass];
     }
-    const int64_t gx = (int64_t)g.n * a.bands * a.segs;
-    if (gx > 0x7fffffff) return hipErrorInvalidValue;
-    static const Kern tab[3][2][2] = {
+    static const GcActKern tab[3][2][2] = {
         {{gconv_act_kernel<16, false, 0>, gconv_act_kernel<16, false, 1>},
          {gconv_act_kernel<16, true, 0>, gconv_act_kernel<16, true, 1>}},
         {{gconv_act_kernel<32, false, 0>, gconv_act_kernel<32, false, 1>},
          {gconv_act_kernel<32, true, 0>, gconv_act_kernel<32, true, 1>}},
         {{gconv_act_kernel<64, false, 0>, gconv_act_kernel<64, false, 1>},
          {gconv_act_kernel<64, true, 0>, gconv_act_kernel<64, true, 1>}}};
-    const Kern f = tab[cg == 16 ? 0 : cg == 32 ? 1 : 2][dgrad ? 1 : 0][pass];
-    hipLaunchKernelGGL(f, dim3((unsigned)gx, (unsigned)groups), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return tab[cg == 16 ? 0 : cg == 32 ? 1 : 2][dgrad ? 1 : 0][pass];
+}
+
+GcWgKern gc_wgrad_kernel(int cg, int stride) {
+    return stride == 2 ? (cg == 16 ? gconv2_wgrad_kernel<16> : cg == 32 ? gconv2_wgrad_kernel<32> : gconv2_wgrad_kernel<64>)
+           : cg == 16  ? gconv_wgrad_kernel<16>
+           : cg == 32  ? gconv_wgrad_kernel<32>
+                       : gconv_wgrad_kernel<64>;
 }
 
 }  // namespace
 
-bool gconv_ok(const ConvGeom& g, int groups) { return g.sh == 1 && g.sw == 1 && gconv2_ok(g, groups); }
-
-bool gconv_shape_ok(const ConvGeom& g, int groups) {
-    if (groups < 2 || groups > 65535 || g.n < 1 || g.c_in < 1 || g.c_in != g.c_out || g.c_in % groups != 0) return false;
-    if (g.kh != 3 || g.kw != 3 || g.sh < 1 || g.sh > 2 || g.sw != g.sh || g.dh != 1 || g.dw != 1) return false;
-    if (g.pt < 0 || g.pt > 2 || g.pl != g.pt || g.pb != g.pt || g.pr != g.pt) return false;
-    if (g.h < 1 || g.w < 1 || g.h + 2 * g.pt < 3 || g.w + 2 * g.pt < 3) return false;
-    if (g.oh != (g.h + 2 * g.pt - 3) / g.sh + 1 || g.ow != (g.w + 2 * g.pt - 3) / g.sh + 1) return false;
-    if (g.cip != g.c_in || g.cop != g.c_out) return false;
-    const int64_t lim = (int64_t)1 << 31;
-    return (int64_t)g.n * g.h * g.w * g.cip < lim && (int64_t)g.n * g.oh * g.ow * g.cop < lim;
-}
-
-bool gconv2_ok(const ConvGeom& g, int groups) {
-    if (!gconv_shape_ok(g, groups)) return false;
-    const int cg = g.c_in / groups;
-    if (cg != 16 && cg != 32 && cg != 64) return false;
-    // every operand below 2^31 bytes: the two maps (gconv_shape_ok) and the slab buffer the weight gradient writes
-    return (int64_t)gc_plan(g, groups) * g.c_out * 9 * cg * 4 < ((int64_t)1 << 31);
-}
-
-hipError_t gconv_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o,
-                     int pass, hipStream_t st) {
-    return gc_act(g, groups, false, x, w, amax, o, pass, st);
-}
-
-hipError_t gconv_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                       const ActOut& o, int pass, hipStream_t st) {
-    return gc_act(g, groups, true, dy, w, amax, o, pass, st);
-}
-
-int gconv_wgrad_slabs(const ConvGeom& g, int groups) { return gconv2_ok(g, groups) ? gc_plan(g, groups) : 0; }
-
-hipError_t gconv_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                       size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer) {
-    if (!gconv2_ok(g, groups) || x == nullptr || dy == nullptr || slab == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    const int ns = gc_plan(g, groups);
-    const size_t one = (size_t)g.c_out * 9 * cg;  // elements of a slab
-    if (ns * one * sizeof(int32_t) > slab_bytes) return hipErrorInvalidValue;
-    GcWgArgs a{};
-    a.x = x;
-    a.dy = dy;
-    a.slab = slab;
-    a.xbytes = (uint32_t)((int64_t)g.n * g.h * g.w * g.cip);
-    a.dbytes = (uint32_t)((int64_t)g.n * g.oh * g.ow * g.cop);
-    a.h = g.h;
-    a.w = g.w;
-    a.oh = g.oh;
-    a.ow = g.ow;
-    a.C = g.c_in;
-    a.pad = g.pt;
-    a.bands = (g.oh + GC_ROWS - 1) / GC_ROWS;
-    a.segs = ((g.ow + 15) / 16 + GC_STRIPS - 1) / GC_STRIPS;
-    if (g.sh == 2) a.segs = gc2_segs(g.ow, cg);
-    a.units = g.n * a.bands * a.segs;
-    using Kern = void (*)(GcWgArgs);
-    const Kern f = g.sh == 2 ? (cg == 16 ? gconv2_wgrad_kernel<16> : cg == 32 ? gconv2_wgrad_kernel<32> : gconv2_wgrad_kernel<64>)
-                   : cg == 16 ? gconv_wgrad_kernel<16>
-                   : cg == 32 ? gconv_wgrad_kernel<32>
-                              : gconv_wgrad_kernel<64>;
-    hipLaunchKernelGGL(f, dim3((unsigned)ns, (unsigned)groups), dim3(256), 0, st, a);
-    if (slabs != nullptr) *slabs = ns;
-    if (defer != nullptr) {  // C-shaped slabs for the update launch's combine
-        defer->slab = slab;
-        defer->splits = ns;
-        defer->slab_stride = (int64_t)one;
-        defer->slab_n = (int64_t)one;
-        defer->slab_map = 0;
-    }
-    return hipGetLastError();
+// a workgroup a group; the weight gradient one slab a workgroup
+const GcKernels& gc_wide() {
+    static const GcKernels k = {gc_segs, [](int, int groups) { return (unsigned)groups; }, [](int) { return 1u; },
+                                0,       gc_act_kernel,                                    gc_wgrad_kernel};
+    return k;
 }
 
 }  // namespace niti

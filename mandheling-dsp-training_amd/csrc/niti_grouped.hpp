@@ -1,12 +1,50 @@
 // niti_grouped.hpp -- what the grouped conv kernel families share (niti_grouped.hip: group widths 16, 32, 64 on the
 // 16x16x64 MFMA; niti_grouped_narrow.hip: 4 and 8 on the 4x4x4 block MFMA; niti_grouped_packed.hip: the other
 // multiples of 8 up to 128, K packed across taps): the launch arguments, the 4 x 4 byte transpose, pass 1's
-// requantisation of a lane's four accumulators and pass 0's range.
+// requantisation of a lane's four accumulators and pass 0's range.  And, for the host: the width rule (gc_width:
+// which family takes a group width, and how it lays out its weights and maps) and the record each family exports
+// for the one host front (niti_grouped_host.hip).
 #pragma once
 #include "niti_device.hpp"
 #include "niti_sgd.hpp"
 
 namespace niti {
+
+// ---- the width rule: the one place that says which group width cg belongs to which family --------------------
+enum GcFamily { GC_NONE, GC_WIDE, GC_NARROW, GC_PACKED };
+struct GcWidth {
+    GcFamily family;  // GC_NONE: no kernel takes the width
+    int cgp;          // the weight pitch: w, its int32 gradient and the slabs are [c_out][9][cgp]
+    bool pitch16;     // the maps' channel pitch: cip == cop == C rounded up to 16 (else C itself)
+    bool c16;         // a chain network's layer of this width needs c_in % 16 == 0
+    int rule;         // the lowest CHAIN_RULE_* whose entry points admit the width
+};
+inline GcWidth gc_width(int cg) {
+    if (cg == 16 || cg == 32 || cg == 64) return {GC_WIDE, cg, false, false, CHAIN_RULE_WIDE};
+    if (cg == 4 || cg == 8) return {GC_NARROW, 16, false, true, CHAIN_RULE_NARROW};
+    if (cg % 8 == 0 && cg >= 24 && cg <= 128) return {GC_PACKED, cg, true, false, CHAIN_RULE_PACKED};
+    return {GC_NONE, cg, false, false, 0};
+}
+
+struct GcActArgs;
+struct GcWgArgs;
+using GcActKern = void (*)(GcActArgs);
+using GcWgKern = void (*)(GcWgArgs);
+// What a kernel family tells the host front: its tiling, its grid and its kernels.  A workgroup takes 4 output
+// rows (a band) of one column segment everywhere.
+struct GcKernels {
+    int (*segs)(int cols, int cg, int stride);  // the column segments of `cols` unit pixels
+    unsigned (*grid_y)(int C, int groups);      // gridDim.y of every launch
+    unsigned (*wgrad_z)(int cg);                // gridDim.z of the weight gradient
+    int min_workgroups;  // the weight gradient's slab cap is at least min_workgroups / grid_y (0: no such term)
+    GcActKern (*act)(int cg, int stride, bool dgrad, int pass);
+    GcWgKern (*wgrad)(int cg, int stride);
+};
+// niti_grouped.hip, _narrow.hip, _packed.hip (behind a host function: a constant at namespace scope would be
+// emitted into the device code as well)
+const GcKernels& gc_wide();
+const GcKernels& gc_narrow();
+const GcKernels& gc_packed();
 
 constexpr int GC_MAX_SLABS = 1024;
 constexpr size_t GC_SLAB_BYTES = size_t(4) << 20;  // of all slabs, past 64 of them: the combine reads every one

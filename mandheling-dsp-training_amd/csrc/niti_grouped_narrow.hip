@@ -1,4 +1,5 @@
-// niti_grouped_narrow.hip -- grouped 3x3 conv layers at group widths 4 and 8 (gconv_narrow_*, niti_kernels.hpp):
+// niti_grouped_narrow.hip -- grouped 3x3 conv layers at group widths 4 and 8 (the kernels and gc_narrow(); launched
+// by niti_grouped_host.hip):
 // groups = G >= 2, c_in = c_out = C = G * cg, C a multiple of 16, stride 1 or 2, one pad 0..2 on every side.
 // What ResNeXt 32x4d's first two stages and the small RegNets run.  Semantics, the two-pass range protocol, the
 // ActOut fields and the slab form are niti_grouped.hip's; the kernels are their own.
@@ -362,59 +363,9 @@ __global__ void __launch_bounds__(256) gcn_wgrad_kernel(GcWgArgs a) {
             for (int h = 0; h < 4; ++h) sl[(e * 9 + t) * 16 + 4 * h + i] = h < NH ? acc[t][h < NH ? h : 0][e] : 0;
 }
 
-inline int gn_bands(int rows) { return (rows + GN_ROWS - 1) / GN_ROWS; }
-inline int gn_segs(int cols) { return (cols + GN_COLS - 1) / GN_COLS; }
-
-// the slabs of the weight gradient: niti_grouped.hip's rule over this kernel's units, and enough workgroups
-// (slabs x 64-channel chunks) to cover the device where the units allow
-int gn_wgrad_plan(const ConvGeom& g) {
-    const int64_t units = (int64_t)g.n * gn_bands(g.oh) * gn_segs(g.ow);
-    const int64_t one = (int64_t)g.c_out * 9 * 16 * sizeof(int32_t);
-    const int64_t chunks = (g.c_in + 63) / 64;
-    const int64_t cap = std::max<int64_t>({64, std::min<int64_t>(GC_MAX_SLABS, (int64_t)GC_SLAB_BYTES / one),
-                                           GN_MIN_WORKGROUPS / chunks});
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, units));
-}
-
-hipError_t gn_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, const int8_t* w, uint32_t* amax,
-                  const ActOut& o, int pass, hipStream_t st) {
-    if (!gconv_narrow_ok(g, groups) || in == nullptr || w == nullptr || amax == nullptr || pass < 0 || pass > 1)
-        return hipErrorInvalidValue;
-    // the fields this launch honours: out, relu (forward), relu_mask (input gradient), the exponents
-    if (o.pool.pool_out != nullptr || o.pool.x != nullptr || o.pool.y != nullptr || o.pool.dx != nullptr ||
-        o.pool.dx_c32 != nullptr || o.out_p16 != nullptr || o.zero_cls != 0 || o.pool3.out != nullptr ||
-        o.pool3.arg != nullptr)
-        return hipErrorInvalidValue;
-    if ((dgrad && o.relu != 0) || (!dgrad && o.relu_mask != nullptr)) return hipErrorInvalidValue;
-    if (pass == 1 && o.out == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    const bool d2 = dgrad && g.sh == 2;
-    GcActArgs a{};
-    a.x = in;
-    a.w = w;
-    a.out = o.out;
-    a.relu_mask = o.relu_mask;
-    a.C = g.c_in;
-    a.ih = dgrad ? g.oh : g.h;
-    a.iw = dgrad ? g.ow : g.w;
-    a.oh = dgrad ? g.h : g.oh;
-    a.ow = dgrad ? g.w : g.ow;
-    a.pad = dgrad && !d2 ? 2 - g.pt : g.pt;
-    a.relu = o.relu;
-    a.xbytes = (uint32_t)((int64_t)g.n * a.ih * a.iw * a.C);
-    a.wbytes = (uint32_t)((int64_t)g.c_out * 9 * 16);
-    // bands / segments over the output; the stride-2 input gradient: over ((y + pad) / 2, (x + pad) / 2)
-    a.bands = gn_bands(d2 ? (g.h - 1 + g.pt) / 2 + 1 : a.oh);
-    a.segs = gn_segs(d2 ? (g.w - 1 + g.pt) / 2 + 1 : a.ow);
-    a.amax = amax;
-    a.exp_in = o.exp_in;
-    a.wscale = o.wscale;
-    a.exp_out = o.exp_out;
-    const int64_t gx = (int64_t)g.n * a.bands * a.segs;
-    if (gx > 0x7fffffff) return hipErrorInvalidValue;
-    using Kern = void (*)(GcActArgs);
+GcActKern gn_act_kernel(int cg, int stride, bool dgrad, int pass) {
     // [cg 4 / 8][forward, input gradient at stride 1; forward, input gradient at stride 2][pass]
-    static const Kern tab[2][4][2] = {
+    static const GcActKern tab[2][4][2] = {
         {{gcn_act_kernel<4, 1, false, 0>, gcn_act_kernel<4, 1, false, 1>},
          {gcn_act_kernel<4, 1, true, 0>, gcn_act_kernel<4, 1, true, 1>},
          {gcn_act_kernel<4, 2, false, 0>, gcn_act_kernel<4, 2, false, 1>},
@@ -423,68 +374,26 @@ hipError_t gn_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, c
          {gcn_act_kernel<8, 1, true, 0>, gcn_act_kernel<8, 1, true, 1>},
          {gcn_act_kernel<8, 2, false, 0>, gcn_act_kernel<8, 2, false, 1>},
          {gcn_dgrad2_kernel<8, 0>, gcn_dgrad2_kernel<8, 1>}}};
-    const Kern f = tab[cg == 8][2 * (g.sh == 2) + (dgrad ? 1 : 0)][pass];
-    hipLaunchKernelGGL(f, dim3((unsigned)gx, (unsigned)((g.c_in + 63) / 64)), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return tab[cg == 8][2 * (stride == 2) + (dgrad ? 1 : 0)][pass];
+}
+
+GcWgKern gn_wgrad_kernel(int cg, int stride) {
+    return stride == 2 ? (cg == 4 ? gcn_wgrad_kernel<4, 2> : gcn_wgrad_kernel<8, 2>)
+                       : (cg == 4 ? gcn_wgrad_kernel<4, 1> : gcn_wgrad_kernel<8, 1>);
 }
 
 }  // namespace
 
-bool gconv_narrow_ok(const ConvGeom& g, int groups) {
-    if (!gconv_shape_ok(g, groups)) return false;
-    const int cg = g.c_in / groups;
-    if (cg != 4 && cg != 8) return false;
-    // (the two maps: gconv_shape_ok) the slab buffer the weight gradient writes, below 2^31 bytes
-    return (int64_t)gn_wgrad_plan(g) * g.c_out * 9 * 16 * 4 < ((int64_t)1 << 31);
-}
-
-hipError_t gconv_narrow_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                            const ActOut& o, int pass, hipStream_t st) {
-    return gn_act(g, groups, false, x, w, amax, o, pass, st);
-}
-
-hipError_t gconv_narrow_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                              const ActOut& o, int pass, hipStream_t st) {
-    return gn_act(g, groups, true, dy, w, amax, o, pass, st);
-}
-
-int gconv_narrow_wgrad_slabs(const ConvGeom& g, int groups) { return gconv_narrow_ok(g, groups) ? gn_wgrad_plan(g) : 0; }
-
-hipError_t gconv_narrow_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer) {
-    if (!gconv_narrow_ok(g, groups) || x == nullptr || dy == nullptr || slab == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    const int ns = gn_wgrad_plan(g);
-    const size_t one = (size_t)g.c_out * 9 * 16;  // elements of a slab
-    if (ns * one * sizeof(int32_t) > slab_bytes) return hipErrorInvalidValue;
-    GcWgArgs a{};
-    a.x = x;
-    a.dy = dy;
-    a.slab = slab;
-    a.xbytes = (uint32_t)((int64_t)g.n * g.h * g.w * g.cip);
-    a.dbytes = (uint32_t)((int64_t)g.n * g.oh * g.ow * g.cop);
-    a.h = g.h;
-    a.w = g.w;
-    a.oh = g.oh;
-    a.ow = g.ow;
-    a.C = g.c_in;
-    a.pad = g.pt;
-    a.bands = gn_bands(g.oh);
-    a.segs = gn_segs(g.ow);
-    a.units = g.n * a.bands * a.segs;
-    using Kern = void (*)(GcWgArgs);
-    const Kern f = g.sh == 2 ? (cg == 4 ? gcn_wgrad_kernel<4, 2> : gcn_wgrad_kernel<8, 2>)
-                             : (cg == 4 ? gcn_wgrad_kernel<4, 1> : gcn_wgrad_kernel<8, 1>);
-    hipLaunchKernelGGL(f, dim3((unsigned)ns, (unsigned)((g.c_in + 63) / 64)), dim3(256), 0, st, a);
-    if (slabs != nullptr) *slabs = ns;
-    if (defer != nullptr) {  // C-shaped slabs for the update launch's combine
-        defer->slab = slab;
-        defer->splits = ns;
-        defer->slab_stride = (int64_t)one;
-        defer->slab_n = (int64_t)one;
-        defer->slab_map = 0;
-    }
-    return hipGetLastError();
+// a workgroup a 64-channel chunk; the weight gradient wants enough workgroups (slabs x chunks) to cover the device
+// where the units allow
+const GcKernels& gc_narrow() {
+    static const GcKernels k = {[](int cols, int, int) { return (cols + GN_COLS - 1) / GN_COLS; },
+                                [](int C, int) { return (unsigned)((C + 63) / 64); },
+                                [](int) { return 1u; },
+                                GN_MIN_WORKGROUPS,
+                                gn_act_kernel,
+                                gn_wgrad_kernel};
+    return k;
 }
 
 }  // namespace niti

@@ -1,5 +1,5 @@
 // niti_grouped_packed.hip -- grouped 3x3 conv layers at the group widths the other two families leave out
-// (gconv_packed_*, niti_kernels.hpp): cg a multiple of 8 from 24 to 128 but 32 and 64, groups = G >= 2, c_in =
+// (the kernels and gc_packed(); launched by niti_grouped_host.hip): cg a multiple of 8 from 24 to 128 but 32 and 64, groups = G >= 2, c_in =
 // c_out = C = G * cg, stride 1 or 2, one pad 0..2 on every side.  What most of the RegNets run (cg 24, 40, 48, 56,
 // 112, 120, 128).  Semantics, the two-pass range protocol, the ActOut fields and the slab protocol are
 // niti_grouped.hip's; the kernels are their own.
@@ -440,19 +440,9 @@ __global__ void __launch_bounds__(256) gcp_wgrad_kernel(GcWgArgs a) {
                 }
 }
 
-inline int gp_bands(int rows) { return (rows + GP_ROWS - 1) / GP_ROWS; }
-inline int gp_segs(int cols, int cg, int stride) {
+int gp_segs(int cols, int cg, int stride) {
     const int s = gp_strips(cg, stride);
     return ((cols + 15) / 16 + s - 1) / s;
-}
-
-// the slabs of the weight gradient: niti_grouped.hip's rule over this kernel's units
-int gp_wgrad_plan(const ConvGeom& g, int groups) {
-    const int cg = g.c_in / groups;
-    const int64_t units = (int64_t)g.n * gp_bands(g.oh) * gp_segs(g.ow, cg, g.sh);
-    const int64_t one = (int64_t)g.c_out * 9 * cg * sizeof(int32_t);
-    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(GC_MAX_SLABS, (int64_t)GC_SLAB_BYTES / one));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, units));
 }
 
 // the kernels of one width: [forward, input gradient at stride 1; forward, input gradient at stride 2][pass]
@@ -490,114 +480,18 @@ const GpKernels* gp_kernels(int cg) {
     }
 }
 
-hipError_t gp_act(const ConvGeom& g, int groups, bool dgrad, const int8_t* in, const int8_t* w, uint32_t* amax,
-                  const ActOut& o, int pass, hipStream_t st) {
-    if (!gconv_packed_ok(g, groups) || in == nullptr || w == nullptr || amax == nullptr || pass < 0 || pass > 1)
-        return hipErrorInvalidValue;
-    // the fields this launch honours: out, relu (forward), relu_mask (input gradient), the exponents
-    if (o.pool.pool_out != nullptr || o.pool.x != nullptr || o.pool.y != nullptr || o.pool.dx != nullptr ||
-        o.pool.dx_c32 != nullptr || o.out_p16 != nullptr || o.zero_cls != 0 || o.pool3.out != nullptr ||
-        o.pool3.arg != nullptr)
-        return hipErrorInvalidValue;
-    if ((dgrad && o.relu != 0) || (!dgrad && o.relu_mask != nullptr)) return hipErrorInvalidValue;
-    if (pass == 1 && o.out == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    const bool d2 = dgrad && g.sh == 2;
-    GcActArgs a{};
-    a.x = in;
-    a.w = w;
-    a.out = o.out;
-    a.relu_mask = o.relu_mask;
-    a.C = g.c_in;
-    a.cp = g.cip;
-    a.ih = dgrad ? g.oh : g.h;
-    a.iw = dgrad ? g.ow : g.w;
-    a.oh = dgrad ? g.h : g.oh;
-    a.ow = dgrad ? g.w : g.ow;
-    a.pad = dgrad && !d2 ? 2 - g.pt : g.pt;
-    a.relu = o.relu;
-    a.xbytes = (uint32_t)((int64_t)g.n * a.ih * a.iw * a.cp);
-    a.wbytes = (uint32_t)((int64_t)g.c_out * 9 * cg);
-    // bands / segments over the output; the stride-2 input gradient: over ((y + pad) / 2, (x + pad) / 2)
-    a.bands = gp_bands(d2 ? (g.h - 1 + g.pt) / 2 + 1 : a.oh);
-    a.segs = gp_segs(d2 ? (g.w - 1 + g.pt) / 2 + 1 : a.ow, cg, g.sh);
-    a.amax = amax;
-    a.exp_in = o.exp_in;
-    a.wscale = o.wscale;
-    a.exp_out = o.exp_out;
-    const int64_t gx = (int64_t)g.n * a.bands * a.segs;
-    if (gx > 0x7fffffff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gp_kernels(cg)->act[2 * (g.sh == 2) + (dgrad ? 1 : 0)][pass], dim3((unsigned)gx, (unsigned)groups),
-                       dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
-bool gconv_packed_ok(const ConvGeom& g, int groups) {
-    // gconv_shape_ok's rule with the channel pitch of niti_geom: C rounded up to 16
-    if (groups < 2 || groups > 65535 || g.n < 1 || g.c_in < 1 || g.c_in != g.c_out || g.c_in % groups != 0) return false;
-    if (g.kh != 3 || g.kw != 3 || g.sh < 1 || g.sh > 2 || g.sw != g.sh || g.dh != 1 || g.dw != 1) return false;
-    if (g.pt < 0 || g.pt > 2 || g.pl != g.pt || g.pb != g.pt || g.pr != g.pt) return false;
-    if (g.h < 1 || g.w < 1 || g.h + 2 * g.pt < 3 || g.w + 2 * g.pt < 3) return false;
-    if (g.oh != (g.h + 2 * g.pt - 3) / g.sh + 1 || g.ow != (g.w + 2 * g.pt - 3) / g.sh + 1) return false;
-    if (g.cip != (g.c_in + 15) / 16 * 16 || g.cop != g.cip) return false;
-    const int cg = g.c_in / groups;
-    if (cg % 8 != 0 || cg < 24 || cg > 128 || cg == 32 || cg == 64) return false;
-    // every operand below 2^31 bytes: the two maps and the slab buffer the weight gradient writes
-    const int64_t lim = (int64_t)1 << 31;
-    return (int64_t)g.n * g.h * g.w * g.cip < lim && (int64_t)g.n * g.oh * g.ow * g.cop < lim &&
-           (int64_t)gp_wgrad_plan(g, groups) * g.c_out * 9 * cg * 4 < lim;
-}
-
-hipError_t gconv_packed_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                            const ActOut& o, int pass, hipStream_t st) {
-    return gp_act(g, groups, false, x, w, amax, o, pass, st);
-}
-
-hipError_t gconv_packed_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                              const ActOut& o, int pass, hipStream_t st) {
-    return gp_act(g, groups, true, dy, w, amax, o, pass, st);
-}
-
-int gconv_packed_wgrad_slabs(const ConvGeom& g, int groups) {
-    return gconv_packed_ok(g, groups) ? gp_wgrad_plan(g, groups) : 0;
-}
-
-hipError_t gconv_packed_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer) {
-    if (!gconv_packed_ok(g, groups) || x == nullptr || dy == nullptr || slab == nullptr) return hipErrorInvalidValue;
-    const int cg = g.c_in / groups;
-    const int ns = gp_wgrad_plan(g, groups);
-    const size_t one = (size_t)g.c_out * 9 * cg;  // elements of a slab
-    if (ns * one * sizeof(int32_t) > slab_bytes) return hipErrorInvalidValue;
-    GcWgArgs a{};
-    a.x = x;
-    a.dy = dy;
-    a.slab = slab;
-    a.xbytes = (uint32_t)((int64_t)g.n * g.h * g.w * g.cip);
-    a.dbytes = (uint32_t)((int64_t)g.n * g.oh * g.ow * g.cop);
-    a.h = g.h;
-    a.w = g.w;
-    a.oh = g.oh;
-    a.ow = g.ow;
-    a.C = g.c_in;
-    a.cp = g.cip;
-    a.pad = g.pt;
-    a.bands = gp_bands(g.oh);
-    a.segs = gp_segs(g.ow, cg, g.sh);
-    a.units = g.n * a.bands * a.segs;
-    const GpKernels* k = gp_kernels(cg);
-    hipLaunchKernelGGL(k->wgrad[g.sh == 2], dim3((unsigned)ns, (unsigned)groups, (unsigned)k->nz), dim3(256), 0, st, a);
-    if (slabs != nullptr) *slabs = ns;
-    if (defer != nullptr) {  // C-shaped slabs for the update launch's combine
-        defer->slab = slab;
-        defer->splits = ns;
-        defer->slab_stride = (int64_t)one;
-        defer->slab_n = (int64_t)one;
-        defer->slab_map = 0;
-    }
-    return hipGetLastError();
+// a workgroup a group; the weight gradient's z the width's item groups
+const GcKernels& gc_packed() {
+    static const GcKernels k = {
+        gp_segs,
+        [](int, int groups) { return (unsigned)groups; },
+        [](int cg) { return (unsigned)gp_kernels(cg)->nz; },
+        0,
+        [](int cg, int stride, bool dgrad, int pass) { return gp_kernels(cg)->act[2 * (stride == 2) + (dgrad ? 1 : 0)][pass]; },
+        [](int cg, int stride) { return gp_kernels(cg)->wgrad[stride == 2]; }};
+    return k;
 }
 
 }  // namespace niti

@@ -331,55 +331,53 @@ hipError_t dwconv_dgrad(const ConvGeom& g, const int8_t* dy, const int8_t* w, ui
 int dwconv_wgrad_slabs(const ConvGeom& g);
 hipError_t dwconv_wgrad(const ConvGeom& g, const int8_t* x, const int8_t* dy, int32_t* slab, size_t slab_bytes,
                         int* slabs, hipStream_t st, SgdJob* defer = nullptr);
-// ---- grouped 3x3 conv layers (niti_grouped.hip) -------------------------------------------------
-// groups >= 2, c_in == c_out == groups * cg with cg 16, 32 or 64, a 3x3 kernel, stride 1 or 2, one pad 0..2 on
-// every side: NITI_Conv_Int8 over the block-diagonal dense weight, on v_mfma_i32_16x16x64_i8.  x / dy NHWC16; w, the
-// int32 gradient and its slabs [c_out][9][cg] (the OHWI16 form of a dense layer with c_in = cg: SgdJob
-// co = c_out, ci = cip = cg, kk = 9).  gconv_ok: the stride-1 set, every operand below 2^31 bytes: what
-// niti_gconv_* admit.
+// ---- grouped 3x3 conv layers (niti_grouped_host.hip over the kernels of niti_grouped.hip, niti_grouped_narrow.hip
+// and niti_grouped_packed.hip) --------------------------------------------------------------------
+// groups >= 2, c_in == c_out == C == groups * cg, a 3x3 kernel, stride 1 or 2 (both ways; oh = (h + 2 pad - 3) /
+// stride + 1), one pad 0..2 on every side: NITI_Conv_Int8 over the block-diagonal dense weight.  The group width
+// picks the kernel family and the layouts (gc_width, niti_grouped.hpp):
+//   cg 16, 32, 64 on v_mfma_i32_16x16x64_i8; x / dy NHWC16 with cip == C; w, the int32 gradient and its slabs
+//     [c_out][9][cg] (the OHWI16 form of a dense layer with c_in = cg: SgdJob co = c_out, ci = cip = cg, kk = 9);
+//   cg 4, 8 on v_mfma_i32_4x4x4_16b_i8, sixteen 4x4x4 blocks an issue, a block a group (cg 4) or half of one (cg 8);
+//     cip == C; w, the gradient and the slabs [c_out][9][16], entries cg..15 zero (SgdJob ci = cg, cip = 16);
+//   cg another multiple of 8 from 24 to 128 on v_mfma_i32_16x16x64_i8 with K packed across the taps; the channel
+//     pitch of x / dy / out that of ConvGeom (cip == cop == C rounded up to 16: C need be no multiple of 16; the
+//     padding is written as zeros); w, the gradient and the slabs [c_out][9][cg], unpadded.
+// At stride 2 the input gradient runs one contraction per parity class.
+// gconv_any_ok: what the launches below take, every operand (the two maps, the slab buffer) below 2^31 bytes.
+bool gconv_any_ok(const ConvGeom& g, int groups);
+// what each C ABI prefix admits of that set: niti_gconv_* (cg 16, 32, 64 at stride 1), niti_gconv2_* (the same
+// widths), niti_gconv_narrow_* (cg 4, 8), niti_gconv_packed_* (the other widths)
 bool gconv_ok(const ConvGeom& g, int groups);
-// the same with stride 2 (both ways) admitted beside stride 1, oh = (h + 2 pad - 3) / stride + 1: what the
-// launches below take (niti_gconv2_*).  At stride 2 the input gradient runs one contraction per parity class.
 bool gconv2_ok(const ConvGeom& g, int groups);
+bool gconv_narrow_ok(const ConvGeom& g, int groups);
+bool gconv_packed_ok(const ConvGeom& g, int groups);
 // the two-pass protocol and the ActOut fields of dwconv_fwd / dwconv_dgrad; hipErrorInvalidValue, nothing
-// launched: !gconv2_ok, a null operand, a field this launch does not honour
+// launched: !gconv_any_ok, a null operand, a field this launch does not honour
 hipError_t gconv_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax, const ActOut& o,
                      int pass, hipStream_t st);
-// the input gradient reads the same w, transposed within the group on its way into LDS
+// the input gradient reads the same w, transposed within the group on its way in
 hipError_t gconv_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
                        const ActOut& o, int pass, hipStream_t st);
-// the weight gradient as *slabs partial sums [c_out][9][cg] int32, as dwconv_wgrad leaves its own
+// the weight gradient as *slabs partial sums in the weight's layout, int32, as dwconv_wgrad leaves its own
 int gconv_wgrad_slabs(const ConvGeom& g, int groups);
 hipError_t gconv_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
                        size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
-// ---- grouped 3x3 conv layers at group widths 4 and 8 (niti_grouped_narrow.hip) ------------------
-// gconv2_ok's set with cg 4 or 8 in place of 16, 32 or 64 (c_in a multiple of 16 still), on v_mfma_i32_4x4x4_16b_i8:
-// sixteen 4x4x4 blocks an issue, a block a group (cg 4) or half of one (cg 8).  w, the int32 gradient and its
-// slabs [c_out][9][16], entries cg..15 zero (SgdJob ci = cg, cip = 16); the protocols, ActOut fields and errors of
-// the five launches above.  gconv_shape_ok: what both families ask of (g, groups) but the group width and the
-// slab bound.
-bool gconv_shape_ok(const ConvGeom& g, int groups);
-bool gconv_narrow_ok(const ConvGeom& g, int groups);
-hipError_t gconv_narrow_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                            const ActOut& o, int pass, hipStream_t st);
-hipError_t gconv_narrow_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                              const ActOut& o, int pass, hipStream_t st);
-int gconv_narrow_wgrad_slabs(const ConvGeom& g, int groups);
-hipError_t gconv_narrow_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
-// ---- grouped 3x3 conv layers at the other group widths (niti_grouped_packed.hip) ----------------
-// gconv2_ok's set with cg a multiple of 8 from 24 to 128 but 32 and 64, and the channel pitch of x / dy / out that
-// of ConvGeom (cip == cop == c_in rounded up to 16: C need be no multiple of 16; the padding is written as zeros), on
-// v_mfma_i32_16x16x64_i8 with K packed across the taps.  w, the int32 gradient and its slabs [c_out][9][cg],
-// unpadded; the protocols, ActOut fields and errors of the launches above.
-bool gconv_packed_ok(const ConvGeom& g, int groups);
-hipError_t gconv_packed_fwd(const ConvGeom& g, int groups, const int8_t* x, const int8_t* w, uint32_t* amax,
-                            const ActOut& o, int pass, hipStream_t st);
-hipError_t gconv_packed_dgrad(const ConvGeom& g, int groups, const int8_t* dy, const int8_t* w, uint32_t* amax,
-                              const ActOut& o, int pass, hipStream_t st);
-int gconv_packed_wgrad_slabs(const ConvGeom& g, int groups);
-hipError_t gconv_packed_wgrad(const ConvGeom& g, int groups, const int8_t* x, const int8_t* dy, int32_t* slab,
-                              size_t slab_bytes, int* slabs, hipStream_t st, SgdJob* defer = nullptr);
+// Which entry points' rule a chain list is checked by (chain_check, niti_step_driver.hpp): CHAIN_RULE_PLAIN refuses
+// stride != 1, CHAIN_RULE_STRIDED honours the layers' strides (niti_model_create_chain3), CHAIN_RULE_WIDE also
+// takes gpool and up to NITI_CHAIN_MAX_LAYERS layers (niti_model_create_chain4 / 5; a list's grouped layers come
+// with niti_chain_layer4's groups); below CHAIN_RULE_WIDE the lists carry skip = gpool = 0
+// CHAIN_RULE_GROUPED2 (niti_model_create_chain6): WIDE, and a grouped layer may have stride 2
+// CHAIN_RULE_NARROW (niti_model_create_chain7): GROUPED2, and a grouped layer's group width may be 4 or 8
+// CHAIN_RULE_PACKED (niti_model_create_chain8): NARROW, and the group widths of gconv_packed_ok, at any c_in
+enum {
+    CHAIN_RULE_PLAIN = 0,
+    CHAIN_RULE_STRIDED = 1,
+    CHAIN_RULE_WIDE = 2,
+    CHAIN_RULE_GROUPED2 = 3,
+    CHAIN_RULE_NARROW = 4,
+    CHAIN_RULE_PACKED = 5
+};
 bool conv_dgrad_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // The speculative pair on the implicit GEMM (plan strategy 3 = STRAT_SPEC, forward / input
 // gradient, no K split; NITI_Conv_Int8.cpp:260-307, NITI_DeConv_Int8.cpp:294-329): pass 0 (launch A)

@@ -775,15 +775,14 @@ int chain_check(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int
         // map; the kernels take 3x3 and 5x5
         if (l.depthwise && (i == 0 || i == n - 1 || on_1x1 || (l.kernel != 3 && l.kernel != 5)))
             return NITI_NOT_SUPPORT;
-        // a grouped layer: as a depthwise layer, and what the kernels take (gconv2_ok): 3x3, stride 1 (the `6`
-        // entry points' rule: or 2), equal group widths of 16, 32 or 64 channels (the `7` entry points' rule: or 4
-        // or 8, gconv_narrow_ok; the `8` entry points' rule: or another multiple of 8 up to 128, gconv_packed_ok)
+        // a grouped layer: as a depthwise layer, and what the kernels take (gconv_any_ok): 3x3, stride 1 (the `6`
+        // entry points' rule: or 2), equal group widths that the rule's entry points admit (gc_width)
         if (l.groups > 1) {
             const int cg = s[0] / l.groups;
+            const GcWidth wd = gc_width(cg);
             if (i == 0 || i == n - 1 || on_1x1 || l.kernel != 3 ||
                 (l.stride != 1 && (rule < CHAIN_RULE_GROUPED2 || l.stride != 2)) || s[1] / l.groups != cg ||
-                (cg != 16 && cg != 32 && cg != 64 && (rule < CHAIN_RULE_NARROW || (cg != 4 && cg != 8) || s[0] % 16 != 0) &&
-                 (rule < CHAIN_RULE_PACKED || cg % 8 != 0 || cg < 24 || cg > 128)))
+                wd.family == GC_NONE || rule < wd.rule || (wd.c16 && s[0] % 16 != 0))
                 return NITI_NOT_SUPPORT;
         }
         if (on_1x1 && (l.kernel != 1 || l.pad != 0)) return NITI_NOT_SUPPORT;
@@ -865,10 +864,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer4* layers, i
                  layers[i].flatten != 0, layers[i].depthwise, strided ? layers[i].stride : 1, layers[i].gpool, layers[i].skip,
                  layers[i].groups > 1 ? layers[i].groups : 1);
     for (const Layer& l : L)
-        if ((l.dw && !dwconv2_ok(l.g)) || (l.groups > 1 && !(l.narrow()   ? gconv_narrow_ok(l.g, l.groups)
-                                                           : l.packed() ? gconv_packed_ok(l.g, l.groups)
-                                                                        : gconv2_ok(l.g, l.groups))))
-            return NITI_NOT_SUPPORT;
+        if ((l.dw && !dwconv2_ok(l.g)) || (l.groups > 1 && !gconv_any_ok(l.g, l.groups))) return NITI_NOT_SUPPORT;
     for (int i = 0; i < nlayers; ++i)
         if (L[i].skip) {
             L[i - L[i].skip].src_of = i;
@@ -972,10 +968,7 @@ int Model::build_chain(int arch_, int batch_, const niti_chain_layer4* layers, i
         l.bar = (uint32_t*)ws.alloc(ROWCONV_BAR_WORDS * 4);
         if (!l.bar || hipMemset(l.bar, 0, ROWCONV_BAR_WORDS * 4) != hipSuccess) return NITI_OUT_OF_MEMORY;
         if (l.own()) {  // its weight gradient's slabs: the layer's own until the update (the deferred combine)
-            const int ns = l.dw         ? dwconv_wgrad_slabs(g)
-                           : l.narrow() ? gconv_narrow_wgrad_slabs(g, l.groups)
-                           : l.packed() ? gconv_packed_wgrad_slabs(g, l.groups)
-                                        : gconv_wgrad_slabs(g, l.groups);
+            const int ns = l.dw ? dwconv_wgrad_slabs(g) : gconv_wgrad_slabs(g, l.groups);
             l.slab16_bytes = (size_t)ns * l.w_elems() * sizeof(int32_t);
             l.slab16 = (int32_t*)ws.alloc(l.slab16_bytes);
             if (!l.slab16) return NITI_OUT_OF_MEMORY;
@@ -1286,10 +1279,8 @@ int Model::fwd_conv_layer(int i, hipStream_t st) {
         // depthwise / grouped: range launch, [all-reduce MAX], recompute-and-requantise launch; the unfused pool / flatten
         const auto none = [](const ActOut&, auto) { return hipErrorNotSupported; };
         const int rc = gemm_ranged(false, false, o, rng(i, 0), l.bar, l.epoch, st, none, none, [&](const ActOut& ao, int ph) {
-            return l.dw         ? dwconv_fwd(g, l.in, l.w, rng(i, 0), ao, ph - 1, st)
-                   : l.narrow() ? gconv_narrow_fwd(g, l.groups, l.in, l.w, rng(i, 0), ao, ph - 1, st)
-                   : l.packed() ? gconv_packed_fwd(g, l.groups, l.in, l.w, rng(i, 0), ao, ph - 1, st)
-                                : gconv_fwd(g, l.groups, l.in, l.w, rng(i, 0), ao, ph - 1, st);
+            return l.dw ? dwconv_fwd(g, l.in, l.w, rng(i, 0), ao, ph - 1, st)
+                        : gconv_fwd(g, l.groups, l.in, l.w, rng(i, 0), ao, ph - 1, st);
         });
         if (rc != NITI_NO_ERROR) return rc;
         probe(i, 0, false, st);
@@ -1352,10 +1343,6 @@ int Model::wgrad_layer(int i, hipStream_t st) {
         SgdJob d{};
         if (l.dw)
             DTRY(dwconv_wgrad(g, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
-        else if (l.narrow())
-            DTRY(gconv_narrow_wgrad(g, l.groups, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
-        else if (l.packed())
-            DTRY(gconv_packed_wgrad(g, l.groups, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
         else
             DTRY(gconv_wgrad(g, l.groups, l.in, l.dy, l.slab16, l.slab16_bytes, &slabs, st, &d));
         if (defer_combine())
@@ -1597,8 +1584,6 @@ int Model::dgrad_layer(int i, hipStream_t st) {
         },
         [&](const ActOut& ao, int ph) {
             if (l.dw) return dwconv_dgrad(g, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
-            if (l.narrow()) return gconv_narrow_dgrad(g, l.groups, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
-            if (l.packed()) return gconv_packed_dgrad(g, l.groups, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
             if (l.groups > 1) return gconv_dgrad(g, l.groups, l.dy, l.w, rng(i, 1), ao, ph - 1, st);
             return ph == 1 ? conv_dgrad_phase1(g, l.dy, l.wT, acc, rng(i, 1), slab, slab_bytes, st, l.subw)
                            : conv_dgrad_phase2(g, l.dy, l.wT, acc, rng(i, 1), ao, slab_bytes, st, l.subw);

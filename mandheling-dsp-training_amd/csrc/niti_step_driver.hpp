@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "niti_coll.hpp"
+#include "niti_grouped.hpp"
 #include "niti_internal.hpp"
 #include "niti_kernels.hpp"
 
@@ -50,8 +51,8 @@ struct ParamLayer {
     int dw = 0;
     // a grouped 3x3 conv of `groups` >= 2 groups (chain driver; niti_grouped.hip): g.c_in == g.c_out == groups * cg;
     // w, dwacc, g8 and the slabs are [c_out][9][cg], the OHWI16 form of a dense layer with c_in = cg (w_ci, w_cip),
-    // [c_out][cg][3][3] on the host, and there is no wT.  Group widths 4 and 8 (narrow(); niti_grouped_narrow.hip)
-    // pad to [c_out][9][16] as any dense layer's c_in does; the widths of niti_grouped_packed.hip (packed()) do not pad
+    // [c_out][cg][3][3] on the host, and there is no wT.  The group width sets the pitch (gc_width, niti_grouped.hpp):
+    // widths 4 and 8 pad to [c_out][9][16] as any dense layer's c_in does, the packed family's widths do not pad
     int groups = 1;
     int kp = 0;  // the im2col column pitch of a first layer that runs over its im2col (0: not one)
     int8_t wscale = 0;
@@ -80,10 +81,8 @@ struct ParamLayer {
     bool own() const { return dw != 0 || groups > 1; }
     int w_co() const { return dw ? 1 : g.c_out; }  // output channels as the weight layouts count them
     int w_ci() const { return g.c_in / groups; }   // input channels so, and their padded count
-    int w_cip() const { return packed() ? w_ci() : groups > 1 ? (g.c_in / groups + 15) / 16 * 16 : g.cip; }
-    bool narrow() const { return groups > 1 && g.c_in / groups < 16; }  // the launches of niti_grouped_narrow.hip
-    // the launches of niti_grouped_packed.hip: every width but 4, 8, 16, 32 and 64; [c_out][9][cg] unpadded
-    bool packed() const { return groups > 1 && w_ci() > 16 && w_ci() != 32 && w_ci() != 64; }
+    int w_cip() const { return groups > 1 ? gc_width(w_ci()).cgp : g.cip; }
+    bool packed() const { return groups > 1 && gc_width(w_ci()).family == GC_PACKED; }  // [c_out][9][cg] unpadded
     int64_t w_elems() const { return (int64_t)w_co() * g.kh * g.kw * w_cip(); }
     int64_t macs() const {
         return (int64_t)og.n * og.oh * og.ow * og.c_out * (dw ? 1 : og.c_in / groups) * og.kh * og.kw;
@@ -355,21 +354,7 @@ std::unique_ptr<StepDriver> make_resnet_driver(const niti_resnet_spec* spec, int
 // niti_model_resnet_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`
 int resnet_check(const niti_resnet_spec* spec, int in_hw, int batch, int* n_layers, int shapes[][8]);
 // a chain model of the caller's layer list (NITI_ARCH_CHAIN), after chain_check at its batch.  rule: which
-// entry points' rule holds -- CHAIN_RULE_PLAIN refuses stride != 1, CHAIN_RULE_STRIDED honours the layers'
-// strides (niti_model_create_chain3), CHAIN_RULE_WIDE also takes gpool and up to NITI_CHAIN_MAX_LAYERS
-// layers (niti_model_create_chain4 / 5; a list's grouped layers come with niti_chain_layer4's groups); below
-// CHAIN_RULE_WIDE the lists carry skip = gpool = 0
-// CHAIN_RULE_GROUPED2 (niti_model_create_chain6): WIDE, and a grouped layer may have stride 2
-// CHAIN_RULE_NARROW (niti_model_create_chain7): GROUPED2, and a grouped layer's group width may be 4 or 8
-// CHAIN_RULE_PACKED (niti_model_create_chain8): NARROW, and the group widths of gconv_packed_ok, at any c_in
-enum {
-    CHAIN_RULE_PLAIN = 0,
-    CHAIN_RULE_STRIDED = 1,
-    CHAIN_RULE_WIDE = 2,
-    CHAIN_RULE_GROUPED2 = 3,
-    CHAIN_RULE_NARROW = 4,
-    CHAIN_RULE_PACKED = 5
-};
+// entry points' rule holds, a CHAIN_RULE_* (niti_kernels.hpp)
 std::unique_ptr<StepDriver> make_chain_list_driver(const niti_chain_layer4* layers, int n, int in_c, int in_hw, int batch,
                                                    int* rc, int rule);
 // niti_model_chain_check's rule (include/niti_hip.h) with the tensor-size bound taken at `batch`

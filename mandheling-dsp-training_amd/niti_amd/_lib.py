@@ -184,6 +184,9 @@ def lib():
     L = C.CDLL(LIB_PATH)
     vp, i32, i64, ci = C.c_void_p, C.c_int32, C.c_int64, C.c_int
     tp = C.POINTER(Tensor)
+    act = [vp, vp, vp, C.POINTER(DwconvOut), ci, vp]
+    layer_entries = {"ok": [], "fwd": act, "dgrad": act, "wgrad": [vp, vp, vp, C.c_size_t, C.POINTER(ci), vp],
+                     "wgrad_slabs": [], "wgrad_reduce": [vp, ci, vp, vp, vp]}
     sig = {
         "niti_version": (C.c_char_p, []),
         "niti_create_execution": (ci, [ci, C.POINTER(ConvCommon), C.POINTER(vp)]),
@@ -253,42 +256,11 @@ def lib():
         "niti_diag_conv0_wgrad_blocks": (None, [C.c_int]),
         "niti_diag_conv0_wgrad_codes": (None, [C.c_int]),
         "niti_diag_conv0_wgrad_codes_launches": (C.c_ulonglong, []),
-        "niti_dwconv_ok": (ci, [C.POINTER(Geom)]),
-        "niti_dwconv_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_dwconv_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_dwconv_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_dwconv_wgrad_slabs": (ci, [C.POINTER(Geom)]),
-        "niti_dwconv_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
-        "niti_gconv_ok": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_gconv_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
-        "niti_gconv2_ok": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv2_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv2_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv2_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_gconv2_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv2_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
-        "niti_gconv_narrow_ok": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_narrow_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_narrow_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_narrow_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_gconv_narrow_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_narrow_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
-        "niti_gconv_packed_ok": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_packed_fwd": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_packed_dgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_gconv_packed_wgrad": (ci, [C.POINTER(Geom), ci, vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_gconv_packed_wgrad_slabs": (ci, [C.POINTER(Geom), ci]),
-        "niti_gconv_packed_wgrad_reduce": (ci, [C.POINTER(Geom), ci, vp, ci, vp, vp, vp]),
-        "niti_dwconv2_ok": (ci, [C.POINTER(Geom)]),
-        "niti_dwconv2_fwd": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_dwconv2_dgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.POINTER(DwconvOut), ci, vp]),
-        "niti_dwconv2_wgrad": (ci, [C.POINTER(Geom), vp, vp, vp, C.c_size_t, C.POINTER(ci), vp]),
-        "niti_dwconv2_wgrad_slabs": (ci, [C.POINTER(Geom)]),
-        "niti_dwconv2_wgrad_reduce": (ci, [C.POINTER(Geom), vp, ci, vp, vp, vp]),
+        # the six entries of a conv layer's prefix, behind the geometry (the grouped prefixes: and the groups)
+        **{f"niti_{p}_{kind}": (ci, lead + rest)
+           for lead, prefixes in (([C.POINTER(Geom)], ("dwconv", "dwconv2")),
+                                  ([C.POINTER(Geom), ci], ("gconv", "gconv2", "gconv_narrow", "gconv_packed")))
+           for p in prefixes for kind, rest in layer_entries.items()},
         "niti_nhwc16_to_chwn16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
         "niti_ohwi16_to_ihwo16": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
         "niti_nchw_to_nhwc16": (ci, [vp, ci, ci, ci, ci, vp, vp]),

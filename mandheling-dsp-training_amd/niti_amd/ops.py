@@ -796,6 +796,7 @@ def _gconv_act(pre, kind, g, groups, a16, w16, amax, pass_, shape, kw):
 def _gconv_cgp_of(cg: int) -> int:
     """A group width as the device layouts pad it: to 16 (a width of 4 or 8: gconv_narrow_*), but not a width of
     gconv_packed_* (a multiple of 8 from 24 up)."""
+    # mirrors gc_width(cg).cgp (csrc/niti_grouped.hpp) on the widths it admits; kept here so that it stays host only
     return cg if cg >= 24 and cg % 8 == 0 else r16(cg)
 
 
