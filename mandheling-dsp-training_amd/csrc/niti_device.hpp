@@ -353,7 +353,7 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, int8_t* lds_wave
                                              soff, 0, 0);
 }
 
-// P16 conversion jobs (niti_wgrad.hip: nhwc16_to_p16_many; niti_kernels.hip: loss_grad_p16)
+// P16 conversion jobs (niti_wgrad.hip: nhwc16_to_p16_many; niti_pointwise.hip: loss_grad_p16)
 struct P16Job {
     const int8_t* in;
     int8_t* out;

@@ -3,7 +3,7 @@
 //
 //   forward      logits = NITI_Conv_Int8 (1x1 over 1x1 maps) of the pooled input, the rescale rule
 //                over the whole batch (NITI_Conv_Int8.cpp:260-307)
-//   loss         NITI_LOSS_Grad (the rows of loss_rows16, niti_kernels.hip)
+//   loss         NITI_LOSS_Grad (the rows of loss_rows16, niti_sgd.hpp)
 //   weight grad  dw = dy^T x, int32, its range published (NITI_GradientConv_Int8.cpp:274-296; the
 //                update launch requantises it with NITI_SGD)
 //   input grad   dx = dy w, rescaled (NITI_DeConv_Int8.cpp:294-329), routed through the previous

@@ -1,4 +1,6 @@
-// niti_kernels.hip -- gfx950 (MI355X / CDNA4) kernels for the NITI int8 training path.
+// niti_kernels.hip -- the implicit-GEMM core of the NITI int8 training path on gfx950 (MI355X / CDNA4): the operand
+// loaders, gemm_kernel and its epilogues, the split-K reduce, wgrad_taps_kernel, the plan table and plan_gemm, the
+// per-op wrappers (conv_*_acc, conv_*_phase1/2, _spec, _fused) and the sub-pixel input gradient.
 //
 // The three GEMM-class ops of the reference (NITI_Conv_Int8, NITI_GradientConv_Int8 /
 // NITI_Matmul_Int8 / NITI_DSPMatmulGradientConv_Int8, NITI_DeConv_Int8) are one
@@ -10,6 +12,12 @@
 // reduces max|acc| per workgroup and atomically max-es it into one word; the requant
 // kernel reads that word (after a kernel boundary -- or an RCCL all-reduce(MAX) in
 // data-parallel exact mode) and applies the shift.
+//
+// The step's other kernels, each behind the entry points of niti_kernels.hpp:
+//   niti_requant.hip    the range and requantisation passes over an int32 tensor (absmax*, requant_*, residual_requant)
+//   niti_conv0.hip      the first layer's forward pass on its im2col copy (conv0_ok, conv0_fwd)
+//   niti_sgd.hip        the split-K combine and NITI_SGD update launches (sgd_*_many, update_bits_set)
+//   niti_pointwise.hip  max pool and its gradients, relu_grad, loss_grad*, grad_exponent, the layout conversions
 #include <stdlib.h>
 
 #include <map>
@@ -2983,2267 +2991,6 @@ hipError_t conv_dgrad_phase2(const ConvGeom& g, const int8_t* dy, const int8_t* 
     return with_dgrad_operand(g, dy, [&](const auto& la) {
         return act_phase2(PLAN_DGRAD, la, lb, g.n * g.h * g.w, g.cip, kc_total, acc, amax, o, ws_bytes / 4, st);
     });
-}
-
-// =====================================================================================
-// Range estimate and requantisation
-// =====================================================================================
-
-// max|a| of one range over blocks [0, nb) of the grid (block b of them), published to amax
-__device__ __forceinline__ void absmax_body(const int32_t* __restrict__ a, int64_t n, uint32_t* __restrict__ amax,
-                                            int64_t b, int64_t nb) {
-    uint32_t m = 0;
-    const int64_t n4 = n / 4;
-    const v4i* a4 = (const v4i*)a;
-    for (int64_t i = b * blockDim.x + threadIdx.x; i < n4; i += nb * blockDim.x) {
-        const v4i v = a4[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t u = uabs32(v[j]);
-            m = m > u ? m : u;
-        }
-    }
-    for (int64_t i = n4 * 4 + b * blockDim.x + threadIdx.x; i < n; i += nb * blockDim.x) {
-        const uint32_t u = uabs32(a[i]);
-        m = m > u ? m : u;
-    }
-    m = wave_max(m);
-    __shared__ uint32_t red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = m > red[i] ? m : red[i];
-        m = m > red[0] ? m : red[0];
-        publish_max(amax, m);
-    }
-}
-
-__global__ void absmax_kernel(const int32_t* __restrict__ a, int64_t n, uint32_t* __restrict__ amax) {
-    absmax_body(a, n, amax, blockIdx.x, gridDim.x);
-}
-
-// several ranges in one launch: job k owns workgroups [b0_k, b0_{k+1})
-__global__ void absmax_many_kernel(AbsmaxJobs J) {
-    int k = 0;
-    while (k + 1 < J.n && blockIdx.x >= J.j[k + 1].b0) ++k;
-    const AbsmaxJob jb = J.j[k];
-    const uint32_t end = k + 1 < J.n ? J.j[k + 1].b0 : gridDim.x;
-    absmax_body(jb.a, jb.n, jb.amax, blockIdx.x - jb.b0, end - jb.b0);
-}
-
-hipError_t absmax_many(const AbsmaxJob* jobs, int n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (n > ABSMAX_MAX_JOBS) return hipErrorInvalidValue;
-    AbsmaxJobs J{};
-    uint32_t wg = 0;
-    for (int i = 0; i < n; ++i) {
-        if (jobs[i].n <= 0) continue;
-        int64_t blocks = (jobs[i].n / 4 + 255) / 256;
-        if (blocks > 128) blocks = 128;
-        if (blocks < 1) blocks = 1;
-        J.j[J.n] = jobs[i];
-        J.j[J.n++].b0 = wg;
-        wg += (uint32_t)blocks;
-    }
-    if (J.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(absmax_many_kernel, dim3(wg), dim3(256), 0, st, J);
-    return hipGetLastError();
-}
-
-hipError_t absmax_i32(const int32_t* a, int64_t n, uint32_t* amax, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    int64_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 512) blocks = 512;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, n, amax);
-    return hipGetLastError();
-}
-
-// forward / deconv rule, NITI_Conv_Int8.cpp:262-307: shift>1 PSTO(shift); ==1 PSTO(2); else raw cast
-// NITI forward shift rule on 16 consecutive channels of one accumulator row
-__device__ __forceinline__ v16c requant16(const int32_t* src, bool raw, int s, int relu) {
-    const v4i* p = (const v4i*)src;
-    v16c q;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const v4i v = p[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            int32_t o = raw ? (int32_t)(int8_t)v[e] : psto_any(v[e], s);
-            if (relu && o < 0) o = 0;
-            q[j * 4 + e] = (signed char)o;
-        }
-    }
-    return q;
-}
-
-__global__ void requant_act_kernel(ActRequant r) {
-    const int bw = bitwidth_of(read_max(r.amax));
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    const int groups = r.ldc / 16;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && r.exp_out != nullptr) {
-        const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-        const int ein = r.exp_in ? (int)*r.exp_in : 0;
-        const int ws = r.wscale ? (int)*r.wscale : 0;
-        *r.exp_out = (int8_t)(ein + ws + inc);
-    }
-    if (r.pool.pool_out != nullptr || r.pool.dx != nullptr) {
-        // one thread per (pooled pixel, 16-channel group)
-        const int H = r.pool.H, W = r.pool.W, ph = H / 2, pw = W / 2;
-        const int64_t np = r.pool.dx != nullptr ? r.rows : r.rows / 4;  // pooled pixels
-        const int64_t total = np * groups;
-        for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
-             t += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t pp = t / groups;
-            const int gi = (int)(t - pp * groups);
-            const int px = (int)(pp % pw);
-            const int64_t rest = pp / pw;
-            const int py = (int)(rest % ph);
-            const int64_t b = rest / ph;
-            const int64_t m0 = (b * H + 2 * py) * W + 2 * px;  // window's first pixel
-            const int64_t win[4] = {m0, m0 + 1, m0 + W, m0 + W + 1};
-            if (r.pool.pool_out != nullptr) {
-                v16c mx;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) mx[j] = (signed char)-128;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const v16c q = requant16(r.acc + win[k] * r.ldc + gi * 16, raw, s, r.relu);
-                    *(v16c*)(r.out_nhwc16 + win[k] * r.ldc + gi * 16) = q;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) mx[j] = q[j] > mx[j] ? q[j] : mx[j];
-                }
-                *(v16c*)(r.pool.pool_out + pp * r.ldc + gi * 16) = mx;
-            } else {
-                const v16c q = requant16(r.acc + pp * r.ldc + gi * 16, raw, s, 0);
-                if (r.out_nhwc16 != nullptr) *(v16c*)(r.out_nhwc16 + pp * r.ldc + gi * 16) = q;
-                const v16c mv = *(const v16c*)(r.pool.y + pp * r.ldc + gi * 16);
-                unsigned done = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const v16c xv = *(const v16c*)(r.pool.x + win[k] * r.ldc + gi * 16);
-                    v16c o;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        const bool take = !((done >> j) & 1u) && xv[j] >= mv[j];
-                        if (take) done |= 1u << j;
-                        signed char d = take ? q[j] : (signed char)0;
-                        if (r.pool.relu && xv[j] <= 0) d = 0;
-                        o[j] = d;
-                    }
-                    *(v16c*)(r.pool.dx + win[k] * r.ldc + gi * 16) = o;
-                }
-            }
-        }
-        return;
-    }
-    const int64_t total = r.rows * groups;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t m = t / groups;
-        const int gi = (int)(t - m * groups);
-        const v4i* src = (const v4i*)(r.acc + m * r.ldc + gi * 16);
-        v16c q;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const v4i v = src[j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int32_t o = raw ? (int32_t)(int8_t)v[e] : psto_any(v[e], s);
-                if (r.relu && o < 0) o = 0;
-                q[j * 4 + e] = (signed char)o;
-            }
-        }
-        if (r.relu_mask != nullptr) {
-            const v16c mk = *(const v16c*)(r.relu_mask + m * r.ldc + gi * 16);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) q[j] = mk[j] > 0 ? q[j] : (signed char)0;
-        }
-        if (r.out_nhwc16 != nullptr) *(v16c*)(r.out_nhwc16 + m * r.ldc + gi * 16) = q;
-        if (r.out_c4 != nullptr) {
-            const int64_t b = m / r.hw, p = m - b * r.hw;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int c = gi * 16 + j;
-                if (c < r.c_real) r.out_c4[(((int64_t)(c >> 2) * r.n + b) * r.hw + p) * 4 + (c & 3)] = q[j];
-            }
-        }
-    }
-}
-
-// Streaming requantisation (the training step's path; out_c4 uses requant_act_kernel above).
-// A unit is 4 channels (one 16-byte int32 load, one 4-byte int8 store): consecutive lanes take
-// consecutive channel quads, so every wave instruction moves whole contiguous runs (a full
-// 1 KiB of accumulator per load), and each thread keeps RQ_U units' loads in flight.
-//   RQ_PLAIN     unit over [rows][ldc/4]: out = requant (+relu) (& relu_mask > 0)
-//   RQ_POOL_FWD  unit over [pooled pixel][ldc/4]: requant (+relu) the 2x2 window -> out, max -> pool_out
-//   RQ_POOL_BWD  unit over [pooled pixel = row][ldc/4]: requant, route to the window's first max
-//                of x (relu: and x > 0) in dx, zero elsewhere (+ optional out)
-enum { RQ_PLAIN = 0, RQ_POOL_FWD = 1, RQ_POOL_BWD = 2 };
-constexpr int RQ_U = 4;
-
-struct RqGeom {
-    FastDiv fq, fpw, fph;  // by quads per row, pooled width, pooled height
-    int qpr, W;            // quads per row, pre-pool width
-    uint32_t units;
-    FastDiv fzw, fzh;      // ActRequant::zc_w / zc_h (zero_cls)
-};
-
-__device__ __forceinline__ uint32_t rq4(v4i v, bool raw, int s, int relu) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        int32_t q = raw ? (int32_t)(int8_t)v[e] : psto_fast(v[e], s);
-        if (relu && q < 0) q = 0;
-        o |= ((uint32_t)q & 0xffu) << (8 * e);
-    }
-    return o;
-}
-__device__ __forceinline__ uint32_t bmax4(uint32_t a, uint32_t b) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int x = (int8_t)(a >> (8 * e)), y = (int8_t)(b >> (8 * e));
-        o |= ((uint32_t)(x > y ? x : y) & 0xffu) << (8 * e);
-    }
-    return o;
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) requant_quad_kernel(ActRequant r, RqGeom g) {
-    const int bw = bitwidth_of(read_max(r.amax));  // whole wave active
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && r.exp_out != nullptr) {
-        const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-        const int ein = r.exp_in ? (int)*r.exp_in : 0;
-        const int ws = r.wscale ? (int)*r.wscale : 0;
-        *r.exp_out = (int8_t)(ein + ws + inc);
-    }
-    const uint32_t stride = gridDim.x * 256u;
-    const int ldc = r.ldc;
-    for (uint32_t u0 = blockIdx.x * 256u + threadIdx.x; u0 < g.units; u0 += stride * RQ_U) {
-        if (MODE == RQ_PLAIN) {
-            v4i v[RQ_U];
-            uint32_t mk[RQ_U];
-#pragma unroll
-            for (int j = 0; j < RQ_U; ++j) {
-                const uint32_t u = u0 + j * stride;
-                bool ld = u < g.units;
-                if (ld && r.zero_cls != 0) {  // a tap-less sub-pixel class: 0, its accumulators unread
-                    const uint32_t row = fdiv(g.fq, u), t = fdiv(g.fzw, row);
-                    const uint32_t x = row - t * g.fzw.d, y = t - fdiv(g.fzh, t) * g.fzh.d;
-                    ld = !((r.zero_cls >> (2 * (y & 1u) + (x & 1u))) & 1);
-                }
-                v[j] = ld ? __builtin_nontemporal_load((const v4i*)r.acc + u) : v4i{0, 0, 0, 0};
-                mk[j] = (r.relu_mask != nullptr && u < g.units) ? ((const uint32_t*)r.relu_mask)[u] : 0x01010101u;
-            }
-#pragma unroll
-            for (int j = 0; j < RQ_U; ++j) {
-                const uint32_t u = u0 + j * stride;
-                if (u >= g.units) break;
-                uint32_t o = rq4(v[j], raw, s, r.relu);
-                if (r.relu_mask != nullptr) {
-                    uint32_t keep = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if ((int8_t)(mk[j] >> (8 * e)) > 0) keep |= 0xffu << (8 * e);
-                    o &= keep;
-                }
-                ((uint32_t*)r.out_nhwc16)[u] = o;
-            }
-        } else {
-            // window rows of each unit
-            int64_t wrow[RQ_U];
-            uint32_t pp_[RQ_U], img_[RQ_U];
-            int cq_[RQ_U];
-#pragma unroll
-            for (int j = 0; j < RQ_U; ++j) {
-                const uint32_t u = u0 + j * stride;
-                const uint32_t uu = u < g.units ? u : 0u;
-                const uint32_t pp = fdiv(g.fq, uu);
-                cq_[j] = (int)(uu - pp * (uint32_t)g.qpr);
-                const uint32_t rest = fdiv(g.fpw, pp);
-                const int px = (int)(pp - rest * g.fpw.d);
-                const uint32_t b = fdiv(g.fph, rest);
-                const int py = (int)(rest - b * g.fph.d);
-                wrow[j] = ((int64_t)b * (2 * g.fph.d) + 2 * py) * g.W + 2 * px;
-                pp_[j] = pp;
-                img_[j] = b;
-            }
-            if (MODE == RQ_POOL_FWD) {
-                v4i v[RQ_U][4];
-#pragma unroll
-                for (int j = 0; j < RQ_U; ++j)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int64_t row = wrow[j] + (k & 1) + (k >> 1) * g.W;
-                        v[j][k] = u0 + j * stride < g.units
-                                      ? __builtin_nontemporal_load((const v4i*)(r.acc + row * ldc) + cq_[j])
-                                      : v4i{0, 0, 0, 0};
-                    }
-#pragma unroll
-                for (int j = 0; j < RQ_U; ++j) {
-                    if (u0 + j * stride >= g.units) break;
-                    uint32_t mx = 0x80808080u;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int64_t row = wrow[j] + (k & 1) + (k >> 1) * g.W;
-                        const uint32_t o = rq4(v[j][k], raw, s, r.relu);
-                        ((uint32_t*)(r.out_nhwc16 + row * ldc))[cq_[j]] = o;
-                        mx = bmax4(mx, o);
-                    }
-                    ((uint32_t*)(r.pool.pool_out + (int64_t)pp_[j] * ldc))[cq_[j]] = mx;
-                }
-            } else {
-                v4i v[RQ_U];
-                uint32_t yv[RQ_U], xv[RQ_U][4];
-#pragma unroll
-                for (int j = 0; j < RQ_U; ++j) {
-                    const bool ok = u0 + j * stride < g.units;
-                    v[j] = ok ? __builtin_nontemporal_load((const v4i*)(r.acc + (int64_t)pp_[j] * ldc) + cq_[j])
-                              : v4i{0, 0, 0, 0};
-                    yv[j] = ok ? ((const uint32_t*)(r.pool.y + (int64_t)pp_[j] * ldc))[cq_[j]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int64_t row = wrow[j] + (k & 1) + (k >> 1) * g.W;
-                        xv[j][k] = ok ? ((const uint32_t*)(r.pool.x + row * ldc))[cq_[j]] : 0u;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < RQ_U; ++j) {
-                    if (u0 + j * stride >= g.units) break;
-                    const uint32_t q = rq4(v[j], raw, s, 0);
-                    if (r.out_nhwc16 != nullptr) ((uint32_t*)(r.out_nhwc16 + (int64_t)pp_[j] * ldc))[cq_[j]] = q;
-                    uint32_t done = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        uint32_t o = 0;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int x = (int8_t)(xv[j][k] >> (8 * e)), m = (int8_t)(yv[j] >> (8 * e));
-                            const bool take = !((done >> e) & 1u) && x >= m;
-                            if (take) done |= 1u << e;
-                            if (take && !(r.pool.relu && x <= 0)) o |= q & (0xffu << (8 * e));
-                        }
-                        const int64_t row = wrow[j] + (k & 1) + (k >> 1) * g.W;
-                        ((uint32_t*)(r.pool.dx + row * ldc))[cq_[j]] = o;
-                        if (r.pool.dx_c32 != nullptr) {  // [img][c / 32][H][W][32]: 4 channels of one pixel
-                            const int64_t hw = (int64_t)(2 * g.fph.d) * g.W;
-                            const int64_t pix = row - (int64_t)img_[j] * hw;
-                            const int c = 4 * cq_[j];
-                            *(uint32_t*)(r.pool.dx_c32 + (((int64_t)img_[j] * (ldc / 32) + c / 32) * hw + pix) * 32 + (c & 31)) = o;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Requantisation passes that also leave the P16 copy ([pixels/16][ldc][16], niti_wgrad.hip) of
-// their output, so the input-gradient chain hands dy to the P16 weight gradient without a layout
-// launch of its own.  A thread takes one channel quad of a run of output pixels covering whole
-// 16-pixel blocks -- G pooled pixels whose 2x2 windows are 4G consecutive dx pixels (G = 4: a pooled row of an 8x8 image, one 4x4 image, four 2x2 images;
-// G = 8: a pooled row of a 16x16 image).  It computes and stores the NHWC16 output exactly as
-// requant_quad_kernel does, then transposes each 4 pixels x 4 channels in registers (v_perm) and
-// writes every block's 4 channels x 16 pixels as 64 contiguous bytes (consecutive lanes,
-// consecutive quads: a wave stores whole 4 KiB runs).
-template <int W>
-__host__ __device__ constexpr int p16_group() { return W == 16 ? 8 : 4; }
-// position, inside the run, of corner k (0: top left, 1: top right, 2, 3: bottom) of pooled pixel j
-template <int W>
-__device__ constexpr int p16_loc(int j, int k) {
-    if constexpr (W >= 8) return (k >> 1) * W + 2 * j + (k & 1);               // one pooled row
-    else if constexpr (W == 4) return (2 * (j >> 1) + (k >> 1)) * 4 + 2 * (j & 1) + (k & 1);  // one image
-    else return 4 * j + 2 * (k >> 1) + (k & 1);                                  // four 2x2 images
-}
-
-template <int MODE, int W>
-__global__ void __launch_bounds__(256) requant_p16_kernel(ActRequant r, RqGeom g) {
-    static_assert(MODE == RQ_POOL_BWD, "the plain pass is requant_p16_plain_kernel");
-    constexpr int G = p16_group<W>();  // pooled pixels per thread
-    constexpr int NPX = 4 * G;         // dx pixels per thread
-    const int bw = bitwidth_of(read_max(r.amax));
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && r.exp_out != nullptr) {
-        const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-        const int ein = r.exp_in ? (int)*r.exp_in : 0;
-        const int ws = r.wscale ? (int)*r.wscale : 0;
-        *r.exp_out = (int8_t)(ein + ws + inc);
-    }
-    const int ldc = r.ldc;
-    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < g.units; u += gridDim.x * 256u) {
-        const uint32_t grp = fdiv(g.fq, u);
-        const int cq = (int)(u - grp * (uint32_t)g.qpr);
-        const int64_t d0 = (int64_t)grp * NPX;  // the run's first output pixel
-        uint32_t d[NPX];
-        {
-            const int64_t p0 = (int64_t)grp * G;  // the run's first pooled pixel
-            v4i v[G];
-            uint32_t yv[G], xv[G][4];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                v[j] = __builtin_nontemporal_load((const v4i*)(r.acc + (p0 + j) * ldc) + cq);
-                yv[j] = ((const uint32_t*)(r.pool.y + (p0 + j) * ldc))[cq];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xv[j][k] = ((const uint32_t*)(r.pool.x + (d0 + p16_loc<W>(j, k)) * ldc))[cq];
-            }
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const uint32_t q = rq4(v[j], raw, s, 0);
-                if (r.out_nhwc16 != nullptr) ((uint32_t*)(r.out_nhwc16 + (p0 + j) * ldc))[cq] = q;
-                uint32_t done = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t o = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int x = (int8_t)(xv[j][k] >> (8 * e)), m = (int8_t)(yv[j] >> (8 * e));
-                        const bool take = !((done >> e) & 1u) && x >= m;
-                        if (take) done |= 1u << e;
-                        if (take && !(r.pool.relu && x <= 0)) o |= q & (0xffu << (8 * e));
-                    }
-                    ((uint32_t*)(r.pool.dx + (d0 + p16_loc<W>(j, k)) * ldc))[cq] = o;
-                    d[p16_loc<W>(j, k)] = o;
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NPX / 16; ++b) {
-            v4i c[4];  // channel e: the block's 16 pixels
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {  // 4x4 byte transpose of pixels 16b + 4t .. 4t + 3
-                const uint32_t a0 = d[16 * b + 4 * t], a1 = d[16 * b + 4 * t + 1], a2 = d[16 * b + 4 * t + 2],
-                               a3 = d[16 * b + 4 * t + 3];
-                const uint32_t t0 = __builtin_amdgcn_perm(a1, a0, 0x05010400u);  // a0.0 a1.0 a0.1 a1.1
-                const uint32_t t1 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);  // a0.2 a1.2 a0.3 a1.3
-                const uint32_t t2 = __builtin_amdgcn_perm(a3, a2, 0x05010400u);
-                const uint32_t t3 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-                c[0][t] = (int)__builtin_amdgcn_perm(t2, t0, 0x05040100u);
-                c[1][t] = (int)__builtin_amdgcn_perm(t2, t0, 0x07060302u);
-                c[2][t] = (int)__builtin_amdgcn_perm(t3, t1, 0x05040100u);
-                c[3][t] = (int)__builtin_amdgcn_perm(t3, t1, 0x07060302u);
-            }
-            int8_t* o = r.out_p16 + ((d0 / 16 + b) * ldc + 4 * cq) * 16;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) *(v4i*)(o + 16 * e) = c[e];
-        }
-    }
-}
-
-// The plain pass with 4 rows per thread (4x the threads of the 16-row form above, which ran
-// latency-bound at one block per CU): lanes 4 cq + sub take rows 4 sub .. 4 sub + 3 of a 16-row
-// block and channel quad cq, so the four lanes of a quad write each channel's 16 P16 bytes as
-// four adjacent dwords.
-__global__ void __launch_bounds__(256) requant_p16_plain_kernel(ActRequant r, RqGeom g) {
-    const int bw = bitwidth_of(read_max(r.amax));
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && r.exp_out != nullptr) {
-        const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-        const int ein = r.exp_in ? (int)*r.exp_in : 0;
-        const int ws = r.wscale ? (int)*r.wscale : 0;
-        *r.exp_out = (int8_t)(ein + ws + inc);
-    }
-    const int ldc = r.ldc;
-    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < g.units; u += gridDim.x * 256u) {
-        const int sub = (int)(u & 3u);
-        const uint32_t qu = u >> 2;
-        const uint32_t blk = fdiv(g.fq, qu);
-        const int cq = (int)(qu - blk * (uint32_t)g.qpr);
-        const int64_t row0 = (int64_t)blk * 16 + 4 * sub;
-        v4i v[4];
-        uint32_t mk[4], d[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = __builtin_nontemporal_load((const v4i*)(r.acc + (row0 + i) * ldc) + cq);
-            mk[i] = r.relu_mask != nullptr ? ((const uint32_t*)(r.relu_mask + (row0 + i) * ldc))[cq] : 0x01010101u;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            uint32_t o = rq4(v[i], raw, s, r.relu);
-            if (r.relu_mask != nullptr) {
-                uint32_t keep = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if ((int8_t)(mk[i] >> (8 * e)) > 0) keep |= 0xffu << (8 * e);
-                o &= keep;
-            }
-            ((uint32_t*)(r.out_nhwc16 + (row0 + i) * ldc))[cq] = o;
-            d[i] = o;
-        }
-        const uint32_t t0 = __builtin_amdgcn_perm(d[1], d[0], 0x05010400u);
-        const uint32_t t1 = __builtin_amdgcn_perm(d[1], d[0], 0x07030602u);
-        const uint32_t t2 = __builtin_amdgcn_perm(d[3], d[2], 0x05010400u);
-        const uint32_t t3 = __builtin_amdgcn_perm(d[3], d[2], 0x07030602u);
-        uint32_t* o = (uint32_t*)(r.out_p16 + ((int64_t)blk * ldc + 4 * cq) * 16) + sub;
-        o[0] = __builtin_amdgcn_perm(t2, t0, 0x05040100u);
-        o[4] = __builtin_amdgcn_perm(t2, t0, 0x07060302u);
-        o[8] = __builtin_amdgcn_perm(t3, t1, 0x05040100u);
-        o[12] = __builtin_amdgcn_perm(t3, t1, 0x07060302u);
-    }
-}
-
-template <int MODE>
-static void launch_requant_p16(const ActRequant& r, RqGeom g, int64_t blocks, hipStream_t st) {
-    switch (r.pool.W) {
-        case 2: hipLaunchKernelGGL((requant_p16_kernel<RQ_POOL_BWD, 2>), dim3((unsigned)blocks), dim3(256), 0, st, r, g); break;
-        case 4: hipLaunchKernelGGL((requant_p16_kernel<RQ_POOL_BWD, 4>), dim3((unsigned)blocks), dim3(256), 0, st, r, g); break;
-        case 8: hipLaunchKernelGGL((requant_p16_kernel<RQ_POOL_BWD, 8>), dim3((unsigned)blocks), dim3(256), 0, st, r, g); break;
-        default: hipLaunchKernelGGL((requant_p16_kernel<RQ_POOL_BWD, 16>), dim3((unsigned)blocks), dim3(256), 0, st, r, g); break;
-    }
-}
-
-bool requant_p16_ok(const ActRequant& r) {
-    if (r.ldc % 16 != 0 || r.out_c4 != nullptr || r.pool.pool_out != nullptr) return false;
-    if (r.pool.dx == nullptr) return r.out_nhwc16 != nullptr && r.rows % 16 == 0;
-    const int W = r.pool.W;
-    if (r.pool.H != W || !(W == 2 || W == 4 || W == 8 || W == 16)) return false;
-    const int gsz = W == 16 ? p16_group<16>() : p16_group<8>();
-    return r.rows % gsz == 0;
-}
-
-// Residual add fused with its requantisation (the rule of niti_resnet.hip): the range comes from a
-// residual_add pass that stores no z (and, data parallel, a MAX all-reduce); this pass recomputes z
-// from the int8 operands and applies the forward rule exactly as requant_act (RQ_PLAIN) on z:
-// out = relu?(PSTO(z, shift) | (int8) z), *ez = e_hi - d, *exp_out = *ez + inc.
-__global__ void __launch_bounds__(256) residual_requant_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ ea,
-                                                               const int8_t* __restrict__ b, const int8_t* __restrict__ eb,
-                                                               int64_t n16, const uint32_t* __restrict__ amax,
-                                                               int8_t* __restrict__ ez, int8_t* __restrict__ exp_out,
-                                                               int relu, const int8_t* __restrict__ relu_mask,
-                                                               int8_t* __restrict__ out, int spec,
-                                                               uint32_t* __restrict__ hint, int pk) {
-    const int xa = *ea, xb = *eb;
-    const bool a_hi = xa >= xb;
-    const int diff = a_hi ? xa - xb : xb - xa;
-    const int d = diff < 23 ? diff : 23, r = diff - d;
-    int bw;
-    if (spec == 1) {  // launch A: the guess; the range is published below
-        bw = (int)spec_pick(hint, relu ? (a_hi ? xa : xb) - d : 0) - 1;  // forward: on z's scale
-        if (bw < 0) bw = 0;  // (no hint yet: B redoes unless the max is 0)
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            __hip_atomic_store(hint + 1, (uint32_t)bw + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        bw = bitwidth_of(read_max(amax));  // whole wave active
-        if (spec == 2) {  // launch B: A's output stands unless the (all-reduced) range differs
-            const int used = __builtin_amdgcn_readfirstlane(
-                                 (int)__hip_atomic_load(hint + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) - 1;
-            if (blockIdx.x == 0 && threadIdx.x < 64) spec_learn(hint, bw, relu ? (a_hi ? xa : xb) - d : 0, threadIdx.x);
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                if (bw != used) __hip_atomic_fetch_add(hint + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int shift = bw - 7;
-                const int e_z = (a_hi ? xa : xb) - d;
-                if (ez != nullptr) *ez = (int8_t)e_z;
-                if (exp_out != nullptr) *exp_out = (int8_t)(e_z + (shift > 1 ? shift : (shift == 1 ? 2 : 0)));
-            }
-            if (bw == used) return;
-        }
-    }
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    if (spec == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-        const int e_z = (a_hi ? xa : xb) - d;
-        if (ez != nullptr) *ez = (int8_t)e_z;
-        if (exp_out != nullptr) *exp_out = (int8_t)(e_z + (shift > 1 ? shift : (shift == 1 ? 2 : 0)));
-    }
-    uint32_t m = 0;
-    if (pk && !raw) {  // the bit-field form (res_rule4)
-        const ResRule k = res_rule(d, r, s);
-        const int8_t* hi = a_hi ? a : b;
-        const int8_t* lo = a_hi ? b : a;
-        int mx = 0, mn = 0;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
-            const v4i vh = ((const v4i*)hi)[i], vl = ((const v4i*)lo)[i];
-            v4i mk;
-            if (relu_mask != nullptr) mk = ((const v4i*)relu_mask)[i];
-            v4i q;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                uint32_t o = relu ? res_rule4<true>((uint32_t)vh[w], (uint32_t)vl[w], k, mx, mn, spec == 1)
-                                  : res_rule4<false>((uint32_t)vh[w], (uint32_t)vl[w], k, mx, mn, spec == 1);
-                if (relu_mask != nullptr) o &= sw_expand(sw_pos_hi((uint32_t)mk[w]));
-                q[w] = (int)o;
-            }
-            ((v4i*)out)[i] = q;
-        }
-        m = max(uabs32(mx), uabs32(mn));
-    } else {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
-        const v16c va = ((const v16c*)a)[i], vb = ((const v16c*)b)[i];
-        v16c mk;
-        if (relu_mask != nullptr) mk = ((const v16c*)relu_mask)[i];
-        v16c q;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int32_t z = residual_z(a_hi ? va[e] : vb[e], a_hi ? vb[e] : va[e], d, r);
-            if (spec == 1) {
-                const uint32_t u = uabs32(z);
-                m = m > u ? m : u;
-            }
-            int32_t o = raw ? (int32_t)(int8_t)z : psto_fast(z, s);
-            if (relu && o < 0) o = 0;
-            if (relu_mask != nullptr && mk[e] <= 0) o = 0;  // the next op's NITI_ReluGrad_Int8, fused
-            q[e] = (signed char)o;
-        }
-        ((v16c*)out)[i] = q;
-    }
-    }
-    if (spec == 1) {  // NITI_RangeEstimate of z for launch B
-        m = wave_max(m);
-        __shared__ uint32_t red[4];
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) publish_max(const_cast<uint32_t*>(amax), max(max(red[0], red[1]), max(red[2], red[3])));
-    }
-}
-
-hipError_t residual_requant(const int8_t* a, const int8_t* ea, const int8_t* b, const int8_t* eb, int64_t n,
-                            const uint32_t* amax, int8_t* ez, int8_t* exp_out, int relu, int8_t* out, hipStream_t st,
-                            const int8_t* relu_mask, int spec, uint32_t* slot) {
-    if (n < 0 || n % 16 != 0 || !a || !b || !ea || !eb || !amax || !out) return hipErrorInvalidValue;
-    if (spec < 0 || spec > 2 || (spec != 0 && slot == nullptr)) return hipErrorInvalidValue;
-    const int64_t n16 = n / 16;
-    int64_t blocks = (n16 + 255) / 256;
-    blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
-    // NITI_RES_PK=0: the 32-bit loop only (an A/B switch for the packed form)
-    static const int pk = getenv("NITI_RES_PK") ? atoi(getenv("NITI_RES_PK")) : 1;
-    hipLaunchKernelGGL(residual_requant_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, ea, b, eb, n16, amax, ez,
-                       exp_out, relu, relu_mask, out, spec, slot, pk);
-    return hipGetLastError();
-}
-
-// ---- first layer on its im2col copy (K = 32) -------------------------------------------------
-// y[p][co] = sum_k xcol[p][k] * w[co][k], k < 32: one v_mfma_i32_32x32x32_i8 per 32 pixels x 32
-// output channels, both operands straight from memory (a lane's 16-byte fragment is 16
-// consecutive k of one row).  Pass 0 publishes max|y| (NITI_RangeEstimate); pass 1 recomputes y
-// and requantises it with the forward rule (as requant_quad_kernel), relu, stores the NHWC16
-// output and, with pool_out, the 2x2 max pool of the relu'd values.  A wave takes a pair of
-// output rows segment by segment (32 pixels of each row), so each pooled pixel's four inputs
-// sit in one lane: the x pairs in adjacent accumulator registers, the y pair in the two rows'
-// accumulators.  Requires OW % 32 == 0 and OH even (VGG's 32x32 and 224x224 first layers).
-struct Conv0 {
-    const int8_t* x;  // xcol [P][32]
-    const int8_t* w;  // [co][32]
-    uint32_t wbytes;
-    int co, cop, oh, ow;
-    int64_t units;    // (image, row pair, 32-pixel segment)
-    uint32_t* amax;   // pass 0 out / pass 1 in
-    int8_t* out;      // NHWC16 [P][cop]
-    int8_t* pool_out; // [P / 4][cop] or null
-    int8_t* pool_c32; // the pooled output as the next layer's C32 input [n][cop/32][oh/2][ow/2][32], or null
-    int8_t* out_c32;  // the (unpooled) output as the next layer's C32 input [n][cop/32][oh][ow][32], or null
-    int8_t* pool_code; // the pool gradient's route (pool_code4) [P / 4][cop], or null
-    const int8_t *exp_in, *wscale;
-    int8_t* exp_out;
-    int relu;
-    // conv0_kernel only: the tensors' sizes for its buffer resources (x; out / out_c32; the pooled
-    // three), every one below 2^31 bytes, and the unit decode's divisions
-    uint32_t xbytes, obytes, pbytes;
-    FastDiv fseg, fpair;
-};
-
-// The general form: any cop % 32 == 0 (the weights loaded per tile inside the unit loop) and
-// tensors of any size (64-bit addresses), one grid-stride unit after another.  The step's first
-// layers (cop <= 64, tensors below 2^31 bytes) run conv0_kernel below instead.
-template <int PASS>
-__global__ void __launch_bounds__(256) conv0_wide_kernel(Conv0 g) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-    const int h = lane >> 5, c = lane & 31;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.w, g.wbytes);
-    int s = 2, shift = 0;
-    bool raw = false;
-    if (PASS == 1) {
-        const int bw = __builtin_amdgcn_readfirstlane(bitwidth_of(read_max(g.amax)));
-        shift = bw - 7;
-        s = shift > 1 ? shift : 2;
-        raw = shift <= 0;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && g.exp_out != nullptr) {
-            const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-            *g.exp_out = (int8_t)((g.exp_in ? (int)*g.exp_in : 0) + (g.wscale ? (int)*g.wscale : 0) + inc);
-        }
-    }
-    const int tiles = g.cop / 32;
-    uint32_t m = 0;
-    const int segs = g.ow / 32, pairs = g.oh / 2;
-    for (int64_t u = wave; u < g.units; u += nwaves) {
-        const int seg = (int)(u % segs);
-        const int64_t rest = u / segs;
-        const int pr = (int)(rest % pairs);
-        const int64_t img = rest / pairs;
-        const int64_t p0 = (img * g.oh + 2 * pr) * g.ow + seg * 32;  // first pixel of the top row segment
-        v4i a[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) a[r] = *(const v4i*)(g.x + (p0 + (int64_t)r * g.ow + c) * 32 + 16 * h);
-        for (int t = 0; t < tiles; ++t) {
-            const v4i b = buf_load16(rw, (uint32_t)((t * 32 + c) * 32 + 16 * h));
-            v16i acc[2];
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, a[r], v16i{}, 0, 0, 0);
-            // acc[r][i]: output channel t * 32 + (i & 3) + 8 (i >> 2) + 4 h, pixel p0 + r * ow + c
-            if (PASS == 0) {
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int ch = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        const uint32_t v = ch < g.co ? uabs32(acc[r][i]) : 0u;
-                        m = m > v ? m : v;
-                    }
-            } else {
-                int8_t q[2][16];
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        int32_t v;
-                        if (raw) {
-                            v = (int32_t)(int8_t)acc[r][i];
-                        } else if (g.relu) {  // PSTO of max(acc, 0): a negative value is 0 whatever its rounding
-                            const uint32_t x = (uint32_t)max(acc[r][i], 0);
-                            const uint32_t qp = __builtin_amdgcn_ubfe(x, s >> 1, s - (s >> 1));
-                            const uint32_t pr = __builtin_amdgcn_ubfe(x, 0, s >> 1) << (s & 1);
-                            v = (int32_t)min((x >> s) + (qp > pr ? 1u : 0u), 127u);
-                        } else {
-                            v = psto_fast(acc[r][i], s);
-                        }
-                        if (g.relu && v < 0) v = 0;
-                        q[r][i] = (int8_t)v;
-                    }
-                // lane (pixel c, half h) holds channels 8j + 4h + 0..3 as dword D[j]; one half-wave
-                // swap per pair (D0, D2), (D1, D3) gives the lower half channels 0..15 and the
-                // upper half 16..31 of its pixel: one 16-byte store per lane and tile
-                auto pack = [&](const int8_t* v) {
-                    uint32_t d[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        d[j] = (uint32_t)(uint8_t)v[4 * j] | (uint32_t)(uint8_t)v[4 * j + 1] << 8 |
-                               (uint32_t)(uint8_t)v[4 * j + 2] << 16 | (uint32_t)(uint8_t)v[4 * j + 3] << 24;
-                    const auto x02 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-                    const auto x13 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-                    return v4i{(int)x02[0], (int)x02[1], (int)x13[0], (int)x13[1]};
-                };
-                v4i qv[2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const v4i v = pack(q[r]);
-                    qv[r] = v;
-                    if (g.out != nullptr) *(v4i*)(g.out + (p0 + (int64_t)r * g.ow + c) * g.cop + t * 32 + 16 * h) = v;
-                    if (g.out_c32 != nullptr)
-                        *(v4i*)(g.out_c32 + (((img * tiles + t) * g.oh + 2 * pr + r) * (int64_t)g.ow + seg * 32 + c) * 32 +
-                                16 * h) = v;
-                }
-                if (g.pool_out != nullptr) {
-                    // vertical max in the lane, horizontal with the neighbour pixel (lane c ^ 1);
-                    // even lanes store their pooled pixel
-                    int8_t pm[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int v0 = q[0][i] > q[1][i] ? q[0][i] : q[1][i];
-                        const int v1 = __shfl_xor(v0, 1, 64);
-                        pm[i] = (int8_t)(v0 > v1 ? v0 : v1);
-                    }
-                    const v4i v = pack(pm);
-                    v4i code{0, 0, 0, 0};
-                    if (g.pool_code != nullptr) {  // the window: (top, bottom) here, the odd neighbour's
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp(qv[0][k], 0xB1, 0xF, 0xF, false);
-                            const uint32_t t3 = (uint32_t)__builtin_amdgcn_mov_dpp(qv[1][k], 0xB1, 0xF, 0xF, false);
-                            code[k] = (int)pool_code4((uint32_t)qv[0][k], t1, (uint32_t)qv[1][k], t3, (uint32_t)v[k],
-                                                      g.relu != 0);
-                        }
-                    }
-                    if ((c & 1) == 0) {
-                        const int64_t pp = (img * (g.oh / 2) + pr) * (g.ow / 2) + seg * 16 + (c >> 1);
-                        *(v4i*)(g.pool_out + pp * g.cop + t * 32 + 16 * h) = v;
-                        if (g.pool_code != nullptr) *(v4i*)(g.pool_code + pp * g.cop + t * 32 + 16 * h) = code;
-                        if (g.pool_c32 != nullptr) {
-                            const int64_t hw2 = (int64_t)(g.oh / 2) * (g.ow / 2);
-                            *(v4i*)(g.pool_c32 + ((img * tiles + t) * hw2 + pp - img * hw2) * 32 + 16 * h) = v;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (PASS == 0) {
-        m = wave_max(m);
-        __shared__ uint32_t red[4];
-        if (lane == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) publish_max(g.amax, max(max(red[0], red[1]), max(red[2], red[3])));
-    }
-}
-
-// The step's form: NT = cop / 32 <= 2 tiles and every tensor below 2^31 bytes (32-bit offsets on
-// buffer resources).  A wave walks the units wave, wave + nwaves, ... of a grid the host sizes (any
-// size computes the same): the range word, the weights' A fragments and the first unit's pixels
-// are loaded together, once per wave, and unit u + 1's pixels are in flight while unit u is
-// requantised and stored.  The rule is chosen once per wave from the (uniform) bit width and relu
-// flag -- the raw cast, the positive PSTO of a relu layer, the signed PSTO -- and each class runs
-// its own straight-line unit loop; the unit's coordinates are wave-uniform (scalar) arithmetic.
-template <int PASS, int NT>
-__global__ void __launch_bounds__(256) conv0_kernel(Conv0 g) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const uint32_t nwaves = gridDim.x * 4, units = (uint32_t)g.units;
-    const int h = lane >> 5, c = lane & 31;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.w, g.wbytes), rx = make_rsrc(g.x, g.xbytes);
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(g.out, g.obytes), rc = make_rsrc(g.out_c32, g.obytes);
-    const __amdgpu_buffer_rsrc_t rp = make_rsrc(g.pool_out, g.pbytes), rpc = make_rsrc(g.pool_c32, g.pbytes);
-    const __amdgpu_buffer_rsrc_t rpk = make_rsrc(g.pool_code, g.pbytes);
-    const uint32_t segs = g.fseg.d, pairs = g.fpair.d, ow = (uint32_t)g.ow, oh = (uint32_t)g.oh, cop = NT * 32u;
-    uint32_t gm = 0;
-    if (PASS == 1) gm = g.amax[lane * MAX_SLOT_STRIDE];
-    v4i wa[NT];  // (rows >= co: past the resource, zeros -- their sums are 0)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) wa[t] = buf_load16(rw, (uint32_t)((t * 32 + c) * 32 + 16 * h));
-    const uint32_t lx = (uint32_t)(c * 32 + 16 * h);
-    // unit u = (img * pairs + pr) * segs + seg; oh = 2 pairs, so its top row's first pixel is
-    // 2 (u / segs) ow + 32 seg.  A unit past the end loads zeros.
-    auto xload = [&](uint32_t u, v4i(&a)[2]) {
-        const uint32_t q = fdiv(g.fseg, u), seg = u - q * segs;
-        const uint32_t o = u < units ? (2u * q * ow + seg * 32u) * 32u + lx : OOB;
-        a[0] = buf_load16(rx, o);
-        a[1] = buf_load16(rx, o + ow * 32u);
-    };
-    v4i a[2];
-    xload(wave, a);
-    int s = 2, cls = 0, lo = -128;
-    if (PASS == 1) {
-        const int shift = __builtin_amdgcn_readfirstlane(bitwidth_of(wave_max(gm))) - 7;
-        s = shift > 1 ? shift : 2;
-        cls = shift <= 0 ? 0 : (g.relu ? 1 : 2);
-        lo = g.relu ? 0 : -128;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && g.exp_out != nullptr) {
-            const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-            *g.exp_out = (int8_t)((g.exp_in ? (int)*g.exp_in : 0) + (g.wscale ? (int)*g.wscale : 0) + inc);
-        }
-    }
-    uint32_t m = 0;
-    // four values' low bytes as a dword, then lane (pixel c, half h)'s channels 8j + 4h + 0..3 =
-    // dword D[j]: one half-wave swap per pair (D0, D2), (D1, D3) gives the lower half channels
-    // 0..15 and the upper half 16..31 of its pixel -- one 16-byte store per lane and tile
-    auto pack = [&](const int32_t* v) {
-        uint32_t d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)v[4 * j + 1], (uint32_t)v[4 * j], 0x0c0c0400u);
-            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)v[4 * j + 3], (uint32_t)v[4 * j + 2], 0x0c0c0400u);
-            d[j] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
-        }
-        const auto x02 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-        const auto x13 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-        return v4i{(int)x02[0], (int)x02[1], (int)x13[0], (int)x13[1]};
-    };
-    auto run = [&](auto rule) {
-        constexpr int RULE = decltype(rule)::value;  // 0 raw cast, 1 PSTO of max(acc, 0), 2 signed PSTO
-        const uint32_t hh = (uint32_t)s >> 1, hs = (uint32_t)s - hh, odd = (uint32_t)s & 1u;
-        auto rq = [&](int32_t v) -> int32_t {
-            if constexpr (RULE == 0) {
-                return max((int32_t)(int8_t)v, lo);
-            } else {  // (under relu a negative value is 0 whatever its rounding)
-                const uint32_t x = RULE == 1 ? (uint32_t)max(v, 0) : uabs32(v);
-                const uint32_t qp = __builtin_amdgcn_ubfe(x, hh, hs), pr = __builtin_amdgcn_ubfe(x, 0, hh) << odd;
-                const int32_t r = (int32_t)min((x >> s) + (qp > pr ? 1u : 0u), 127u);
-                return RULE == 1 ? r : (v < 0 ? -r : r);
-            }
-        };
-        for (uint32_t u = wave; u < units; u += nwaves) {
-            v4i an[2];
-            xload(u + nwaves, an);
-            const uint32_t q = fdiv(g.fseg, u), seg = u - q * segs;
-            const uint32_t img = fdiv(g.fpair, q), pr = q - img * pairs;
-            const uint32_t p0 = 2u * q * ow + seg * 32u;           // first pixel of the top row segment
-            const uint32_t pp = q * (ow / 2) + seg * 16u + (c >> 1);  // this lane pair's pooled pixel
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                v16i acc[2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-                    acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wa[t], a[r], v16i{}, 0, 0, 0);
-                // acc[r][i]: output channel t * 32 + (i & 3) + 8 (i >> 2) + 4 h, pixel p0 + r * ow + c
-                if (PASS == 0) {
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) m = max(m, uabs32(acc[r][i]));
-                    continue;
-                }
-                int32_t v[2][16];
-                v4i qv[2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) v[r][i] = rq(acc[r][i]);
-                    qv[r] = pack(v[r]);
-                    if (g.out != nullptr) buf_store16(ro, (p0 + r * ow + c) * cop + t * 32 + 16 * h, qv[r]);
-                    if (g.out_c32 != nullptr)
-                        buf_store16(rc, (((img * NT + t) * oh + 2 * pr + r) * ow + seg * 32u + c) * 32u + 16 * h, qv[r]);
-                }
-                if (g.pool_out != nullptr) {
-                    // vertical max in the lane, horizontal with the neighbour pixel (lane c ^ 1, a
-                    // quad_perm move); even lanes store their pooled pixel
-                    int32_t pm[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int v0 = max(v[0][i], v[1][i]);
-                        pm[i] = max(v0, __builtin_amdgcn_mov_dpp(v0, 0xB1, 0xF, 0xF, false));
-                    }
-                    const v4i pv = pack(pm);
-                    v4i code{0, 0, 0, 0};
-                    if (g.pool_code != nullptr) {  // the window: (top, bottom) here, the odd neighbour's
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp(qv[0][k], 0xB1, 0xF, 0xF, false);
-                            const uint32_t t3 = (uint32_t)__builtin_amdgcn_mov_dpp(qv[1][k], 0xB1, 0xF, 0xF, false);
-                            code[k] = (int)pool_code4((uint32_t)qv[0][k], t1, (uint32_t)qv[1][k], t3, (uint32_t)pv[k],
-                                                      g.relu != 0);
-                        }
-                    }
-                    if ((c & 1) == 0) {
-                        const uint32_t po = pp * cop + t * 32 + 16 * h;
-                        buf_store16(rp, po, pv);
-                        if (g.pool_code != nullptr) buf_store16(rpk, po, code);
-                        if (g.pool_c32 != nullptr)
-                            buf_store16(rpc, (((img * NT + t) * pairs + pr) * (ow / 2) + seg * 16u + (c >> 1)) * 32u + 16 * h, pv);
-                    }
-                }
-            }
-            a[0] = an[0];
-            a[1] = an[1];
-        }
-    };
-    if (PASS == 0 || cls == 0)
-        run(std::integral_constant<int, 0>{});
-    else if (cls == 1)
-        run(std::integral_constant<int, 1>{});
-    else
-        run(std::integral_constant<int, 2>{});
-    if (PASS == 0) {
-        m = wave_max(m);
-        __shared__ uint32_t red[4];
-        if (lane == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) publish_max(g.amax, max(max(red[0], red[1]), max(red[2], red[3])));
-    }
-}
-
-// diagnostic: conv0_kernel's grid (niti_diag_conv0_blocks; 0: one resident wave of workgroups)
-static std::atomic<int> g_conv0_blocks{0};
-void diag_conv0_blocks(int n) { g_conv0_blocks = n > 0 ? n : 0; }
-
-bool conv0_ok(const ConvGeom& g) {
-    return g.kh == 1 && g.kw == 1 && g.c_in == 32 && g.cip == 32 && g.ow % 32 == 0 && g.oh % 2 == 0 && g.sh == 1 &&
-           g.pt == 0 && g.cop % 32 == 0;
-}
-
-hipError_t conv0_fwd(const ConvGeom& g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const ActOut& o,
-                     int pass, hipStream_t st, int8_t* pool_c32, int8_t* out_c32, int8_t* pool_code) {
-    // (out may be null when the pooled output is kept: pool_out + pool_code carry everything the
-    // backward pass reads)
-    if (!conv0_ok(g) || o.relu_mask != nullptr) return hipErrorInvalidValue;
-    if (o.out == nullptr && (pass == 1 && (o.pool.pool_out == nullptr || pool_code == nullptr))) return hipErrorInvalidValue;
-    if ((pool_c32 != nullptr || pool_code != nullptr) && o.pool.pool_out == nullptr) return hipErrorInvalidValue;
-    Conv0 k{};
-    k.x = xcol;
-    k.w = w;
-    k.wbytes = (uint32_t)((int64_t)g.c_out * 32);
-    k.co = g.c_out;
-    k.cop = g.cop;
-    k.oh = g.oh;
-    k.ow = g.ow;
-    k.units = (int64_t)g.n * (g.oh / 2) * (g.ow / 32);
-    k.amax = amax;
-    k.out = o.out;
-    k.pool_out = o.pool.pool_out;
-    k.pool_c32 = pool_c32;
-    k.out_c32 = out_c32;
-    k.pool_code = pool_code;
-    k.exp_in = o.exp_in;
-    k.wscale = o.wscale;
-    k.exp_out = o.exp_out;
-    k.relu = o.relu;
-    int64_t blocks = (k.units + 3) / 4;
-    const int64_t pixels = (int64_t)g.n * g.oh * g.ow;
-    if (g.cop > 64 || pixels * 64 >= ((int64_t)1 << 31)) {
-        blocks = blocks > 1024 ? 1024 : blocks;
-        if (pass == 0)
-            hipLaunchKernelGGL(conv0_wide_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, k);
-        else
-            hipLaunchKernelGGL(conv0_wide_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, k);
-        return hipGetLastError();
-    }
-    k.xbytes = (uint32_t)(pixels * 32);
-    k.obytes = (uint32_t)(pixels * g.cop);
-    k.pbytes = (uint32_t)(pixels / 4 * g.cop);
-    k.fseg = make_fastdiv((uint32_t)(g.ow / 32));
-    k.fpair = make_fastdiv((uint32_t)(g.oh / 2));
-    using Kern = void (*)(Conv0);
-    const Kern f = pass == 0 ? (g.cop == 32 ? conv0_kernel<0, 1> : conv0_kernel<0, 2>)
-                             : (g.cop == 32 ? conv0_kernel<1, 1> : conv0_kernel<1, 2>);
-    // one resident wave of workgroups, each wave walking its share of the units (speed only)
-    const int forced = g_conv0_blocks.load();
-    const int res = forced > 0 ? forced : resident_wgs((const void*)f);
-    if (res > 0 && blocks > res) blocks = res;
-    hipLaunchKernelGGL(f, dim3((unsigned)blocks), dim3(256), 0, st, k);
-    return hipGetLastError();
-}
-
-// The requantisation with the 3x3 / 2 (pad 1) max pool fused (ActRequant::pool3, ResNet-18's
-// stem: NITI_Conv_Int8.cpp:266-307's rescale + relu, then NITI_Maxpool_Int8.cpp:24-72 over the
-// int8 result, first maximum in (ky, kx) order), so the pre-pool int8 image is neither written
-// (unless out_nhwc16) nor read back by a pool pass.  One thread per pooled column strip of
-// RQ3_ROWS pooled rows and 4 channels: each step requantises the two new input rows' three
-// columns and carries the last one down as the next window's top row, so the accumulators are
-// read once vertically (plus one row per strip); the horizontal overlap (the shared column of
-// neighbouring windows) is the neighbouring lanes' load of the same lines.  VALU-bound before
-// the relu forms below (~700 operations per pooled quad: 160 us for the batch-128 stem).
-constexpr int RQ3_ROWS = 4;  // (2-28 measured: 103-113 us, profiles/r05_stem_pool.txt)
-struct Rq3Geom {
-    FastDiv fq, fow, fch;  // by quads per row, pooled width, strips per image
-    int qpr, H, W, OH, rows;  // rows: pooled rows per strip
-    uint32_t units;
-    int remap;  // one thread per unit, blocks XCD-remapped (else grid-stride)
-};
-__device__ __forceinline__ void pool3_take(uint32_t o, int k, uint32_t& m, uint32_t& a) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int ov = (int8_t)(o >> (8 * e)), mv = (int8_t)(m >> (8 * e)), av = (int8_t)(a >> (8 * e));
-        if (av < 0 || ov > mv) {
-            m = (m & ~(0xffu << (8 * e))) | (o & (0xffu << (8 * e)));
-            a = (a & ~(0xffu << (8 * e))) | ((uint32_t)k << (8 * e));
-        }
-    }
-}
-// relu(PSTO(v, s)) of four accumulators, packed (rq4 with relu and s >= 2, in fewer VALU
-// operations: a <= 0 gives 0 either way, so the sign paths go; the pool is VALU-bound otherwise)
-__device__ __forceinline__ uint32_t rq4_relu(v4i v, int s) {
-    const int h = s >> 1, odd = s & 1;
-    uint32_t o = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const uint32_t x = (uint32_t)max(v[e], 0);
-        const uint32_t qp = __builtin_amdgcn_ubfe(x, h, s - h), pr = __builtin_amdgcn_ubfe(x, 0, h) << odd;
-        const uint32_t q = min((x >> s) + (qp > pr ? 1u : 0u), 127u);
-        o |= q << (8 * e);
-    }
-    return o;
-}
-// pool3_take for bytes in [0, 127] (relu outputs), four at once: where o > m (strict: the first
-// maximum stays), m = o and a = k
-__device__ __forceinline__ void pool3_take_u7(uint32_t o, uint32_t k4, uint32_t& m, uint32_t& a) {
-    const uint32_t gt = ((o | 0x80808080u) - m - 0x01010101u) & 0x80808080u;  // bytes: 127 + o - m >= 128
-    const uint32_t mask = (gt >> 7) * 0xffu;
-    m = (m & ~mask) | (o & mask);
-    a = (a & ~mask) | (k4 & mask);
-}
-
-template <bool RELU>
-__global__ void __launch_bounds__(256) requant_pool3_kernel(ActRequant r, Rq3Geom g) {
-    // (wave-uniform: scalar branches below)
-    const int bw = __builtin_amdgcn_readfirstlane(bitwidth_of(read_max(r.amax)));
-    const int shift = bw - 7;
-    const int s = shift > 1 ? shift : 2;
-    const bool raw = shift <= 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && r.exp_out != nullptr) {
-        const int inc = shift > 1 ? shift : (shift == 1 ? 2 : 0);
-        const int ein = r.exp_in ? (int)*r.exp_in : 0;
-        const int ws = r.wscale ? (int)*r.wscale : 0;
-        *r.exp_out = (int8_t)(ein + ws + inc);
-    }
-    const uint32_t qpr = (uint32_t)g.qpr;
-    const int OW = (int)g.fow.d;
-    const int64_t RS = (int64_t)g.W * qpr;  // input row stride, quads
-    const uint32_t bid = g.remap ? (uint32_t)xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-    auto rq = [&](const v4i& v) { return RELU && !raw ? rq4_relu(v, s) : rq4(v, raw, s, RELU); };
-    auto take = [&](uint32_t o, int k, uint32_t& m, uint32_t& a) {
-        if (RELU)
-            pool3_take_u7(o, 0x01010101u * (uint32_t)k, m, a);
-        else
-            pool3_take(o, k, m, a);
-    };
-    for (uint32_t u = bid * 256u + threadIdx.x; u < g.units; u += g.remap ? g.units : gridDim.x * 256u) {
-        const uint32_t pix = fdiv(g.fq, u), q = u - pix * qpr;
-        const uint32_t t = fdiv(g.fow, pix), ox = pix - t * g.fow.d;
-        const uint32_t b = fdiv(g.fch, t), ch = t - b * g.fch.d;
-        const int oy0 = (int)ch * g.rows, oy1 = min(g.OH, oy0 + g.rows);
-        const int x0 = 2 * (int)ox - 1;
-        const bool c0 = x0 >= 0, c2 = x0 + 2 < g.W;
-        // columns x0, x0 + 1, x0 + 2 of a row as offsets from column x0 + 1 (a column outside the
-        // image reads column x0 + 1 instead: loaded, never taken)
-        const int64_t o0 = c0 ? -(int64_t)qpr : 0, o2 = c2 ? (int64_t)qpr : 0;
-        const v4i* p = (const v4i*)r.acc + ((int64_t)b * g.H * g.W + 2 * oy0 * g.W + x0 + 1) * qpr + q;
-        uint32_t* y0 = r.out_nhwc16 ? (uint32_t*)r.out_nhwc16 + (p - (const v4i*)r.acc) : nullptr;
-        // the two input rows 2 oy, 2 oy + 1 at p (the second: the first again past the image)
-        auto load = [&](const v4i* p, int oy, v4i* a) {
-            const v4i* p1 = 2 * oy + 1 < g.H ? p + RS : p;
-            a[0] = p[o0];
-            a[1] = p[0];
-            a[2] = p[o2];
-            a[3] = p1[o0];
-            a[4] = p1[0];
-            a[5] = p1[o2];
-        };
-        uint32_t top[3] = {0, 0, 0};
-        if (oy0 > 0) {
-            const v4i* pt = p - RS;
-            top[0] = rq(pt[o0]);
-            top[1] = rq(pt[0]);
-            top[2] = rq(pt[o2]);
-        }
-        auto step = [&](const v4i* a, int oy) {
-            const bool r2 = 2 * oy + 1 < g.H;
-            uint32_t mid[3], bot[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                mid[k] = rq(a[k]);
-                bot[k] = rq(a[3 + k]);
-            }
-            // bytes: max, position.  With relu every value is >= 0: start from 0 at the window's
-            // first position, later positions taken where strictly greater (the first maximum)
-            uint32_t m = RELU ? 0u : 0x80808080u;
-            uint32_t am = RELU ? 0x01010101u * (uint32_t)((oy > 0 ? 0 : 3) + (c0 ? 0 : 1)) : 0xffffffffu;
-            if (oy > 0) {
-                if (c0) take(top[0], 0, m, am);
-                take(top[1], 1, m, am);
-                if (c2) take(top[2], 2, m, am);
-            }
-            if (c0) take(mid[0], 3, m, am);
-            take(mid[1], 4, m, am);
-            if (c2) take(mid[2], 5, m, am);
-            if (r2) {
-                if (c0) take(bot[0], 6, m, am);
-                take(bot[1], 7, m, am);
-                if (c2) take(bot[2], 8, m, am);
-            }
-            const int64_t po = (((int64_t)b * g.OH + oy) * OW + ox) * qpr + q;
-            ((uint32_t*)r.pool3.out)[po] = m;
-            ((uint32_t*)r.pool3.arg)[po] = am;
-            if (y0 != nullptr) {  // each pre-pool pixel once: rows 2 oy, 2 oy + 1 x columns x0 + 1, x0 + 2
-                uint32_t* d = y0 + (int64_t)(oy - oy0) * 2 * RS;
-                d[0] = mid[1];
-                if (c2) d[qpr] = mid[2];
-                if (r2) {
-                    d[RS] = bot[1];
-                    if (c2) d[RS + qpr] = bot[2];
-                }
-            }
-            top[0] = bot[0];
-            top[1] = bot[1];
-            top[2] = bot[2];
-        };
-        // two register sets, each step's rows loaded one step ahead
-        v4i A[6], B[6];
-        load(p, oy0, A);
-        for (int oy = oy0;;) {
-            if (oy + 1 < oy1) load(p + 2 * RS, oy + 1, B);
-            step(A, oy);
-            if (++oy >= oy1) break;
-            p += 2 * RS;
-            if (oy + 1 < oy1) load(p + 2 * RS, oy + 1, A);
-            step(B, oy);
-            if (++oy >= oy1) break;
-            p += 2 * RS;
-        }
-    }
-}
-
-hipError_t requant_act(const ActRequant& r, hipStream_t st) {
-    if (r.ldc % 16 != 0 || r.acc == nullptr || r.amax == nullptr) return hipErrorInvalidValue;
-    if (r.pool.pool_out != nullptr || r.pool.dx != nullptr) {
-        if (r.pool.H % 2 || r.pool.W % 2 || r.pool.H <= 0 || r.pool.W <= 0) return hipErrorInvalidValue;
-        if (r.pool.pool_out != nullptr && (r.out_nhwc16 == nullptr || r.rows % ((int64_t)r.pool.H * r.pool.W)))
-            return hipErrorInvalidValue;
-        if (r.pool.dx != nullptr && (r.pool.x == nullptr || r.pool.y == nullptr ||
-                                     r.rows % ((int64_t)(r.pool.H / 2) * (r.pool.W / 2))))
-            return hipErrorInvalidValue;
-    }
-    if (r.pool.dx_c32 != nullptr && (r.pool.dx == nullptr || r.out_p16 != nullptr || r.ldc % 32 != 0))
-        return hipErrorInvalidValue;
-    if (r.zero_cls != 0 && (r.out_p16 != nullptr || r.out_c4 != nullptr)) return hipErrorInvalidValue;
-    if (r.pool3.out != nullptr) {
-        const Pool3& p = r.pool3;
-        if (r.out_p16 != nullptr || r.out_c4 != nullptr || r.zero_cls != 0 || r.pool.pool_out != nullptr ||
-            r.pool.dx != nullptr || r.relu_mask != nullptr || p.arg == nullptr || r.ldc % 4 != 0 || p.H <= 0 ||
-            p.W <= 0 || p.OH != (p.H - 1) / 2 + 1 || p.OW != (p.W - 1) / 2 + 1 || r.rows % ((int64_t)p.H * p.W) != 0)
-            return hipErrorInvalidValue;
-        Rq3Geom g;
-        g.qpr = r.ldc / 4;
-        g.H = p.H;
-        g.W = p.W;
-        g.OH = p.OH;
-        static const int rows_env = getenv("NITI_RQ3_ROWS") ? atoi(getenv("NITI_RQ3_ROWS")) : RQ3_ROWS;
-        static const int remap_env = getenv("NITI_RQ3_REMAP") ? atoi(getenv("NITI_RQ3_REMAP")) : 0;
-        g.rows = rows_env > 0 ? rows_env : RQ3_ROWS;
-        const int strips = (p.OH + g.rows - 1) / g.rows;
-        const int64_t units = r.rows / ((int64_t)p.H * p.W) * strips * p.OW * g.qpr;
-        if (units >= (int64_t)1 << 31) return hipErrorInvalidValue;
-        g.units = (uint32_t)units;
-        g.fq = make_fastdiv((uint32_t)g.qpr);
-        g.fow = make_fastdiv((uint32_t)p.OW);
-        g.fch = make_fastdiv((uint32_t)strips);
-        int64_t blocks = (units + 255) / 256;
-        g.remap = remap_env != 0 && blocks <= ((int64_t)1 << 24);
-        if (!g.remap && blocks > 8192) blocks = 8192;
-        if (blocks < 1) blocks = 1;
-        if (r.relu)
-            hipLaunchKernelGGL(requant_pool3_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        else
-            hipLaunchKernelGGL(requant_pool3_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        return hipGetLastError();
-    }
-    if (r.out_p16 != nullptr) {  // the output (dx with the pool gradient) also as its P16 copy
-        if (!requant_p16_ok(r)) return hipErrorInvalidValue;
-        RqGeom g{};
-        g.qpr = r.ldc / 4;
-        g.W = r.pool.W;
-        const int gsz = r.pool.dx == nullptr ? 16 : (r.pool.W == 16 ? p16_group<16>() : p16_group<8>());
-        // plain: a thread per (16-row block, quad, quarter); pool gradient: per (run, quad)
-        const int64_t units = r.rows / gsz * g.qpr * (r.pool.dx == nullptr ? 4 : 1);
-        if (units >= (int64_t)1 << 31) return hipErrorInvalidValue;
-        if (units == 0) return hipSuccess;
-        g.units = (uint32_t)units;
-        g.fq = make_fastdiv((uint32_t)g.qpr);
-        int64_t blocks = (units + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        if (r.pool.dx == nullptr)
-            hipLaunchKernelGGL(requant_p16_plain_kernel, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        else
-            launch_requant_p16<RQ_POOL_BWD>(r, g, blocks, st);
-        return hipGetLastError();
-    }
-    if (r.out_c4 == nullptr) {
-        const bool pf = r.pool.pool_out != nullptr, pb = r.pool.dx != nullptr;
-        if (!pf && !pb && r.out_nhwc16 == nullptr) return hipErrorInvalidValue;
-        RqGeom g;
-        g.qpr = r.ldc / 4;
-        g.W = r.pool.W;
-        const int64_t rows = pf ? r.rows / 4 : r.rows;  // pooled pixels for the pool modes
-        const int64_t units = rows * g.qpr;
-        if (units >= (int64_t)1 << 31) return hipErrorInvalidValue;
-        g.units = (uint32_t)units;
-        g.fq = make_fastdiv((uint32_t)g.qpr);
-        if (pf || pb) {
-            g.fpw = make_fastdiv((uint32_t)(r.pool.W / 2));
-            g.fph = make_fastdiv((uint32_t)(r.pool.H / 2));
-        }
-        if (r.zero_cls != 0) {
-            if (pf || pb || r.zc_h <= 0 || r.zc_w <= 0 || r.rows % ((int64_t)r.zc_h * r.zc_w)) return hipErrorInvalidValue;
-            g.fzw = make_fastdiv((uint32_t)r.zc_w);
-            g.fzh = make_fastdiv((uint32_t)r.zc_h);
-        }
-        int64_t blocks = (units + 256 * RQ_U - 1) / (256 * RQ_U);
-        if (blocks > 2048) blocks = 2048;
-        if (blocks < 1) blocks = 1;
-        if (pf)
-            hipLaunchKernelGGL(requant_quad_kernel<RQ_POOL_FWD>, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        else if (pb)
-            hipLaunchKernelGGL(requant_quad_kernel<RQ_POOL_BWD>, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        else
-            hipLaunchKernelGGL(requant_quad_kernel<RQ_PLAIN>, dim3((unsigned)blocks), dim3(256), 0, st, r, g);
-        return hipGetLastError();
-    }
-    const int64_t total = r.rows * (r.ldc / 16);
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(requant_act_kernel, dim3((unsigned)blocks), dim3(256), 0, st, r);
-    return hipGetLastError();
-}
-
-__global__ void requant_grad_kernel(const int32_t* __restrict__ acc, int64_t n, const uint32_t* __restrict__ amax,
-                                    int rule, int8_t* __restrict__ g_out, int8_t* __restrict__ w) {
-    const int bw = bitwidth_of(read_max(amax));
-    const int s = bw - rule;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t g = bw == 0 ? 0 : psto_any(acc[i], s);
-        if (g_out) g_out[i] = (int8_t)g;
-        if (w) w[i] = (int8_t)clip127((int32_t)w[i] - g);
-    }
-}
-
-hipError_t requant_grad(const int32_t* acc, int64_t n, const uint32_t* amax, int rule, int8_t* g_out, int8_t* w,
-                        hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(requant_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, acc, n, amax, rule, g_out, w);
-    return hipGetLastError();
-}
-
-// Fused NITI_SGD step on a 64(co) x 64(ci) tile of one tap: g = gradient rule(acc), w <- clip(w - g)
-// in OHWI16, and the updated weights also written transposed (IHWO16, the input-gradient B
-// operand) through an LDS tile -- the transposed copy never needs a pass of its own.
-// One 64 (co) x 64 (ci) tile of one tap: g = rule(acc, range), w <- clip(w - g, +-127) in OHWI16,
-// the same tile transposed through LDS into IHWO16 (the input-gradient operand), g to g_out.
-// bw: NITI_RangeEstimate of the job's gradient (read once per job by the caller)
-// (sgd_tile: niti_sgd.hpp)
-
-// Every layer's NITI_SGD update of a step in one launch: block b belongs to the job whose
-// [start, start + tiles) range holds it (the updates are independent; the input gradients
-// that read the old weights have all run by then).
-// The deferred split-K combines of a step's P16 weight gradients, all layers in one launch ahead
-// of the update (one launch instead of one reduce per layer, each of which left the chip mostly
-// idle: 576 blocks of a few loads each): chunk c (1024 elements of one job's acc, 4 per thread) =
-// the sum of the job's slabs, its max into the job's range.  A small gradient over many splits
-// takes splitk_reduce's form instead: G lanes per 16-byte group, each summing every G-th split,
-// a shuffle tree to finish (a chunk is then 1024 / G elements; sgd_combine_lanes).
-// (A grid barrier inside the update
-// launch instead measured +275 us per VGG-11 step: 1536-2048 arrivals on one counter.)
-__global__ void __launch_bounds__(256) sgd_combine_kernel(SgdJobs jobs) {
-    const int chunks = jobs.cstart[jobs.n];
-    // a block's chunks ascend, so its jobs do too: the running max of the current job is
-    // published once when the block leaves it (one atomic per wave per job, not per chunk --
-    // ResNet-18's ~15 K chunks of per-chunk atomics on a few range words cost ~50 us)
-    uint32_t m = 0;
-    int cur = -1;
-    for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
-        int j = 0;
-        while (j + 1 < jobs.n && c >= jobs.cstart[j + 1]) ++j;
-        if (j != cur) {
-            if (cur >= 0) {
-                const uint32_t w = wave_max(m);
-                if ((threadIdx.x & 63) == 0) publish_max(const_cast<uint32_t*>(jobs.job[cur].amax), w);
-            }
-            cur = j;
-            m = 0;
-        }
-        const SgdJob& J = jobs.job[j];
-        // G lanes share an element group and split its slabs among them (sgd_combine_lanes: 1 for
-        // a job with a few chunks per split; block-uniform, so every lane reaches the shuffles)
-        const int G = sgd_combine_lanes(J.splits, J.slab_n);
-        const int g = threadIdx.x & (G - 1);
-        const int64_t e = ((int64_t)(c - jobs.cstart[j]) * (256 / G) + threadIdx.x / G) * 4;
-        int64_t de = e;  // the acc element this slab element sums into
-        bool live = J.slab != nullptr && e < J.slab_n;
-        if (live && J.slab_map == 1) {  // SlabTapsBlocked (splitk_reduce's map), on 16-byte units
-            const uint32_t u = (uint32_t)(e >> 2);
-            const uint32_t tile = u / 4608u, rem = u - tile * 4608u;
-            const uint32_t row = rem / 72u, rc = rem - row * 72u;
-            const uint32_t t = rc / 8u, part = rc - t * 8u;
-            FastDiv ft;
-            ft.m = J.tb_m;
-            ft.s = J.tb_s;
-            const uint32_t tco = fdiv(ft, tile), tci = tile - tco * (uint32_t)J.tb_tiles_ci;
-            const int co = (int)(tco * 64u + row);
-            live = co < J.co;
-            de = ((int64_t)co * J.tb_ld4 + t * J.tb_cip4 + tci * 8u + part) * 4;
-        }
-        v4i s = {0, 0, 0, 0};
-        if (live) {
-            const v4i* base = (const v4i*)(J.slab + e);
-            const int64_t st4 = J.slab_stride / 4;
-            for (int z0 = g; z0 < J.splits; z0 += 8 * G) {  // up to 8 independent loads in flight
-                v4i v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int z = z0 + q * G;
-                    v[q] = z < J.splits ? __builtin_nontemporal_load(base + (int64_t)z * st4) : v4i{0, 0, 0, 0};
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s += v[q];
-            }
-        }
-        for (int o = G >> 1; o > 0; o >>= 1) {  // (the lanes of a group are live together)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s[q] += __shfl_xor(s[q], o, 64);
-        }
-        if (live && g == 0) {
-            *(v4i*)(const_cast<int32_t*>(J.acc) + de) = s;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t u = uabs32(s[q]);
-                m = m > u ? m : u;
-            }
-        }
-    }
-    if (cur >= 0) {
-        const uint32_t w = wave_max(m);
-        if ((threadIdx.x & 63) == 0) publish_max(const_cast<uint32_t*>(jobs.job[cur].amax), w);
-    }
-}
-
-// bits: the update-bits table the jobs with rule < 0 name a word of (sgd_rule_word; a launch without
-// one passes any readable word: word 0 is loaded, and ignored, for a job with an immediate rule)
-__global__ void sgd_update_kernel(SgdJobs jobs, int total, const int32_t* __restrict__ bits) {
-    __shared__ int8_t T[64][64 + 4];
-    // a block takes tiles b, b + gridDim, ...: one resident wave of blocks instead of a full
-    // wave plus a straggling partial one.  The next tile's operands are loaded before this one is
-    // finished, and a tile's loads are issued before its job's range is read (the range word's
-    // dependent read and wave reduction then overlap the operand fetch).
-    struct Tile {
-        int j, ci0, co0, k;
-    };
-    auto locate = [&](int bb) {
-        Tile t;
-        int b = bb, j = 0;
-        while (j + 1 < jobs.n && b >= jobs.start[j + 1]) ++j;
-        const SgdJob& J = jobs.job[j];
-        b -= jobs.start[j];
-        const int tx = (J.cip + 63) / 64, ty = (J.cop + 63) / 64;
-        const int k = b / (tx * ty), rem = b - k * tx * ty;
-        t.j = j;
-        t.ci0 = (rem % tx) * 64;
-        t.co0 = (rem / tx) * 64;
-        t.k = k;
-        return t;
-    };
-    int bb = blockIdx.x;
-    if (bb >= total) return;
-    if (!NITI_SGD_PREFETCH) {  // one tile at a time
-        int last_j = -1, bw = 0, rule = 0;
-        for (; bb < total; bb += gridDim.x) {
-            const Tile t = locate(bb);
-            if (t.j != last_j) {
-                const int word = sgd_rule_word(jobs.job[t.j], bits);
-                bw = bitwidth_of(read_max(jobs.job[t.j].amax));
-                rule = sgd_rule_of(jobs.job[t.j], word);
-                last_j = t.j;
-            }
-            if (bb != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed reads are done
-            sgd_tile(jobs.job[t.j], bw, rule, t.ci0, t.co0, t.k, T);
-        }
-        return;
-    }
-    Tile cur = locate(bb);
-    SgdTileIn cin, nin;  // (named, not an indexed pair: a dynamically indexed array would live in scratch)
-    sgd_tile_load(jobs.job[cur.j], cur.ci0, cur.co0, cur.k, cin);
-    int last_j = -1, bw = 0, rule = 0;
-    for (; bb < total; bb += gridDim.x) {
-        const int nb = bb + gridDim.x;
-        Tile nxt = cur;
-        if (nb < total) {
-            nxt = locate(nb);
-            sgd_tile_load(jobs.job[nxt.j], nxt.ci0, nxt.co0, nxt.k, nin);
-        }
-        if (cur.j != last_j) {
-            const int word = sgd_rule_word(jobs.job[cur.j], bits);
-            bw = bitwidth_of(read_max(jobs.job[cur.j].amax));
-            rule = sgd_rule_of(jobs.job[cur.j], word);
-            last_j = cur.j;
-        }
-        if (bb != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed reads are done
-        sgd_tile_finish(jobs.job[cur.j], bw, rule, cur.ci0, cur.co0, cur.k, cin, T);
-        cur = nxt;
-        cin = nin;
-    }
-}
-
-// the deferred combines of sgd_update_many alone (the autotuner times a weight-gradient set with them)
-hipError_t sgd_combine_many(const SgdJob* jobs, int n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (n > SGD_MAX_JOBS) return hipErrorInvalidValue;
-    SgdJobs J{};
-    J.n = n;
-    int chunks = 0;
-    for (int i = 0; i < n; ++i) {
-        J.job[i] = jobs[i];
-        J.cstart[i] = chunks;
-        if (jobs[i].slab != nullptr) {
-            if (jobs[i].splits < 1 || jobs[i].slab_stride % 4 != 0 || jobs[i].slab_n % 4 != 0) return hipErrorInvalidValue;
-            chunks += sgd_combine_chunks(jobs[i].splits, jobs[i].slab_n);
-        }
-    }
-    J.cstart[n] = chunks;
-    if (chunks > 0) hipLaunchKernelGGL(sgd_combine_kernel, dim3(chunks < 2048 ? chunks : 2048), dim3(256), 0, st, J);
-    return hipGetLastError();
-}
-
-hipError_t sgd_update_many(const SgdJob* jobs, int n, hipStream_t st, const int32_t* bits) {
-    if (n <= 0) return hipSuccess;
-    if (n > SGD_MAX_JOBS) return hipErrorInvalidValue;
-    for (int i = 0; i < n; ++i)  // a job that names a table word needs the table
-        if (jobs[i].rule < 1 && bits == nullptr) return hipErrorInvalidValue;
-    SgdJobs J{};
-    J.n = n;
-    int total = 0, chunks = 0;
-    for (int i = 0; i < n; ++i) {
-        J.job[i] = jobs[i];
-        J.start[i] = total;
-        J.cstart[i] = chunks;
-        total += ((jobs[i].cip + 63) / 64) * ((jobs[i].cop + 63) / 64) * jobs[i].kk;
-        if (jobs[i].slab != nullptr) {
-            if (jobs[i].splits < 1 || jobs[i].slab_stride % 4 != 0 || jobs[i].slab_n % 4 != 0) return hipErrorInvalidValue;
-            chunks += sgd_combine_chunks(jobs[i].splits, jobs[i].slab_n);
-        }
-    }
-    J.cstart[n] = chunks;
-    if (chunks > 0) {  // the deferred combines first (same stream: the update reads their sums)
-        const int cgrid = chunks < 2048 ? chunks : 2048;
-        hipLaunchKernelGGL(sgd_combine_kernel, dim3(cgrid), dim3(256), 0, st, J);
-    }
-    const int grid = total < 1536 ? total : 1536;  // 6 blocks per CU
-    // (no table: the first job's range word stands in as the readable word no job uses)
-    const int32_t* table = bits != nullptr ? bits : (const int32_t*)jobs[0].amax;
-    if (table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sgd_update_kernel, dim3(grid), dim3(256), 0, st, J, total, table);
-    return hipGetLastError();
-}
-
-hipError_t sgd_update(const int32_t* acc, const uint32_t* amax, int rule, int co, int ci, int kk, int cip, int cop,
-                      int8_t* w, int8_t* wT, int8_t* g_out, hipStream_t st) {
-    SgdJob j{acc, amax, rule, co, ci, kk, cip, cop, w, wT, g_out};
-    return sgd_update_many(&j, 1, st);
-}
-
-// The update-bits words (include/niti_hip.h): word first + t <- v[t], the values travelling as kernel
-// arguments so the change is an ordinary launch on the caller's stream (ordered between steps, and
-// ahead of a replayed graph's update launches, which read the words); one thread per word.
-__global__ void update_bits_set_kernel(int32_t* __restrict__ bits, int first, int count, UpdateBitsArgs v) {
-    const int t = (int)threadIdx.x;
-    if (t < count) bits[first + t] = v.b[t];
-}
-hipError_t update_bits_set(int32_t* bits, int first, int count, const int32_t* values, hipStream_t st) {
-    if (bits == nullptr || values == nullptr || first < 0 || count < 0) return hipErrorInvalidValue;
-    for (int lo = 0; lo < count; lo += UPDATE_BITS_PER_LAUNCH) {
-        UpdateBitsArgs v{};
-        const int c = count - lo < UPDATE_BITS_PER_LAUNCH ? count - lo : UPDATE_BITS_PER_LAUNCH;
-        for (int t = 0; t < c; ++t) v.b[t] = values[lo + t];
-        hipLaunchKernelGGL(update_bits_set_kernel, dim3(1), dim3(UPDATE_BITS_PER_LAUNCH), 0, st, bits, first + lo, c, v);
-    }
-    return hipGetLastError();
-}
-
-// =====================================================================================
-// The rest of the step: pool / relu-grad / loss-grad
-// =====================================================================================
-
-// NITI_Maxpool_Int8.cpp:24-72 (kernel clipped to the input); one thread per 16 channels (32-bit
-// index math: the host keeps the thread count below 2^31).  With `arg`, each window's first-max
-// position (ky * k + kx, in NITI_CPUPoolGrad_Int8.cpp:21-77's order) goes there too: the first
-// element equal to the max is the first one >= it, the backward pass's choice (on a map smaller
-// than the kernel the two windows differ: see below).
-__global__ void maxpool_kernel(const int8_t* __restrict__ x, int n, int h, int w, int cp, int k, int s, int p,
-                               int8_t* __restrict__ y, int oh, int ow, int8_t* __restrict__ arg) {
-    const uint32_t groups = cp / 16;
-    const uint32_t total = (uint32_t)n * oh * ow * groups;
-    const int kh = k < h ? k : h, kw = k < w ? k : w;
-    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-        uint32_t r = t;
-        const int gi = (int)(r % groups);
-        r /= groups;
-        const int ox = (int)(r % (uint32_t)ow);
-        r /= (uint32_t)ow;
-        const int oy = (int)(r % (uint32_t)oh);
-        const int b = (int)(r / (uint32_t)oh);
-        const int sx0 = ox * s - p, sy0 = oy * s - p;
-        v16c m, a;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            m[j] = (signed char)-128;
-            a[j] = (signed char)-1;
-        }
-        for (int yy = max(0, -sy0); yy < min(kh, h - sy0); ++yy)
-            for (int xx = max(0, -sx0); xx < min(kw, w - sx0); ++xx) {
-                const v16c v = *(const v16c*)(x + (((int64_t)b * h + sy0 + yy) * w + sx0 + xx) * cp + gi * 16);
-                const signed char pos = (signed char)(yy * k + xx);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const bool take = a[j] < 0 || v[j] > m[j];
-                    m[j] = take ? v[j] : m[j];
-                    a[j] = take ? pos : a[j];
-                }
-            }
-        *(v16c*)(y + (int64_t)t * 16) = m;
-        if (arg != nullptr && (kh < k || kw < k)) {
-            // A map smaller than the kernel: the reference clips the forward's window (above) but not
-            // the gradient's scan, which takes the first in-image element >= the max of the whole
-            // k x k window (NITI_CPUPoolGrad_Int8.cpp:21-77).  That element is what arg records.
-#pragma unroll
-            for (int j = 0; j < 16; ++j) a[j] = (signed char)-1;
-            for (int yy = max(0, -sy0); yy < min(k, h - sy0); ++yy)
-                for (int xx = max(0, -sx0); xx < min(k, w - sx0); ++xx) {
-                    const v16c v = *(const v16c*)(x + (((int64_t)b * h + sy0 + yy) * w + sx0 + xx) * cp + gi * 16);
-                    const signed char pos = (signed char)(yy * k + xx);
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) a[j] = (a[j] < 0 && v[j] >= m[j]) ? pos : a[j];
-                }
-        }
-        if (arg != nullptr) *(v16c*)(arg + (int64_t)t * 16) = a;
-    }
-}
-
-hipError_t maxpool_nhwc16(const int8_t* x, int n, int h, int w, int cp, int k, int s, int p, int8_t* y, int oh, int ow,
-                          hipStream_t st, int8_t* arg) {
-    const int64_t total = (int64_t)n * oh * ow * (cp / 16);
-    if (total >= ((int64_t)1 << 31) || cp % 16 != 0) return hipErrorInvalidValue;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, n, h, w, cp, k, s, p, y, oh, ow, arg);
-    return hipGetLastError();
-}
-
-// NITI_CPUPoolGrad_Int8.cpp:21-77 in gather form: input pixel (iy,ix) receives, from every
-// window containing it, dy if it is that window's first (ky,kx) element with x >= max.
-// Optionally fused NITI_CPUReluGrad_Int8 (out = x > 0 ? dx : 0).
-__global__ void maxpool_grad_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ y,
-                                    const int8_t* __restrict__ dy, int n, int h, int w, int cp, int k, int s,
-                                    int p, int oh, int ow, int relu, int8_t* __restrict__ dx) {
-    const int groups = cp / 16;
-    const int64_t total = (int64_t)n * h * w * groups;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        int64_t r = t;
-        const int gi = (int)(r % groups);
-        r /= groups;
-        const int ix = (int)(r % w);
-        r /= w;
-        const int iy = (int)(r % h);
-        const int b = (int)(r / h);
-        const v16c xv = *(const v16c*)(x + (((int64_t)b * h + iy) * w + ix) * cp + gi * 16);
-        v16c acc;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0;
-        // windows (oy, ox) with oy*s - p <= iy < oy*s - p + k
-        const int oy_lo = max(0, (iy + p - k + s) / s), oy_hi = min(oh - 1, (iy + p) / s);
-        const int ox_lo = max(0, (ix + p - k + s) / s), ox_hi = min(ow - 1, (ix + p) / s);
-        for (int oy = oy_lo; oy <= oy_hi; ++oy)
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                const int sy0 = oy * s - p, sx0 = ox * s - p;
-                if (iy < sy0 || iy >= sy0 + k || ix < sx0 || ix >= sx0 + k) continue;
-                const int64_t po = (((int64_t)b * oh + oy) * ow + ox) * cp + gi * 16;
-                const v16c mv = *(const v16c*)(y + po);
-                const v16c dv = *(const v16c*)(dy + po);
-                // is (iy,ix) the first element >= max in this window, per channel?
-                unsigned first = 0xffffu;
-                for (int ky = 0; ky < k; ++ky) {
-                    const int sy = sy0 + ky;
-                    if (sy < 0 || sy >= h) continue;
-                    for (int kx = 0; kx < k; ++kx) {
-                        const int sx = sx0 + kx;
-                        if (sx < 0 || sx >= w) continue;
-                        if (sy == iy && sx == ix) goto done;
-                        {
-                            const v16c ov = *(const v16c*)(x + (((int64_t)b * h + sy) * w + sx) * cp + gi * 16);
-#pragma unroll
-                            for (int j = 0; j < 16; ++j)
-                                if (ov[j] >= mv[j]) first &= ~(1u << j);
-                        }
-                    }
-                }
-            done:
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (((first >> j) & 1u) && xv[j] >= mv[j]) acc[j] = (signed char)(acc[j] + dv[j]);
-            }
-        if (relu) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = xv[j] > 0 ? acc[j] : (signed char)0;
-        }
-        *(v16c*)(dx + (((int64_t)b * h + iy) * w + ix) * cp + gi * 16) = acc;
-    }
-}
-
-// Non-overlapping windows (k == s, no padding, windows tile the input): one thread per window
-// and 16 channels scans its k*k pixels once in the reference's (ky, kx) order.
-__global__ void maxpool_grad_tiled_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ y,
-                                          const int8_t* __restrict__ dy, int n, int h, int w, int cp, int k,
-                                          int oh, int ow, int relu, int8_t* __restrict__ dx) {
-    const int groups = cp / 16;
-    const int64_t total = (int64_t)n * oh * ow * groups;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        int64_t r = t;
-        const int gi = (int)(r % groups);
-        r /= groups;
-        const int ox = (int)(r % ow);
-        r /= ow;
-        const int oy = (int)(r % oh);
-        const int b = (int)(r / oh);
-        const int64_t po = (((int64_t)b * oh + oy) * ow + ox) * cp + gi * 16;
-        const v16c mv = *(const v16c*)(y + po);
-        const v16c dv = *(const v16c*)(dy + po);
-        unsigned done = 0;
-        for (int ky = 0; ky < k; ++ky)
-            for (int kx = 0; kx < k; ++kx) {
-                const int64_t pi = (((int64_t)b * h + oy * k + ky) * w + ox * k + kx) * cp + gi * 16;
-                const v16c xv = *(const v16c*)(x + pi);
-                v16c o;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const bool take = !((done >> j) & 1u) && xv[j] >= mv[j];
-                    if (take) done |= 1u << j;
-                    signed char d = take ? dv[j] : (signed char)0;
-                    if (relu && xv[j] <= 0) d = 0;
-                    o[j] = d;
-                }
-                *(v16c*)(dx + pi) = o;
-            }
-    }
-}
-
-hipError_t maxpool_relu_grad_nhwc16(const int8_t* x, const int8_t* y, const int8_t* dy, int n, int h, int w, int cp,
-                                    int k, int s, int p, int oh, int ow, int relu, int8_t* dx, hipStream_t st) {
-    if (k == s && p == 0 && oh * k == h && ow * k == w) {
-        const int64_t total = (int64_t)n * oh * ow * (cp / 16);
-        int64_t blocks = (total + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(maxpool_grad_tiled_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, y, dy, n, h, w, cp,
-                           k, oh, ow, relu, dx);
-        return hipGetLastError();
-    }
-    const int64_t total = (int64_t)n * h * w * (cp / 16);
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(maxpool_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, y, dy, n, h, w, cp, k, s, p,
-                       oh, ow, relu, dx);
-    return hipGetLastError();
-}
-
-// Overlapping windows in two passes over a caller workspace (the generic kernel above re-reads up
-// to 8 x vectors per window for every input pixel).  Pass 1, per window and 16 channels: the
-// position (ky * k + kx, in NITI_CPUPoolGrad_Int8.cpp's order, in-image elements only) of the
-// first element >= the window max y.  Pass 2, per input pixel: the sum (int8, wrapping, as the
-// reference's accumulation) of dy over the windows whose first max is this pixel, then the relu
-// mask.  Results equal maxpool_grad_kernel's.
-__global__ void maxpool_argmax_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ y, int n, int h, int w,
-                                      int cp, int k, int s, int p, int oh, int ow, int8_t* __restrict__ arg) {
-    const int groups = cp / 16;
-    const int64_t total = (int64_t)n * oh * ow * groups;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        int64_t r = t;
-        const int gi = (int)(r % groups);
-        r /= groups;
-        const int ox = (int)(r % ow);
-        r /= ow;
-        const int oy = (int)(r % oh);
-        const int b = (int)(r / oh);
-        const v16c mv = *(const v16c*)(y + t * 16);
-        v16c a;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) a[j] = (signed char)-1;
-        uint32_t open = 0xffffu;
-        const int sy0 = oy * s - p, sx0 = ox * s - p;
-        for (int ky = 0; ky < k && open; ++ky) {
-            const int sy = sy0 + ky;
-            if (sy < 0 || sy >= h) continue;
-            for (int kx = 0; kx < k && open; ++kx) {
-                const int sx = sx0 + kx;
-                if (sx < 0 || sx >= w) continue;
-                const v16c xv = *(const v16c*)(x + (((int64_t)b * h + sy) * w + sx) * cp + gi * 16);
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (((open >> j) & 1u) && xv[j] >= mv[j]) {
-                        a[j] = (signed char)(ky * k + kx);
-                        open &= ~(1u << j);
-                    }
-            }
-        }
-        *(v16c*)(arg + t * 16) = a;
-    }
-}
-
-__global__ void maxpool_grad_gather_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ arg,
-                                           const int8_t* __restrict__ dy, int n, int h, int w, int cp, int k, int s,
-                                           int p, int oh, int ow, int relu, int8_t* __restrict__ dx,
-                                           const int8_t* __restrict__ pooled) {
-    const bool ymask = relu && pooled != nullptr;  // the relu mask from the window's pooled value
-    const uint32_t groups = cp / 16;
-    const uint32_t total = (uint32_t)n * h * w * groups;  // < 2^31 (host)
-    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-        uint32_t r = t;
-        const int gi = (int)(r % groups);
-        r /= groups;
-        const int ix = (int)(r % (uint32_t)w);
-        r /= (uint32_t)w;
-        const int iy = (int)(r % (uint32_t)h);
-        const int b = (int)(r / (uint32_t)h);
-        v16c acc;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0;
-        const int oy_lo = max(0, (iy + p - k + s) / s), oy_hi = min(oh - 1, (iy + p) / s);
-        const int ox_lo = max(0, (ix + p - k + s) / s), ox_hi = min(ow - 1, (ix + p) / s);
-        for (int oy = oy_lo; oy <= oy_hi; ++oy)
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                const int ky = iy - (oy * s - p), kx = ix - (ox * s - p);
-                if (ky < 0 || ky >= k || kx < 0 || kx >= k) continue;
-                const int64_t po = (((int64_t)b * oh + oy) * ow + ox) * cp + gi * 16;
-                const v16c av = *(const v16c*)(arg + po);
-                const v16c dv = *(const v16c*)(dy + po);
-                v16c pv;
-                if (ymask) pv = *(const v16c*)(pooled + po);
-                const signed char me = (signed char)(ky * k + kx);
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (av[j] == me && (!ymask || pv[j] > 0)) acc[j] = (signed char)(acc[j] + dv[j]);
-            }
-        if (relu && !ymask) {
-            const v16c xv = *(const v16c*)(x + (int64_t)t * 16);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = xv[j] > 0 ? acc[j] : (signed char)0;
-        }
-        *(v16c*)(dx + (int64_t)t * 16) = acc;
-    }
-}
-
-// The same gather for the 3x3 / 2 pad-1 pool with the relu mask from the pooled output (ResNet-18's
-// stem): four bytes at a time per 32-bit word (first-max match, pooled > 0, wrapping int8 sum)
-// instead of a byte loop -- the byte form is VALU-bound.  Pooled values are relu outputs (>= 0).
-struct PoolGradGeom {
-    FastDiv fg, fw, fh;  // by 16-channel groups, input width, input height
-    int oh, ow;
-    uint32_t total;
-};
-__global__ void __launch_bounds__(256) maxpool3_grad_pooled_kernel(const uint4* __restrict__ arg, const uint4* __restrict__ dy,
-                                                                   const uint4* __restrict__ pooled, PoolGradGeom g,
-                                                                   uint4* __restrict__ dx) {
-    const uint32_t groups = g.fg.d, w = g.fw.d, h = g.fh.d;
-    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < g.total; t += gridDim.x * 256u) {
-        const uint32_t r0 = fdiv(g.fg, t), gi = t - r0 * groups;
-        const uint32_t r1 = fdiv(g.fw, r0), ix = r0 - r1 * w;
-        const uint32_t b = fdiv(g.fh, r1), iy = r1 - b * h;
-        uint32_t acc[4] = {0, 0, 0, 0};
-        // windows oy with 2 oy - 1 <= iy <= 2 oy + 1 (ky = iy + 1 - 2 oy), likewise ox
-        const int oy_lo = ((int)iy) >> 1, oy_hi = min(g.oh - 1, ((int)iy + 1) >> 1);
-        const int ox_lo = ((int)ix) >> 1, ox_hi = min(g.ow - 1, ((int)ix + 1) >> 1);
-        for (int oy = oy_lo; oy <= oy_hi; ++oy)
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                const uint32_t me = (uint32_t)(((int)iy + 1 - 2 * oy) * 3 + ((int)ix + 1 - 2 * ox)) * 0x01010101u;
-                const int64_t po = (((int64_t)b * g.oh + oy) * g.ow + ox) * groups + gi;
-                const uint4 av = arg[po], dv = dy[po], pv = pooled[po];
-                const uint32_t aw[4] = {av.x, av.y, av.z, av.w}, dw[4] = {dv.x, dv.y, dv.z, dv.w},
-                               pw[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t d = aw[e] ^ me;  // 0 bytes: this pixel is the window's first max
-                    const uint32_t hit = ~(((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d | 0x7f7f7f7fu);
-                    const uint32_t pos = ((pw[e] & 0x7f7f7f7fu) + 0x7f7f7f7fu) & ~pw[e] & 0x80808080u;  // pooled > 0
-                    const uint32_t c = dw[e] & (((hit & pos) >> 7) * 0xffu);
-                    acc[e] = ((acc[e] & 0x7f7f7f7fu) + (c & 0x7f7f7f7fu)) ^ ((acc[e] ^ c) & 0x80808080u);
-                }
-            }
-        dx[t] = uint4{acc[0], acc[1], acc[2], acc[3]};
-    }
-}
-
-hipError_t maxpool_relu_grad_ws(const int8_t* x, const int8_t* y, const int8_t* dy, int n, int h, int w, int cp, int k,
-                                int s, int p, int oh, int ow, int relu, int8_t* ws, int8_t* dx, hipStream_t st) {
-    if (cp % 16 != 0 || k <= 0 || k > 11 || s <= 0 || ws == nullptr) return hipErrorInvalidValue;
-    const int64_t tw = (int64_t)n * oh * ow * (cp / 16), tx = (int64_t)n * h * w * (cp / 16);
-    if (tx >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    auto blocks = [](int64_t t) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((t + 255) / 256, 8192)); };
-    hipLaunchKernelGGL(maxpool_argmax_kernel, dim3(blocks(tw)), dim3(256), 0, st, x, y, n, h, w, cp, k, s, p, oh, ow, ws);
-    hipLaunchKernelGGL(maxpool_grad_gather_kernel, dim3(blocks(tx)), dim3(256), 0, st, x, ws, dy, n, h, w, cp, k, s, p,
-                       oh, ow, relu, dx, (const int8_t*)nullptr);
-    return hipGetLastError();
-}
-
-// the same gradient from the first-max positions the forward maxpool_nhwc16 wrote (`arg`): one pass
-hipError_t maxpool_relu_grad_arg(const int8_t* x, const int8_t* arg, const int8_t* dy, int n, int h, int w, int cp,
-                                 int k, int s, int p, int oh, int ow, int relu, int8_t* dx, hipStream_t st,
-                                 const int8_t* pooled) {
-    if (cp % 16 != 0 || k <= 0 || k > 11 || s <= 0 || arg == nullptr) return hipErrorInvalidValue;
-    if (relu && pooled == nullptr && x == nullptr) return hipErrorInvalidValue;
-    const int64_t tx = (int64_t)n * h * w * (cp / 16);
-    if (tx >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    if (relu && pooled != nullptr && k == 3 && s == 2 && p == 1 && oh == (h - 1) / 2 + 1 && ow == (w - 1) / 2 + 1) {
-        PoolGradGeom g;
-        g.fg = make_fastdiv((uint32_t)(cp / 16));
-        g.fw = make_fastdiv((uint32_t)w);
-        g.fh = make_fastdiv((uint32_t)h);
-        g.oh = oh;
-        g.ow = ow;
-        g.total = (uint32_t)tx;
-        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tx + 255) / 256, 8192));
-        hipLaunchKernelGGL(maxpool3_grad_pooled_kernel, dim3(blocks), dim3(256), 0, st, (const uint4*)arg,
-                           (const uint4*)dy, (const uint4*)pooled, g, (uint4*)dx);
-        return hipGetLastError();
-    }
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tx + 255) / 256, 8192));
-    hipLaunchKernelGGL(maxpool_grad_gather_kernel, dim3(blocks), dim3(256), 0, st, x, arg, dy, n, h, w, cp, k, s, p, oh,
-                       ow, relu, dx, pooled);
-    return hipGetLastError();
-}
-
-__global__ void relu_grad_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ dy, int64_t n16,
-                                 int64_t n, int8_t* __restrict__ out) {
-    const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    for (int64_t i = t0; i < n16; i += (int64_t)gridDim.x * blockDim.x) {
-        const v16c xv = ((const v16c*)x)[i];
-        const v16c dv = ((const v16c*)dy)[i];
-        v16c o;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[j] = xv[j] > 0 ? dv[j] : (signed char)0;
-        ((v16c*)out)[i] = o;
-    }
-    const int64_t e = n16 * 16 + t0;  // the last n % 16 elements
-    if (e < n) out[e] = x[e] > 0 ? dy[e] : (int8_t)0;
-}
-
-hipError_t relu_grad_nhwc16(const int8_t* x, const int8_t* dy, int64_t n, int8_t* out, hipStream_t st) {
-    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)out) & 15) return hipErrorInvalidValue;  // 16-byte vectors
-    const int64_t n16 = n / 16;
-    int64_t blocks = (n16 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(relu_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, dy, n16, n, out);
-    return hipGetLastError();
-}
-
-__global__ void __launch_bounds__(256) loss_grad_kernel(const int8_t* __restrict__ logits, int batch, int classes,
-                                                        int ld, const int8_t* __restrict__ ascale_p,
-                                                        const int32_t* __restrict__ labels, int8_t* __restrict__ out) {
-    loss_rows16(logits, batch, classes, ld, ascale_p, labels, out, blockIdx.x * blockDim.x + threadIdx.x);
-}
-// The loss gradient and the backward pass's P16 copies of the layer inputs in one launch: the
-// first lw workgroups take the loss rows, the rest the conversion jobs (independent data: the
-// copies read forward activations only).  Saves a launch at the head of the backward pass.
-__global__ void __launch_bounds__(256) loss_grad_p16_kernel(const int8_t* __restrict__ logits, int batch, int classes,
-                                                            int ld, const int8_t* __restrict__ ascale_p,
-                                                            const int32_t* __restrict__ labels,
-                                                            int8_t* __restrict__ out, int lw, P16Jobs J) {
-    __shared__ __attribute__((aligned(16))) int8_t tile[16 * 1024];
-    if ((int)blockIdx.x < lw)
-        loss_rows16(logits, batch, classes, ld, ascale_p, labels, out, blockIdx.x * blockDim.x + threadIdx.x);
-    else
-        p16_convert_block(J, blockIdx.x - lw, tile);
-}
-
-// Exponent of a requantised weight gradient, for the DSP op slots whose graph carries one:
-// the applied PSTO shift bw - rule (0 when the gradient is all zero), as the DSP ops add their
-// requantisation shift to exp_in + wscale (NITI_DSPTransposeGradientConv_Int8.cpp:438-439).
-__global__ void grad_exponent_kernel(const uint32_t* __restrict__ amax, int rule, int8_t* __restrict__ out) {
-    const int bw = bitwidth_of(read_max(amax));  // whole wave active
-    if (threadIdx.x == 0) *out = (int8_t)(bw == 0 ? 0 : bw - rule);
-}
-hipError_t grad_exponent(const uint32_t* amax, int rule, int8_t* out, hipStream_t st) {
-    hipLaunchKernelGGL(grad_exponent_kernel, dim3(1), dim3(64), 0, st, amax, rule, out);
-    return hipGetLastError();
-}
-
-// The same arithmetic for wide class rows (ImageNet heads, up to LOSS_WIDE_MAXC classes): one
-// 256-thread block per sample, the row's max / sums reduced in LDS (int64, exact).
-constexpr int LOSS_WIDE_PER = 8;
-constexpr int LOSS_WIDE_MAXC = 256 * LOSS_WIDE_PER;
-__device__ int64_t block_reduce_i64(int64_t v, bool is_max, int64_t* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = is_max ? (red[tid] > red[tid + o] ? red[tid] : red[tid + o]) : red[tid] + red[tid + o];
-        __syncthreads();
-    }
-    const int64_t r = red[0];
-    __syncthreads();
-    return r;
-}
-__global__ void __launch_bounds__(256) loss_grad_wide_kernel(const int8_t* __restrict__ logits, int classes, int ld,
-                                                             const int8_t* __restrict__ ascale_p,
-                                                             const int32_t* __restrict__ labels,
-                                                             int8_t* __restrict__ out) {
-    __shared__ int64_t red[256];
-    const int i = blockIdx.x, tid = threadIdx.x;
-    const int as = (int)*ascale_p;
-    const int8_t* L = logits + (int64_t)i * ld;
-    int64_t o[LOSS_WIDE_PER];
-    if (as > -7) {
-        int64_t sv[LOSS_WIDE_PER];
-        int64_t mx = INT64_MIN;
-#pragma unroll
-        for (int k = 0; k < LOSS_WIDE_PER; ++k) {
-            const int j = tid + 256 * k;
-            if (j < classes) {
-                int64_t t = (int64_t)L[j] * 47274;
-                t = t / (1 << 15);
-                sv[k] = as >= 0 ? t * ipow2_64(as) : t / ipow2_64(-as);
-                mx = mx > sv[k] ? mx : sv[k];
-            }
-        }
-        mx = block_reduce_i64(mx, true, red) - 10;
-#pragma unroll
-        for (int k = 0; k < LOSS_WIDE_PER; ++k) {
-            const int j = tid + 256 * k;
-            int64_t t = j < classes ? sv[k] - mx : 0;
-            t = t > 0 ? t : 0;
-            o[k] = j < classes ? ipow2_64(t) - 1 : 0;
-        }
-    } else {
-        const int64_t base = ipow2_64(1 - 2 * (int64_t)as);
-        const int64_t sb = ipow2_64(1 - (int64_t)as);
-#pragma unroll
-        for (int k = 0; k < LOSS_WIDE_PER; ++k) {
-            const int j = tid + 256 * k;
-            const int64_t t = j < classes ? L[j] : 0;
-            o[k] = j < classes ? base + t * sb + t * t : 0;
-        }
-    }
-    int64_t part = 0;
-#pragma unroll
-    for (int k = 0; k < LOSS_WIDE_PER; ++k) part += o[k];
-    const int64_t sum = block_reduce_i64(part, false, red);
-    part = 0;
-#pragma unroll
-    for (int k = 0; k < LOSS_WIDE_PER; ++k) {
-        const int j = tid + 256 * k;
-        o[k] = j < classes ? (o[k] * (1 << 11)) / sum : 0;
-        part += o[k];
-    }
-    const int64_t gs = block_reduce_i64(part, false, red);
-    const int tgt = labels[i];
-    int8_t* O = out + (int64_t)i * ld;
-    for (int j = tid; j < ld; j += 256) {
-        const int k = j >> 8;
-        int32_t gf = 0;
-#pragma unroll
-        for (int q = 0; q < LOSS_WIDE_PER; ++q)
-            if (q == k) gf = (int32_t)(j == tgt ? o[q] - gs : o[q]);
-        O[j] = j < classes ? (int8_t)psto_any(gf, 4) : (int8_t)0;
-    }
-}
-
-hipError_t p16_jobs_build(const P16Conv* jobs, int n, hipStream_t st, P16Jobs* out, uint32_t* wgs_out);
-
-hipError_t loss_grad_p16(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale,
-                         const int32_t* labels, int8_t* out, const P16Conv* jobs, int n, hipStream_t st) {
-    if (classes > LOSS_MAXC || ld > LOSS_WIDE_MAXC || classes > ld) {
-        hipError_t e = loss_grad(logits, batch, classes, ld, ascale, labels, out, st);
-        return e != hipSuccess ? e : nhwc16_to_p16_many(jobs, n, st);
-    }
-    P16Jobs J;
-    uint32_t wg = 0;
-    hipError_t e = p16_jobs_build(jobs, n, st, &J, &wg);
-    if (e != hipSuccess) return e;
-    const int lw = (batch + 15) / 16;
-    if (J.n == 0) wg = 0;
-    hipLaunchKernelGGL(loss_grad_p16_kernel, dim3((unsigned)lw + wg), dim3(256), 0, st, logits, batch, classes, ld,
-                       ascale, labels, out, lw, J);
-    return hipGetLastError();
-}
-
-hipError_t loss_grad(const int8_t* logits, int batch, int classes, int ld, const int8_t* ascale, const int32_t* labels,
-                     int8_t* out, hipStream_t st) {
-    if (classes > ld || classes > LOSS_WIDE_MAXC || ld > LOSS_WIDE_MAXC) return hipErrorInvalidValue;
-    if (classes > LOSS_MAXC) {
-        hipLaunchKernelGGL(loss_grad_wide_kernel, dim3((unsigned)batch), dim3(256), 0, st, logits, classes, ld, ascale,
-                           labels, out);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(loss_grad_kernel, dim3((batch + 15) / 16), dim3(256), 0, st, logits, batch, classes, ld, ascale,
-                       labels, out);
-    return hipGetLastError();
-}
-
-// =====================================================================================
-// Layout transforms
-// =====================================================================================
-
-// NHWC16 -> CHWN16 through an LDS tile: block = (pixel, 64 images, 64 channels).
-__global__ void nhwc16_to_chwn16_kernel(const int8_t* __restrict__ in, int n, int hw, int cp, int np,
-                                        int8_t* __restrict__ out) {
-    __shared__ int8_t tile[64][64 + 4];
-    const int pix = blockIdx.x;
-    const int n0 = blockIdx.y * 64, c0 = blockIdx.z * 64;
-    const int t = threadIdx.x;
-    {   // read: row = image, 4 x 16B chunks of channels
-        const int r = t >> 2, ch = (t & 3) * 16;
-        v16c v;
-        if (n0 + r < n && c0 + ch < cp)
-            v = *(const v16c*)(in + ((int64_t)(n0 + r) * hw + pix) * cp + c0 + ch);
-        else
-            for (int j = 0; j < 16; ++j) v[j] = 0;
-        for (int j = 0; j < 16; ++j) tile[r][ch + j] = v[j];
-    }
-    __syncthreads();
-    {   // write: row = channel, 4 x 16B chunks of images
-        const int c = t >> 2, nb = (t & 3) * 16;
-        if (c0 + c < cp && n0 + nb < np) {
-            v16c v;
-            for (int j = 0; j < 16; ++j) v[j] = tile[nb + j][c];
-            *(v16c*)(out + ((int64_t)(c0 + c) * hw + pix) * np + n0 + nb) = v;
-        }
-    }
-}
-
-hipError_t nhwc16_to_chwn16(const int8_t* in, int n, int hw, int cp, int np, int8_t* out, hipStream_t st) {
-    dim3 grid(hw, (np + 63) / 64, (cp + 63) / 64);
-    hipLaunchKernelGGL(nhwc16_to_chwn16_kernel, grid, dim3(256), 0, st, in, n, hw, cp, np, out);
-    return hipGetLastError();
-}
-
-struct OhwiToIhwo {
-    const int8_t* w;
-    int co, ci, kk, cip, cop;
-    int8_t* wt;
-    __device__ void operator()(int64_t i) const {  // i over [ci][kk][cop]
-        const int o = (int)(i % cop);
-        const int64_t r = i / cop;
-        const int k = (int)(r % kk);
-        const int c = (int)(r / kk);
-        wt[i] = o < co ? w[((int64_t)o * kk + k) * cip + c] : (int8_t)0;
-    }
-};
-hipError_t ohwi16_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cip, int cop, int8_t* wt, hipStream_t st) {
-    return launch_map((int64_t)ci * kk * cop, OhwiToIhwo{w, co, ci, kk, cip, cop, wt}, st);
-}
-
-struct C4ToNhwc16 {
-    const int8_t* x;
-    int n, c, hw, cp;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [n][hw][cp]
-        const int ch = (int)(i % cp);
-        const int64_t r = i / cp;
-        const int64_t p = r % hw;
-        const int64_t b = r / hw;
-        out[i] = ch < c ? x[(((int64_t)(ch >> 2) * n + b) * hw + p) * 4 + (ch & 3)] : (int8_t)0;
-    }
-};
-hipError_t c4_to_nhwc16(const int8_t* x, int n, int c, int hw, int cp, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)n * hw * cp, C4ToNhwc16{x, n, c, hw, cp, out}, st);
-}
-
-struct NchwToNhwc16 {
-    const int8_t* x;
-    int n, c, hw, cp;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {
-        const int ch = (int)(i % cp);
-        const int64_t r = i / cp;
-        const int64_t p = r % hw;
-        const int64_t b = r / hw;
-        out[i] = ch < c ? x[((int64_t)b * c + ch) * hw + p] : (int8_t)0;
-    }
-};
-hipError_t nchw_to_nhwc16(const int8_t* x, int n, int c, int hw, int cp, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)n * hw * cp, NchwToNhwc16{x, n, c, hw, cp, out}, st);
-}
-
-struct NchwToChwn16 {
-    const int8_t* x;
-    int n, c, hw, cp, np;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [cp][hw][np]
-        const int b = (int)(i % np);
-        const int64_t r = i / np;
-        const int64_t p = r % hw;
-        const int ch = (int)(r / hw);
-        out[i] = (ch < c && b < n) ? x[((int64_t)b * c + ch) * hw + p] : (int8_t)0;
-    }
-};
-hipError_t nchw_to_chwn16(const int8_t* x, int n, int c, int hw, int cp, int np, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)cp * hw * np, NchwToChwn16{x, n, c, hw, cp, np, out}, st);
-}
-
-struct C4ToChwn16 {
-    const int8_t* x;
-    int n, c, hw, cp, np;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {
-        const int b = (int)(i % np);
-        const int64_t r = i / np;
-        const int64_t p = r % hw;
-        const int ch = (int)(r / hw);
-        out[i] = (ch < c && b < n) ? x[(((int64_t)(ch >> 2) * n + b) * hw + p) * 4 + (ch & 3)] : (int8_t)0;
-    }
-};
-hipError_t c4_to_chwn16(const int8_t* x, int n, int c, int hw, int cp, int np, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)cp * hw * np, C4ToChwn16{x, n, c, hw, cp, np, out}, st);
-}
-
-struct Nhwc16ToNchw {
-    const int8_t* x;
-    int n, c, hw, cp;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [n][c][hw]
-        const int64_t p = i % hw;
-        const int64_t r = i / hw;
-        const int ch = (int)(r % c);
-        const int64_t b = r / c;
-        out[i] = x[(b * hw + p) * cp + ch];
-    }
-};
-hipError_t nhwc16_to_nchw(const int8_t* x, int n, int c, int hw, int cp, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)n * c * hw, Nhwc16ToNchw{x, n, c, hw, cp, out}, st);
-}
-
-struct OihwToOhwi16 {
-    const int8_t* w;
-    int co, ci, kk, cip, rev;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [co][kk][cip]
-        const int c = (int)(i % cip);
-        const int64_t r = i / cip;
-        const int k = (int)(r % kk);
-        const int64_t o = r / kk;
-        const int ks = rev ? kk - 1 - k : k;  // rotate180 == reversing the KH*KW plane
-        out[i] = c < ci ? w[(o * ci + c) * kk + ks] : (int8_t)0;
-    }
-};
-hipError_t oihw_to_ohwi16(const int8_t* w, int co, int ci, int kk, int cip, int8_t* out, hipStream_t st,
-                          bool reverse_taps) {
-    return launch_map((int64_t)co * kk * cip, OihwToOhwi16{w, co, ci, kk, cip, reverse_taps ? 1 : 0, out}, st);
-}
-
-struct OihwToIhwo16 {
-    const int8_t* w;
-    int co, ci, kk, cop;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [ci][kk][cop]
-        const int o = (int)(i % cop);
-        const int64_t r = i / cop;
-        const int k = (int)(r % kk);
-        const int64_t c = r / kk;
-        out[i] = o < co ? w[((int64_t)o * ci + c) * kk + k] : (int8_t)0;
-    }
-};
-hipError_t oihw_to_ihwo16(const int8_t* w, int co, int ci, int kk, int cop, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)ci * kk * cop, OihwToIhwo16{w, co, ci, kk, cop, out}, st);
-}
-
-struct Ohwi16ToOihw {
-    const int8_t* w;
-    int co, ci, kk, cip;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {  // i over [co][ci][kk]
-        const int k = (int)(i % kk);
-        const int64_t r = i / kk;
-        const int c = (int)(r % ci);
-        const int64_t o = r / ci;
-        out[i] = w[(o * kk + k) * cip + c];
-    }
-};
-hipError_t ohwi16_to_oihw(const int8_t* w, int co, int ci, int kk, int cip, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)co * ci * kk, Ohwi16ToOihw{w, co, ci, kk, cip, out}, st);
-}
-
-struct PadRows {
-    const int8_t* in;
-    int rows, cols, ld;
-    int8_t* out;
-    __device__ void operator()(int64_t i) const {
-        const int c = (int)(i % ld);
-        const int64_t r = i / ld;
-        out[i] = c < cols ? in[r * cols + c] : (int8_t)0;
-    }
-};
-hipError_t pad_rows(const int8_t* in, int rows, int cols, int ld, int8_t* out, hipStream_t st) {
-    return launch_map((int64_t)rows * ld, PadRows{in, rows, cols, ld, out}, st);
-}
-
-struct TransposeI32 {
-    const int32_t* in;
-    int rows, cols, ld;
-    int32_t* out;
-    __device__ void operator()(int64_t i) const {  // out [cols][rows]
-        const int r = (int)(i % rows);
-        const int64_t c = i / rows;
-        out[i] = in[(int64_t)r * ld + c];
-    }
-};
-hipError_t transpose_i32(const int32_t* in, int rows, int cols, int ld, int32_t* out, hipStream_t st) {
-    return launch_map((int64_t)rows * cols, TransposeI32{in, rows, cols, ld, out}, st);
 }
 
 }  // namespace niti

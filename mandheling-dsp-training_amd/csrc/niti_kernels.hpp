@@ -283,7 +283,7 @@ struct ActOut {
 // can take ActOut::pool); otherwise it recomputes the GEMM with a requantising epilogue
 bool conv_fwd_phase2_separate(const ConvGeom& g, size_t ws_bytes);
 // the first layer as a K = 32 conv over its im2col copy (1x1 geometry, OW % 32 == 0, OH even):
-// range pass + requantise / relu / 2x2 pool pass on register-fed MFMAs (niti_kernels.hip)
+// range pass + requantise / relu / 2x2 pool pass on register-fed MFMAs (niti_conv0.hip)
 bool conv0_ok(const ConvGeom& g);
 // pass 0: range into amax; pass 1: requantise with it (a MAX all-reduce may sit between them)
 hipError_t conv0_fwd(const ConvGeom& g, const int8_t* xcol, const int8_t* w, uint32_t* amax, const ActOut& o,

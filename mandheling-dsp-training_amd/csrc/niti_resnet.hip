@@ -12,7 +12,7 @@
 // e_z + inc), relu included for a block output.  The global pool is the sum over the pixels
 // (int32, the exponent unchanged) followed by the same requantisation; its gradient hands dy to
 // every pixel of the image.  oracle/niti_resnet_ref.py restates all three.  The fused form
-// (residual_requant in niti_kernels.hip) takes the range in a pass without z and recomputes z
+// (residual_requant in niti_requant.hip) takes the range in a pass without z and recomputes z
 // from the int8 operands while requantising: 2 x 2 int8 reads instead of an int32 write + read.
 #include "niti_device.hpp"
 #include "niti_gridbar.hpp"
@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(256) residual_fused_kernel(ResFused p) {
         if (lane == 0) gbw = g;
     }
     __syncthreads();
-    const int shift = gbw - 7;  // as residual_requant_kernel (niti_kernels.hip)
+    const int shift = gbw - 7;  // as residual_requant_kernel (niti_requant.hip)
     const int s = shift > 1 ? shift : 2;
     const bool raw = shift <= 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {

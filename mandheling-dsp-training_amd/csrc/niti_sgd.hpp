@@ -1,5 +1,5 @@
 // niti_sgd.hpp -- the range / PSTO helpers and one NITI_SGD tile, shared by the GEMM epilogues,
-// the update launch (niti_kernels.hip) and the fused row kernels' side updates (niti_rowconv.hip).
+// the update launch (niti_sgd.hip) and the fused row kernels' side updates (niti_rowconv.hip).
 #pragma once
 
 #include "niti_device.hpp"
@@ -171,7 +171,7 @@ __device__ __forceinline__ void sgd_tile(const SgdJob& J, int bw, int rule, int 
     sgd_tile_finish(J, bw, rule, ci0, co0, k, in, T);
 }
 
-// NITI_LOSS_Grad rows (niti_kernels.hip loss_grad*, niti_head.hip): see loss_grad in niti_kernels.hpp
+// NITI_LOSS_Grad rows (niti_pointwise.hip loss_grad*, niti_head.hip): see loss_grad in niti_kernels.hpp
 __device__ __forceinline__ int64_t ipow2_64(int64_t t) { return (int64_t)pow2_x86((int)(t & 31)); }
 // v / ipow2_64(k) (C division, truncation toward zero) by shifts: the divisor is 2^(k & 31) as an
 // int32, so -2^31 when k & 31 == 31 (no 64-bit division)

@@ -11,64 +11,66 @@ Every requantise case pins the range in word 0 of a zeroed range buffer (PINS: b
 shift 1, bw 9 / 16 / 31 PSTO); accumulators stay inside it and every seventh one is an exact
 half-way value of PSTO's rounding.
 
-What each group guards (file:line of mandheling-dsp-training_amd/csrc at the time of writing):
+What each group guards (file and function of mandheling-dsp-training_amd/csrc):
 
 every group
-   niti_kernels.hip:3201-3210, :3355-3364, :3430-3439, :3859-3868   each variant's own copy of the
+   niti_requant.hip, requant_quad_kernel, requant_p16_kernel, requant_p16_plain_kernel,
+   requant_pool3_kernel   each variant's own copy of the
                       prologue: raw / shift 1 runs PSTO 2 / PSTO by the pinned range, and exp_out =
                       int8(exp_in + wscale + inc), which wraps in one case per group (120 + 5 + 9)
 
 A. pool forward (requant_quad_kernel<RQ_POOL_FWD>)
-   niti_kernels.hip:3252-3258   unit -> (pooled pixel, quad) -> window rows by three fast divisions:
+   niti_requant.hip, requant_quad_kernel   unit -> (pooled pixel, quad) -> window rows by three fast divisions:
                       2 x 6 x 10 x 48 divides by 12, 5 and 3
-   niti_kernels.hip:3276-3284   bmax4 from -128 and the pre-pool store of all four corners
-   niti_kernels.hip:3213, :3269, :3275   the outer loop's second, ragged pass (2,097,456 units)
+   niti_requant.hip, requant_quad_kernel and bmax4   bmax4 from -128 and the pre-pool store of all four corners
+   niti_requant.hip, requant_quad_kernel   the outer loop's second, ragged pass (2,097,456 units)
+                      and the RQ_POOL_FWD load guard and break
 
 B. pool backward (requant_quad_kernel<RQ_POOL_BWD>)
-   niti_kernels.hip:3313-3314   first max wins (done): windows with a tie at a positive max and
+   niti_requant.hip, requant_quad_kernel   first max wins (done): windows with a tie at a positive max and
                       all-equal windows
-   niti_kernels.hip:3315        the relu gradient's x <= 0: windows whose max is 0
-   niti_kernels.hip:3305        the optional requantised dy
-   niti_kernels.hip:3319-3324   the C32 copy's index (three channel blocks at ldc 96)
-   niti_kernels.hip:3213, :3291, :3303   the ragged second pass
+   niti_requant.hip, requant_quad_kernel   the relu gradient's x <= 0: windows whose max is 0
+   niti_requant.hip, requant_quad_kernel   the optional requantised dy (out_nhwc16)
+   niti_requant.hip, requant_quad_kernel   the C32 copy's index (dx_c32) (three channel blocks at ldc 96)
+   niti_requant.hip, requant_quad_kernel   the ragged second pass: the RQ_POOL_BWD load guard and break
 
 C. P16 plain (requant_p16_plain_kernel)
-   niti_kernels.hip:3442-3446   (block, quad, quarter) of a unit; ldc 80 divides by 20
-   niti_kernels.hip:3456-3463   relu and the mask's > 0
-   niti_kernels.hip:3467-3475   the v_perm transposes and the P16 address
-   niti_kernels.hip:3441        the grid-stride loop (524,336 units on 2048 blocks)
+   niti_requant.hip, requant_p16_plain_kernel   (block, quad, quarter) of a unit; ldc 80 divides by 20
+   niti_requant.hip, requant_p16_plain_kernel   relu and the mask's > 0
+   niti_requant.hip, requant_p16_plain_kernel   the v_perm transposes and the P16 address
+   niti_requant.hip, requant_p16_plain_kernel   the grid-stride loop (524,336 units on 2048 blocks)
 
 D. P16 pool backward (requant_p16_kernel<RQ_POOL_BWD, W>)
-   niti_kernels.hip:3344-3348   p16_loc of W = 2 (four images per run), 4 (one image), 8 and 16
+   niti_requant.hip, p16_loc   p16_loc of W = 2 (four images per run), 4 (one image), 8 and 16
                       (one pooled row); more than one run per image and more than one image
-   niti_kernels.hip:3393-3398   the same first-max / relu routing, kept for the transposes
-   niti_kernels.hip:3403-3420   4 x 4 byte transposes into P16 blocks; NPX / 16 = 2 blocks at W = 16
+   niti_requant.hip, requant_p16_kernel   the same first-max / relu routing, kept for the transposes
+   niti_requant.hip, requant_p16_kernel   4 x 4 byte transposes into P16 blocks; NPX / 16 = 2 blocks at W = 16
 
 E. zero_cls (requant_quad_kernel<RQ_PLAIN>)
-   niti_kernels.hip:3221-3225   the class of a unit's pixel: rows by zc_w, then by zc_h; bit
+   niti_requant.hip, requant_quad_kernel (zero_cls)   the class of a unit's pixel: rows by zc_w, then by zc_h; bit
                       2 (y & 1) + (x & 1); the skipped accumulators hold 0x7fffffff / INT32_MIN,
                       which requantise to -1 / 0 raw and to +-127 otherwise if they are read
-   niti_kernels.hip:3226        no load where skipped
+   niti_requant.hip, requant_quad_kernel (zero_cls)   no load where skipped
 
 F. 3x3 / 2 pool (requant_pool3_kernel<RELU>)
-   niti_kernels.hip:3886-3889   c0 / c2: the last window's right column outside an odd-width image
-   niti_kernels.hip:3894, :3910 r2: the bottom row outside an odd-height image
-   niti_kernels.hip:3920        the relu form's first position (oy > 0 ? 0 : 3) + (c0 ? 0 : 1)
-   niti_kernels.hip:3835-3845   rq4_relu against PSTO + relu
-   niti_kernels.hip:3849-3854   pool3_take_u7's strict >: the first maximum stays
-   niti_kernels.hip:3884, :3902-3908, :3946-3948   strips: the carried top row, a one-row last strip
+   niti_requant.hip, requant_pool3_kernel   c0 / c2: the last window's right column outside an odd-width image
+   niti_requant.hip, requant_pool3_kernel (load, step)   r2: the bottom row outside an odd-height image
+   niti_requant.hip, requant_pool3_kernel (step)   the relu form's first position (oy > 0 ? 0 : 3) + (c0 ? 0 : 1)
+   niti_requant.hip, rq4_relu   rq4_relu against PSTO + relu
+   niti_requant.hip, pool3_take_u7   pool3_take_u7's strict >: the first maximum stays
+   niti_requant.hip, requant_pool3_kernel (oy0 / oy1, top, the two register sets)   strips: the carried top row, a one-row last strip
                       (OH = 9 in strips of 4; NITI_RQ3_ROWS = 1 and 3 in child processes)
-   niti_kernels.hip:3937-3944   each pre-pool pixel written once
-   niti_kernels.hip:3872, :3880 NITI_RQ3_REMAP=1: one unit per thread on remapped blocks
+   niti_requant.hip, requant_pool3_kernel (step, y0)   each pre-pool pixel written once
+   niti_requant.hip, requant_pool3_kernel (bid, the unit loop)   NITI_RQ3_REMAP=1: one unit per thread on remapped blocks
 
 G. stem pool pair (maxpool_kernel's arg, maxpool_grad_gather_kernel, maxpool3_grad_pooled_kernel)
-   niti_kernels.hip:4287-4296   the first-max position beside the max
-   niti_kernels.hip:4299-4312   on a map smaller than the kernel (1 x 1 and 2 x 2 under 3 x 3 and
+   niti_pointwise.hip, maxpool_kernel   the first-max position beside the max
+   niti_pointwise.hip, maxpool_kernel   on a map smaller than the kernel (1 x 1 and 2 x 2 under 3 x 3 and
                       5 x 5) the reference clips the forward's window but not the gradient's scan:
                       y is the clipped window's max, arg the element the gradient routes to
-   niti_kernels.hip:4506-4520   the gather's window range and pooled > 0
-   niti_kernels.hip:4549-4553   the packed kernel's window range and position word
-   niti_kernels.hip:4560-4564   first-max match, pooled > 0 (0, 1, 127, negative bytes) and the
+   niti_pointwise.hip, maxpool_grad_gather_kernel   the gather's window range and pooled > 0
+   niti_pointwise.hip, maxpool3_grad_pooled_kernel   the packed kernel's window range and position word
+   niti_pointwise.hip, maxpool3_grad_pooled_kernel   first-max match, pooled > 0 (0, 1, 127, negative bytes) and the
                       carry-less int8 sum: four windows of 127 add to 508 -> -4
 """
 from __future__ import annotations

@@ -5,7 +5,8 @@ Every reference here is the CPU oracle (oracle/niti_oracle.py, oracle/niti_resne
 numpy on int64 / int32; none is a GPU kernel.  Inputs and references are built once per case
 (lru_cache) and handed out read-only.
 
-What each group guards (file:line of mandheling-dsp-training_amd/csrc at the time of writing):
+What each group guards (file:line, or file and function, of mandheling-dsp-training_amd/csrc at the
+time of writing):
 
 A. SGD update (niti_sgd_update, niti_sgd_update_wf)
    niti_sgd.hpp:92    g = PSTO(acc, bw - rule), 0 when bw == 0: the pinned ranges 0 / 1 (bw == 0),
@@ -18,14 +19,14 @@ A. SGD update (niti_sgd_update, niti_sgd_update_wf)
    niti_sgd.hpp:100   the WF byte index (an off-by-one in any factor moves at least one byte)
    niti_sgd.hpp:104   zero rows co..cop of the tile -> zero columns co..cop of wT (:113)
    niti_sgd.hpp:129   the transposed WF byte index, tap 8 - k
-   niti_kernels.hip:4193, :4247   the update's grid-stride loop: 896 x 896 x 9 has 1764 tiles on a
+   niti_sgd.hip, sgd_update_kernel   the update's grid-stride loops (both forms): 896 x 896 x 9 has 1764 tiles on a
                       1536-block grid, so 228 blocks take a second tile (a dropped or repeated
                       tile leaves the 77 fill or a twice-updated weight)
    niti_capi.hip:536  wf with ci % 32 != 0 is NOT_SUPPORT
 
 B. Residual ops (niti_residual_add, niti_residual_requant, niti_residual_requant_relu_grad)
-   niti_kernels.hip:3537   raw = shift <= 0: amp 1 / 40 / 64 / 3 cases (amp 64: 128 wraps to -128)
-   niti_kernels.hip:3536   shift == 1 runs PSTO 2: amp 127 gap 0 (max 254)
+   niti_requant.hip, residual_requant_kernel   raw = shift <= 0: amp 1 / 40 / 64 / 3 cases (amp 64: 128 wraps to -128)
+   niti_requant.hip, residual_requant_kernel   shift == 1 runs PSTO 2 (s): amp 127 gap 0 (max 254)
    niti_device.hpp:122     rr = min(r, 7): gaps 31 / 32 / 64 / 127 / 200 / 255 have r = 8 .. 232
                            (without the min the bit-field extract leaves lo's byte)
    niti_device.hpp:142     min(.., 127): hi = -128 at gap >= 23 gives |z| = 2^30 -> q = 128
@@ -33,25 +34,25 @@ B. Residual ops (niti_residual_add, niti_residual_requant, niti_residual_requant
                            takes r mod 32, which is 0 at gaps 55 and 87 (lo unshifted: wrong z)
                            (hi * 2^23 + (0 or -1) requantises to the same byte either way, so at
                            large gaps lo's exact value shows in residual_add's z, not in out)
-   niti_resnet.hip:32, niti_kernels.hip:3540-3541   ez / exp_out as int8: e_hi = 127 cases
-   niti_kernels.hip:3558, :3579   the relu-gradient mask (> 0: -128 and 0 drop, 1 and 127 keep)
-   niti_resnet.hip:34, niti_kernels.hip:3549, :3565   the 2048-block grid-stride loops: n =
+   niti_resnet.hip:32; niti_requant.hip, residual_requant_kernel   ez / exp_out as int8: e_hi = 127 cases
+   niti_requant.hip, residual_requant_kernel   the relu-gradient mask of both loops (> 0: -128 and 0 drop, 1 and 127 keep)
+   niti_resnet.hip:34; niti_requant.hip, residual_requant_kernel   the 2048-block grid-stride loops: n =
                            2048 * 256 * 16 + 16 * 300 makes a second, ragged pass of 300 chunks
-   niti_kernels.hip:3544, :3565   NITI_RES_PK=0 sends PSTO cases down the 32-bit loop too
+   niti_requant.hip, residual_requant_kernel (pk)   NITI_RES_PK=0 sends PSTO cases down the 32-bit loop too
 
 C. niti_requant_act (requant_quad_kernel<RQ_PLAIN>)
-   niti_kernels.hip:3203-3204   raw / shift 1 / PSTO by the pinned range
-   niti_kernels.hip:3209        exp_out = int8(exp_in + wscale + inc) wraps (120 + 5 + 9)
-   niti_kernels.hip:3213        the outer loop: 2,099,200 quads = one full pass of 4 loads per
+   niti_requant.hip, requant_quad_kernel   raw / shift 1 / PSTO by the pinned range
+   niti_requant.hip, requant_quad_kernel   exp_out = int8(exp_in + wscale + inc) wraps (120 + 5 + 9)
+   niti_requant.hip, requant_quad_kernel   the outer loop: 2,099,200 quads = one full pass of 4 loads per
                                 thread on 2048 blocks plus a 2048-quad tail
-   niti_kernels.hip:3227, :3232 the tail's load guard and break (an unmasked tail reads and
+   niti_requant.hip, requant_quad_kernel   the RQ_PLAIN tail's load guard and break (an unmasked tail reads and
                                 writes past the tensor or leaves quads unwritten)
-   niti_kernels.hip:3184, :3238 relu, and the mask's > 0
+   niti_requant.hip, rq4 and requant_quad_kernel   relu, and the mask's > 0
 
 D. Layout helpers and the sum pool
-   niti_kernels.hip:4857        nchw_to_chwn16: pad channels and pad images 0
-   niti_kernels.hip:4777, :4786 nhwc16_to_chwn16: the 64 x 64 tile guards (n = 70, cp = 144)
-   niti_kernels.hip:4939, :4889 ohwi16_to_oihw, nhwc16_to_nchw index maps
+   niti_pointwise.hip, NchwToChwn16   nchw_to_chwn16: pad channels and pad images 0
+   niti_pointwise.hip, nhwc16_to_chwn16_kernel   nhwc16_to_chwn16: the 64 x 64 tile guards (n = 70, cp = 144)
+   niti_pointwise.hip, Ohwi16ToOihw and Nhwc16ToNchw   ohwi16_to_oihw, nhwc16_to_nchw index maps
    niti_resnet.hip:194-208      sum_pool over 5 blocks publishing one range
 """
 from __future__ import annotations
